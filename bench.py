@@ -2,14 +2,19 @@
 """Benchmark of the MI355X DocumentAnalyzer hot path (contract: task prompt / DESIGN.md §8).
 
     python bench.py --gpus N --steps K --warmup W [--workload analyzer|detector|recognizer] [--model-set lite|default]
-                    [--pages 64] [--wave 8] [--in-flight 3]
+                    [--pages 64] [--wave 8] [--in-flight 3] [--dump-outputs DIR] [--full]
 
 One rank = ONE process per GPU.  Under torchrun the rank comes from the environment; `python bench.py --gpus N` without
 one spawns its own N ranks (same protocol: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*).  A "step" is one pass of the hot
 path over one batch of synthetic 1600x1200 pages (uint8 BGR, as `cv2.imread` would hand them over); the analyzer
-workload starts from HOST pages - pinned staging and the H2D copies are inside the clock.  Rank 0 prints ONE JSON line: BASELINE.json's metric (pages/s, whole job), the roofline of the
-dominant kernel (live HIP-event timing of every implicit-GEMM convolution launch on its own stream, in a serial pass
-of the same program) and, at N=1, the CPU baseline (oracle restatement of the reference's PyTorch-CPU path).
+workload starts from HOST pages - pinned staging and the H2D copies are inside the clock.  Rank 0 prints ONE JSON line: BASELINE.json's metric (pages/s, whole job).
+A plain run sets up, warms up, times the K steps and prints that line, nothing more.  `--full` adds the legs that take runs
+of their own: the roofline of the dominant kernel (live HIP-event timing of every implicit-GEMM convolution launch on its
+own stream, in a serial pass of the same program), at N=1 the secondary metrics and the CPU baseline (oracle restatement of
+the reference's PyTorch-CPU path), and the device / host memory high-water of every leg.  `--no-roofline`, `--no-secondary`
+and `--no-cpu-baseline` leave single legs out of a `--full` run; `--roofline-only` is the roofline pass alone.
+`--dump-outputs DIR` writes what rank 0's timed path returned in its LAST step as DIR/<name>.npy (see dump_outputs), so
+that two builds can be compared output for output on the same seeded inputs.
 
 workload analyzer (default; BASELINE.json configs[3]): DBNet text detector, PARSeq recogniser, RT-DETRv2 layout
   parser, RT-DETRv2 table-structure recogniser, host post-processing and aggregation, through the product's multi-page
@@ -435,6 +440,65 @@ def two_roof_bound(table):
                     "frac = sum of those bounds / sum of the measured launch times"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+NONE_VALUE = -2.0  # what flatten_result writes for a field that is None
+DUMP_SAMPLE = 1 << 21  # values kept of a larger array: a fixed, seeded sample (np.random.default_rng(0), sorted flat indices)
+
+
+def _numbers(x):
+    """The values of a number or of a (nested) list of numbers only, in order; None for anything else."""
+    if isinstance(x, (int, float)):
+        return [float(x)]
+    if isinstance(x, (list, tuple)):
+        vals = [_numbers(v) for v in x]
+        if all(v is not None for v in vals):
+            return [f for v in vals for f in v]
+    return None
+
+
+def flatten_result(obj, path, out):
+    """The numbers of a result the timed path hands its caller (the product's schemas, lists, strings, numbers), appended to
+    flat lists keyed by field path: every list's length under `<path>.len` (a box or quad - numbers only - is one list),
+    strings as their code points followed by -1, None as -2 (finite, and no code point, length, order or index is negative) - so
+    that the same fields of two runs line up value for value."""
+    if isinstance(obj, (list, tuple)):
+        out.setdefault(f"{path}.len", []).append(len(obj))
+        nums = _numbers(obj) if obj else None
+        if nums is not None:
+            out.setdefault(path, []).extend(nums)
+            return
+        for x in obj:
+            flatten_result(x, path, out)
+    elif hasattr(type(obj), "model_fields"):  # pydantic schema: its fields in declaration order
+        for name in type(obj).model_fields:
+            flatten_result(getattr(obj, name), f"{path}.{name}", out)
+    elif isinstance(obj, dict):
+        for k in sorted(obj):
+            flatten_result(obj[k], f"{path}.{k}", out)
+    elif isinstance(obj, str):
+        out.setdefault(path, []).extend([ord(c) for c in obj] + [-1])
+    elif obj is None:
+        out.setdefault(path, []).append(NONE_VALUE)
+    else:
+        out.setdefault(path, []).append(float(obj))
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays`: name -> float tensor / ndarray (written as float32) or list of numbers from flatten_result (float64).  An
+    array of more than DUMP_SAMPLE values is replaced by the values at DUMP_SAMPLE seeded flat indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach().float().cpu().numpy()
+        a = np.asarray(a, dtype=np.float32 if isinstance(a, np.ndarray) else np.float64).ravel()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB"
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def cpu_timed(fn, n_warm, n_timed, budget_s):
     """n_warm untimed + up to n_timed timed repetitions of fn(i) (stops early past budget_s, never below 1 timed)."""
     for i in range(n_warm):
@@ -500,9 +564,14 @@ def recognizer_workload(args, rank, local_rank, world, device, lib):
         dt = float(tt.item())
     if rank != 0:
         return None
-    cpu = None
-    roof = conv_roofline(lib, step, args.lines, "line", "conv_igemm / conv_splitk (every linear layer of the ViT encoder and the decoder)")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        res = {}
+        flatten_result(out, "lines", res)
+        dump_outputs(args.dump_outputs, res)
+    cpu = roof = None
+    if args.full:
+        roof = conv_roofline(lib, step, args.lines, "line", "conv_igemm / conv_splitk (every linear layer of the ViT encoder and the decoder)")
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import pipeline as op
         from oracle.parseq import PRESETS, make_cfg
 
@@ -720,6 +789,10 @@ def main():
     ap.add_argument("--no-roofline", action="store_true", help="skip the serial roofline pass (pipeline sweeps: only the timed region)")
     ap.add_argument("--roofline-only", action="store_true",
                     help="skip the timed region: only the serial roofline pass (the command profiles/ runs under rocprofv3)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline pass, the secondary metrics, the CPU baseline and the memory "
+                         "high-water record (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -734,7 +807,7 @@ def main():
     assert DRY or torch.cuda.is_available(), "bench.py needs a HIP device"
     device = rank_device(local_rank)
     lib = None if DRY else _lib.load()
-    hw = HighWater() if (rank == 0 and not DRY) else None
+    hw = HighWater() if (rank == 0 and not DRY and args.full) else None
 
     def leg(name):
         if hw is not None:
@@ -795,7 +868,7 @@ def main():
             res = an.serve(host_pages * int(k), wave=args.wave, in_flight=args.in_flight)
             assert len(res) == len(host_pages) * int(k)
             failed += sum(isinstance(r, BaseException) for r in res)
-            return res[-1]
+            return res[-len(host_pages):]  # the last step's results, in page order
 
         names = {"lite": "DBNet dbnetv2_1 + PARSeq parseq-tiny-dynw-v4 (dynamic_width, batch_bucketing, source_downscale)",
                  "default": "DBNet dbnetv2_1 + PARSeq parseq-large-v4_1 (fixed 800 px canvas, batch_size 128 per page)"}
@@ -857,13 +930,22 @@ def main():
         rows = ydist.all_gather_scalars([len(seeds) * args.steps / dt_local, failed], device)
         per_rank = {"pages_per_s_min": round(min(r[0] for r in rows), 3), "pages_per_s_max": round(max(r[0] for r in rows), 3),
                     "failed_pages": int(sum(r[1] for r in rows))}
+        if rank == 0 and args.dump_outputs:
+            if args.workload == "analyzer":  # every page's DocumentAnalyzerSchema; a failed page is its exception
+                res = {"page_failed": [float(isinstance(r, BaseException)) for r in out]}
+                for r in out:
+                    if not isinstance(r, BaseException):
+                        flatten_result(r, "page", res)
+            else:
+                res = {"binary": out}
+            dump_outputs(args.dump_outputs, res)
 
     # ---- roofline leg: per-launch HIP events around the conv kernel, in a SERIAL pass of the same program: the same analyzer,
     # one wave at a time, the two chains of a wave one after the other on one stream - so that a launch's event pair
     # brackets that kernel alone.  `python bench.py --roofline-only` under rocprofv3 is the same pass (profiles/).
     roof = None
     leg("roofline: serial pass with per-launch events")
-    if rank == 0 and not DRY and not args.no_roofline:
+    if rank == 0 and not DRY and (args.full or args.roofline_only) and not args.no_roofline:
         kern = ("conv_igemm_split / conv_f16_dma / conv_f16_astat / k_vit_mlp_f16 (fp16-split MFMA implicit GEMM: the chip-filling conv / linear launches of the four nets, the ViT MLP halves as one launch each) + conv_igemm / "
                 "conv_splitk (exact fp32 MFMA: the stems and the grid-starved launches), max|x| passes included" if split_mode() else
                 "conv_igemm / conv_splitk (fp32 MFMA implicit GEMM: every conv / linear layer of the four nets)")
@@ -924,7 +1006,7 @@ def main():
 
     # ---- secondary metrics (rank 0, N=1): the recogniser's lines/s and the default model set, in this same process
     secondary = None
-    if rank == 0 and world == 1 and args.workload == "analyzer" and not (DRY or args.roofline_only or args.no_secondary):
+    if rank == 0 and world == 1 and args.workload == "analyzer" and args.full and not (DRY or args.roofline_only or args.no_secondary):
         # a failing secondary leg must not cost the run its headline line: the error is reported in its place
         secondary = {}
         for name, fn in (("pages_per_s_exact_fp32", lambda: {"pages_per_s_exact_fp32": exact_fp32_metrics(args, an, host_pages)}),
@@ -943,7 +1025,7 @@ def main():
     # ---- CPU baseline leg (rank 0, N=1): oracle chain on the host cores, bounded sample
     cpu = None
     leg("cpu_baseline: oracle chain on the host cores")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not DRY and not args.roofline_only:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not DRY and not args.roofline_only:
         if args.workload == "analyzer":
             charset = an.text_recognizer.charset
             # one page through the CPU chain costs 13 s on an idle 128-core host and 46 s on a loaded one (both seen on the

@@ -7,6 +7,8 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,3 +67,17 @@ def test_eight_self_spawned_ranks_strong_scaling_with_a_poisoned_page():
     assert abs(line["value"] * line["ms_per_step"] / 1e3 - 50) < 1e-2  # the whole job's pages over the max-over-ranks time
     assert line["rccl"]["ranks"] == 8 and line["rccl"]["weights_crc_equal"] is True
     assert line["per_rank"]["failed_pages"] == 2  # the poisoned page, once per timed step
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--steps K runs K timed steps and --dump-outputs DIR writes what the last of them returned (the stub pages' seeds, in
+    page order, and which pages failed); two runs with the same arguments write the same arrays."""
+    for d in ("a", "b"):
+        line = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--pages", "5", "--wave", "2",
+                     "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d)])
+        assert line["steps"] == 3 and abs(line["value"] * line["ms_per_step"] / 1e3 - 5) < 1e-2
+    for name in ("page", "page_failed"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "page.npy").tolist() == [0, 1, 2, 3, 4]
+    assert not np.load(tmp_path / "a" / "page_failed.npy").any()

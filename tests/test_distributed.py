@@ -195,6 +195,8 @@ class _FailingAnalyzer(_StubAnalyzer):
 def _failing_worker(rank, world, port, q, mode):
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port), YMK_TEST_FAIL=mode)
+    # serve_sharded picks cuda:<local rank> when a device is visible: on a host with one GPU, rank 1 would ask for a second
+    torch.cuda.is_available = lambda: False
     from yomitoku_amd import distributed as yd
 
     def ck():
