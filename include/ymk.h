@@ -271,6 +271,45 @@ int ymk_op_maxpool3x3s2(const float* x_dev, int n, int h, int w, int c, float* y
 int ymk_op_upsample_bilinear(const float* x_dev, int n, int h, int w, int c, int oh, int ow, const float* add_dev,
                              float* y_dev, void* stream);
 
+/* ---- single operators of the RT-DETRv2 decoder (yomitoku_amd/csrc/ymk_det.hip; the launch functions ymk_rtdetr.cpp calls).
+ * level_hw: HOST array {h0, w0, h1, w1, h2, w2} of the three token grids; token rows are level-major across the b images:
+ * row(i, t) = b * off[l] + i * h[l] * w[l] + (t - off[l]) for token t of level l of image i (off[l]: tokens of the levels
+ * before l).  ntok = the sum of h[l] * w[l].
+ * topk_tokens: logits [rows][nc] -> idx [b][k]: per image the k tokens of largest max-over-classes logit, in rank order
+ *   (descending value, lowest token id among equal values); 1 <= k <= min(2048, ntok).  Allocates the b * ntok key words itself.
+ * gather_queries: idx [b][k] (each in [0, ntok), checked) -> content [b][k][d] = om[row(i, idx)], ref [b][k][4] =
+ *   sigmoid(bbox[row][:] + anchors[idx][:]) (anchors: [ntok][4]).
+ * refine_boxes: out[i] = sigmoid(delta[i] + inverse_sigmoid(ref[i])), inverse_sigmoid clipping at 1e-5, over n floats.
+ * mask_rows: out[row(i, t)][:] = valid[t] * in[row(i, t)][:] (valid: [ntok]); d a multiple of 4.
+ * deform_sample: multi-scale deformable attention sampling, 8 heads x 32 channels x 3 levels x 4 points: offs [b*k][8][3][4][2],
+ *   attw [b*k][8][12] (soft-maxed over the 12), ref [b*k][4] (cx, cy, w, h), value rows of ldv floats (>= 256; the model's
+ *   value_dev points inside a [rows][6 * 256] buffer) -> out [b*k][256]. */
+int ymk_op_topk_tokens(const float* logits_dev, int b, const int* level_hw, int nc, int k, int* idx_dev, void* stream);
+int ymk_op_gather_queries(const float* om_dev, const float* bbox_dev, const float* anchors_dev, const int* idx_dev, int b,
+                          const int* level_hw, int k, int d, float* content_dev, float* ref_dev, void* stream);
+int ymk_op_refine_boxes(const float* delta_dev, const float* ref_dev, float* out_dev, int64_t n, void* stream);
+int ymk_op_mask_rows(const float* in_dev, const float* valid_dev, int b, const int* level_hw, int d, float* out_dev, void* stream);
+int ymk_op_deform_sample(const float* offs_dev, const float* attw_dev, const float* ref_dev, const float* value_dev, int ldv, int b,
+                         const int* level_hw, int k, float* out_dev, void* stream);
+/* NHWC fp32, c a multiple of 4: AvgPool2d(2, 2, 0, ceil_mode=True) -> [n][(h+1)/2][(w+1)/2][c]; nearest x2 -> [n][2h][2w][c] */
+int ymk_op_avgpool2x2_ceil(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream);
+int ymk_op_upsample_nearest2x(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream);
+
+/* ---- single operators of the DBNet++ head (ymk_dbnet.cpp).
+ * deconv2x2: act(ConvTranspose2d(cin, cout, 2, stride 2)(x) * scale + bias) through the convolution path's EPI_DECONV2X2
+ *   epilogue and the model's panel packing; w_host [cin][cout][2][2], scale / bias [cout] (host, may be null); x [n][h][w][cin],
+ *   y [n][2h][2w][cout].  Operand precision as ymk_op_conv2d ("conv_split", "conv_split_tile").
+ * deconv2x2_to1_sigmoid: sigmoid(ConvTranspose2d(64, 1, 2, stride 2)(x) + bias); w_host [64][4] (= [64][1][2][2]), x [n][h][w][64],
+ *   y [n][2h][2w].
+ * dbnet_asf: ScaleChannelSpatialAttention + the per-scale multiply of ScaleFeatureSelection on the ASF conv's output ax
+ *   [n][h][w][64] and the concatenated features fuse [n][h][w][256] -> out [n][h][w][256]; w1_host [cmid][64], w2_host [64][cmid]
+ *   (channel_wise), sp33_host [9], sp11 (spatial_wise), watt_host [4][64] (attention_wise). */
+int ymk_op_deconv2x2(const float* x_dev, int n, int h, int w, int cin, const float* w_host, int cout, const float* scale_host,
+                     const float* bias_host, int act, float* y_dev, void* stream);
+int ymk_op_deconv2x2_to1_sigmoid(const float* x_dev, int n, int h, int w, const float* w_host, float bias, float* y_dev, void* stream);
+int ymk_op_dbnet_asf(const float* ax_dev, const float* fuse_dev, int n, int h, int w, const float* w1_host, const float* w2_host,
+                     int cmid, const float* sp33_host, float sp11, const float* watt_host, float* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,3 +162,147 @@ def attention(q, k, v, heads, scale=None, mask_qk=None, key_padding_mask=None, u
             "ymk_op_attention",
         )
     return o
+
+
+# ---- the RT-DETRv2 decoder's token kernels: rows are level-major across the images (include/ymk.h, ymk_op_topk_tokens)
+def _level_hw(levels):
+    """levels ((h0, w0), (h1, w1), (h2, w2)) -> the HOST int array {h0, w0, h1, w1, h2, w2} of the ABI."""
+    import ctypes
+
+    flat = [int(v) for hw in levels for v in hw]
+    assert len(flat) == 6
+    return (ctypes.c_int * 6)(*flat)
+
+
+def topk_tokens(logits, b, levels, k):
+    """logits [b * ntok, nc] (device, level-major rows) -> idx [b, k] int32: per image the k best tokens in rank order."""
+    lib = _lib.load()
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+    lg = logits.contiguous()
+    idx = torch.empty((b, k), dtype=torch.int32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _lib.check(lib.ymk_op_topk_tokens(lg.data_ptr(), b, _level_hw(levels), lg.shape[1], k, idx.data_ptr(),
+                                          _lib.current_stream_ptr()), "ymk_op_topk_tokens")
+    return idx
+
+
+def gather_queries(om, bbox, anchors, idx, levels):
+    """om [rows, d], bbox [rows, 4], anchors [ntok, 4], idx [b, k] int32 (device) -> (content [b, k, d], ref [b, k, 4])."""
+    lib = _lib.load()
+    b, k = idx.shape
+    d = om.shape[1]
+    om, bbox, anchors, idx = (t.contiguous() for t in (om, bbox, anchors, idx))
+    content = torch.empty((b, k, d), dtype=torch.float32, device=om.device)
+    ref = torch.empty((b, k, 4), dtype=torch.float32, device=om.device)
+    with torch.cuda.device(om.device):
+        _lib.check(lib.ymk_op_gather_queries(om.data_ptr(), bbox.data_ptr(), anchors.data_ptr(), idx.data_ptr(), b, _level_hw(levels), k, d,
+                                             content.data_ptr(), ref.data_ptr(), _lib.current_stream_ptr()), "ymk_op_gather_queries")
+    return content, ref
+
+
+def refine_boxes(delta, ref):
+    """sigmoid(delta + inverse_sigmoid(ref)), elementwise over same-shaped device tensors."""
+    lib = _lib.load()
+    delta, ref = delta.float().contiguous(), ref.float().contiguous()
+    assert delta.shape == ref.shape
+    out = torch.empty_like(delta)
+    with torch.cuda.device(delta.device):
+        _lib.check(lib.ymk_op_refine_boxes(delta.data_ptr(), ref.data_ptr(), out.data_ptr(), delta.numel(), _lib.current_stream_ptr()),
+                   "ymk_op_refine_boxes")
+    return out
+
+
+def mask_rows(x, valid, b, levels):
+    """x [b * ntok, d] (level-major rows), valid [ntok] (device) -> valid[token] * x[row]."""
+    lib = _lib.load()
+    x, valid = x.float().contiguous(), valid.float().contiguous()
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_mask_rows(x.data_ptr(), valid.data_ptr(), b, _level_hw(levels), x.shape[1], out.data_ptr(),
+                                        _lib.current_stream_ptr()), "ymk_op_mask_rows")
+    return out
+
+
+def deform_sample(offs, attw, ref, value_buf, col, b, levels, k):
+    """offs [b*k, 8, 12, 2], attw [b*k, 8, 12], ref [b*k, 4]; the value rows are columns col .. col+255 of value_buf
+    [b * ntok, ldv] (all on the device) -> [b*k, 256]."""
+    lib = _lib.load()
+    offs, attw, ref = (t.float().contiguous() for t in (offs, attw, ref))
+    assert value_buf.is_contiguous() and value_buf.dtype == torch.float32 and 0 <= col and col + 256 <= value_buf.shape[1]
+    out = torch.empty((b * k, 256), dtype=torch.float32, device=offs.device)
+    with torch.cuda.device(offs.device):
+        _lib.check(lib.ymk_op_deform_sample(offs.data_ptr(), attw.data_ptr(), ref.data_ptr(), value_buf.data_ptr() + 4 * col,
+                                            value_buf.shape[1], b, _level_hw(levels), k, out.data_ptr(), _lib.current_stream_ptr()),
+                   "ymk_op_deform_sample")
+    return out
+
+
+def avgpool2x2_ceil(x):
+    """AvgPool2d(2, 2, 0, ceil_mode=True) of an NCHW device tensor (C a multiple of 4)."""
+    lib = _lib.load()
+    n, c, h, w = x.shape
+    xh = _nhwc(x.float())
+    y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_avgpool2x2_ceil(xh.data_ptr(), n, h, w, c, y.data_ptr(), _lib.current_stream_ptr()), "ymk_op_avgpool2x2_ceil")
+    return _nchw(y)
+
+
+def upsample_nearest2x(x):
+    """Nearest x2 up-sampling of an NCHW device tensor (C a multiple of 4)."""
+    lib = _lib.load()
+    n, c, h, w = x.shape
+    xh = _nhwc(x.float())
+    y = torch.empty((n, 2 * h, 2 * w, c), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_upsample_nearest2x(xh.data_ptr(), n, h, w, c, y.data_ptr(), _lib.current_stream_ptr()),
+                   "ymk_op_upsample_nearest2x")
+    return _nchw(y)
+
+
+# ---- the DBNet++ head
+def deconv2x2(x, weight, scale=None, bias=None, act="none"):
+    """act(ConvTranspose2d(cin, cout, 2, 2)(x) * scale + bias) through the convolution path's scattering epilogue; x NCHW on the
+    device, weight [cin, cout, 2, 2] (any device)."""
+    lib = _lib.load()
+    n, cin, h, w = x.shape
+    cout = weight.shape[1]
+    assert weight.shape == (cin, cout, 2, 2)
+    xh = _nhwc(x.float())
+    wh = weight.detach().float().cpu().contiguous()
+    sh = scale.detach().float().cpu().contiguous() if scale is not None else None
+    bh = bias.detach().float().cpu().contiguous() if bias is not None else None
+    y = torch.empty((n, 2 * h, 2 * w, cout), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_deconv2x2(xh.data_ptr(), n, h, w, cin, wh.data_ptr(), cout, _lib.ptr(sh), _lib.ptr(bh), ACT[act],
+                                        y.data_ptr(), _lib.current_stream_ptr()), "ymk_op_deconv2x2")
+    return _nchw(y)
+
+
+def deconv2x2_to1_sigmoid(x, weight, bias):
+    """sigmoid(ConvTranspose2d(64, 1, 2, 2)(x) + bias): x NCHW (C = 64) on the device, weight [64, 1, 2, 2] -> [n, 1, 2h, 2w]."""
+    lib = _lib.load()
+    n, c, h, w = x.shape
+    xh = _nhwc(x.float())
+    wh = weight.detach().float().cpu().reshape(c, 4).contiguous()
+    y = torch.empty((n, 1, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_deconv2x2_to1_sigmoid(xh.data_ptr(), n, h, w, wh.data_ptr(), float(bias), y.data_ptr(),
+                                                    _lib.current_stream_ptr()), "ymk_op_deconv2x2_to1_sigmoid")
+    return y
+
+
+def dbnet_asf(ax, fuse, w1, w2, sp33, sp11, watt):
+    """ScaleChannelSpatialAttention(ax) applied per scale to fuse (ScaleFeatureSelection): ax [n, 64, h, w], fuse [n, 256, h, w]
+    NCHW on the device; w1 [cmid, 64], w2 [64, cmid], sp33 [3, 3], sp11 float, watt [4, 64] (any device) -> [n, 256, h, w]."""
+    lib = _lib.load()
+    n, c, h, w = ax.shape
+    cmid = w1.shape[0]
+    axh, fh = _nhwc(ax.float()), _nhwc(fuse.float())
+    host = [t.detach().float().cpu().contiguous() for t in (w1, w2, sp33, watt)]
+    y = torch.empty((n, h, w, 256), dtype=torch.float32, device=ax.device)
+    with torch.cuda.device(ax.device):
+        _lib.check(lib.ymk_op_dbnet_asf(axh.data_ptr(), fh.data_ptr(), n, h, w, host[0].data_ptr(), host[1].data_ptr(), cmid,
+                                        host[2].data_ptr(), float(sp11), host[3].data_ptr(), y.data_ptr(), _lib.current_stream_ptr()),
+                   "ymk_op_dbnet_asf")
+    return _nchw(y)

@@ -90,6 +90,28 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     ),
+    "ymk_op_topk_tokens": (c_int, [c_void_p, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_gather_queries": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p],
+    ),
+    "ymk_op_refine_boxes": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ymk_op_mask_rows": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int), c_int, c_void_p, c_void_p]),
+    "ymk_op_deform_sample": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_int), c_int, c_void_p, c_void_p],
+    ),
+    "ymk_op_avgpool2x2_ceil": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_upsample_nearest2x": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_deconv2x2": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    ),
+    "ymk_op_deconv2x2_to1_sigmoid": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p]),
+    "ymk_op_dbnet_asf": (
+        c_int,
+        [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
+    ),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // extern "C" surface of libymk_hip.so (declared in include/ymk.h).
 #include "../../include/ymk.h"
 #include "ymk_common.h"
+#include "ymk_det.h"
 #include "ymk_seq.h"
 
 namespace ymk {
@@ -462,6 +463,162 @@ int ymk_op_upsample_bilinear(const float* x_dev, int n, int h, int w, int c, int
   Tensor out{y_dev, n, oh, ow, c, c};
   Tensor add{const_cast<float*>(add_dev), n, oh, ow, c, c};
   upsample_bilinear((hipStream_t)stream, in, out, add_dev ? &add : nullptr);
+  YMK_API_END
+}
+
+// ---- single operators of the detection transformer and of the DBNet++ head (the launch functions the models call)
+namespace {
+// level_hw = {h0, w0, h1, w1, h2, w2} (host) -> the geometry ymk_rtdetr.cpp builds for B images
+ymk::DetGeom det_geom_arg(int b, const int* level_hw) {
+  YMK_CHECK(level_hw != nullptr && b >= 1, "det op: b >= 1 and a level_hw array");
+  const int h[3] = {level_hw[0], level_hw[2], level_hw[4]}, w[3] = {level_hw[1], level_hw[3], level_hw[5]};
+  long ntok = 0;
+  for (int l = 0; l < 3; ++l) {
+    YMK_CHECK(h[l] >= 1 && w[l] >= 1, "det op: every level needs at least one token");
+    ntok += (long)h[l] * w[l];
+  }
+  YMK_CHECK((long)b * ntok < (1L << 30), "det op: too many tokens");
+  return ymk::make_det_geom(b, h, w);
+}
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+}  // namespace
+
+int ymk_op_topk_tokens(const float* logits_dev, int b, const int* level_hw, int nc, int k, int* idx_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  const DetGeom g = det_geom_arg(b, level_hw);
+  YMK_CHECK(logits_dev && idx_dev && nc >= 1, "topk: bad argument");
+  YMK_CHECK(k >= 1 && k <= 2048 && k <= g.ntok, "topk: 1 <= k <= min(2048, tokens)");
+  hipStream_t s = (hipStream_t)stream;
+  DevicePool pool;  // the b * ntok key words
+  unsigned* keys = reinterpret_cast<unsigned*>(pool.alloc((size_t)g.B * g.ntok));
+  topk_tokens(s, logits_dev, nc, g, k, keys, idx_dev);
+  YMK_HIP(hipStreamSynchronize(s));  // pool frees the keys on return
+  YMK_API_END
+}
+
+int ymk_op_gather_queries(const float* om_dev, const float* bbox_dev, const float* anchors_dev, const int* idx_dev, int b,
+                          const int* level_hw, int k, int d, float* content_dev, float* ref_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  const DetGeom g = det_geom_arg(b, level_hw);
+  YMK_CHECK(om_dev && bbox_dev && anchors_dev && idx_dev && content_dev && ref_dev && k >= 1 && d >= 1, "gather: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int> idx((size_t)b * k);  // the kernel trusts its indices: a test entry point checks them first
+  YMK_HIP(hipMemcpyAsync(idx.data(), idx_dev, idx.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+  YMK_HIP(hipStreamSynchronize(s));
+  for (int v : idx) YMK_CHECK(v >= 0 && v < g.ntok, "gather: token index out of range");
+  gather_queries(s, om_dev, bbox_dev, anchors_dev, idx_dev, g, k, d, content_dev, ref_dev);
+  YMK_API_END
+}
+
+int ymk_op_refine_boxes(const float* delta_dev, const float* ref_dev, float* out_dev, int64_t n, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(delta_dev && ref_dev && out_dev && n >= 0, "refine: bad argument");
+  ymk::refine_boxes((hipStream_t)stream, delta_dev, ref_dev, out_dev, (size_t)n);
+  YMK_API_END
+}
+
+int ymk_op_mask_rows(const float* in_dev, const float* valid_dev, int b, const int* level_hw, int d, float* out_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  const DetGeom g = det_geom_arg(b, level_hw);
+  YMK_CHECK(in_dev && valid_dev && out_dev && d >= 4 && d % 4 == 0, "mask_rows: d must be a positive multiple of 4");
+  YMK_CHECK(aligned16(in_dev) && aligned16(out_dev), "mask_rows: rows must be 16 B aligned");
+  mask_rows((hipStream_t)stream, in_dev, valid_dev, out_dev, g, d);
+  YMK_API_END
+}
+
+int ymk_op_deform_sample(const float* offs_dev, const float* attw_dev, const float* ref_dev, const float* value_dev, int ldv, int b,
+                         const int* level_hw, int k, float* out_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  const DetGeom g = det_geom_arg(b, level_hw);
+  YMK_CHECK(offs_dev && attw_dev && ref_dev && value_dev && out_dev && k >= 1, "deform_sample: bad argument");
+  // 8 heads x 32 channels per value row, read as float4; ref rows and output rows as float4
+  YMK_CHECK(ldv >= 256 && ldv % 4 == 0, "deform_sample: ldv >= 256, a multiple of 4");
+  YMK_CHECK(aligned16(value_dev) && aligned16(ref_dev) && aligned16(out_dev), "deform_sample: value / ref / out must be 16 B aligned");
+  deform_sample((hipStream_t)stream, offs_dev, attw_dev, ref_dev, value_dev, ldv, g, k, out_dev);
+  YMK_API_END
+}
+
+int ymk_op_avgpool2x2_ceil(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && y_dev && n >= 1 && h >= 1 && w >= 1 && c >= 4 && c % 4 == 0, "avgpool: c must be a positive multiple of 4");
+  Tensor in{const_cast<float*>(x_dev), n, h, w, c, c};
+  Tensor out{y_dev, n, (h + 1) / 2, (w + 1) / 2, c, c};
+  avgpool2x2_ceil((hipStream_t)stream, in, out);
+  YMK_API_END
+}
+
+int ymk_op_upsample_nearest2x(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && y_dev && n >= 1 && h >= 1 && w >= 1 && c >= 4 && c % 4 == 0, "nearest2x: c must be a positive multiple of 4");
+  Tensor in{const_cast<float*>(x_dev), n, h, w, c, c};
+  Tensor out{y_dev, n, 2 * h, 2 * w, c, c};
+  upsample_nearest2x((hipStream_t)stream, in, out);
+  YMK_API_END
+}
+
+int ymk_op_deconv2x2(const float* x_dev, int n, int h, int w, int cin, const float* w_host, int cout, const float* scale_host,
+                     const float* bias_host, int act, float* y_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && w_host && y_dev && n >= 1 && h >= 1 && w >= 1, "deconv2x2: bad argument");
+  YMK_CHECK(cin >= 4 && cin % 4 == 0 && cout >= 4 && cout % 4 == 0, "deconv2x2: cin and cout must be positive multiples of 4");
+  DevicePool pool;
+  const ConvW cw = make_deconv2x2_panel(pool, w_host, cin, cout, scale_host, bias_host);
+  Tensor in{const_cast<float*>(x_dev), n, h, w, cin, cin};
+  Tensor out{y_dev, n, 2 * h, 2 * w, cout, cout};
+  ConvArgs a;
+  a.act = act;
+  a.epi = EPI_DECONV2X2;
+  SplitCtxOwner split_ctx;  // as ymk_op_conv2d: exact fp32 unless the process-wide option says otherwise
+  ConvSplitScope scope(-1, split_ctx.get(), 0);
+  conv2d((hipStream_t)stream, in, cw, a, out);
+  YMK_HIP(hipStreamSynchronize((hipStream_t)stream));  // pool frees the panel on return
+  YMK_API_END
+}
+
+int ymk_op_deconv2x2_to1_sigmoid(const float* x_dev, int n, int h, int w, const float* w_host, float bias, float* y_dev,
+                                 void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && w_host && y_dev && n >= 1 && h >= 1 && w >= 1, "deconv_to1: bad argument");
+  YMK_CHECK(aligned16(x_dev), "deconv_to1: input must be 16 B aligned");
+  DevicePool pool;
+  const float* wd = pool.upload(w_host, 64 * 4);
+  Tensor in{const_cast<float*>(x_dev), n, h, w, 64, 64};
+  deconv2x2_to1_sigmoid((hipStream_t)stream, in, wd, bias, y_dev);
+  YMK_HIP(hipStreamSynchronize((hipStream_t)stream));  // pool frees the weights on return
+  YMK_API_END
+}
+
+int ymk_op_dbnet_asf(const float* ax_dev, const float* fuse_dev, int n, int h, int w, const float* w1_host, const float* w2_host,
+                     int cmid, const float* sp33_host, float sp11, const float* watt_host, float* out_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(ax_dev && fuse_dev && out_dev && w1_host && w2_host && sp33_host && watt_host && n >= 1 && h >= 1 && w >= 1,
+            "asf: bad argument");
+  YMK_CHECK(cmid >= 1 && cmid <= 64, "asf: 1 <= cmid <= 64");
+  YMK_CHECK(aligned16(ax_dev) && aligned16(fuse_dev) && aligned16(out_dev), "asf: tensors must be 16 B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  DevicePool pool;
+  const float* w1 = pool.upload(w1_host, (size_t)cmid * 64);
+  const float* w2 = pool.upload(w2_host, (size_t)64 * cmid);
+  const float* sp33 = pool.upload(sp33_host, 9);
+  const float* watt = pool.upload(watt_host, 4 * 64);
+  float* gap_scr = pool.alloc((size_t)GAP_CHUNKS * n * 64);
+  float* gap = pool.alloc((size_t)n * 64);
+  float* gate = pool.alloc((size_t)n * 64);
+  float* cmean = pool.alloc((size_t)n * h * w);
+  Tensor x{const_cast<float*>(ax_dev), n, h, w, 64, 64};
+  Tensor fuse{const_cast<float*>(fuse_dev), n, h, w, 256, 256};
+  Tensor out{out_dev, n, h, w, 256, 256};
+  asf_block(s, x, w1, w2, cmid, sp33, sp11, watt, fuse, gap_scr, gap, gate, cmean, out);
+  YMK_HIP(hipStreamSynchronize(s));  // pool frees weights and scratch on return
   YMK_API_END
 }
 

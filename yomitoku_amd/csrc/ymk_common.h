@@ -318,6 +318,12 @@ void asf_channel_mean(hipStream_t s, const Tensor& x, const float* gate_nc, floa
 void asf_apply(hipStream_t s, const Tensor& x, const float* gate_nc, const float* mean_nhw,
                const float* w_sp3x3, float w_sp1x1, const float* w_att /*[4][c]*/,
                const Tensor& fuse /*4*c ch*/, const Tensor& out);
+// the whole ASF block in the order ScaleChannelSpatialAttention.forward uses: global_avgpool -> asf_channel_gate ->
+// asf_channel_mean -> asf_apply.  x: (n,h,w,64) = the block's conv output; fuse: (n,h,w,256); scratch (device): gap_scr
+// GAP_CHUNKS*n*64, gap / gate n*64, cmean n*h*w floats
+void asf_block(hipStream_t s, const Tensor& x, const float* w1 /*[cmid][64]*/, const float* w2 /*[64][cmid]*/, int cmid,
+               const float* w_sp3x3, float w_sp1x1, const float* w_att /*[4][64]*/, const Tensor& fuse, float* gap_scr,
+               float* gap, float* gate, float* cmean, const Tensor& out);
 // final ConvTranspose2d(c->1, 2, 2) + bias + sigmoid: in (n,h,w,c) -> out plane (n, 2h, 2w)
 void deconv2x2_to1_sigmoid(hipStream_t s, const Tensor& in, const float* w_c4 /*[c][4]*/, float bias,
                            float* out);
@@ -366,6 +372,9 @@ ConvW make_conv(DevicePool& pool, const WeightStore& ws, const std::string& conv
 // nn.Linear(in,out): weight [out][in] (+bias) -> 1x1 conv panel
 ConvW make_linear(DevicePool& pool, const WeightStore& ws, const std::string& prefix, bool has_bias = true);
 ConvW make_linear_raw(DevicePool& pool, const float* w_out_in, const float* bias, int out, int in);
+// ConvTranspose2d(ci, co, 2, 2) weight [ci][co][2][2] -> the 1 x 1 panel conv2d's EPI_DECONV2X2 epilogue scatters: output
+// column N = (a*2+b)*co + o; scale / bias ([co], or null) repeated for each of the four (a, b)
+ConvW make_deconv2x2_panel(DevicePool& pool, const float* w_ci_co_2_2, int ci, int co, const float* scale, const float* bias);
 // A STATIC max|x| record for the output of LayerNorm(gamma, beta) over d elements: a normalised element is at most sqrt(d - 1)
 // in magnitude, so |y| <= sqrt(d) max|gamma| + max|beta| whatever the input - a bound a few times above the real maximum,
 // which is all the power-of-two scale of the fp16-split kernels needs (ymk_conv_split.hip).  No pass, no atomics.

@@ -62,30 +62,22 @@ class DBNetModel : public Model {
     }
     bin_conv_ = make_conv(pool, ws, d + "binarize.0", d + "binarize.1");
     {
-      // ConvTranspose2d(64,64,2,2): weight [ci][co][a][b] -> 1x1 panel with N = (a*2+b)*64 + co
+      // ConvTranspose2d(64,64,2,2) + BatchNorm: a 1x1 panel with N = (a*2+b)*64 + co (make_deconv2x2_panel)
       const HostTensor& w = ws.get(d + "binarize.3.weight");
       const HostTensor& b = ws.get(d + "binarize.3.bias");
       const int ci = (int)w.dims[0], co = (int)w.dims[1];
       YMK_CHECK(w.dims[2] == 2 && w.dims[3] == 2, "binarize.3 must be a 2x2 transposed conv");
-      std::vector<float> lin((size_t)4 * co * ci);
-      for (int c = 0; c < ci; ++c)
-        for (int o = 0; o < co; ++o)
-          for (int ab = 0; ab < 4; ++ab) lin[((size_t)ab * co + o) * ci + c] = w.data[((size_t)c * co + o) * 4 + ab];
       const HostTensor& g = ws.get(d + "binarize.4.weight");
       const HostTensor& be = ws.get(d + "binarize.4.bias");
       const HostTensor& m = ws.get(d + "binarize.4.running_mean");
       const HostTensor& v = ws.get(d + "binarize.4.running_var");
-      std::vector<float> sc(4 * co), bi(4 * co);
-      for (int ab = 0; ab < 4; ++ab)
-        for (int o = 0; o < co; ++o) {
-          const float s = g.data[o] / std::sqrt(v.data[o] + 1e-5f);
-          sc[ab * co + o] = s;
-          bi[ab * co + o] = be.data[o] + (b.data[o] - m.data[o]) * s;
-        }
-      deconv1_ = make_linear_raw(pool, lin.data(), nullptr, 4 * co, ci);
-      deconv1_.scale = pool.upload(sc);
-      deconv1_.bias = pool.upload(bi);
-      pool.note(deconv1_);  // (the panel with its scale: what the split copy folds the row's power of two into)
+      std::vector<float> sc(co), bi(co);
+      for (int o = 0; o < co; ++o) {
+        const float s = g.data[o] / std::sqrt(v.data[o] + 1e-5f);
+        sc[o] = s;
+        bi[o] = be.data[o] + (b.data[o] - m.data[o]) * s;
+      }
+      deconv1_ = make_deconv2x2_panel(pool, w.data.data(), ci, co, sc.data(), bi.data());
     }
     {
       const HostTensor& w = ws.get(d + "binarize.6.weight");  // [64][1][2][2] == [c][ab]
@@ -240,12 +232,7 @@ class DBNetModel : public Model {
     float* cmean = arena.alloc_f((size_t)n * fh * fw);
     Tensor fused = arena.tensor(n, fh, fw, 256);
     fused.amax = fuse.amax;  // fuse times attention weights in (0, 1) (sigmoids): bounded by fuse's max|x|
-    if (!dry) {
-      global_avgpool(s, ax, gap_scr, gap);
-      asf_channel_gate(s, gap, asf_w1_, asf_w2_, n, asf_c_, asf_cmid_, gate);
-      asf_channel_mean(s, ax, gate, cmean);
-      asf_apply(s, ax, gate, cmean, asf_sp33_, asf_sp11_, asf_watt_, fuse, fused);
-    }
+    if (!dry) asf_block(s, ax, asf_w1_, asf_w2_, asf_cmid_, asf_sp33_, asf_sp11_, asf_watt_, fuse, gap_scr, gap, gate, cmean, fused);
     // ---- binarize head
     Tensor b0 = conv(s, fused, bin_conv_, 1, 1, 1, ACT_RELU);
     Tensor b1 = arena.tensor(n, 2 * fh, 2 * fw, 64);

@@ -13,6 +13,21 @@ struct DetGeom {
   int ntok;       // tokens per image (8400 at 640x640, 18900 at 960x960)
 };
 
+// the geometry of B images whose three levels are h[l] x w[l]
+inline DetGeom make_det_geom(int B, const int h[3], const int w[3]) {
+  DetGeom g;
+  g.B = B;
+  g.ntok = 0;
+  for (int l = 0; l < 3; ++l) {
+    g.h[l] = h[l];
+    g.w[l] = w[l];
+    g.hw[l] = g.h[l] * g.w[l];
+    g.off[l] = g.ntok;
+    g.ntok += g.hw[l];
+  }
+  return g;
+}
+
 void add_bcast(hipStream_t s, const float* a, const float* b, int rows_mod, float* out, int M, int D);
 void mask_rows(hipStream_t s, const float* in, const float* valid, float* out, const DetGeom& g, int D);
 // keys_scratch: B * ntok words of device scratch

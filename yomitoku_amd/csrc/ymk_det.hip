@@ -66,8 +66,8 @@ void mask_rows(hipStream_t s, const float* in, const float* valid, float* out, c
 
 // ---------------------------------------------------------------- top-k per image over max-class logits
 // torch.topk(enc_outputs_logits.max(-1).values, K) per image (rtdetrv2_decoder.py:752-756): the K best tokens in rank
-// order (descending value, ascending token id among equal values).  One 1024-thread block per image, any token count
-// (8400 at 640^2, 18900 at 960^2 - the cell detector), K <= 2048 (300 / 1500):
+// order (descending value, ascending token id among equal values; -0.0 equals +0.0).  One 1024-thread block per image,
+// any token count (8400 at 640^2, 18900 at 960^2 - the cell detector), K <= 2048 (300 / 1500):
 //   1. radix select on the order-preserving 32-bit image of the value (12 + 12 + 8 bits, 4096-bin LDS histograms):
 //      the exact K-th largest value T, how many tokens lie strictly above it, how many of the tokens equal to T are
 //      still needed;
@@ -78,7 +78,8 @@ __device__ __forceinline__ unsigned topk_key(const float* __restrict__ logits, i
   const float* row = logits + (size_t)token_row(g, b, k) * nc;
   float m = row[0];
   for (int c = 1; c < nc; ++c) m = fmaxf(m, row[c]);
-  const unsigned u = __float_as_uint(m);
+  // -0.0 is canonicalised to +0.0 first: torch.topk compares them equal, so a -0 / +0 tie goes by token id like any other
+  const unsigned u = __float_as_uint(m == 0.f ? 0.f : m);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // larger float <=> larger unsigned
 }
 

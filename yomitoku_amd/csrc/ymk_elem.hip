@@ -344,6 +344,16 @@ void asf_apply(hipStream_t s, const Tensor& x, const float* gate_nc, const float
   YMK_HIP(hipGetLastError());
 }
 
+void asf_block(hipStream_t s, const Tensor& x, const float* w1, const float* w2, int cmid, const float* w_sp3x3, float w_sp1x1,
+               const float* w_att, const Tensor& fuse, float* gap_scr, float* gap, float* gate, float* cmean, const Tensor& out) {
+  YMK_CHECK(x.c == 64 && fuse.n == x.n && fuse.h == x.h && fuse.w == x.w && out.n == x.n && out.h == x.h && out.w == x.w,
+            "asf: shapes");
+  global_avgpool(s, x, gap_scr, gap);
+  asf_channel_gate(s, gap, w1, w2, x.n, x.c, cmid, gate);
+  asf_channel_mean(s, x, gate, cmean);
+  asf_apply(s, x, gate, cmean, w_sp3x3, w_sp1x1, w_att, fuse, out);
+}
+
 // ---------------------------------------------------------------- final ConvTranspose2d(C->1,2,2)+bias+sigmoid
 // 16 lanes per input pixel (C=64); each input pixel emits a 2x2 output patch.
 __global__ void k_deconv_to1(const float* __restrict__ in, const float* __restrict__ w, float bias, float* __restrict__ out,

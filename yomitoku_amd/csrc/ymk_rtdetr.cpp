@@ -365,16 +365,8 @@ class RtdetrModel : public Model {
     const Tensor* outs[3] = {&F3, &N4, &N5};
 
     // ---------------- decoder input: level-major token memory
-    DetGeom g;
-    g.B = B;
-    g.ntok = 0;
-    for (int l = 0; l < 3; ++l) {
-      g.h[l] = outs[l]->h;
-      g.w[l] = outs[l]->w;
-      g.hw[l] = g.h[l] * g.w[l];
-      g.off[l] = g.ntok;
-      g.ntok += g.hw[l];
-    }
+    const int lh[3] = {outs[0]->h, outs[1]->h, outs[2]->h}, lw[3] = {outs[0]->w, outs[1]->w, outs[2]->w};
+    const DetGeom g = make_det_geom(B, lh, lw);
     const int R = B * g.ntok;
     float* mem = arena.alloc_f((size_t)R * D);
     for (int l = 0; l < 3; ++l) {

@@ -236,6 +236,25 @@ ConvW make_linear_raw(DevicePool& pool, const float* w_out_in, const float* bias
   return c;
 }
 
+ConvW make_deconv2x2_panel(DevicePool& pool, const float* w, int ci, int co, const float* scale, const float* bias) {
+  std::vector<float> lin((size_t)4 * co * ci);
+  for (int c = 0; c < ci; ++c)
+    for (int o = 0; o < co; ++o)
+      for (int ab = 0; ab < 4; ++ab) lin[((size_t)ab * co + o) * ci + c] = w[((size_t)c * co + o) * 4 + ab];
+  ConvW p = make_linear_raw(pool, lin.data(), nullptr, 4 * co, ci);
+  if (scale == nullptr && bias == nullptr) return p;
+  std::vector<float> sc(scale ? 4 * co : 0), bi(bias ? 4 * co : 0);
+  for (int ab = 0; ab < 4; ++ab)
+    for (int o = 0; o < co; ++o) {
+      if (scale) sc[ab * co + o] = scale[o];
+      if (bias) bi[ab * co + o] = bias[o];
+    }
+  if (scale) p.scale = pool.upload(sc);
+  if (bias) p.bias = pool.upload(bi);
+  pool.note(p);  // (the panel with its scale: what the split copy folds the row's power of two into)
+  return p;
+}
+
 float layernorm_output_bound(const std::vector<float>& gamma, const std::vector<float>& beta) {
   float g = 0.f, b = 0.f;
   for (float v : gamma) g = std::max(g, std::fabs(v));
