@@ -75,7 +75,19 @@ int ymk_dbnet_forward(ymk_model* m, const float* x_dev, int n, int h, int w, flo
  * number of valid rows per sample (101 when refine_iters >= 1, else the AR steps executed),
  * *ar_steps the greedy steps executed before every row held an <eos>.  The call blocks until the AR loop
  * has stopped (the host polls a mapped flag two steps behind the device - the reference's early-stop test,
- * models/parseq.py:245-250) and returns with the refinement pass still queued on the stream. */
+ * models/parseq.py:245-250) and returns with the refinement pass still queued on the stream.
+ *
+ * Non-autoregressive mode - the model parameter "decode_ar" = 0 (the reference's `decode_ar: 0`, models/parseq.py:253-262; 1, the
+ * default, is the greedy loop above; any other value is refused by ymk_model_finalize): the context is <bos> alone and all
+ * max_label_length+1 positions are asked in ONE decoder pass, followed by the refine_iters cloze passes (the first takes the
+ * arg-max of that pass over all rows).  The part of the query stream that depends on weights only - up to the cross
+ * attention's query projection - is built once by ymk_model_finalize; per call the work starts at the cross attention
+ * over each sample's own encoder memory (ymk_op_nar_cross_attention below).  The repetition stop never applies (the
+ * reference arms it inside the AR loop only).  *out_len = max_label_length+1 and *ar_steps = 0, for every group.  There is no
+ * step loop, no mapped flag, no copy back: in this mode ymk_parseq_forward[_groups] only queues work on the stream and
+ * returns without having waited on anything.  (The grouped call hands its row tables to the device through one of 64 slots
+ * of pinned memory; it waits - counted in "syncs_in_forward" - only if the copy out of the slot it is about to reuse, issued
+ * 64 grouped calls earlier, has still not run.) */
 int ymk_parseq_dims(ymk_model* m, int* num_steps, int* num_classes);
 int ymk_parseq_forward(ymk_model* m, const float* x_dev, int b, int w, float* logits_dev, int* out_len, int* ar_steps,
                        void* stream);
@@ -165,7 +177,7 @@ int ymk_prof_begin(void);
  *                        launch with K <= 512, bit 4: accumulators of ragged-Cout launches stored straight from registers;
  *                        bit 2: that direct epilogue for every plain store (A/B runs).  3 = the round-2 kernels.  Every setting
  *                        computes the same bits (tests/test_ops_gpu.py::test_conv_epilogue_variants_are_bit_identical).
- *   "dec_rows" (0)       samples per block of the fused greedy step: 0 = by row count, 1 / 2 / 4 forced (bit-identical results)
+ *   "dec_rows" (0)       samples per block of the fused greedy step: 0 = by row count, 1 / 2 / 3 / 4 forced (bit-identical results)
  *   "parseq_no_rowmax" (0)  1: the fused greedy loop writes every step's logits and arg-maxes them from memory (round-2 form);
  *                        0: the vocabulary head's epilogue reduces each 64-column tile to (max, column) and no AR logits exist
  *   "rowmax_tile" (0)    the kernel of that head where 128 x 128 tiles fill the chip: 0 = the A-stationary kernel, one column block
@@ -211,7 +223,8 @@ int ymk_debug_option(const char* key, int value);
 /* Launch counters since the process started, for tests that must know a route was really taken: "astat_launches" (the
  * A-stationary short-K kernel), "ln_fused_launches" (those of them that carried a LayerNorm in their operand load),
  * "planes_written_launches" / "planes_read_launches" (convolutions whose output / input lives in HBM as fp16 planes),
- * "mlp_fused_launches" (ViT MLP halves run as one launch), "rowmax_wide_launches" (row-max heads on anything but the 128 x 64 tile).
+ * "mlp_fused_launches" (ViT MLP halves run as one launch), "rowmax_wide_launches" (row-max heads on anything but the 128 x 64 tile),
+ * "nar_forwards" (PARSeq forwards run in the non-autoregressive mode, "decode_ar" = 0).
  * And what a forward must NOT do (round 6): a ymk_*_forward whose workspace the caller sized first (ymk_model_reserve) never
  * allocates or frees device / pinned memory, never builds a weight copy and never waits for a stream - the split weight
  * copies and the max|x| words of the precision a model runs are built by ymk_model_finalize (and by ymk_model_set_param
@@ -267,6 +280,12 @@ int ymk_op_layernorm(const float* x_dev, int rows, int d, const float* g_dev, co
 int ymk_op_attention(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int b, int heads, int lq,
                      int lk, int hd, float scale, const unsigned char* mask_qk_dev, const unsigned char* kpm_dev,
                      int use_small, void* stream);
+/* The cross attention of PARSeq's non-autoregressive pass (yomitoku_amd/csrc/ymk_nar_attn.hip): ONE query table q [lq][heads * hd]
+ * shared by all b samples; sample i attends its own keys / values - rows i * lk .. of k / v ([rows][heads * hd]), or, with the
+ * device tables koff / klen ([b] each, both or neither), rows koff[i] .. koff[i] + klen[i] - 1 (klen >= 1; lk is then unused).
+ * o [b][lq][heads * hd] = softmax(scale * q k^T) v per head, fp32 softmax, no masks.  heads <= 8, hd <= 96. */
+int ymk_op_nar_cross_attention(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int b, int heads, int lq,
+                               int lk, int hd, float scale, const int* koff_dev, const int* klen_dev, void* stream);
 int ymk_op_maxpool3x3s2(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream);
 int ymk_op_upsample_bilinear(const float* x_dev, int n, int h, int w, int c, int oh, int ow, const float* add_dev,
                              float* y_dev, void* stream);

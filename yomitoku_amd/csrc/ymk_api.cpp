@@ -25,6 +25,7 @@ bool parseq_debug_option(const std::string& key, int value);
 bool decstep_debug_option(const std::string& key, int value);
 bool conv_split_debug_option(const std::string& key, int value);
 bool conv_split_stat(const std::string& key, long long* value);
+bool parseq_stat(const std::string& key, long long* value);
 void amax_check_counters(long long* out4);
 }  // namespace ymk
 
@@ -239,7 +240,7 @@ int ymk_stat(const char* key, int64_t* value) {
   YMK_API_BEGIN
   YMK_CHECK(key != nullptr && value != nullptr, "null argument");
   long long v = 0;
-  YMK_CHECK(ymk::conv_split_stat(std::string(key), &v) || ymk::runtime_stat(std::string(key), &v), std::string("unknown counter: ") + key);
+  YMK_CHECK(ymk::conv_split_stat(std::string(key), &v) || ymk::runtime_stat(std::string(key), &v) || ymk::parseq_stat(std::string(key), &v), std::string("unknown counter: ") + key);
   *value = v;
   YMK_API_END
 }
@@ -443,6 +444,19 @@ int ymk_op_attention(const float* q_dev, const float* k_dev, const float* v_dev,
   } else
     ymk::flash_attention((hipStream_t)stream, q_dev, k_dev, v_dev, o_dev, b, heads, lq, lk, hd, D, D, D, D, (long)lq * D,
                          (long)lk * D, (long)lk * D, (long)lq * D, scale);
+  YMK_API_END
+}
+
+int ymk_op_nar_cross_attention(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int b, int heads, int lq,
+                               int lk, int hd, float scale, const int* koff_dev, const int* klen_dev, void* stream) {
+  YMK_API_BEGIN
+  const int D = heads * hd;
+  YMK_CHECK((koff_dev == nullptr) == (klen_dev == nullptr), "offset and length tables come in pairs");
+  ymk::SeqTab tab;
+  tab.koff = koff_dev;
+  tab.klen = klen_dev;
+  ymk::nar_cross_attention((hipStream_t)stream, q_dev, k_dev, v_dev, o_dev, b, heads, lq, lk, hd, D, D, D, D, (long)lk * D, (long)lk * D,
+                           (long)lq * D, scale, koff_dev ? &tab : nullptr);
   YMK_API_END
 }
 

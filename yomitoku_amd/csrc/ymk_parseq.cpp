@@ -10,8 +10,11 @@
 //     mapped word per step, two steps behind the device (the "every row has an <eos>" test,
 //     models/parseq.py:245-250); the steps queued past the stop are no-ops;
 //   - decoder widths <= 256 run a whole AR step as one kernel (ymk_decstep.hip), wider ones as GEMMs.
+// decode_ar = 0 (models/parseq.py:253-262) replaces the greedy loop by ONE decoder pass over all positions with <bos> as
+// the only context: no loop, no host flag, no stream wait - see run() and ymk_nar_attn.hip.
 #include <sched.h>
 
+#include <array>
 #include <atomic>
 
 #include <optional>
@@ -42,6 +45,12 @@ bool parseq_debug_option(const std::string& key, int value) {
   else if (key == "parseq_no_ln_fusion") g_parseq_no_ln_fusion = value;
   else if (key == "parseq_no_mlp_fusion") g_parseq_no_mlp_fusion = value;
   else if (key == "ar_publish") g_ar_publish = value;
+  else return false;
+  return true;
+}
+static std::atomic<long long> g_nar_forwards{0};  // ymk_stat("nar_forwards"): forwards run in the non-autoregressive mode
+bool parseq_stat(const std::string& key, long long* value) {
+  if (key == "nar_forwards") *value = g_nar_forwards.load();
   else return false;
   return true;
 }
@@ -82,7 +91,8 @@ class ParseqModel : public Model {
     rep_p1_ = (int)param("rep_min_run_p1", 8);
     rep_min_ = (int)param("rep_min_repeats", 3);
     YMK_CHECK((int)param("dec_depth", 1) == 1, "only decoder depth 1 is implemented (all shipped configs)");
-    YMK_CHECK((int)param("decode_ar", 1) == 1, "only decode_ar=1 is implemented (all shipped configs)");
+    decode_ar_ = (int)param("decode_ar", 1);
+    YMK_CHECK(decode_ar_ == 0 || decode_ar_ == 1, "decode_ar must be 0 (non-autoregressive) or 1 (greedy autoregressive)");
     YMK_CHECK(D_ == Dd_, "encoder and decoder widths must match (cross attention has no kdim)");
     YMK_CHECK(D_ % eh_ == 0 && Dd_ % dh_ == 0, "embed dim must divide by heads");
     C_ = ntok_ - 2;
@@ -195,8 +205,14 @@ class ParseqModel : public Model {
       void* dm = dev_malloc(m.size());
       YMK_HIP(hipMemcpy(dm, m.data(), m.size(), hipMemcpyHostToDevice));
       qmask_ = (unsigned char*)dm;
-      host_flags_ = (int*)host_malloc_pinned((size_t)nsteps_ * sizeof(int), hipHostMallocMapped);
-      YMK_HIP(hipHostGetDevicePointer((void**)&host_flags_dev_, host_flags_, 0));
+      if (decode_ar_) {
+        host_flags_ = (int*)host_malloc_pinned((size_t)nsteps_ * sizeof(int), hipHostMallocMapped);
+        YMK_HIP(hipHostGetDevicePointer((void**)&host_flags_dev_, host_flags_, 0));
+      }
+    }
+    if (!decode_ar_) {
+      make_nar_prefix(d);
+      for (hipEvent_t& e : nar_ev_) YMK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     ws.clear();
     finalized = true;
@@ -206,6 +222,8 @@ class ParseqModel : public Model {
     dev_free(qmask_);
     host_free_pinned(host_flags_);
     host_free_pinned(stage_);
+    for (hipEvent_t e : nar_ev_)
+      if (e) (void)hipEventDestroy(e);
   }
 
   int num_classes() const { return C_; }
@@ -258,15 +276,17 @@ class ParseqModel : public Model {
     arena.reset();
     run(&g, 1, nullptr, nullptr, nullptr, s);
     arena.dry_run = false;
-    const size_t need = arena.used() + (size_t)nsteps_ * max_lines * sizeof(int) + 512;
+    // (the greedy loop's per-step group counters of up to max_lines groups on top; the non-autoregressive pass has none)
+    const size_t need = arena.used() + (decode_ar_ ? (size_t)nsteps_ * max_lines * sizeof(int) : 0) + 512;
     arena.reset();
     if (need > arena.capacity()) {
       YMK_HIP(hipStreamSynchronize(s));
       arena.reserve(need);
     }
-    const size_t want = (size_t)3 * max_lines + (size_t)nsteps_ * max_lines + max_lines;
+    const size_t want = decode_ar_ ? (size_t)3 * max_lines + (size_t)nsteps_ * max_lines + max_lines : (size_t)NAR_SLOTS * 3 * max_lines;
     if (want > stage_cap_) {
       YMK_HIP(hipStreamSynchronize(s));
+      nar_ev_used_.fill(false);
       host_free_pinned(stage_);
       stage_ = nullptr;
       stage_cap_ = 0;
@@ -291,6 +311,78 @@ class ParseqModel : public Model {
     gemm(s, tmp, M, D, D, w, act, nullptr, 0, out, out_ld, nullptr, nullptr, EPI_STORE, ln_rec, out_rec);
   }
 
+  // decode_ar = 0: the query stream up to the cross attention's W_q depends on weights alone.  The context is the single
+  // row sqrt(D) emb[<bos>] (no position term, models/parseq.py:144), normed by norm_c; a softmax over one key is 1, so
+  // the self attention returns out_proj(W_v c + b_v) + bias for every position of every sample (norm_q and the
+  // self-attention W_q never matter).  Position i of the query stream is then x_i = pos_queries[i] + that row, and the
+  // cross attention asks q_i = W_q norm1(x_i) + b_q.  Both [NS][D] tables are built here, in double, once per model.
+  void make_nar_prefix(const std::string& d) {
+    const int D = Dd_, NS = nsteps_;
+    auto lnorm = [&](const std::vector<double>& x, const std::vector<float>& g, const std::vector<float>& b) {
+      double mean = 0.0, var = 0.0;
+      for (double v : x) mean += v;
+      mean /= D;
+      for (double v : x) var += (v - mean) * (v - mean);
+      const double rstd = 1.0 / std::sqrt(var / D + 1e-5);
+      std::vector<double> y(D);
+      for (int i = 0; i < D; ++i) y[i] = (x[i] - mean) * rstd * g[i] + b[i];
+      return y;
+    };
+    auto linear = [&](const std::vector<double>& x, const float* w, const float* b) {  // w: [D][D] row-major (out, in)
+      std::vector<double> y(D);
+      for (int o = 0; o < D; ++o) {
+        double a = b[o];
+        for (int k = 0; k < D; ++k) a += (double)w[(size_t)o * D + k] * x[k];
+        y[o] = a;
+      }
+      return y;
+    };
+    const std::vector<float>& em = ws.get("text_embed.embedding.weight").data;
+    const std::vector<float>& pq = ws.get("pos_queries").data;
+    const HostTensor& sw = ws.get(d + "self_attn.in_proj_weight");
+    const HostTensor& sb = ws.get(d + "self_attn.in_proj_bias");
+    const HostTensor& cw = ws.get(d + "cross_attn.in_proj_weight");
+    const HostTensor& cb = ws.get(d + "cross_attn.in_proj_bias");
+    std::vector<double> c(D);
+    for (int i = 0; i < D; ++i) c[i] = std::sqrt((double)D) * em[(size_t)bos_ * D + i];
+    c = lnorm(c, ws.get(d + "norm_c.weight").data, ws.get(d + "norm_c.bias").data);
+    const std::vector<double> v = linear(c, sw.data.data() + (size_t)2 * D * D, sb.data.data() + 2 * D);
+    const std::vector<double> a = linear(v, ws.get(d + "self_attn.out_proj.weight").data.data(), ws.get(d + "self_attn.out_proj.bias").data.data());
+    std::vector<float> xs((size_t)NS * D), qs((size_t)NS * D);
+    std::vector<double> x(D);
+    for (int i = 0; i < NS; ++i) {
+      for (int k = 0; k < D; ++k) {
+        xs[(size_t)i * D + k] = (float)((double)pq[(size_t)i * D + k] + a[k]);
+        x[k] = xs[(size_t)i * D + k];  // the cross attention's residual is the fp32 row the device holds
+      }
+      const std::vector<double> q = linear(lnorm(x, ws.get(d + "norm1.weight").data, ws.get(d + "norm1.bias").data), cw.data.data(), cb.data.data());
+      for (int k = 0; k < D; ++k) qs[(size_t)i * D + k] = (float)q[k];
+    }
+    nar_x_ = pool.upload(xs);
+    nar_q_ = pool.upload(qs);
+  }
+
+  // a slot of the pinned staging buffer for the ragged tables of a non-autoregressive forward.  Such a forward returns with
+  // its H2D copy still queued, so consecutive calls take consecutive slots; a slot is reused only when the event recorded
+  // behind its copy has completed - which it has unless NAR_SLOTS grouped forwards are queued ahead (then: one counted wait)
+  int* nar_stage_slot(size_t ints, hipStream_t s, int* slot) {
+    if (ints * NAR_SLOTS > stage_cap_) {
+      forward_sync(s);
+      nar_ev_used_.fill(false);
+      host_free_pinned(stage_);
+      stage_ = nullptr;
+      stage_cap_ = 0;
+      stage_ = (int*)host_malloc_pinned(2 * ints * NAR_SLOTS * sizeof(int), hipHostMallocDefault);
+      stage_cap_ = 2 * ints * NAR_SLOTS;
+    }
+    *slot = (int)(nar_next_++ % NAR_SLOTS);
+    if (nar_ev_used_[*slot] && hipEventQuery(nar_ev_[*slot]) != hipSuccess) {
+      forward_sync(s);
+      nar_ev_used_.fill(false);
+    }
+    return stage_ + (size_t)*slot * (stage_cap_ / NAR_SLOTS);
+  }
+
   // query-stream tail shared by the AR step and the refinement pass:
   //   q (in/out, [M][Dd]) already holds query + self-attention; adds cross attention and the FFN,
   //   then decoder.norm + head -> out rows (ld_out floats apart)
@@ -309,6 +401,13 @@ class ParseqModel : public Model {
     else
       small_attention(s, t2, memkv, memkv + D, t, B, dh_, Lq, L, hd, D, 2 * D, 2 * D, D, (long)Lq * D, (long)L * 2 * D,
                       (long)L * 2 * D, (long)Lq * D, scale, nullptr, 0, nullptr, 0, mem);
+    tail_after_attention(s, q, M, t, h, out, ld_out);
+  }
+
+  // the rest of the query stream once `t` holds the cross-attention output: out_proj + residual into q, the FFN,
+  // decoder.norm + head -> out rows
+  void tail_after_attention(hipStream_t s, float* q, int M, float* t, float* h, float* out, int ld_out) {
+    const int D = Dd_;
     gemm(s, t, M, D, D, ca_o_, ACT_NONE, q, D, q, D, nullptr, nullptr, EPI_STORE, memkv_rec_);
     ln(s, q, n2g_, n2b_, 1e-5f, t, M, D);
     unsigned* h_rec = arena.amax_next();
@@ -333,6 +432,8 @@ class ParseqModel : public Model {
       x4_max = std::max(x4_max, (size_t)groups[g].B * img_h_ * groups[g].W * 4);
     }
     const bool ragged = ng > 1;
+    const bool nar = decode_ar_ == 0;
+    const bool ctx = !nar || refine_ > 0;  // a context stream exists: greedy steps and / or refinement passes
     // ---------------- encoder
     arena.amax_begin(s, 160);  // max|x| records (ymk_common.h): two per encoder block, one per decoder-tail call, K|V
     float* x4buf = arena.alloc_f(x4_max);
@@ -344,13 +445,13 @@ class ParseqModel : public Model {
     float* mem = arena.alloc_f((size_t)M * D);
     float* memkv = arena.alloc_f((size_t)M * 2 * D);
     int* tab = (int*)arena.alloc_bytes((size_t)3 * B * sizeof(int));  // [B] first token row | [B] token rows | [B] group
-    int* gopen = (int*)arena.alloc_bytes((size_t)nsteps_ * ng * sizeof(int));  // [step][group]: rows still open
+    int* gopen = nar ? nullptr : (int*)arena.alloc_bytes((size_t)nsteps_ * ng * sizeof(int));  // [step][group]: rows still open
     // ---------------- decoder buffers
     const int MR = B * NS;
-    float* qsa = arena.alloc_f((size_t)NS * D);        // W_q(norm_q(pos_queries)) - shared by the batch
-    float* posq_t = arena.alloc_f((size_t)MR * D);     // pos_queries tiled over the batch (refinement residual)
-    float* cn = arena.alloc_f((size_t)MR * D);         // norm_c(content)
-    float* skv = arena.alloc_f((size_t)MR * 2 * D);    // self-attention K|V cache
+    float* qsa = ctx ? arena.alloc_f((size_t)NS * D) : nullptr;        // W_q(norm_q(pos_queries)) - shared by the batch
+    float* posq_t = ctx ? arena.alloc_f((size_t)MR * D) : nullptr;     // pos_queries tiled over the batch (refinement residual)
+    float* cn = ctx ? arena.alloc_f((size_t)MR * D) : nullptr;         // norm_c(content)
+    float* skv = ctx ? arena.alloc_f((size_t)MR * 2 * D) : nullptr;    // self-attention K|V cache
     float* qcur = arena.alloc_f((size_t)MR * D);
     float* t1 = arena.alloc_f((size_t)MR * D);
     float* t2 = arena.alloc_f((size_t)MR * D);
@@ -358,43 +459,53 @@ class ParseqModel : public Model {
     // greedy steps through the fused decoder kernel, with a refinement pass to follow: the AR logits are only ever arg-maxed
     // (models/parseq.py:224), so the vocabulary head reduces each 64-column tile to (max, column) in its epilogue and no
     // [B][steps][C] logit buffer exists at all (1.9 GB at 655 rows); otherwise the steps' logits are kept - they are the output
-    const bool fused = parseq_dec_step_supported(D, dh_, lin1_.cout, Lmax, NS) && !parseq_unfused();
+    // (the non-autoregressive pass has no steps: neither form of the AR logits exists, its logits go straight to the output)
+    const bool fused = !nar && parseq_dec_step_supported(D, dh_, lin1_.cout, Lmax, NS) && !parseq_unfused();
     const bool ar_rowmax = fused && refine_ > 0 && !parseq_no_rowmax();
     const int head_tiles = (C + ROWMAX_TILE_N - 1) / ROWMAX_TILE_N;
-    float* arlog = ar_rowmax ? nullptr : arena.alloc_f((size_t)MR * C);
+    float* arlog = (nar || ar_rowmax) ? nullptr : arena.alloc_f((size_t)MR * C);
     float* armax = ar_rowmax ? arena.alloc_f((size_t)B * head_tiles * 2) : nullptr;
-    int* tok = (int*)arena.alloc_bytes((size_t)MR * sizeof(int));
-    int* raw = (int*)arena.alloc_bytes((size_t)MR * sizeof(int));
-    int* tok2 = (int*)arena.alloc_bytes((size_t)MR * sizeof(int));
-    int* state = (int*)arena.alloc_bytes((size_t)B * 4 * sizeof(int));
-    int* not_done = (int*)arena.alloc_bytes((size_t)2 * NS * sizeof(int));
-    unsigned char* kpm = (unsigned char*)arena.alloc_bytes((size_t)MR);
+    int* tok = nar ? nullptr : (int*)arena.alloc_bytes((size_t)MR * sizeof(int));
+    int* raw = ctx ? (int*)arena.alloc_bytes((size_t)MR * sizeof(int)) : nullptr;
+    int* tok2 = ctx ? (int*)arena.alloc_bytes((size_t)MR * sizeof(int)) : nullptr;
+    int* state = nar ? nullptr : (int*)arena.alloc_bytes((size_t)B * 4 * sizeof(int));
+    int* not_done = nar ? nullptr : (int*)arena.alloc_bytes((size_t)2 * NS * sizeof(int));
+    unsigned char* kpm = ctx ? (unsigned char*)arena.alloc_bytes((size_t)MR) : nullptr;
     if (dry) return;
 
     SeqTab enc_tab, mem_tab;
     if (ragged) {
       // the tables travel through a pinned staging buffer owned by the model: a forward returns only after its
       // greedy loop has been observed to finish, so the previous call's copy has long left the buffer
+      // (a non-autoregressive forward observes nothing: it rotates through slots of the buffer instead, nar_stage_slot)
       const size_t want = (size_t)3 * B + (size_t)NS * ng + ng;  // tables out | per-step group counters back | group step counts out
-      if (want > stage_cap_) {
+      int slot = -1;
+      int* st = nar ? nar_stage_slot((size_t)3 * B, s, &slot) : nullptr;
+      if (!nar && want > stage_cap_) {
         host_free_pinned(stage_);
         stage_ = nullptr;
         stage_cap_ = 0;
         stage_ = (int*)host_malloc_pinned(2 * want * sizeof(int), hipHostMallocDefault);
         stage_cap_ = 2 * want;
       }
+      if (!nar) st = stage_;
       int row = 0, b = 0;
       for (int g = 0; g < ng; ++g) {
         const int L = gh_ * (groups[g].W / pw_);
         for (int i = 0; i < groups[g].B; ++i, ++b) {
-          stage_[b] = row;
-          stage_[B + b] = L;
-          stage_[2 * B + b] = g;
+          st[b] = row;
+          st[B + b] = L;
+          st[2 * B + b] = g;
           row += L;
         }
       }
-      YMK_HIP(hipMemcpyAsync(tab, stage_, (size_t)3 * B * sizeof(int), hipMemcpyHostToDevice, s));
-      YMK_HIP(hipMemsetAsync(gopen, 0, (size_t)NS * ng * sizeof(int), s));
+      YMK_HIP(hipMemcpyAsync(tab, st, (size_t)3 * B * sizeof(int), hipMemcpyHostToDevice, s));
+      if (nar) {
+        YMK_HIP(hipEventRecord(nar_ev_[slot], s));
+        nar_ev_used_[slot] = true;
+      } else {
+        YMK_HIP(hipMemsetAsync(gopen, 0, (size_t)NS * ng * sizeof(int), s));
+      }
       enc_tab.qoff = enc_tab.koff = mem_tab.koff = tab;
       enc_tab.qlen = enc_tab.klen = mem_tab.klen = tab + B;
     }
@@ -447,11 +558,55 @@ class ParseqModel : public Model {
     // ---------------- decoder: batch-invariant pieces + memory K|V
     memkv_rec_ = arena.amax_next();
     gemm(s, mem, M, D, D, ca_kv_, ACT_NONE, nullptr, 0, memkv, 2 * D, nullptr, nullptr, EPI_STORE, enc_n_rec_, memkv_rec_);
-    ln(s, posq_, nqg_, nqb_, 1e-5f, t1, NS, D);
-    gemm(s, t1, NS, D, D, sa_q_, ACT_NONE, nullptr, 0, qsa, D);
-    init_decode(s, tok, NS, state, bos_, pad_, B);  // tok[:, 0] = bos, rest pad; state = {0, 0, -1, 0}
     const int dhd = D / dh_;
     const float dscale = 1.f / std::sqrt((float)dhd);
+    if (ctx) {
+      ln(s, posq_, nqg_, nqb_, 1e-5f, t1, NS, D);
+      gemm(s, t1, NS, D, D, sa_q_, ACT_NONE, nullptr, 0, qsa, D);
+    }
+    // the refinement passes (models/parseq.py:264-299).  The context of the first one is the greedy loop's tokens (S_first
+    // positions of `raw`; per group its own step count) or - from_logits - the arg-max of the logits already in place.
+    auto refine_passes = [&](int S_first, bool from_logits) {
+      tile_rows(s, posq_, NS, D, posq_t, B);
+      int S_in = S_first;
+      const int* prev_raw = raw;
+      for (int it = 0; it < refine_; ++it) {
+        if (it > 0 || from_logits) {
+          row_argmax(s, logits, MR, C, raw);
+          S_in = NS;
+        }
+        refine_prep(s, prev_raw, NS, S_in, bos_, eos_, tok2, kpm, B, (it == 0 && ng > 1 && !from_logits) ? gid : nullptr, gopen);
+        // rows >= S_in of the context buffer are never written: whatever the workspace held there before (another forward's
+        // activations - or, after the arena grew, any bit pattern, NaNs included) would set the fp16 scale of the K|V
+        // projection below, which takes max|x| over ALL its input rows: zero them (100 MB at wave scale: ~20 us)
+        if (S_in < NS) YMK_HIP(hipMemsetAsync(cn, 0, (size_t)MR * D * sizeof(float), s));
+        ctx_embed_ln(s, tok2, NS, 0, S_in, emb_, posq_, ncg_, ncb_, 1e-5f, cn, NS, D, B);
+        // project every row of the [B][NS] context buffer; rows >= S_in are stale but never attended (Lk = S_in)
+        gemm(s, cn, MR, D, D, sa_kv_, ACT_NONE, nullptr, 0, skv, 2 * D);
+        small_attention(s, qsa, skv, skv + D, t1, B, dh_, NS, S_in, dhd, D, 2 * D, 2 * D, D, 0, (long)NS * 2 * D,
+                        (long)NS * 2 * D, (long)NS * D, dscale, qmask_, NS, kpm, NS);
+        gemm(s, t1, MR, D, D, sa_o_, ACT_NONE, posq_t, D, qcur, D);
+        stream_tail(s, qcur, MR, B, NS, memkv, L, mem_t, t1, t2, hdec, logits, C);
+      }
+    };
+    if (nar) {
+      // ---------------- non-autoregressive pass: <bos> is the whole context, all NS positions are asked at once.  The query
+      // stream up to W_q of the cross attention is the model's [NS][D] tables (make_nar_prefix); per-sample work starts at the
+      // cross attention over the sample's own memory K|V.  Queued work only: no step loop, no host flag, no copy back, no wait.
+      // rep_cut never applies (the reference sets it inside the AR loop only).
+      ++g_nar_forwards;
+      tile_rows(s, nar_x_, NS, D, qcur, B);
+      nar_cross_attention(s, nar_q_, memkv, memkv + D, t1, B, dh_, NS, L, dhd, D, 2 * D, 2 * D, D, (long)L * 2 * D, (long)L * 2 * D,
+                          (long)NS * D, dscale, mem_t);
+      tail_after_attention(s, qcur, MR, t1, hdec, logits, C);
+      if (refine_ > 0) refine_passes(NS, true);
+      for (int g = 0; g < ng; ++g) {
+        out_len[g] = NS;
+        ar_steps[g] = 0;
+      }
+      return;
+    }
+    init_decode(s, tok, NS, state, bos_, pad_, B);  // tok[:, 0] = bos, rest pad; state = {0, 0, -1, 0}
     // Early stop without stalling the queue: step i notes in not_done[i] whether any row still lacks an <eos> (0 / 1: rows
     // store, they do not count - ymk_seq.hip) and publishes it to mapped pinned host memory; the host reads the flag of step
     // i - LAG, so up to LAG speculative steps are in flight.  A speculative step's greedy kernel sees
@@ -550,27 +705,7 @@ class ParseqModel : public Model {
     }
 
     if (refine_ > 0) {
-      tile_rows(s, posq_, NS, D, posq_t, B);
-      int S_in = steps;
-      const int* prev_raw = raw;
-      for (int it = 0; it < refine_; ++it) {
-        if (it > 0) {
-          row_argmax(s, logits, MR, C, raw);
-          S_in = NS;
-        }
-        refine_prep(s, prev_raw, NS, S_in, bos_, eos_, tok2, kpm, B, (it == 0 && ng > 1) ? gid : nullptr, gopen);
-        // rows >= S_in of the context buffer are never written: whatever the workspace held there before (another forward's
-        // activations - or, after the arena grew, any bit pattern, NaNs included) would set the fp16 scale of the K|V
-        // projection below, which takes max|x| over ALL its input rows: zero them (100 MB at wave scale: ~20 us)
-        if (S_in < NS) YMK_HIP(hipMemsetAsync(cn, 0, (size_t)MR * D * sizeof(float), s));
-        ctx_embed_ln(s, tok2, NS, 0, S_in, emb_, posq_, ncg_, ncb_, 1e-5f, cn, NS, D, B);
-        // project every row of the [B][NS] context buffer; rows >= S_in are stale but never attended (Lk = S_in)
-        gemm(s, cn, MR, D, D, sa_kv_, ACT_NONE, nullptr, 0, skv, 2 * D);
-        small_attention(s, qsa, skv, skv + D, t1, B, dh_, NS, S_in, dhd, D, 2 * D, 2 * D, D, 0, (long)NS * 2 * D,
-                        (long)NS * 2 * D, (long)NS * D, dscale, qmask_, NS, kpm, NS);
-        gemm(s, t1, MR, D, D, sa_o_, ACT_NONE, posq_t, D, qcur, D);
-        stream_tail(s, qcur, MR, B, NS, memkv, L, mem_t, t1, t2, hdec, logits, C);
-      }
+      refine_passes(steps, false);
       if (rep_on_) rep_cut(s, logits, (long)NS * C, C, NS, state, eos_, B);
       for (int g = 0; g < ng; ++g) out_len[g] = NS;
     } else {
@@ -581,6 +716,12 @@ class ParseqModel : public Model {
   }
 
   int ph_ = 4, pw_ = 8, img_h_ = 32, img_w_ = 800, D_ = 192, eh_ = 6, depth_ = 12, Dd_ = 192, dh_ = 6;
+  static constexpr int NAR_SLOTS = 64;
+  int decode_ar_ = 1;
+  float *nar_x_ = nullptr, *nar_q_ = nullptr;  // decode_ar = 0: [NS][D] query stream before / queries of the cross attention
+  std::array<hipEvent_t, NAR_SLOTS> nar_ev_{};  // decode_ar = 0: behind the table copy out of staging slot i
+  std::array<bool, NAR_SLOTS> nar_ev_used_{};
+  uint64_t nar_next_ = 0;
   int ntok_ = 7121, maxlen_ = 100, refine_ = 1, rep_on_ = 1, rep_pmax_ = 8, rep_p1_ = 8, rep_min_ = 3;
   int C_ = 0, eos_ = 0, bos_ = 0, pad_ = 0, nsteps_ = 101, gh_ = 8, full_gw_ = 100;
   ConvW patch_;

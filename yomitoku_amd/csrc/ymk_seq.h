@@ -27,6 +27,12 @@ void small_attention(hipStream_t s, const float* q, const float* k, const float*
                      int hd, int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, float scale,
                      const unsigned char* mask_qk, int ld_mask, const unsigned char* kpm, int ld_kpm,
                      const SeqTab* tab = nullptr);
+// Cross attention of PARSeq's non-autoregressive pass (ymk_nar_attn.hip): ONE [Lq][heads * hd] query table shared by all B
+// samples, each attending its own keys / values (batch strides bsk / bsv, or the (koff, klen) pair of `tab`); a block reads a
+// sample's K|V rows once for all heads.  No masks, fp32 softmax.  heads <= 8, hd <= 96.
+void nar_cross_attention(hipStream_t s, const float* q, const float* k, const float* v, float* o, int B, int H, int Lq, int Lk,
+                         int hd, int ldq, int ldk, int ldv, int ldo, long bsk, long bsv, long bso, float scale,
+                         const SeqTab* tab = nullptr);
 // decode state at the start of a forward: tok[b][:] = pad, tok[b][0] = bos, state[b] = {0, 0, -1, 0}
 void init_decode(hipStream_t s, int* tok, int ld_tok, int* state, int bos_id, int pad_id, int B);
 
