@@ -49,7 +49,24 @@ void ymk_model_destroy(ymk_model* m);
  *   2 / 3   two / three bf16 planes, 3 / 6 MFMAs (2: products to 2^-15 only - evaluation)
  *   -1  follow the process-wide ymk_debug_option("conv_split") if set, else the default.
  * parseq only: "conv_split_encoder" - the same choice for the ViT blocks' linear layers alone (the decoder and the
- * vocabulary head then follow "conv_split"). */
+ * vocabulary head then follow "conv_split").
+ *
+ * "workspace_reuse" (0 | 1, default 0; any time outside a forward) - how the model lays its activations out in its workspace:
+ *   0   the bump arena: every buffer of a forward gets bytes of its own, the workspace is the SUM of a forward's buffers;
+ *   1   planned: buffers that are never alive at the same time share bytes.  The dry run that sizes the workspace (at
+ *       ymk_model_reserve, or on the host at the head of the first forward of a new shape) records every allocation and the
+ *       point where its last user has been enqueued, a deterministic greedy planner (ymk_op_plan_workspace below) turns the
+ *       record into one offset per allocation, and forwards replay the table: nothing is searched or allocated inside a
+ *       forward, and the four "in_forward" counters of ymk_stat stay where they are.  Outputs are bit-identical to mode 0.
+ *   A change drops the cached plans; the next ymk_model_reserve sizes the workspace anew (it may shrink).  An unset parameter
+ *   follows ymk_debug_option("workspace_reuse") / the environment variable YMK_WORKSPACE_REUSE (yomitoku_amd/_lib.py).
+ *   The stream rule: reuse is sound because all launches of a forward are ordered on ONE stream, the one the call was given.
+ *   Buffers touched by anything that stream does not order - the caller after the forward returns, a later ABI call, a host
+ *   flag - are never released ("Planned workspaces", has the audit per net).  As in mode 0, consecutive forwards
+ *   of one handle must be issued on one stream or be ordered by the caller.
+ *   ymk_stat: "workspace_planned_forwards"; "ws_plan_bytes_last" / "ws_bump_bytes_last" / "ws_live_bound_last" = bytes the
+ *   last plan (made or replayed) needs / the bump arena needs for the same trace / the largest sum of live bytes at one point
+ *   of the trace, which no plan can beat.  ymk_model_workspace_bytes keeps reporting the slab actually held. */
 int ymk_model_set_param(ymk_model* m, const char* key, double value);
 int ymk_model_set_tensor(ymk_model* m, const char* name, const float* host_data, int ndim, const int64_t* dims);
 int ymk_model_finalize(ymk_model* m);
@@ -59,6 +76,13 @@ int ymk_model_finalize(ymk_model* m);
  * differ in rows and width).  dbnet: n images of h x w (either orientation); rtdetr: n images of h x w; parseq: n
  * text lines over all groups of a call, each at most w pixels wide (h ignored). */
 int ymk_model_reserve(ymk_model* m, int n, int h, int w, void* stream);
+/* The planner of "workspace_reuse" = 1 on a caller-supplied trace; host only, no device.  Allocation k (call order) has
+ * sizes[k] bytes, rounded up to 256 here, and is alive from position k until release_pos[k] = the number of allocations
+ * made when it was released (> k); negative or >= n = never released.  offsets_out[k]: multiples of 256 such that two
+ * allocations alive at the same position never overlap; *peak_out = the slab the plan needs, *live_bound_out = the largest
+ * sum of (rounded) sizes alive at one position: live_bound <= peak <= sum of sizes.  Deterministic. */
+int ymk_op_plan_workspace(int64_t n, const int64_t* sizes, const int64_t* release_pos, int64_t* offsets_out, int64_t* peak_out,
+                          int64_t* live_bound_out);
 /* bytes of HBM held by the model's weights / workspace */
 int64_t ymk_model_weight_bytes(const ymk_model* m);
 int64_t ymk_model_workspace_bytes(const ymk_model* m);

@@ -24,6 +24,7 @@ SIGNATURES = {
     "ymk_model_set_tensor": (c_int, [c_void_p, c_char_p, c_void_p, c_int, POINTER(c_int64)]),
     "ymk_model_finalize": (c_int, [c_void_p]),
     "ymk_model_reserve": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ymk_op_plan_workspace": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "ymk_model_weight_bytes": (c_int64, [c_void_p]),
     "ymk_model_workspace_bytes": (c_int64, [c_void_p]),
     "ymk_dbnet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -146,6 +147,8 @@ def load():
     spec = os.environ.get("YMK_DEBUG_OPTIONS", "")
     if os.environ.get("YMK_CONV_SPLIT"):
         spec += ",conv_split=" + os.environ["YMK_CONV_SPLIT"]
+    if os.environ.get("YMK_WORKSPACE_REUSE"):  # planned workspaces for every model that does not say otherwise itself
+        spec += ",workspace_reuse=" + os.environ["YMK_WORKSPACE_REUSE"]
     for item in filter(None, (x.strip() for x in spec.split(","))):
         key, _, value = item.partition("=")
         if lib.ymk_debug_option(key.strip().encode(), int(value)) != 0:
@@ -172,6 +175,16 @@ def stat(key: str) -> int:
 def debug_option(key: str, value: int):
     """Test / measurement knob of the library (include/ymk.h: ymk_debug_option)."""
     check(load().ymk_debug_option(key.encode(), int(value)), f"ymk_debug_option({key})")
+
+
+def plan_workspace(sizes, release_pos):
+    """(offsets, peak, live_bound) of the workspace planner on a trace (include/ymk.h: ymk_op_plan_workspace; host only)."""
+    n = len(sizes)
+    arr = c_int64 * max(1, n)
+    off, peak, live = arr(), c_int64(), c_int64()
+    check(load().ymk_op_plan_workspace(n, arr(*[int(v) for v in sizes]), arr(*[int(v) for v in release_pos]), off,
+                                       ctypes.byref(peak), ctypes.byref(live)), "ymk_op_plan_workspace")
+    return [int(off[i]) for i in range(n)], int(peak.value), int(live.value)
 
 
 def amax_check_counters():

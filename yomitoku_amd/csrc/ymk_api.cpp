@@ -126,8 +126,12 @@ void ymk_model_destroy(ymk_model* m) {
 int ymk_model_set_param(ymk_model* m, const char* key, double value) {
   YMK_API_BEGIN
   YMK_CHECK(m && key, "null argument");
-  m->impl->params[key] = value;
   const std::string k(key);
+  if (k == "workspace_reuse") {
+    YMK_CHECK(value == 0.0 || value == 1.0 || value == -1.0, "workspace_reuse must be 0 or 1 (-1: follow the process-wide default)");
+    YMK_CHECK(!ymk::in_forward(), "workspace_reuse cannot change inside a forward");
+  }
+  m->impl->params[key] = value;
   if (m->impl->finalized && (k == "conv_split" || k == "conv_split_encoder")) {  // a precision switched between forwards: its copies now
     YMK_HIP(hipSetDevice(m->device));
     m->impl->prebuild_split();
@@ -231,7 +235,7 @@ int ymk_debug_option(const char* key, int value) {
   YMK_CHECK(key != nullptr, "null key");
   const std::string k(key);
   YMK_CHECK(ymk::conv_debug_option(k, value) || ymk::parseq_debug_option(k, value) || ymk::decstep_debug_option(k, value) ||
-                ymk::conv_split_debug_option(k, value),
+                ymk::conv_split_debug_option(k, value) || ymk::runtime_debug_option(k, value),
             "unknown debug option: " + k);
   YMK_API_END
 }
@@ -282,6 +286,23 @@ int ymk_prof_launch_table(double* ms, double* flop, double* bytes, double* mfma_
 }
 
 // ------------------------------------------------------------------ single operators
+int ymk_op_plan_workspace(int64_t n, const int64_t* sizes, const int64_t* release_pos, int64_t* offsets_out, int64_t* peak_out,
+                          int64_t* live_bound_out) {
+  YMK_API_BEGIN
+  YMK_CHECK(n >= 0 && (n == 0 || (sizes && offsets_out)), "plan_workspace: bad argument");
+  std::vector<size_t> sz((size_t)n), off((size_t)n);
+  for (int64_t k = 0; k < n; ++k) {
+    YMK_CHECK(sizes[k] >= 0, "plan_workspace: negative size");
+    sz[(size_t)k] = (size_t)sizes[k];
+  }
+  size_t peak = 0, live = 0;
+  ymk::plan_workspace((size_t)n, sz.data(), release_pos, off.data(), &peak, &live);
+  for (int64_t k = 0; k < n; ++k) offsets_out[k] = (int64_t)off[(size_t)k];
+  if (peak_out) *peak_out = (int64_t)peak;
+  if (live_bound_out) *live_bound_out = (int64_t)live;
+  YMK_API_END
+}
+
 int ymk_op_conv2d(const float* x_dev, int n, int h, int w, int c, const float* w_host_oihw, int cout, int cin, int kh,
                   int kw, const float* scale_host, const float* bias_host, const float* res_dev, int stride, int pad,
                   int dil, int act, int tap4, float* y_dev, void* stream) {

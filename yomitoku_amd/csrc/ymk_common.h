@@ -103,29 +103,86 @@ struct Tensor {
   }
 };
 
-// Bump allocator over one hipMalloc'd slab. reset() at the start of a forward.
+// ---------------------------------------------------------------- workspace
+// One slab per model, handed out in call order; reset() at the start of a forward.  Two modes (include/ymk.h, "workspace_reuse"):
+//   bump    (default) every allocation gets fresh bytes behind the previous one: the slab is the SUM of a forward's buffers;
+//   planned release() marks a buffer dead, the dry run that sizes the slab records per allocation (size, position of its
+//           release), plan_workspace() turns the record into one offset per allocation such that buffers alive at the same
+//           time never share bytes, and the real run REPLAYS the plan: the k-th allocation returns base + offset[k] after
+//           checking that its size is the recorded one.  No search, no map and no allocation inside a forward.
+// release(p): the owner calls it after the LAST launch that reads or writes the buffer has been enqueued.  Sound only while
+// every such launch and every later user of the bytes are ordered on one stream (the forward's); a buffer someone else still
+// reads - the caller, a later ABI call, a host flag - is simply never released.  A no-op in bump mode.
+constexpr size_t WS_ALIGN = 256;
+constexpr int64_t WS_NEVER = -1;  // release position of an allocation that lives to the end of the forward
+// The planner (host only, deterministic: the same trace gives the same plan).  Allocation k (call order) has size[k] bytes
+// (rounded up to WS_ALIGN here) and is alive from position k until release_pos[k] = the number of allocations made when it
+// was released (> k), or WS_NEVER / >= n: to the end.  Greedy best-fit in three orders (longest-lived first, largest first,
+// call order), the smallest peak wins.  offsets[k] are multiples of WS_ALIGN; *live_bound = the largest sum of sizes alive
+// at one position - what no plan can beat; live_bound <= *peak <= sum of sizes.
+void plan_workspace(size_t n, const size_t* size, const int64_t* release_pos, size_t* offsets, size_t* peak, size_t* live_bound);
+
 class Arena {
  public:
   ~Arena();
   void reserve(size_t bytes);  // grows (re-allocates) if needed; only legal when empty
-  void reset() { off_ = 0; }
+  void reset();
   float* alloc_f(size_t count);
   void* alloc_bytes(size_t bytes);
   Tensor tensor(int n, int h, int w, int c);
+  void release(const void* p);
+  void release(const Tensor& t) { release(t.p); }
   size_t used() const { return off_; }
   size_t high_water() const { return high_; }
   size_t capacity() const { return cap_; }
   bool dry_run = false;  // when true only measures (returns fake pointers)
   // max|x| records of this forward: `records` of them carved from the arena and zeroed on stream s (call once, right
-  // after reset()); amax_next() hands them out, null once they are used up (the consumer then makes its own pass)
+  // after reset()); amax_next() hands them out, null once they are used up (the consumer then makes its own pass).
+  // Never released.  s is also the stream the "workspace_poison" fills of this forward go to.
   void amax_begin(hipStream_t s, int records);
   unsigned* amax_next();
+  // ---- planned mode
+  bool planned() const { return planned_; }
+  // switches the mode; true when it changed: cached plans are dropped and the next reserve() may SHRINK the slab
+  bool set_planned(bool on);
+  bool resize_pending() const { return resize_pending_; }
+  // after a dry run (dry_run already false): the bytes the shape needs.  bump: used(); planned: plans the recorded trace,
+  // caches the plan under `key`, selects it for the replays to come and returns its peak.  bound = true (ymk_model_reserve):
+  // the plan is also kept as a BOUND - a later trace with the same calls and no larger buffer fits into the bound's offsets
+  // as they are, and takes them when a plan of its own would not fit the slab (a greedy planner is not monotone in the
+  // sizes; this makes "a forward within the reserved bound never grows the workspace" hold in planned mode too)
+  size_t plan_commit(uint64_t key, bool bound = false);
+  // planned mode: selects the cached plan of `key` if there is one (no dry run needed); always false in bump mode
+  bool plan_select(uint64_t key, size_t* need);
+  // reset() for a real run; counts the forward and publishes the plan's figures in planned mode (ymk_stat)
+  void forward_begin();
  private:
+  struct Plan {
+    std::vector<size_t> size, off;
+    std::vector<int64_t> rel;         // release position per allocation (the trace)
+    std::vector<uint32_t> rel_order;  // the r-th release() call of the forward frees allocation rel_order[r]
+    size_t peak = 0, bump = 0, live = 0;
+  };
+  void publish(const Plan& p) const;
   char* base_ = nullptr;
   size_t cap_ = 0, off_ = 0, high_ = 0;
   unsigned* amax_pool_ = nullptr;
   int amax_n_ = 0, amax_used_ = 0;
+  hipStream_t stream_ = nullptr;
+  bool planned_ = false, resize_pending_ = false;
+  std::map<uint64_t, Plan> plans_;
+  std::vector<Plan> bounds_;
+  const Plan* cur_ = nullptr;
+  size_t k_ = 0, r_ = 0;  // replay cursors: next allocation / next release
+  // the dry run's record
+  std::vector<size_t> t_size_, t_at_;  // size and fake (bump) offset per allocation
+  std::vector<int64_t> t_rel_;
+  std::vector<uint32_t> t_rel_order_;
 };
+// process-wide switches (ymk_debug_option): "workspace_reuse" = mode of models without a "workspace_reuse" parameter,
+// "workspace_poison" = fill released ranges with 0xFF bytes on the forward's stream (tests)
+bool runtime_debug_option(const std::string& key, int value);
+bool workspace_reuse_default();
 
 // device side of the records
 __device__ __forceinline__ void amax_fold(unsigned& am, float v) { am = max(am, __float_as_uint(fabsf(v))); }
@@ -388,6 +445,12 @@ class Model {
   virtual void finalize() = 0;
   // size the workspace once for the largest forward the caller will issue (see ymk_model_reserve in include/ymk.h)
   virtual void reserve(int n, int h, int w, hipStream_t s) = 0;
+  // "workspace_reuse" parameter (0 | 1), else the process-wide default: puts the arena into that mode.  Called at the head
+  // of every forward / reserve; true when the mode changed (the caller forgets its shape key)
+  bool sync_workspace_mode() {
+    const int p = (int)param("workspace_reuse", -1);
+    return arena.set_planned(p >= 0 ? p != 0 : workspace_reuse_default());
+  }
   WeightStore ws;
   std::map<std::string, double> params;
   double param(const std::string& k, double dflt) const {

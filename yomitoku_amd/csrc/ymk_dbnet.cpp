@@ -95,37 +95,42 @@ class DBNetModel : public Model {
     ForwardScope forward_scope;
     ConvSplitScope split_scope(conv_split(), split_ctx.get(), SPLIT_MODEL_DEFAULT);
     YMK_CHECK(n > 0 && h % 32 == 0 && w % 32 == 0 && h >= 32 && w >= 32, "dbnet input must be a multiple of 32");
-    const uint64_t key = ((uint64_t)n << 40) | ((uint64_t)h << 20) | (uint64_t)w;
+    const uint64_t key = shape_key(n, h, w);
+    if (sync_workspace_mode()) shape_key_ = 0;
     if (key != shape_key_) {
-      arena.dry_run = true;
-      arena.reset();
-      run(x_nchw, n, h, w, prob, s);
-      arena.dry_run = false;
-      const size_t need = arena.used();
-      arena.reset();
+      size_t need = 0;
+      if (!arena.plan_select(key, &need)) {  // (planned mode: the shape's plan may be cached - no dry run then)
+        arena.dry_run = true;
+        arena.reset();
+        run(x_nchw, n, h, w, prob, s);
+        arena.dry_run = false;
+        need = arena.plan_commit(key);
+        arena.reset();
+      }
       if (need > arena.capacity()) {
         forward_sync(s);
         arena.reserve(need);
       }
       shape_key_ = key;
     }
-    arena.reset();
+    arena.forward_begin();
     run(x_nchw, n, h, w, prob, s);
   }
 
   void reserve(int n, int h, int w, hipStream_t s) override {
     YMK_CHECK(finalized, "model not finalized");
     YMK_CHECK(n > 0 && h % 32 == 0 && w % 32 == 0 && h >= 32 && w >= 32, "dbnet reserve: sizes must be multiples of 32");
+    sync_workspace_mode();
     size_t need = 0;
     for (int turn = 0; turn < 2; ++turn) {  // either orientation of the page
       arena.dry_run = true;
       arena.reset();
       run(nullptr, n, turn ? w : h, turn ? h : w, nullptr, s);
       arena.dry_run = false;
-      need = std::max(need, arena.used());
+      need = std::max(need, arena.plan_commit(shape_key(n, turn ? w : h, turn ? h : w), /*bound=*/true));
       arena.reset();
     }
-    if (need > arena.capacity()) {
+    if (need > arena.capacity() || arena.resize_pending()) {
       YMK_HIP(hipStreamSynchronize(s));
       arena.reserve(need);
     }
@@ -133,6 +138,8 @@ class DBNetModel : public Model {
   }
 
  private:
+  static uint64_t shape_key(int n, int h, int w) { return ((uint64_t)n << 40) | ((uint64_t)h << 20) | (uint64_t)w; }
+
   // `rec`: the max|x| record the launch folds its outputs into (ymk_common.h); by default a fresh one for a fresh output
   Tensor conv(hipStream_t s, const Tensor& in, const ConvW& w, int stride, int pad, int dil, int act,
               const Tensor* res = nullptr, const Tensor* into = nullptr, unsigned* rec = nullptr, bool out_planes = false) {
@@ -168,9 +175,13 @@ class DBNetModel : public Model {
     const bool planes = conv_planes_pair_ok(x, b.c1, a1, b.c2, a2);
     Tensor t1 = conv(s, x, b.c1, 1, 0, 1, ACT_RELU, nullptr, nullptr, nullptr, planes);
     Tensor t2 = conv(s, t1, b.c2, b.stride, b.dil, b.dil, ACT_RELU);
+    arena.release(t1);  // ("workspace_reuse": a buffer dies once its last reader is enqueued; the block's input is the caller's)
     Tensor idn = x;
     if (b.has_down) idn = conv(s, x, b.down, b.stride, 0, 1, ACT_NONE);
-    return conv(s, t2, b.c3, 1, 0, 1, ACT_RELU, &idn);
+    Tensor out = conv(s, t2, b.c3, 1, 0, 1, ACT_RELU, &idn);
+    arena.release(t2);
+    if (b.has_down) arena.release(idn);
+    return out;
   }
 
   void run(const float* x_nchw, int n, int h, int w, float* prob, hipStream_t s) {
@@ -179,17 +190,24 @@ class DBNetModel : public Model {
     Tensor x4 = arena.tensor(n, h, w, 4);
     if (!dry) nchw3_to_nhwc4(s, x_nchw, n, h, w, x4);
     Tensor c1 = conv(s, x4, stem_, 2, 3, 1, ACT_RELU);
+    arena.release(x4);
     Tensor p = arena.tensor(n, (c1.h + 2 - 3) / 2 + 1, (c1.w + 2 - 3) / 2 + 1, c1.c);
     p.amax = c1.amax;  // a maximum over windows of c1: bounded by c1's own max|x|
     if (!dry) maxpool3x3s2(s, c1, p);
+    arena.release(c1);
     Tensor feat[4];
     Tensor cur = p;
     for (int L = 0; L < 4; ++L) {
-      for (const Bottleneck& b : layers_[L]) cur = bottleneck(s, cur, b);
+      for (const Bottleneck& b : layers_[L]) {
+        Tensor next = bottleneck(s, cur, b);
+        if (L == 0 || cur.p != feat[L - 1].p) arena.release(cur);  // a stage's output lives until the decoder has read it
+        cur = next;
+      }
       feat[L] = cur;
     }
     // ---- decoder (dbnet_plus.py:200-230)
     Tensor p4 = conv(s, feat[3], in_proj_[3], 1, 0, 1, ACT_NONE);
+    arena.release(feat[3]);
     Tensor p3;
     if (feat[2].h == p4.h && feat[2].w == p4.w) {
       p3 = conv(s, feat[2], in_proj_[2], 1, 0, 1, ACT_NONE, &p4);
@@ -197,13 +215,19 @@ class DBNetModel : public Model {
       Tensor up = arena.tensor(n, feat[2].h, feat[2].w, p4.c);
       if (!dry) upsample_bilinear(s, p4, up, nullptr);
       p3 = conv(s, feat[2], in_proj_[2], 1, 0, 1, ACT_NONE, &up);
+      arena.release(up);
     }
+    arena.release(feat[2]);
     Tensor up3 = arena.tensor(n, feat[1].h, feat[1].w, p3.c);
     if (!dry) upsample_bilinear(s, p3, up3, nullptr);
     Tensor p2 = conv(s, feat[1], in_proj_[1], 1, 0, 1, ACT_NONE, &up3);
+    arena.release(up3);
+    arena.release(feat[1]);
     Tensor up2 = arena.tensor(n, feat[0].h, feat[0].w, p2.c);
     if (!dry) upsample_bilinear(s, p2, up2, nullptr);
     Tensor p1 = conv(s, feat[0], in_proj_[0], 1, 0, 1, ACT_NONE, &up2);
+    arena.release(up2);
+    arena.release(feat[0]);
 
     const int fh = p1.h, fw = p1.w;
     Tensor fuse = arena.tensor(n, fh, fw, 256);
@@ -214,6 +238,9 @@ class DBNetModel : public Model {
       Tensor o4 = conv(s, p4, out_proj_[3], 1, 1, 1, ACT_NONE, nullptr, nullptr, fuse.amax);
       Tensor o3 = conv(s, p3, out_proj_[2], 1, 1, 1, ACT_NONE, nullptr, nullptr, fuse.amax);
       Tensor o2 = conv(s, p2, out_proj_[1], 1, 1, 1, ACT_NONE, nullptr, nullptr, fuse.amax);
+      arena.release(p4);
+      arena.release(p3);
+      arena.release(p2);
       Tensor s0 = fuse.slice_c(0, 64), s1 = fuse.slice_c(64, 64), s2 = fuse.slice_c(128, 64), s3 = fuse.slice_c(192, 64);
       if (!dry) {
         // nn.Upsample(scale_factor=4 / 4 / 2): output = floor(in * scale)
@@ -222,7 +249,11 @@ class DBNetModel : public Model {
         upsample_bilinear(s, o3, s1, nullptr);
         upsample_bilinear(s, o2, s2, nullptr);
       }
+      arena.release(o4);
+      arena.release(o3);
+      arena.release(o2);
       conv(s, p1, out_proj_[0], 1, 1, 1, ACT_NONE, nullptr, &s3);
+      arena.release(p1);
     }
     // ---- adaptive scale fusion
     Tensor ax = conv(s, fuse, asf_conv_, 1, 1, 1, ACT_NONE);
@@ -233,8 +264,15 @@ class DBNetModel : public Model {
     Tensor fused = arena.tensor(n, fh, fw, 256);
     fused.amax = fuse.amax;  // fuse times attention weights in (0, 1) (sigmoids): bounded by fuse's max|x|
     if (!dry) asf_block(s, ax, asf_w1_, asf_w2_, asf_cmid_, asf_sp33_, asf_sp11_, asf_watt_, fuse, gap_scr, gap, gate, cmean, fused);
+    arena.release(fuse);
+    arena.release(ax);
+    arena.release(gap_scr);
+    arena.release(gap);
+    arena.release(gate);
+    arena.release(cmean);
     // ---- binarize head
     Tensor b0 = conv(s, fused, bin_conv_, 1, 1, 1, ACT_RELU);
+    arena.release(fused);
     Tensor b1 = arena.tensor(n, 2 * fh, 2 * fw, 64);
     if (!dry) {
       ConvArgs a;

@@ -240,26 +240,28 @@ class ParseqModel : public Model {
     ForwardScope forward_scope;
     ConvSplitScope split_scope(conv_split(), split_ctx.get(), SPLIT_MODEL_DEFAULT);
     YMK_CHECK(ng > 0, "parseq: no mini-batch");
-    uint64_t key = 1469598103934665603ull;
-    for (int g = 0; g < ng; ++g) {
+    for (int g = 0; g < ng; ++g)
       YMK_CHECK(groups[g].x != nullptr && groups[g].B > 0 && groups[g].W >= pw_ && groups[g].W % pw_ == 0 && groups[g].W <= img_w_,
                 "parseq input width must be a multiple of the patch width, <= img_w");
-      key = (key ^ (((uint64_t)groups[g].B << 32) | (uint64_t)groups[g].W)) * 1099511628211ull;
-    }
+    const uint64_t key = shape_key(groups, ng);
+    if (sync_workspace_mode()) shape_key_ = 0;
     if (key != shape_key_) {
-      arena.dry_run = true;
-      arena.reset();
-      run(groups, ng, logits, out_len, ar_steps, s);
-      arena.dry_run = false;
-      const size_t need = arena.used();
-      arena.reset();
+      size_t need = 0;
+      if (!arena.plan_select(key, &need)) {  // (planned mode: the shape's plan may be cached - no dry run then)
+        arena.dry_run = true;
+        arena.reset();
+        run(groups, ng, logits, out_len, ar_steps, s);
+        arena.dry_run = false;
+        need = arena.plan_commit(key);
+        arena.reset();
+      }
       if (need > arena.capacity()) {
         forward_sync(s);
         arena.reserve(need + need / 4);  // ragged workloads change shape every call: leave head room, grow rarely
       }
       shape_key_ = key;
     }
-    arena.reset();
+    arena.forward_begin();
     run(groups, ng, logits, out_len, ar_steps, s);
   }
 
@@ -272,14 +274,19 @@ class ParseqModel : public Model {
     max_w -= max_w % pw_;
     // one group holding every line: the largest input staging buffer; the per-group tables of up to max_lines groups on top
     const PGroup g{reinterpret_cast<const float*>(uintptr_t(4096)), max_lines, max_w};
+    sync_workspace_mode();
     arena.dry_run = true;
     arena.reset();
-    run(&g, 1, nullptr, nullptr, nullptr, s);
+    // (the greedy loop's per-step group counters of up to max_lines groups on top; the non-autoregressive pass has none.
+    // A planned workspace sizes that buffer for max_lines groups inside the trace instead: every buffer of a forward within
+    // the bound is then no larger than the bound's, which is what lets it fall back on the bound's plan - Arena::plan_commit)
+    run(&g, 1, nullptr, nullptr, nullptr, s, arena.planned() ? max_lines : 0);
     arena.dry_run = false;
-    // (the greedy loop's per-step group counters of up to max_lines groups on top; the non-autoregressive pass has none)
-    const size_t need = arena.used() + (decode_ar_ ? (size_t)nsteps_ * max_lines * sizeof(int) : 0) + 512;
+    // (cached under a key no forward asks for: the bound's trace is not the trace of the one-group forward of that shape)
+    const size_t need = arena.plan_commit(~shape_key(&g, 1), /*bound=*/true) +
+                        ((decode_ar_ && !arena.planned()) ? (size_t)nsteps_ * max_lines * sizeof(int) : 0) + 512;
     arena.reset();
-    if (need > arena.capacity()) {
+    if (need > arena.capacity() || arena.resize_pending()) {
       YMK_HIP(hipStreamSynchronize(s));
       arena.reserve(need);
     }
@@ -297,6 +304,12 @@ class ParseqModel : public Model {
   }
 
  private:
+  static uint64_t shape_key(const PGroup* groups, int ng) {
+    uint64_t key = 1469598103934665603ull;
+    for (int g = 0; g < ng; ++g) key = (key ^ (((uint64_t)groups[g].B << 32) | (uint64_t)groups[g].W)) * 1099511628211ull;
+    return key;
+  }
+
   void ln(hipStream_t s, const float* x, const float* g, const float* b, float eps, float* y, int M, int D) {
     layernorm(s, x, D, 0, g, b, eps, y, D, M, D);
   }
@@ -417,7 +430,8 @@ class ParseqModel : public Model {
     gemm(s, t, M, D, D, head_, ACT_NONE, nullptr, 0, out, ld_out, nullptr, nullptr, EPI_STORE, dn_rec_);
   }
 
-  void run(const PGroup* groups, int ng, float* logits, int* out_len, int* ar_steps, hipStream_t s) {
+  // gopen_groups: size the per-step group counters for at least that many groups (reserve() in planned mode)
+  void run(const PGroup* groups, int ng, float* logits, int* out_len, int* ar_steps, hipStream_t s, int gopen_groups = 0) {
     const bool dry = arena.dry_run;
     const int D = D_, hd = D / eh_;
     const int NS = nsteps_, C = C_;
@@ -445,33 +459,60 @@ class ParseqModel : public Model {
     float* mem = arena.alloc_f((size_t)M * D);
     float* memkv = arena.alloc_f((size_t)M * 2 * D);
     int* tab = (int*)arena.alloc_bytes((size_t)3 * B * sizeof(int));  // [B] first token row | [B] token rows | [B] group
-    int* gopen = nar ? nullptr : (int*)arena.alloc_bytes((size_t)nsteps_ * ng * sizeof(int));  // [step][group]: rows still open
-    // ---------------- decoder buffers
+    int* gopen = nar ? nullptr : (int*)arena.alloc_bytes((size_t)nsteps_ * std::max(ng, gopen_groups) * sizeof(int));  // [step][group]: rows still open
+    // ---------------- decoder buffers.  The bump arena takes them here, as it always has.  A planned workspace
+    // ("workspace_reuse") takes them once the encoder's buffers have been released, so that they share those bytes: the plan
+    // only needs the same calls in the same order in the dry run and in the real one, which alloc_decoder() gives.
     const int MR = B * NS;
-    float* qsa = ctx ? arena.alloc_f((size_t)NS * D) : nullptr;        // W_q(norm_q(pos_queries)) - shared by the batch
-    float* posq_t = ctx ? arena.alloc_f((size_t)MR * D) : nullptr;     // pos_queries tiled over the batch (refinement residual)
-    float* cn = ctx ? arena.alloc_f((size_t)MR * D) : nullptr;         // norm_c(content)
-    float* skv = ctx ? arena.alloc_f((size_t)MR * 2 * D) : nullptr;    // self-attention K|V cache
-    float* qcur = arena.alloc_f((size_t)MR * D);
-    float* t1 = arena.alloc_f((size_t)MR * D);
-    float* t2 = arena.alloc_f((size_t)MR * D);
-    float* hdec = arena.alloc_f((size_t)MR * lin1_.cout);
-    // greedy steps through the fused decoder kernel, with a refinement pass to follow: the AR logits are only ever arg-maxed
-    // (models/parseq.py:224), so the vocabulary head reduces each 64-column tile to (max, column) in its epilogue and no
-    // [B][steps][C] logit buffer exists at all (1.9 GB at 655 rows); otherwise the steps' logits are kept - they are the output
-    // (the non-autoregressive pass has no steps: neither form of the AR logits exists, its logits go straight to the output)
     const bool fused = !nar && parseq_dec_step_supported(D, dh_, lin1_.cout, Lmax, NS) && !parseq_unfused();
     const bool ar_rowmax = fused && refine_ > 0 && !parseq_no_rowmax();
     const int head_tiles = (C + ROWMAX_TILE_N - 1) / ROWMAX_TILE_N;
-    float* arlog = (nar || ar_rowmax) ? nullptr : arena.alloc_f((size_t)MR * C);
-    float* armax = ar_rowmax ? arena.alloc_f((size_t)B * head_tiles * 2) : nullptr;
-    int* tok = nar ? nullptr : (int*)arena.alloc_bytes((size_t)MR * sizeof(int));
-    int* raw = ctx ? (int*)arena.alloc_bytes((size_t)MR * sizeof(int)) : nullptr;
-    int* tok2 = ctx ? (int*)arena.alloc_bytes((size_t)MR * sizeof(int)) : nullptr;
-    int* state = nar ? nullptr : (int*)arena.alloc_bytes((size_t)B * 4 * sizeof(int));
-    int* not_done = nar ? nullptr : (int*)arena.alloc_bytes((size_t)2 * NS * sizeof(int));
-    unsigned char* kpm = ctx ? (unsigned char*)arena.alloc_bytes((size_t)MR) : nullptr;
-    if (dry) return;
+    float *qsa = nullptr, *posq_t = nullptr, *cn = nullptr, *skv = nullptr, *qcur = nullptr, *t1 = nullptr, *t2 = nullptr, *hdec = nullptr;
+    float *arlog = nullptr, *armax = nullptr;
+    int *tok = nullptr, *raw = nullptr, *tok2 = nullptr, *state = nullptr, *not_done = nullptr;
+    unsigned char* kpm = nullptr;
+    auto alloc_decoder = [&]() {
+      qsa = ctx ? arena.alloc_f((size_t)NS * D) : nullptr;        // W_q(norm_q(pos_queries)) - shared by the batch
+      posq_t = ctx ? arena.alloc_f((size_t)MR * D) : nullptr;     // pos_queries tiled over the batch (refinement residual)
+      cn = ctx ? arena.alloc_f((size_t)MR * D) : nullptr;         // norm_c(content)
+      skv = ctx ? arena.alloc_f((size_t)MR * 2 * D) : nullptr;    // self-attention K|V cache
+      qcur = arena.alloc_f((size_t)MR * D);
+      t1 = arena.alloc_f((size_t)MR * D);
+      t2 = arena.alloc_f((size_t)MR * D);
+      hdec = arena.alloc_f((size_t)MR * lin1_.cout);
+      // greedy steps through the fused decoder kernel, with a refinement pass to follow: the AR logits are only ever arg-maxed
+      // (models/parseq.py:224), so the vocabulary head reduces each 64-column tile to (max, column) in its epilogue and no
+      // [B][steps][C] logit buffer exists at all (1.9 GB at 655 rows); otherwise the steps' logits are kept - they are the output
+      // (the non-autoregressive pass has no steps: neither form of the AR logits exists, its logits go straight to the output)
+      arlog = (nar || ar_rowmax) ? nullptr : arena.alloc_f((size_t)MR * C);
+      armax = ar_rowmax ? arena.alloc_f((size_t)B * head_tiles * 2) : nullptr;
+      tok = nar ? nullptr : (int*)arena.alloc_bytes((size_t)MR * sizeof(int));
+      raw = ctx ? (int*)arena.alloc_bytes((size_t)MR * sizeof(int)) : nullptr;
+      tok2 = ctx ? (int*)arena.alloc_bytes((size_t)MR * sizeof(int)) : nullptr;
+      state = nar ? nullptr : (int*)arena.alloc_bytes((size_t)B * 4 * sizeof(int));
+      not_done = nar ? nullptr : (int*)arena.alloc_bytes((size_t)2 * NS * sizeof(int));
+      kpm = ctx ? (unsigned char*)arena.alloc_bytes((size_t)MR) : nullptr;
+    };
+    // the encoder's buffers die with the launches named here - all of them on stream s, like everything that follows
+    auto release_patchify = [&]() { arena.release(x4buf); };
+    auto release_encoder = [&]() {  // after the final LayerNorm has read xs
+      arena.release(xs);
+      arena.release(y);
+      arena.release(qkv);
+      arena.release(att);
+      arena.release(hbuf);
+    };
+    const bool late = arena.planned();
+    if (!late) alloc_decoder();
+    if (dry) {
+      if (late) {  // the real run's calls, in its order
+        release_patchify();
+        release_encoder();
+        alloc_decoder();
+        arena.release(mem);
+      }
+      return;
+    }
 
     SeqTab enc_tab, mem_tab;
     if (ragged) {
@@ -530,6 +571,7 @@ class ParseqModel : public Model {
         row += (size_t)Bg * gh_ * gw;
       }
     }
+    if (late) release_patchify();
     const float scale = 1.f / std::sqrt((float)hd);
     // "conv_split_encoder" (>= 0): operand precision of the ViT blocks' linear layers alone - the memory K|V projection, the
     // decoder and the vocabulary head then follow "conv_split" (the logits come straight out of the head GEMM, so its
@@ -554,10 +596,15 @@ class ParseqModel : public Model {
     }
     ln(s, xs, enc_ng_, enc_nb_, 1e-6f, mem, M, D);
     enc_scope.reset();
+    if (late) {
+      release_encoder();
+      alloc_decoder();
+    }
 
     // ---------------- decoder: batch-invariant pieces + memory K|V
     memkv_rec_ = arena.amax_next();
     gemm(s, mem, M, D, D, ca_kv_, ACT_NONE, nullptr, 0, memkv, 2 * D, nullptr, nullptr, EPI_STORE, enc_n_rec_, memkv_rec_);
+    if (late) arena.release(mem);  // the encoder memory has one reader, its K|V projection
     const int dhd = D / dh_;
     const float dscale = 1.f / std::sqrt((float)dhd);
     if (ctx) {

@@ -194,34 +194,39 @@ class RtdetrModel : public Model {
     const int tok = (H / 8) * (W / 8) + (H / 16) * (W / 16) + (H / 32) * (W / 32);
     YMK_CHECK(tok == ntok_, "input size does not match the checkpoint's anchors (eval_spatial_size)");
     YMK_CHECK((H / 32) * (W / 32) == aifi_pos_rows_, "AIFI position table does not match the input size");
-    const uint64_t key = ((uint64_t)B << 40) | ((uint64_t)H << 20) | (uint64_t)W;
+    const uint64_t key = shape_key(B, H, W);
+    if (sync_workspace_mode()) shape_key_ = 0;
     if (key != shape_key_) {
-      arena.dry_run = true;
-      arena.reset();
-      run(x, B, H, W, logits, boxes, s);
-      arena.dry_run = false;
-      const size_t need = arena.used();
-      arena.reset();
+      size_t need = 0;
+      if (!arena.plan_select(key, &need)) {  // (planned mode: the shape's plan may be cached - no dry run then)
+        arena.dry_run = true;
+        arena.reset();
+        run(x, B, H, W, logits, boxes, s);
+        arena.dry_run = false;
+        need = arena.plan_commit(key);
+        arena.reset();
+      }
       if (need > arena.capacity()) {
         forward_sync(s);
         arena.reserve(need);
       }
       shape_key_ = key;
     }
-    arena.reset();
+    arena.forward_begin();
     run(x, B, H, W, logits, boxes, s);
   }
 
   void reserve(int n, int h, int w, hipStream_t s) override {
     YMK_CHECK(finalized, "model not finalized");
     YMK_CHECK(n > 0 && h % 32 == 0 && w % 32 == 0, "rtdetr reserve: sizes must be multiples of 32");
+    sync_workspace_mode();
     arena.dry_run = true;
     arena.reset();
     run(nullptr, n, h, w, nullptr, nullptr, s);
     arena.dry_run = false;
-    const size_t need = arena.used();
+    const size_t need = arena.plan_commit(shape_key(n, h, w), /*bound=*/true);
     arena.reset();
-    if (need > arena.capacity()) {
+    if (need > arena.capacity() || arena.resize_pending()) {
       YMK_HIP(hipStreamSynchronize(s));
       arena.reserve(need);
     }
@@ -229,6 +234,7 @@ class RtdetrModel : public Model {
   }
 
  private:
+  static uint64_t shape_key(int n, int h, int w) { return ((uint64_t)n << 40) | ((uint64_t)h << 20) | (uint64_t)w; }
   bool dry() const { return arena.dry_run; }
 
   Tensor conv(hipStream_t s, const Tensor& in, const ConvW& w, int stride, int pad, int act, const Tensor* res = nullptr,
@@ -251,9 +257,16 @@ class RtdetrModel : public Model {
   }
 
   Tensor csp_fwd(hipStream_t s, const Tensor& x, const Csp& c) {
+    // ("workspace_reuse": arena.release() once the last reader of a buffer is enqueued; the input x is the caller's)
     Tensor x1 = conv(s, x, c.conv1, 1, 0, ACT_SILU);
-    for (int j = 0; j < 3; ++j) x1 = conv(s, x1, c.rep[j], 1, 1, ACT_SILU);
-    return conv(s, x, c.conv2, 1, 0, ACT_SILU, &x1, nullptr, /*res_post=*/true);
+    for (int j = 0; j < 3; ++j) {
+      Tensor next = conv(s, x1, c.rep[j], 1, 1, ACT_SILU);
+      arena.release(x1);
+      x1 = next;
+    }
+    Tensor out = conv(s, x, c.conv2, 1, 0, ACT_SILU, &x1, nullptr, /*res_post=*/true);
+    arena.release(x1);
+    return out;
   }
 
   float* lin(hipStream_t s, const float* in, int M, const ConvW& w, int act, const float* res = nullptr, float* out = nullptr) {
@@ -265,7 +278,16 @@ class RtdetrModel : public Model {
   float* mlp3_fwd(hipStream_t s, const float* in, int M, const Mlp3& m) {
     float* a = lin(s, in, M, m.l0, ACT_RELU);
     float* b = lin(s, a, M, m.l1, ACT_RELU);
-    return lin(s, b, M, m.l2, ACT_NONE);
+    arena.release(a);
+    float* c = lin(s, b, M, m.l2, ACT_NONE);
+    arena.release(b);
+    return c;
+  }
+  // LayerNorm of a temporary that dies with it
+  float* ln_take(hipStream_t s, float* in, int M, const float* g, const float* b) {
+    float* out = ln(s, in, M, g, b);
+    arena.release(in);
+    return out;
   }
   float* ln(hipStream_t s, const float* in, int M, const float* g, const float* b) {
     float* out = arena.alloc_f((size_t)M * 256);
@@ -280,11 +302,16 @@ class RtdetrModel : public Model {
     Tensor x4 = arena.tensor(B, H, W, 4);
     if (!dry()) nchw3_to_nhwc4(s, x, B, H, W, x4);
     Tensor c = conv(s, x4, stem_[0], 2, 1, ACT_RELU);
-    c = conv(s, c, stem_[1], 1, 1, ACT_RELU);
-    c = conv(s, c, stem_[2], 1, 1, ACT_RELU);
+    arena.release(x4);
+    for (int i = 1; i < 3; ++i) {
+      Tensor next = conv(s, c, stem_[i], 1, 1, ACT_RELU);
+      arena.release(c);
+      c = next;
+    }
     Tensor p = arena.tensor(B, (c.h - 1) / 2 + 1, (c.w - 1) / 2 + 1, c.c);
     p.amax = c.amax;  // window maxima of c: bounded by c's max|x|
     if (!dry()) maxpool3x3s2(s, c, p);
+    arena.release(c);
     Tensor feat[4];
     Tensor cur = p;
     for (int st = 0; st < 4; ++st) {
@@ -297,6 +324,7 @@ class RtdetrModel : public Model {
         const bool planes = conv_planes_pair_ok(cur, k.a, pa, k.b, pb);
         Tensor t1 = conv(s, cur, k.a, 1, 0, ACT_RELU, nullptr, nullptr, false, planes);
         Tensor t2 = conv(s, t1, k.b, k.stride, 1, ACT_RELU);
+        arena.release(t1);
         Tensor sh = cur;
         if (k.has_short) {
           Tensor src = cur;
@@ -306,8 +334,14 @@ class RtdetrModel : public Model {
             if (!dry()) avgpool2x2_ceil(s, cur, src);
           }
           sh = conv(s, src, k.shortc, 1, 0, ACT_NONE);
+          if (k.pool) arena.release(src);
         }
-        cur = conv(s, t2, k.c, 1, 0, ACT_RELU, &sh);
+        Tensor next = conv(s, t2, k.c, 1, 0, ACT_RELU, &sh);
+        arena.release(t2);
+        if (k.has_short) arena.release(sh);
+        // the block's input dies here unless it is a stage output the encoder reads (C3, C4; C5 is the last `cur`)
+        if (!(st >= 2 && cur.p == feat[st - 1].p)) arena.release(cur);
+        cur = next;
       }
       feat[st] = cur;
     }
@@ -315,21 +349,29 @@ class RtdetrModel : public Model {
 
     // ---------------- HybridEncoder
     Tensor P5 = conv(s, C5, enc_in_[2], 1, 0, ACT_NONE);
+    arena.release(C5);
     const int T = P5.h * P5.w, M5 = B * T;
     {  // AIFI: post-LN encoder layer on the coarsest level, q = k = src + pos, v = src
       float* sp = arena.alloc_f((size_t)M5 * D);
       if (!dry()) add_bcast(s, P5.p, aifi_pos_, T, sp, M5, D);
       float* qk = lin(s, sp, M5, aifi_qk_, ACT_NONE);
+      arena.release(sp);
       float* v = lin(s, P5.p, M5, aifi_v_, ACT_NONE);
       float* att = arena.alloc_f((size_t)M5 * D);
       if (!dry())
         flash_attention(s, qk, qk + D, v, att, B, 8, T, T, 32, 2 * D, 2 * D, D, D, (long)T * 2 * D, (long)T * 2 * D,
                         (long)T * D, (long)T * D, 1.f / std::sqrt(32.f));
+      arena.release(qk);
+      arena.release(v);
       float* t = lin(s, att, M5, aifi_o_, ACT_NONE, P5.p);
-      float* s1 = ln(s, t, M5, aifi_n1g_, aifi_n1b_);
+      arena.release(att);
+      float* s1 = ln_take(s, t, M5, aifi_n1g_, aifi_n1b_);
       float* h = lin(s, s1, M5, aifi_l1_, ACT_GELU);
       float* t2 = lin(s, h, M5, aifi_l2_, ACT_NONE, s1);
+      arena.release(h);
+      arena.release(s1);
       if (!dry()) layernorm(s, t2, D, 0, aifi_n2g_, aifi_n2b_, 1e-5f, P5.p, D, M5, D);  // back into the feature map
+      arena.release(t2);
       P5.amax = nullptr;  // rewritten in place: the convolution's record no longer describes it
     }
     Tensor catA = arena.tensor(B, C4.h, C4.w, 2 * D);     // [up(L5) | P4]
@@ -345,23 +387,31 @@ class RtdetrModel : public Model {
     Tensor sA0 = catA.slice_c(0, D), sA1 = catA.slice_c(D, D), sB0 = catB.slice_c(0, D), sB1 = catB.slice_c(D, D);
     Tensor sP00 = catP0.slice_c(0, D), sP01 = catP0.slice_c(D, D), sP10 = catP1.slice_c(0, D), sP11 = catP1.slice_c(D, D);
     conv(s, C4, enc_in_[1], 1, 0, ACT_NONE, nullptr, &sA1);
+    arena.release(C4);
     conv(s, C3, enc_in_[0], 1, 0, ACT_NONE, nullptr, &sB1);
+    arena.release(C3);
     conv(s, P5, lateral_[0], 1, 0, ACT_SILU, nullptr, &sP11);  // L5
+    arena.release(P5);
     if (!dry()) {
       upsample_nearest2x(s, sP11, sA0);
       amax_merge(s, catA.amax, catP1.amax);  // (catP1's record holds L5 alone at this point)
     }
     Tensor F4 = csp_fwd(s, catA, fpn_[0]);
+    arena.release(catA);
     conv(s, F4, lateral_[1], 1, 0, ACT_SILU, nullptr, &sP01);  // L4
+    arena.release(F4);
     if (!dry()) {
       upsample_nearest2x(s, sP01, sB0);
       amax_merge(s, catB.amax, catP0.amax);
     }
     Tensor F3 = csp_fwd(s, catB, fpn_[1]);
+    arena.release(catB);
     conv(s, F3, down_[0], 2, 1, ACT_SILU, nullptr, &sP00);
     Tensor N4 = csp_fwd(s, catP0, pan_[0]);
+    arena.release(catP0);
     conv(s, N4, down_[1], 2, 1, ACT_SILU, nullptr, &sP10);
     Tensor N5 = csp_fwd(s, catP1, pan_[1]);
+    arena.release(catP1);
     const Tensor* outs[3] = {&F3, &N4, &N5};
 
     // ---------------- decoder input: level-major token memory
@@ -372,10 +422,13 @@ class RtdetrModel : public Model {
     for (int l = 0; l < 3; ++l) {
       Tensor dst{mem + (size_t)B * g.off[l] * D, B, g.h[l], g.w[l], D, D};
       conv(s, *outs[l], dec_in_[l], 1, 0, ACT_NONE, nullptr, &dst);
+      arena.release(*outs[l]);
     }
     float* mm = arena.alloc_f((size_t)R * D);
     if (!dry()) mask_rows(s, mem, valid_, mm, g, D);
-    float* om = ln(s, lin(s, mm, R, enc_proj_, ACT_NONE), R, eng_, enb_);
+    float* ep = lin(s, mm, R, enc_proj_, ACT_NONE);
+    arena.release(mm);
+    float* om = ln_take(s, ep, R, eng_, enb_);
     float* elog = lin(s, om, R, enc_score_, ACT_NONE);
     float* ebox = mlp3_fwd(s, om, R, enc_bbox_);
     int* idx = (int*)arena.alloc_bytes((size_t)B * nq_ * sizeof(int));
@@ -387,36 +440,65 @@ class RtdetrModel : public Model {
       topk_tokens(s, elog, nc_, g, nq_, topk_keys, idx);
       gather_queries(s, om, ebox, anchors_, idx, g, nq_, D, tgt, ref);
     }
+    arena.release(om);
+    arena.release(elog);
+    arena.release(ebox);
+    arena.release(idx);
+    arena.release(topk_keys);
     float* vall = lin(s, mem, R, value_all_, ACT_NONE);  // every layer's value projection at once
+    arena.release(mem);
     const int ldv = nl_ * D;
 
     for (int i = 0; i < nl_; ++i) {
       const DecLayer& L = layers_[i];
-      float* qpe = lin(s, lin(s, ref, MQ, qph0_, ACT_RELU), MQ, qph1_, ACT_NONE);
+      float* qp0 = lin(s, ref, MQ, qph0_, ACT_RELU);
+      float* qpe = lin(s, qp0, MQ, qph1_, ACT_NONE);
+      arena.release(qp0);
       float* q = arena.alloc_f((size_t)MQ * D);
       if (!dry()) add_bcast(s, tgt, qpe, MQ, q, MQ, D);
       float* qk = lin(s, q, MQ, L.sa_qk, ACT_NONE);
+      arena.release(q);
       float* v = lin(s, tgt, MQ, L.sa_v, ACT_NONE);
       float* att = arena.alloc_f((size_t)MQ * D);
       if (!dry())
         flash_attention(s, qk, qk + D, v, att, B, 8, nq_, nq_, 32, 2 * D, 2 * D, D, D, (long)nq_ * 2 * D, (long)nq_ * 2 * D,
                         (long)nq_ * D, (long)nq_ * D, 1.f / std::sqrt(32.f));
-      tgt = ln(s, lin(s, att, MQ, L.sa_o, ACT_NONE, tgt), MQ, L.n1g, L.n1b);
+      arena.release(qk);
+      arena.release(v);
+      // each sub-layer: out = LayerNorm(tgt + f(...)); the old tgt dies with the GEMM that adds it, the sum with the LayerNorm
+      float* sum = lin(s, att, MQ, L.sa_o, ACT_NONE, tgt);
+      arena.release(att);
+      arena.release(tgt);
+      tgt = ln_take(s, sum, MQ, L.n1g, L.n1b);
       float* q2 = arena.alloc_f((size_t)MQ * D);
       if (!dry()) add_bcast(s, tgt, qpe, MQ, q2, MQ, D);
+      arena.release(qpe);
       float* of = lin(s, q2, MQ, L.offs, ACT_NONE);
       float* aw = lin(s, q2, MQ, L.attw, ACT_NONE);
+      arena.release(q2);
       float* smp = arena.alloc_f((size_t)MQ * D);
       if (!dry()) deform_sample(s, of, aw, ref, vall + (size_t)i * D, ldv, g, nq_, smp);
-      tgt = ln(s, lin(s, smp, MQ, L.outp, ACT_NONE, tgt), MQ, L.n2g, L.n2b);
+      arena.release(of);
+      arena.release(aw);
+      sum = lin(s, smp, MQ, L.outp, ACT_NONE, tgt);
+      arena.release(smp);
+      arena.release(tgt);
+      tgt = ln_take(s, sum, MQ, L.n2g, L.n2b);
       float* hh = lin(s, tgt, MQ, L.lin1, ACT_RELU);
-      tgt = ln(s, lin(s, hh, MQ, L.lin2, ACT_NONE, tgt), MQ, L.n3g, L.n3b);
+      sum = lin(s, hh, MQ, L.lin2, ACT_NONE, tgt);
+      arena.release(hh);
+      arena.release(tgt);
+      tgt = ln_take(s, sum, MQ, L.n3g, L.n3b);
       float* delta = mlp3_fwd(s, tgt, MQ, L.bbox);
       const bool last = i == nl_ - 1;
       float* nref = last ? boxes : arena.alloc_f((size_t)MQ * 4);
       if (!dry()) refine_boxes(s, delta, ref, nref, (size_t)MQ * 4);
+      arena.release(delta);
+      arena.release(ref);  // (the last layer's boxes are the caller's buffer: never released, the loop ends there)
       if (last) {
         lin(s, tgt, MQ, score_, ACT_NONE, nullptr, logits);
+        arena.release(tgt);
+        arena.release(vall);
       }
       ref = nref;
     }

@@ -1,5 +1,6 @@
 // Host runtime of libymk_hip.so: error slot, arena, weight store, state-dict -> packed panels.
 #include "ymk_common.h"
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -51,12 +52,13 @@ void note_lazy_panel_build() {
 void note_arena_grow() {
   if (t_forward_depth > 0) ++g_arena_grows_in_forward;
 }
+static bool workspace_stat(const std::string& key, long long* value);
 bool runtime_stat(const std::string& key, long long* value) {
   if (key == "allocs_in_forward") *value = g_allocs_in_forward.load();
   else if (key == "arena_grows_in_forward") *value = g_arena_grows_in_forward.load();
   else if (key == "lazy_panel_builds") *value = g_lazy_panel_builds.load();
   else if (key == "syncs_in_forward") *value = g_syncs_in_forward.load();
-  else return false;
+  else return workspace_stat(key, value);
   return true;
 }
 static bool env_flag(const char* name) {
@@ -76,28 +78,247 @@ bool debug_hazard_no_finalize_sync() {
   return on;
 }
 
+// ---------------------------------------------------------------- workspace planner (ymk_common.h)
+namespace {
+struct Placed {
+  size_t off, end;
+  int64_t from, to;  // alive over positions [from, to)
+};
+// greedy best-fit of the allocations in `order`; returns the peak
+size_t place_in_order(const std::vector<uint32_t>& order, const std::vector<size_t>& sz, const std::vector<int64_t>& to, std::vector<size_t>& off) {
+  std::vector<Placed> placed;  // sorted by offset
+  placed.reserve(order.size());
+  size_t peak = 0;
+  for (uint32_t k : order) {
+    const int64_t from = (int64_t)k, until = to[k];
+    const size_t need = sz[k];
+    // walk the placed buffers whose lifetime meets this one's, lowest first; keep the tightest gap that fits
+    size_t cursor = 0, best = SIZE_MAX, best_gap = SIZE_MAX;
+    for (const Placed& p : placed) {
+      if (p.to <= from || until <= p.from) continue;
+      if (p.off > cursor) {
+        const size_t gap = p.off - cursor;
+        if (gap >= need && gap < best_gap) {
+          best_gap = gap;
+          best = cursor;
+        }
+      }
+      if (p.end > cursor) cursor = p.end;
+    }
+    if (best == SIZE_MAX) best = cursor;  // above everything it overlaps with
+    off[k] = best;
+    const Placed me{best, best + need, from, until};
+    auto it = placed.begin();
+    while (it != placed.end() && it->off <= best) ++it;
+    placed.insert(it, me);
+    if (me.end > peak) peak = me.end;
+  }
+  return peak;
+}
+}  // namespace
+
+void plan_workspace(size_t n, const size_t* size, const int64_t* release_pos, size_t* offsets, size_t* peak, size_t* live_bound) {
+  YMK_CHECK(n < (size_t)1 << 31, "plan_workspace: too many allocations");
+  std::vector<size_t> sz(n);
+  std::vector<int64_t> to(n);
+  size_t sum = 0;
+  for (size_t k = 0; k < n; ++k) {
+    sz[k] = (size[k] + WS_ALIGN - 1) & ~(WS_ALIGN - 1);
+    sum += sz[k];
+    const int64_t r = release_pos ? release_pos[k] : WS_NEVER;
+    YMK_CHECK(r < 0 || r > (int64_t)k, "plan_workspace: allocation " + std::to_string(k) + " released before it was made");
+    to[k] = (r < 0 || r > (int64_t)n) ? (int64_t)n : r;
+  }
+  // the lower bound: bytes alive at each position
+  std::vector<int64_t> delta(n + 1, 0);
+  for (size_t k = 0; k < n; ++k) {
+    delta[k] += (int64_t)sz[k];
+    delta[(size_t)to[k]] -= (int64_t)sz[k];
+  }
+  int64_t live = 0, live_max = 0;
+  for (size_t k = 0; k < n; ++k) {
+    live += delta[k];
+    live_max = std::max(live_max, live);
+  }
+  std::vector<uint32_t> order(n);
+  std::vector<size_t> off(n), best_off(n);
+  size_t best_peak = SIZE_MAX;
+  for (int pass = 0; pass < 3 && best_peak != (size_t)live_max; ++pass) {
+    for (size_t k = 0; k < n; ++k) order[k] = (uint32_t)k;
+    if (pass == 0)
+      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const int64_t la = to[a] - (int64_t)a, lb = to[b] - (int64_t)b;
+        return la != lb ? la > lb : sz[a] > sz[b];
+      });
+    else if (pass == 1)
+      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return sz[a] > sz[b]; });
+    const size_t pk = place_in_order(order, sz, to, off);
+    if (pk < best_peak) {
+      best_peak = pk;
+      best_off.swap(off);
+    }
+  }
+  if (n == 0) best_peak = 0;
+  YMK_CHECK(best_peak <= sum && (size_t)live_max <= best_peak, "plan_workspace: inconsistent plan");
+  for (size_t k = 0; k < n; ++k) offsets[k] = best_off[k];
+  if (peak) *peak = best_peak;
+  if (live_bound) *live_bound = (size_t)live_max;
+}
+
 // ---------------------------------------------------------------- Arena
+static std::atomic<int> g_ws_reuse_default{0}, g_ws_poison{0};
+static std::atomic<long long> g_ws_planned_forwards{0}, g_ws_plan_bytes{0}, g_ws_bump_bytes{0}, g_ws_live_bound{0};
+bool runtime_debug_option(const std::string& key, int value) {
+  if (key == "workspace_reuse") g_ws_reuse_default = value != 0;
+  else if (key == "workspace_poison") g_ws_poison = value != 0;
+  else return false;
+  return true;
+}
+bool workspace_reuse_default() { return g_ws_reuse_default.load(std::memory_order_relaxed) != 0; }
+static bool workspace_stat(const std::string& key, long long* value) {
+  if (key == "workspace_planned_forwards") *value = g_ws_planned_forwards.load();
+  else if (key == "ws_plan_bytes_last") *value = g_ws_plan_bytes.load();
+  else if (key == "ws_bump_bytes_last") *value = g_ws_bump_bytes.load();
+  else if (key == "ws_live_bound_last") *value = g_ws_live_bound.load();
+  else return false;
+  return true;
+}
+
 Arena::~Arena() { dev_free(base_); }
 void Arena::reserve(size_t bytes) {
-  if (bytes <= cap_) return;
-  YMK_CHECK(off_ == 0, "arena reserve while in use");
+  if (bytes <= cap_ && !resize_pending_) return;
+  YMK_CHECK(off_ == 0 && k_ == 0, "arena reserve while in use");
+  if (bytes == cap_) {
+    resize_pending_ = false;
+    return;
+  }
+  if (bytes < cap_) {  // the mode changed: plans made for the old slab go with it (set_planned dropped them; be sure)
+    plans_.clear();
+    cur_ = nullptr;  // (the bounds stay: the reservation being made is sized from them)
+  }
   note_arena_grow();
   dev_free(base_);
   base_ = nullptr;
   cap_ = 0;
   base_ = (char*)dev_malloc(bytes);
   cap_ = bytes;
+  resize_pending_ = false;
+}
+void Arena::reset() {
+  off_ = 0;
+  k_ = r_ = 0;
+  if (dry_run && planned_) {
+    t_size_.clear();
+    t_at_.clear();
+    t_rel_.clear();
+    t_rel_order_.clear();
+  }
+}
+bool Arena::set_planned(bool on) {
+  if (on == planned_) return false;
+  planned_ = on;
+  plans_.clear();
+  bounds_.clear();
+  cur_ = nullptr;
+  resize_pending_ = true;
+  return true;
 }
 void* Arena::alloc_bytes(size_t bytes) {
-  const size_t a = (bytes + 255) & ~(size_t)255;
+  const size_t a = (bytes + WS_ALIGN - 1) & ~(WS_ALIGN - 1);
+  if (planned_ && !dry_run) {  // replay: a table lookup
+    YMK_CHECK(cur_ != nullptr && k_ < cur_->size.size(), "planned workspace: allocation " + std::to_string(k_) + " is not in the plan");
+    YMK_CHECK(cur_->size[k_] == a, "planned workspace: allocation " + std::to_string(k_) + " asks " + std::to_string(a) +
+                                       " bytes, the plan recorded " + std::to_string(cur_->size[k_]));
+    const size_t at = cur_->off[k_++];
+    YMK_CHECK(at + a <= cap_, "arena overflow: need " + std::to_string(at + a) + " have " + std::to_string(cap_));
+    return base_ + at;
+  }
   const size_t at = off_;
   off_ += a;
   if (off_ > high_) high_ = off_;
-  if (dry_run) return (void*)(uintptr_t)(4096 + at);  // aligned fake address, never dereferenced
+  if (dry_run) {
+    if (planned_) {
+      t_size_.push_back(a);
+      t_at_.push_back(at);
+      t_rel_.push_back(WS_NEVER);
+    }
+    return (void*)(uintptr_t)(4096 + at);  // aligned fake address, never dereferenced
+  }
   YMK_CHECK(off_ <= cap_, "arena overflow: need " + std::to_string(off_) + " have " + std::to_string(cap_));
   return base_ + at;
 }
+void Arena::release(const void* p) {
+  if (!planned_ || p == nullptr) return;
+  if (dry_run) {  // the fake addresses grow with the call order: find the allocation by bisection
+    const size_t at = (size_t)(uintptr_t)p - 4096;
+    const auto it = std::lower_bound(t_at_.begin(), t_at_.end(), at);
+    YMK_CHECK(it != t_at_.end() && *it == at, "workspace release: not the start of an allocation of this forward");
+    const size_t k = (size_t)(it - t_at_.begin());
+    YMK_CHECK(t_rel_[k] == WS_NEVER, "workspace release: allocation " + std::to_string(k) + " released twice");
+    t_rel_[k] = (int64_t)t_size_.size();
+    t_rel_order_.push_back((uint32_t)k);
+    return;
+  }
+  YMK_CHECK(cur_ != nullptr && r_ < cur_->rel_order.size(), "planned workspace: release " + std::to_string(r_) + " is not in the plan");
+  const uint32_t k = cur_->rel_order[r_++];
+  YMK_CHECK((const char*)p == base_ + cur_->off[k], "planned workspace: release " + std::to_string(r_ - 1) + " does not match the plan");
+  if (g_ws_poison.load(std::memory_order_relaxed)) YMK_HIP(hipMemsetAsync(base_ + cur_->off[k], 0xFF, cur_->size[k], stream_));
+}
+size_t Arena::plan_commit(uint64_t key, bool bound) {
+  if (!planned_) return off_;
+  if (plans_.size() >= 64) {  // ragged workloads change shape on every call: keep the cache small
+    plans_.clear();
+    cur_ = nullptr;
+  }
+  Plan& p = plans_[key];
+  p.size = t_size_;
+  p.rel = t_rel_;
+  p.rel_order = t_rel_order_;
+  p.off.assign(t_size_.size(), 0);
+  p.bump = off_;
+  plan_workspace(p.size.size(), p.size.data(), p.rel.data(), p.off.data(), &p.peak, &p.live);
+  if (!bound && p.peak > cap_) {
+    for (const Plan& b : bounds_) {
+      bool covers = b.peak <= cap_ && b.size.size() == p.size.size() && b.rel == p.rel;
+      for (size_t k = 0; covers && k < p.size.size(); ++k) covers = p.size[k] <= b.size[k];
+      if (!covers) continue;
+      p.off = b.off;
+      p.peak = 0;
+      for (size_t k = 0; k < p.size.size(); ++k) p.peak = std::max(p.peak, p.off[k] + p.size[k]);
+      break;
+    }
+  }
+  if (bound) {
+    if (bounds_.size() >= 8) bounds_.erase(bounds_.begin());
+    bounds_.push_back(p);
+  }
+  cur_ = &p;
+  publish(p);
+  return p.peak;
+}
+bool Arena::plan_select(uint64_t key, size_t* need) {
+  if (!planned_) return false;
+  const auto it = plans_.find(key);
+  if (it == plans_.end()) return false;
+  cur_ = &it->second;
+  *need = cur_->peak;
+  reset();
+  return true;
+}
+void Arena::publish(const Plan& p) const {
+  g_ws_plan_bytes = (long long)p.peak;
+  g_ws_bump_bytes = (long long)p.bump;
+  g_ws_live_bound = (long long)p.live;
+}
+void Arena::forward_begin() {
+  reset();
+  if (!planned_) return;
+  YMK_CHECK(cur_ != nullptr, "planned workspace: no plan selected");
+  ++g_ws_planned_forwards;
+  publish(*cur_);
+}
 void Arena::amax_begin(hipStream_t s, int records) {
+  stream_ = s;
   amax_n_ = records;
   amax_used_ = 0;
   const size_t bytes = (size_t)records * AMAX_REC_WORDS * sizeof(unsigned);

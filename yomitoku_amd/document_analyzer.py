@@ -47,9 +47,9 @@ def ocr_aggregate(det_outputs, rec_outputs):
 
 
 class OCR:
-    def __init__(self, configs={}, device="cuda", visualize=False):
-        det_kwargs = {"device": device, "visualize": visualize}
-        rec_kwargs = {"device": device, "visualize": visualize}
+    def __init__(self, configs={}, device="cuda", visualize=False, workspace_reuse=False):
+        det_kwargs = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
+        rec_kwargs = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
         if not isinstance(configs, dict):
             raise ValueError(_USAGE)
         det_kwargs.update(configs.get("text_detector", {}))
@@ -66,9 +66,9 @@ class OCR:
 
 # ---------------------------------------------------------------------------------------------- layout
 class LayoutAnalyzer:
-    def __init__(self, configs={}, device="cuda", visualize=False):
-        lp_kwargs = {"device": device, "visualize": visualize}
-        ts_kwargs = {"device": device, "visualize": visualize}
+    def __init__(self, configs={}, device="cuda", visualize=False, workspace_reuse=False):
+        lp_kwargs = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
+        ts_kwargs = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
         if not isinstance(configs, dict):
             raise ValueError(_USAGE)
         lp_kwargs.update(configs.get("layout_parser", {}))
@@ -311,16 +311,13 @@ def _chain_priorities():
 
 class DocumentAnalyzer:
     def __init__(self, configs={}, device="cuda", visualize=False, ignore_meta=False, reading_order="auto",
-                 split_text_across_cells=False, ignore_ruby=False, ruby_threshold=2.0):
+                 split_text_across_cells=False, ignore_ruby=False, ruby_threshold=2.0, workspace_reuse=False):
+        # workspace_reuse: every network plans its workspace so that dead activations share bytes (include/ymk.h,
+        # "workspace_reuse"; the same results from a fraction of the device memory); a module's own config entry wins
+        common = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
         default_configs = {
-            "ocr": {
-                "text_detector": {"device": device, "visualize": visualize},
-                "text_recognizer": {"device": device, "visualize": visualize},
-            },
-            "layout_analyzer": {
-                "layout_parser": {"device": device, "visualize": visualize},
-                "table_structure_recognizer": {"device": device, "visualize": visualize},
-            },
+            "ocr": {"text_detector": dict(common), "text_recognizer": dict(common)},
+            "layout_analyzer": {"layout_parser": dict(common), "table_structure_recognizer": dict(common)},
         }
         self.reading_order = reading_order
         if not isinstance(configs, dict):

@@ -135,7 +135,7 @@ class LayoutParser(BaseModule):
     model_catalog = LayoutParserModelCatalog()
 
     def __init__(self, model_name="rtdetrv2v2", path_cfg=None, device="cuda", visualize=False, from_pretrained=True,
-                 infer_onnx=False):
+                 infer_onnx=False, workspace_reuse=False):
         super().__init__()
         if infer_onnx:
             raise NotImplementedError("the ONNX backend is out of scope of the MI355X path (infer_onnx=False only)")
@@ -147,6 +147,8 @@ class LayoutParser(BaseModule):
         weights_path = getattr(peek, "weights_path", None)
         use_local = bool(weights_path) and os.path.exists(weights_path)
         self.load_model(model_name, path_cfg, from_pretrained=(from_pretrained and not use_local))
+        if workspace_reuse:  # planned workspace (include/ymk.h, "workspace_reuse"); False leaves the process-wide default in force
+            self.model.set_workspace_reuse(True)
         if use_local:
             load_local_checkpoint(self.model, weights_path, getattr(self._cfg, "weights_key", "ema"))
         self.device = device

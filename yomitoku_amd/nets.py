@@ -62,6 +62,7 @@ class HipNet:
         self._sd = None
         self.training = False
         self._conv_split = None
+        self._workspace_reuse = None
 
     # -- nn.Module-ish surface used by the reference modules (eval/to)
     def eval(self):
@@ -106,6 +107,8 @@ class HipNet:
                 _lib.check(lib.ymk_model_set_param(h, b"conv_split", float(self._conv_split)), "set_param conv_split")
             for k, v in getattr(self, "_extra_params", {}).items():
                 _lib.check(lib.ymk_model_set_param(h, k.encode(), float(v)), f"set_param {k}")
+            if self._workspace_reuse is not None:
+                _lib.check(lib.ymk_model_set_param(h, b"workspace_reuse", float(self._workspace_reuse)), "set_param workspace_reuse")
             for name, t in self._sd.items():
                 if not torch.is_floating_point(t):
                     continue
@@ -132,6 +135,22 @@ class HipNet:
         if self._h is not None:
             _lib.check(_lib.load().ymk_model_set_param(self._h, b"conv_split", float(-1 if planes is None else int(planes))),
                        "set_param conv_split")
+        return self
+
+    def set_workspace_reuse(self, on):
+        """Workspace layout of THIS model (include/ymk.h, "workspace_reuse"): True = planned - activations that are never
+        alive together share bytes, same outputs bit for bit from a smaller workspace; False = the bump arena; None = follow
+        the process-wide switch (ymk_debug_option("workspace_reuse") / YMK_WORKSPACE_REUSE), which defaults to the bump arena.
+        Kept across rebuilds.  A change on a live handle forgets its reservations: the next forward (or reserve) sizes the
+        workspace for the new mode."""
+        on = None if on is None else bool(on)
+        changed = on != self._workspace_reuse
+        self._workspace_reuse = on
+        if self._h is not None and changed:
+            _lib.check(_lib.load().ymk_model_set_param(self._h, b"workspace_reuse", float(-1 if on is None else int(on))),
+                       "set_param workspace_reuse")
+            self._reserved = []
+            self._reserve_tried_for = None
         return self
 
     def set_param(self, key: str, value: float):

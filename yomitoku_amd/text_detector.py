@@ -88,11 +88,13 @@ class TextDetector(BaseModule):
     model_catalog = TextDetectorModelCatalog()
 
     def __init__(self, model_name="dbnetv2_1", path_cfg=None, device="cuda", visualize=False, from_pretrained=True,
-                 infer_onnx=False):
+                 infer_onnx=False, workspace_reuse=False):
         super().__init__()
         if infer_onnx:
             raise NotImplementedError("the ONNX backend is out of scope of the MI355X path (infer_onnx=False only)")
         self.load_model(model_name, path_cfg, from_pretrained=from_pretrained)
+        if workspace_reuse:  # planned workspace (include/ymk.h, "workspace_reuse"); False leaves the process-wide default in force
+            self.model.set_workspace_reuse(True)
         self.device = device
         self.visualize = visualize
         self.model.eval()

@@ -116,11 +116,14 @@ class TextRecognizer(BaseModule):
 
     def __init__(self, model_name="parseq-large-v4_1", path_cfg=None, device="cuda", visualize=False, from_pretrained=True,
                  infer_onnx=False, rec_orientation_fallback=False, rec_orientation_fallback_thresh=0.75,
-                 batch_bucketing=False, dynamic_width=False, num_parallel_batches=1, source_downscale=False):
+                 batch_bucketing=False, dynamic_width=False, num_parallel_batches=1, source_downscale=False,
+                 workspace_reuse=False):
         super().__init__()
         if infer_onnx:
             raise NotImplementedError("the ONNX backend is out of scope of the MI355X path (infer_onnx=False only)")
         self.load_model(model_name, path_cfg, from_pretrained=from_pretrained)
+        if workspace_reuse:  # planned workspace (include/ymk.h, "workspace_reuse"); False leaves the process-wide default in force
+            self.model.set_workspace_reuse(True)
         self.charset = load_charset(self._cfg.charset)
         self.tokenizer = ParseqTokenizer(self.charset)
         if len(self.tokenizer) != int(self._cfg.num_tokens):
@@ -383,13 +386,17 @@ class TextRecognizer(BaseModule):
             if rep is None or rep._source_sd is not self.model._sd:
                 if rep is not None:
                     rep.close()
-                rep = type(self.model)(self.model.cfg).load_state_dict(self.model._sd).to(self.device)
+                rep = type(self.model)(self.model.cfg).load_state_dict(self.model._sd)
+                rep.set_workspace_reuse(self.model._workspace_reuse)  # before the handle exists: its first reservation is in the mode
+                rep.to(self.device)
                 rep._source_sd = self.model._sd
                 rep.tokenizer = self.tokenizer
                 rep.reserve_once(*self._reserve_bounds(), self.device)
                 self._replicas[lane] = rep
             if rep._conv_split != self.model._conv_split:
                 rep.set_conv_split(self.model._conv_split)
+            if rep._workspace_reuse != self.model._workspace_reuse:
+                rep.set_workspace_reuse(self.model._workspace_reuse)
             for k, v in getattr(self.model, "_extra_params", {}).items():
                 if getattr(rep, "_extra_params", {}).get(k) != v:
                     rep.set_param(k, v)
