@@ -353,6 +353,59 @@ int ymk_op_deconv2x2_to1_sigmoid(const float* x_dev, int n, int h, int w, const 
 int ymk_op_dbnet_asf(const float* ax_dev, const float* fuse_dev, int n, int h, int w, const float* w1_host, const float* w2_host,
                      int cmid, const float* sp33_host, float sp11, const float* watt_host, float* out_dev, void* stream);
 
+/* ---- single operators of the PARSeq greedy decode (yomitoku_amd/csrc/ymk_decstep.hip, ymk_seq.hip; the launch functions
+ * ymk_parseq.cpp calls, one launch per call; tests/test_parseq_decstep_gpu.py, tests/test_parseq_greedy_ops_gpu.py).
+ * parseq_dec_step: the fused decoder step of position `step` for b samples (k_parseq_dec_step_rows): content row of tok[i][step]
+ *   -> norm_c -> K|V appended as row `step` of skv [b][ns][2 d]; query `step` = pos_queries + self attention over rows 0..step,
+ *   + cross attention over the sample's memkv rows ([.][2 d]: K then V; sample i owns rows i * l .. i * l + l - 1, or - with the
+ *   device tables mem_off / mem_len, both or neither - rows mem_off[i] .. + mem_len[i] - 1, 1 <= mem_len <= l), + MLP, decoder.norm
+ *   -> out [b][d].  Host weights in nn.Linear layout ([out][in]): the two in_proj_weight [3 d][d] / in_proj_bias [3 d], the two
+ *   out_proj, linear1 [f][d], linear2 [d][f]; they are transposed by the function the model's finalize uses.  ln_host: ten host
+ *   vectors [d] - weight, bias of norm_q, norm_c, norm1, norm2, decoder.norm in that order (the norm_q pair may be null: the
+ *   step reads it through qsa only).  emb_host [ntok][d], posq_host [ns][d] (pos_queries), qsa_host [ns][d] = the self attention's
+ *   query projection of norm_q(pos_queries), as given.  tok [b][ns] (ids in [0, ntok): the kernel trusts them).
+ *   prev_not_done (device word, may be null): 0 = a speculative step, nothing is written.  gid [b] / gopen [ns][ng] (both or
+ *   neither): row i belongs to mini-batch gid[i]; a row whose gopen[step - 1][gid] is 0 is frozen (neither out nor skv written).
+ *   Refuses (error, nothing launched) what parseq_dec_step_supported refuses: d <= 256, d % 4 == 0, heads <= 8, d / heads a
+ *   power of two >= 4, f <= 1024, f % 4 == 0, l <= 1024, ns <= 1024.  Rows per block: ymk_debug_option("dec_rows").
+ *   Uploads the weights on every call and waits for the stream before it returns.
+ * greedy_step: k_greedy_step in the flag form the recogniser runs (open rows STORE 1 into *not_done and gopen[step][gid]; no
+ *   mapped host word - the counting form of "ar_publish" 0 is not exported): arg-max of row i of logits (c floats, row stride
+ *   ld_b floats; partials = 1: c <= 256 (max, column-as-int-bits) pairs, lowest column among equal maxima) -> raw[i][step]; for
+ *   step + 1 < num_steps the next context token tok[i][step + 1] - <eos> instead when the repetition detector (rep_on, periods
+ *   1..period_max, a run of min_run_p1 for period 1, min_repeats units otherwise) fires on tok[i][1..step + 1]; state [b][4] =
+ *   {has_eos, rep_done, rep_cut (-1 none), unused}.  prev_not_done / gid / gopen as above (a frozen row only gets raw = eos).
+ * refine_prep: tok2[i][t] = t == 0 ? bos : raw[i][t - 1], kpm[i][t] = an <eos> at or before t in tok2, or t >= gsteps[gid[i]]
+ *   (gid / gsteps: both or neither), for t < s_len <= ld_tok; kpm is [b][ld_tok] bytes.
+ * rep_cut: for rows with 0 <= state[i][2] < s_len: logits[i][cut][:] = -30, [eos_id] = +30 (logits [b][ld_b], ld_b >= s_len * c).
+ * row_argmax: out[r] = first maximal column of row r of logits [rows][c] (torch.argmax; an all -inf row gives 0).
+ *   ymk_parseq_token_stats above is the same reduction plus the arg-max's probability.
+ * ctx_embed_ln: out[i][pos][:] = LayerNorm(sqrt(d) emb[tok[i][pos]] + (pos > 0 ? posq[pos - 1] : 0); g, b, eps) for pos0 <= pos <
+ *   pos0 + npos; tok [b][ld_tok], out [b][out_rows][d]; d <= 1024 (refused otherwise).  All pointers device.
+ * init_decode: tok [b][ld_tok] = pad with column 0 = bos, state [b][4] = {0, 0, -1, 0}; ld_tok >= 4.
+ * tile_rows: dst [b][rows][d] = src [rows][d] (rows * d a multiple of 4).
+ * add_pos_embed: x [b][gh][gw][d] += pos[(r * full_gw + c)][d] in place (gw <= full_gw: the dynamic-width crop), d % 4 == 0. */
+int ymk_op_parseq_dec_step(int d, int heads, int f, const float* sa_in_w_host, const float* sa_in_b_host, const float* sa_out_w_host,
+                           const float* sa_out_b_host, const float* ca_in_w_host, const float* ca_in_b_host,
+                           const float* ca_out_w_host, const float* ca_out_b_host, const float* lin1_w_host, const float* lin1_b_host,
+                           const float* lin2_w_host, const float* lin2_b_host, const float* const* ln_host, const float* emb_host,
+                           int ntok, const float* posq_host, const float* qsa_host, const int* tok_dev, float* skv_dev,
+                           const float* memkv_dev, const int* mem_off_dev, const int* mem_len_dev, const int* prev_not_done_dev,
+                           const int* gid_dev, const int* gopen_dev, int ng, int step, int b, int l, int ns, float* out_dev,
+                           void* stream);
+int ymk_op_greedy_step(const float* logits_dev, int64_t ld_b, int c, int step, int num_steps, int* tok_dev, int* raw_dev, int ld_tok,
+                       int* state_dev, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats, int* not_done_dev,
+                       const int* prev_not_done_dev, const int* gid_dev, int* gopen_dev, int ng, int partials, int b, void* stream);
+int ymk_op_refine_prep(const int* raw_dev, int ld_tok, int s_len, int bos_id, int eos_id, int* tok2_dev, unsigned char* kpm_dev, int b,
+                       const int* gid_dev, const int* gsteps_dev, void* stream);
+int ymk_op_rep_cut(float* logits_dev, int64_t ld_b, int c, int s_len, const int* state_dev, int eos_id, int b, void* stream);
+int ymk_op_row_argmax(const float* logits_dev, int rows, int c, int* out_dev, void* stream);
+int ymk_op_ctx_embed_ln(const int* tok_dev, int ld_tok, int pos0, int npos, const float* emb_dev, const float* posq_dev,
+                        const float* g_dev, const float* b_dev, float eps, float* out_dev, int out_rows, int d, int b, void* stream);
+int ymk_op_init_decode(int* tok_dev, int ld_tok, int* state_dev, int bos_id, int pad_id, int b, void* stream);
+int ymk_op_tile_rows(const float* src_dev, int rows, int d, float* dst_dev, int b, void* stream);
+int ymk_op_add_pos_embed(float* x_dev, const float* pos_dev, int b, int gh, int gw, int full_gw, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -306,3 +306,177 @@ def dbnet_asf(ax, fuse, w1, w2, sp33, sp11, watt):
                                         host[2].data_ptr(), float(sp11), host[3].data_ptr(), y.data_ptr(), _lib.current_stream_ptr()),
                    "ymk_op_dbnet_asf")
     return _nchw(y)
+
+
+# ---- the PARSeq greedy decode (include/ymk.h: "single operators of the PARSeq greedy decode")
+DEC_STEP_WEIGHTS = ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                    "cross_attn.in_proj_weight", "cross_attn.in_proj_bias", "cross_attn.out_proj.weight", "cross_attn.out_proj.bias",
+                    "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias")
+DEC_STEP_NORMS = ("norm_q", "norm_c", "norm1", "norm2", "decoder.norm")
+
+
+def _i32(t, device):
+    return None if t is None else t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def parseq_dec_step(w, heads, qsa, tok, skv, memkv, out, step, L, mem_off=None, mem_len=None, prev_not_done=None, gid=None,
+                    gopen=None, ng=1):
+    """One launch of the fused decoder step, IN PLACE on skv [B, NS, 2D] and out [B, D] (device, fp32).  w: host fp32 tensors
+    under the names DEC_STEP_WEIGHTS, "<norm>.weight" / "<norm>.bias" for DEC_STEP_NORMS, "emb" [ntok, D], "pos_queries" [NS, D];
+    qsa [NS, D] host.  tok [B, NS] int32, memkv [rows, 2D], the optional tables int32, all on the device."""
+    import ctypes
+
+    lib = _lib.load()
+    B, NS, D2 = skv.shape
+    D = D2 // 2
+    F = w["linear1.weight"].shape[0]
+    ntok = w["emb"].shape[0]
+    dev = skv.device
+    for t in (tok, skv, memkv, out):
+        assert t.is_cuda and t.is_contiguous()
+    assert tok.dtype == torch.int32 and tok.shape == (B, NS) and out.shape == (B, D) and memkv.shape[1] == 2 * D
+    assert w["pos_queries"].shape == (NS, D) and qsa.shape == (NS, D) and w["emb"].shape[1] == D
+    # the kernel trusts its indices: check what it will dereference
+    if 0 <= step < NS:
+        assert 0 <= int(tok[:, step].min()) and int(tok[:, step].max()) < ntok
+    if mem_off is not None:
+        assert mem_off.dtype == mem_len.dtype == torch.int32 and mem_off.shape == mem_len.shape == (B,)
+        assert int(mem_len.min()) >= 1 and int(mem_len.max()) <= L and int(mem_off.min()) >= 0
+        assert int((mem_off + mem_len).max()) <= memkv.shape[0]
+    else:
+        assert memkv.shape[0] >= B * L
+    if gid is not None:
+        assert gid.dtype == gopen.dtype == torch.int32 and gid.shape == (B,) and gopen.shape == (NS, ng)
+        assert 0 <= int(gid.min()) and int(gid.max()) < ng
+    host = [w[n].detach().float().cpu().contiguous() for n in DEC_STEP_WEIGHTS]
+    norms = [w[f"{n}.{k}"].detach().float().cpu().contiguous() for n in DEC_STEP_NORMS for k in ("weight", "bias")]
+    ln = (ctypes.c_void_p * 10)(*[t.data_ptr() for t in norms])
+    emb, posq, qs = (t.detach().float().cpu().contiguous() for t in (w["emb"], w["pos_queries"], qsa))
+    with torch.cuda.device(dev):
+        _lib.check(lib.ymk_op_parseq_dec_step(D, heads, F, *[t.data_ptr() for t in host], ln, emb.data_ptr(), ntok, posq.data_ptr(),
+                                              qs.data_ptr(), tok.data_ptr(), skv.data_ptr(), memkv.data_ptr(), _lib.ptr(mem_off),
+                                              _lib.ptr(mem_len), _lib.ptr(prev_not_done), _lib.ptr(gid), _lib.ptr(gopen), ng, step, B, L,
+                                              NS, out.data_ptr(), _lib.current_stream_ptr()), "ymk_op_parseq_dec_step")
+
+
+def greedy_step(logits, C, step, num_steps, tok, raw, state, not_done, eos_id=0, rep=(1, 8, 8, 3), prev_not_done=None, gid=None,
+                gopen=None, ng=1, partials=0):
+    """One launch of k_greedy_step (flag form), IN PLACE on tok / raw [B, ld_tok], state [B, 4], not_done [1], gopen [num_steps,
+    ng] (int32, device).  logits [B, ld_b] fp32: C logits per row, or - partials - C (max, column bits) pairs.
+    rep = (rep_on, period_max, min_run_p1, min_repeats)."""
+    lib = _lib.load()
+    B, ld_tok = tok.shape
+    for t in (logits, tok, raw, state, not_done):
+        assert t.is_cuda and t.is_contiguous()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == B and logits.shape[1] >= C * (2 if partials else 1)
+    assert tok.dtype == raw.dtype == state.dtype == not_done.dtype == torch.int32
+    assert raw.shape == tok.shape and state.shape == (B, 4) and 0 <= step < num_steps <= ld_tok
+    if gid is not None:
+        assert gid.dtype == gopen.dtype == torch.int32 and gid.shape == (B,) and gopen.shape[1] == ng and gopen.shape[0] >= num_steps
+        assert 0 <= int(gid.min()) and int(gid.max()) < ng
+    with torch.cuda.device(tok.device):
+        _lib.check(lib.ymk_op_greedy_step(logits.data_ptr(), logits.shape[1], C, step, num_steps, tok.data_ptr(), raw.data_ptr(), ld_tok,
+                                          state.data_ptr(), eos_id, rep[0], rep[1], rep[2], rep[3], not_done.data_ptr(),
+                                          _lib.ptr(prev_not_done), _lib.ptr(gid), _lib.ptr(gopen), ng, partials, B,
+                                          _lib.current_stream_ptr()), "ymk_op_greedy_step")
+
+
+def refine_prep(raw, S, bos_id, eos_id, gid=None, gsteps=None):
+    """raw [B, ld_tok] int32 (device) -> (tok2 [B, ld_tok] int32, kpm [B, ld_tok] uint8), both pre-filled with the sentinel 77."""
+    lib = _lib.load()
+    B, ld_tok = raw.shape
+    assert raw.is_cuda and raw.is_contiguous() and raw.dtype == torch.int32 and 1 <= S <= ld_tok
+    if gid is not None:
+        assert gid.dtype == gsteps.dtype == torch.int32 and gid.shape == (B,) and 0 <= int(gid.min()) and int(gid.max()) < gsteps.numel()
+    tok2 = torch.full((B, ld_tok), 77, dtype=torch.int32, device=raw.device)
+    kpm = torch.full((B, ld_tok), 77, dtype=torch.uint8, device=raw.device)
+    with torch.cuda.device(raw.device):
+        _lib.check(lib.ymk_op_refine_prep(raw.data_ptr(), ld_tok, S, bos_id, eos_id, tok2.data_ptr(), kpm.data_ptr(), B, _lib.ptr(gid),
+                                          _lib.ptr(gsteps), _lib.current_stream_ptr()), "ymk_op_refine_prep")
+    return tok2, kpm
+
+
+def rep_cut(logits, S, state, eos_id):
+    """IN PLACE on logits [B, rows, C] fp32 (device, rows >= S); state [B, 4] int32."""
+    lib = _lib.load()
+    B, rows, C = logits.shape
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32 and 0 <= S <= rows
+    assert state.dtype == torch.int32 and state.shape == (B, 4) and state.is_contiguous() and 0 <= eos_id < C
+    with torch.cuda.device(logits.device):
+        _lib.check(lib.ymk_op_rep_cut(logits.data_ptr(), rows * C, C, S, state.data_ptr(), eos_id, B, _lib.current_stream_ptr()),
+                   "ymk_op_rep_cut")
+
+
+def row_argmax(logits):
+    """logits [rows, C] fp32 (device) -> int32 [rows]."""
+    lib = _lib.load()
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32 and logits.dim() == 2
+    out = torch.full((logits.shape[0],), -7, dtype=torch.int32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _lib.check(lib.ymk_op_row_argmax(logits.data_ptr(), logits.shape[0], logits.shape[1], out.data_ptr(), _lib.current_stream_ptr()),
+                   "ymk_op_row_argmax")
+    return out
+
+
+def token_stats(logits):
+    """ymk_parseq_token_stats: logits [rows, C] fp32 (device) -> (ids int32 [rows], probs fp32 [rows])."""
+    lib = _lib.load()
+    assert logits.is_cuda and logits.is_contiguous() and logits.dtype == torch.float32 and logits.dim() == 2
+    ids = torch.full((logits.shape[0],), -7, dtype=torch.int32, device=logits.device)
+    probs = torch.full((logits.shape[0],), -7.0, dtype=torch.float32, device=logits.device)
+    with torch.cuda.device(logits.device):
+        _lib.check(lib.ymk_parseq_token_stats(logits.data_ptr(), logits.shape[0], logits.shape[1], ids.data_ptr(), probs.data_ptr(),
+                                              _lib.current_stream_ptr()), "ymk_parseq_token_stats")
+    return ids, probs
+
+
+def ctx_embed_ln(tok, pos0, npos, emb, posq, g, b, eps, out):
+    """IN PLACE on out [B, out_rows, D] (device): rows pos0 .. pos0 + npos - 1 of every sample.  tok [B, ld_tok] int32."""
+    lib = _lib.load()
+    B, out_rows, D = out.shape
+    for t in (tok, emb, posq, g, b, out):
+        assert t.is_cuda and t.is_contiguous()
+    assert tok.dtype == torch.int32 and tok.shape[0] == B and emb.shape[1] == D and posq.shape[1] == D and g.numel() == b.numel() == D
+    if npos > 0 and D <= 1024:  # the kernel trusts its indices
+        assert 0 <= pos0 and pos0 + npos <= min(tok.shape[1], out_rows) and pos0 + npos - 1 <= posq.shape[0]
+        used = tok[:, pos0:pos0 + npos]
+        assert 0 <= int(used.min()) and int(used.max()) < emb.shape[0]
+    with torch.cuda.device(out.device):
+        _lib.check(lib.ymk_op_ctx_embed_ln(tok.data_ptr(), tok.shape[1], pos0, npos, emb.data_ptr(), posq.data_ptr(), g.data_ptr(),
+                                           b.data_ptr(), float(eps), out.data_ptr(), out_rows, D, B, _lib.current_stream_ptr()),
+                   "ymk_op_ctx_embed_ln")
+
+
+def init_decode(B, ld_tok, bos_id, pad_id, device):
+    """-> (tok [B, ld_tok], state [B, 4]) int32, both pre-filled with the sentinel 77."""
+    lib = _lib.load()
+    tok = torch.full((B, ld_tok), 77, dtype=torch.int32, device=device)
+    state = torch.full((B, 4), 77, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.ymk_op_init_decode(tok.data_ptr(), ld_tok, state.data_ptr(), bos_id, pad_id, B, _lib.current_stream_ptr()),
+                   "ymk_op_init_decode")
+    return tok, state
+
+
+def tile_rows(src, B):
+    """src [rows, D] fp32 (device) -> [B, rows, D]."""
+    lib = _lib.load()
+    assert src.is_cuda and src.is_contiguous() and src.dtype == torch.float32 and src.dim() == 2
+    rows, D = src.shape
+    dst = torch.full((B, rows, D), -7.0, dtype=torch.float32, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(lib.ymk_op_tile_rows(src.data_ptr(), rows, D, dst.data_ptr(), B, _lib.current_stream_ptr()), "ymk_op_tile_rows")
+    return dst
+
+
+def add_pos_embed(x, pos, full_gw):
+    """x [B, gh, gw, D] fp32 (device), pos [full_gh * full_gw, D] -> x + pos[r * full_gw + c] (a copy; the op works in place)."""
+    lib = _lib.load()
+    B, gh, gw, D = x.shape
+    assert x.is_cuda and x.dtype == torch.float32 and pos.is_cuda and pos.is_contiguous() and pos.dtype == torch.float32
+    assert gw <= full_gw and pos.shape[1] == D and pos.shape[0] >= (gh - 1) * full_gw + gw
+    y = x.contiguous().clone()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_add_pos_embed(y.data_ptr(), pos.data_ptr(), B, gh, gw, full_gw, D, _lib.current_stream_ptr()),
+                   "ymk_op_add_pos_embed")
+    return y

@@ -117,6 +117,26 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     ),
+    "ymk_op_parseq_dec_step": (
+        c_int,
+        [c_int, c_int, c_int] + [c_void_p] * 12 + [POINTER(c_void_p), c_void_p, c_int, c_void_p, c_void_p]
+        + [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    ),
+    "ymk_op_greedy_step": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
+    ),
+    "ymk_op_refine_prep": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "ymk_op_rep_cut": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "ymk_op_row_argmax": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_ctx_embed_ln": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p],
+    ),
+    "ymk_op_init_decode": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "ymk_op_tile_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ymk_op_add_pos_embed": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

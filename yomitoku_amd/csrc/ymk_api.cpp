@@ -1,6 +1,7 @@
 // extern "C" surface of libymk_hip.so (declared in include/ymk.h).
 #include "../../include/ymk.h"
 #include "ymk_common.h"
+#include "ymk_decstep.h"
 #include "ymk_det.h"
 #include "ymk_seq.h"
 
@@ -654,6 +655,118 @@ int ymk_op_dbnet_asf(const float* ax_dev, const float* fuse_dev, int n, int h, i
   Tensor out{out_dev, n, h, w, 256, 256};
   asf_block(s, x, w1, w2, cmid, sp33, sp11, watt, fuse, gap_scr, gap, gate, cmean, out);
   YMK_HIP(hipStreamSynchronize(s));  // pool frees weights and scratch on return
+  YMK_API_END
+}
+
+// ---- single operators of the PARSeq greedy decode (the launch functions ymk_parseq.cpp calls)
+int ymk_op_parseq_dec_step(int d, int heads, int f, const float* sa_in_w_host, const float* sa_in_b_host, const float* sa_out_w_host,
+                           const float* sa_out_b_host, const float* ca_in_w_host, const float* ca_in_b_host,
+                           const float* ca_out_w_host, const float* ca_out_b_host, const float* lin1_w_host, const float* lin1_b_host,
+                           const float* lin2_w_host, const float* lin2_b_host, const float* const* ln_host, const float* emb_host,
+                           int ntok, const float* posq_host, const float* qsa_host, const int* tok_dev, float* skv_dev,
+                           const float* memkv_dev, const int* mem_off_dev, const int* mem_len_dev, const int* prev_not_done_dev,
+                           const int* gid_dev, const int* gopen_dev, int ng, int step, int b, int l, int ns, float* out_dev,
+                           void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  // refused before anything is uploaded or launched (parseq_dec_step checks again)
+  YMK_CHECK(d >= 4 && heads >= 1 && f >= 4 && l >= 1 && ns >= 1 && parseq_dec_step_supported(d, heads, f, l, ns),
+            "fused decoder step: unsupported geometry");
+  YMK_CHECK(sa_in_w_host && sa_in_b_host && sa_out_w_host && sa_out_b_host && ca_in_w_host && ca_in_b_host && ca_out_w_host &&
+                ca_out_b_host && lin1_w_host && lin1_b_host && lin2_w_host && lin2_b_host && ln_host && emb_host && posq_host && qsa_host,
+            "dec_step: a host weight is null");
+  for (int i = 2; i < 10; ++i) YMK_CHECK(ln_host[i] != nullptr, "dec_step: a LayerNorm vector is null");
+  YMK_CHECK(tok_dev && skv_dev && memkv_dev && out_dev && b >= 1 && ntok >= 1 && step >= 0 && step < ns, "dec_step: bad argument");
+  YMK_CHECK((mem_off_dev == nullptr) == (mem_len_dev == nullptr), "dec_step: mem_off and mem_len come in pairs");
+  YMK_CHECK((gid_dev == nullptr) == (gopen_dev == nullptr) && ng >= 1, "dec_step: gid and gopen come in pairs, ng >= 1");
+  YMK_CHECK(aligned16(skv_dev) && aligned16(memkv_dev) && aligned16(out_dev), "dec_step: skv / memkv / out must be 16 B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  DevicePool pool;
+  DecStepW w{};
+  const DecStepHostW hw{sa_in_w_host, sa_in_b_host, sa_out_w_host, sa_out_b_host, ca_in_w_host, ca_in_b_host, ca_out_w_host,
+                        ca_out_b_host, lin1_w_host, lin1_b_host, lin2_w_host, lin2_b_host, d, heads, f};
+  make_dec_step_weights(pool, hw, w);
+  w.emb = pool.upload(emb_host, (size_t)ntok * d);
+  w.posq = pool.upload(posq_host, (size_t)ns * d);
+  w.qsa = pool.upload(qsa_host, (size_t)ns * d);
+  w.ncg = pool.upload(ln_host[2], d); w.ncb = pool.upload(ln_host[3], d);
+  w.n1g = pool.upload(ln_host[4], d); w.n1b = pool.upload(ln_host[5], d);
+  w.n2g = pool.upload(ln_host[6], d); w.n2b = pool.upload(ln_host[7], d);
+  w.dng = pool.upload(ln_host[8], d); w.dnb = pool.upload(ln_host[9], d);
+  parseq_dec_step(s, w, tok_dev, ns, step, skv_dev, ns, memkv_dev, l, mem_off_dev, mem_len_dev, out_dev, prev_not_done_dev, b, gid_dev,
+                  gopen_dev, ng);
+  YMK_HIP(hipStreamSynchronize(s));  // pool frees the weights on return
+  YMK_API_END
+}
+
+int ymk_op_greedy_step(const float* logits_dev, int64_t ld_b, int c, int step, int num_steps, int* tok_dev, int* raw_dev, int ld_tok,
+                       int* state_dev, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats, int* not_done_dev,
+                       const int* prev_not_done_dev, const int* gid_dev, int* gopen_dev, int ng, int partials, int b, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(logits_dev && tok_dev && raw_dev && state_dev && not_done_dev && b >= 1 && c >= 1, "greedy_step: bad argument");
+  YMK_CHECK(step >= 0 && step < num_steps && num_steps <= ld_tok, "greedy_step: 0 <= step < num_steps <= ld_tok");
+  YMK_CHECK(ld_b >= (int64_t)c * (partials ? 2 : 1), "greedy_step: rows overlap");
+  YMK_CHECK(!partials || (((uintptr_t)logits_dev | (uintptr_t)(ld_b * 4)) & 7) == 0, "greedy_step: (max, column) pairs must be 8 B aligned");
+  YMK_CHECK((gid_dev == nullptr) == (gopen_dev == nullptr) && ng >= 1, "greedy_step: gid and gopen come in pairs, ng >= 1");
+  YMK_CHECK(period_max >= 0, "greedy_step: period_max >= 0");
+  ymk::greedy_step((hipStream_t)stream, logits_dev, (long)ld_b, c, step, num_steps, tok_dev, raw_dev, ld_tok, state_dev, eos_id, rep_on,
+                   period_max, min_run_p1, min_repeats, not_done_dev, prev_not_done_dev, /*arrived=*/nullptr, /*host_flag=*/nullptr, b,
+                   gid_dev, gopen_dev, ng, partials);
+  YMK_API_END
+}
+
+int ymk_op_refine_prep(const int* raw_dev, int ld_tok, int s_len, int bos_id, int eos_id, int* tok2_dev, unsigned char* kpm_dev, int b,
+                       const int* gid_dev, const int* gsteps_dev, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(raw_dev && tok2_dev && kpm_dev && b >= 1 && s_len >= 1 && s_len <= ld_tok, "refine_prep: bad argument");
+  YMK_CHECK((gid_dev == nullptr) == (gsteps_dev == nullptr), "refine_prep: gid and gsteps come in pairs");
+  ymk::refine_prep((hipStream_t)stream, raw_dev, ld_tok, s_len, bos_id, eos_id, tok2_dev, kpm_dev, b, gid_dev, gsteps_dev);
+  YMK_API_END
+}
+
+int ymk_op_rep_cut(float* logits_dev, int64_t ld_b, int c, int s_len, const int* state_dev, int eos_id, int b, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(logits_dev && state_dev && b >= 1 && c >= 1 && s_len >= 0 && ld_b >= (int64_t)s_len * c, "rep_cut: bad argument");
+  ymk::rep_cut((hipStream_t)stream, logits_dev, (long)ld_b, c, s_len, state_dev, eos_id, b);
+  YMK_API_END
+}
+
+int ymk_op_row_argmax(const float* logits_dev, int rows, int c, int* out_dev, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(logits_dev && out_dev && rows >= 0 && c >= 1, "row_argmax: bad argument");
+  ymk::row_argmax((hipStream_t)stream, logits_dev, rows, c, out_dev);
+  YMK_API_END
+}
+
+int ymk_op_ctx_embed_ln(const int* tok_dev, int ld_tok, int pos0, int npos, const float* emb_dev, const float* posq_dev,
+                        const float* g_dev, const float* b_dev, float eps, float* out_dev, int out_rows, int d, int b, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(tok_dev && emb_dev && posq_dev && g_dev && b_dev && out_dev && b >= 1 && d >= 1, "ctx_embed_ln: bad argument");
+  YMK_CHECK(pos0 >= 0 && npos >= 0 && pos0 + npos <= ld_tok && pos0 + npos <= out_rows, "ctx_embed_ln: positions outside the rows");
+  ymk::ctx_embed_ln((hipStream_t)stream, tok_dev, ld_tok, pos0, npos, emb_dev, posq_dev, g_dev, b_dev, eps, out_dev, out_rows, d, b);
+  YMK_API_END
+}
+
+int ymk_op_init_decode(int* tok_dev, int ld_tok, int* state_dev, int bos_id, int pad_id, int b, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(tok_dev && state_dev && b >= 0, "init_decode: bad argument");
+  ymk::init_decode((hipStream_t)stream, tok_dev, ld_tok, state_dev, bos_id, pad_id, b);
+  YMK_API_END
+}
+
+int ymk_op_tile_rows(const float* src_dev, int rows, int d, float* dst_dev, int b, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(src_dev && dst_dev && rows >= 0 && d >= 0 && b >= 0 && ((size_t)rows * d) % 4 == 0, "tile_rows: rows * d must be a multiple of 4");
+  YMK_CHECK(aligned16(src_dev) && aligned16(dst_dev), "tile_rows: tensors must be 16 B aligned");
+  ymk::tile_rows((hipStream_t)stream, src_dev, rows, d, dst_dev, b);
+  YMK_API_END
+}
+
+int ymk_op_add_pos_embed(float* x_dev, const float* pos_dev, int b, int gh, int gw, int full_gw, int d, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(x_dev && pos_dev && b >= 1 && gh >= 1 && gw >= 1 && gw <= full_gw && d >= 4 && d % 4 == 0, "add_pos_embed: bad argument");
+  YMK_CHECK(aligned16(x_dev) && aligned16(pos_dev), "add_pos_embed: tensors must be 16 B aligned");
+  ymk::add_pos_embed((hipStream_t)stream, x_dev, pos_dev, b, gh, gw, full_gw, d);
   YMK_API_END
 }
 

@@ -12,6 +12,17 @@ struct DecStepW {
   int D, H, F;
 };
 
+// the decoder layer's matrices as the state dict holds them (host, nn.Linear layout [out][in]): self / cross attention
+// in_proj_weight [3 D][D] + in_proj_bias [3 D], the two out_proj, linear1 [F][D], linear2 [D][F]
+struct DecStepHostW {
+  const float *sa_in_w, *sa_in_b, *sa_out_w, *sa_out_b, *ca_in_w, *ca_in_b, *ca_out_w, *ca_out_b, *l1_w, *l1_b, *l2_w, *l2_b;
+  int D, H, F;
+};
+// uploads the transposed copies ([in][out]) and the biases the fused step reads and fills W's matrix fields and D, H, F: the K|V
+// rows of the self attention's in_proj, the query rows of the cross attention's.  The tables (emb, posq, qsa) and the LayerNorm
+// vectors stay the caller's.  One function for ymk_parseq.cpp finalize and for ymk_op_parseq_dec_step.
+void make_dec_step_weights(DevicePool& pool, const DecStepHostW& h, DecStepW& W);
+
 bool parseq_dec_step_supported(int D, int H, int F, int L, int NS);
 // gid / gopen (grouped forward): row b belongs to mini-batch gid[b]; gopen[step][g] = rows of g still lacking an <eos>
 // after that step.  A block whose mini-batch closed at an earlier step does nothing.

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <atomic>
 #include <string>
+#include <vector>
 
 #include "ymk_common.h"
 #include "ymk_decstep.h"
@@ -383,6 +384,31 @@ void parseq_dec_step(hipStream_t s, const DecStepW& W, const int* tok, int ld_to
   YMK_TRY_ROWS(1);
 #undef YMK_TRY_ROWS
   throw Error("fused decoder step: not even one row per block fits the LDS this device grants a workgroup");
+}
+
+void make_dec_step_weights(DevicePool& pool, const DecStepHostW& h, DecStepW& W) {
+  auto tr = [&](const float* w, int out, int in) {
+    std::vector<float> t((size_t)out * in);
+    for (int o = 0; o < out; ++o)
+      for (int k = 0; k < in; ++k) t[(size_t)k * out + o] = w[(size_t)o * in + k];
+    return pool.upload(t);
+  };
+  const int D = h.D, F = h.F;
+  W.D = D;
+  W.H = h.H;
+  W.F = F;
+  W.Wkv_t = tr(h.sa_in_w + (size_t)D * D, 2 * D, D);
+  W.bkv = pool.upload(h.sa_in_b + D, 2 * D);
+  W.Wo1_t = tr(h.sa_out_w, D, D);
+  W.bo1 = pool.upload(h.sa_out_b, D);
+  W.Wq_t = tr(h.ca_in_w, D, D);
+  W.bq = pool.upload(h.ca_in_b, D);
+  W.Wo2_t = tr(h.ca_out_w, D, D);
+  W.bo2 = pool.upload(h.ca_out_b, D);
+  W.W1_t = tr(h.l1_w, F, D);
+  W.b1 = pool.upload(h.l1_b, F);
+  W.W2_t = tr(h.l2_w, D, F);
+  W.b2 = pool.upload(h.l2_b, D);
 }
 
 bool parseq_dec_step_supported(int D, int H, int F, int L, int NS) {

@@ -25,8 +25,6 @@
 
 namespace ymk {
 
-void tile_rows(hipStream_t s, const float* src, int rows, int D, float* dst, int B);
-
 static std::atomic<int> g_parseq_unfused{0};  // ymk_debug_option("parseq_unfused", 1): per-op decoder path for every width (tests)
 static bool parseq_unfused() { return g_parseq_unfused.load(std::memory_order_relaxed) != 0; }
 static std::atomic<int> g_parseq_no_rowmax{0};  // ymk_debug_option("parseq_no_rowmax", 1): keep the AR logits (A/B, tests)
@@ -144,32 +142,21 @@ class ParseqModel : public Model {
     split_mha("cross_attn", ca_q_, ca_kv_, ca_o_);
     {
       // transposed copies ([in][out]) for the fused one-kernel decoder step (ymk_decstep.hip)
-      auto tr = [&](const float* w, int out, int in) {
-        std::vector<float> t((size_t)out * in);
-        for (int o = 0; o < out; ++o)
-          for (int k = 0; k < in; ++k) t[(size_t)k * out + o] = w[(size_t)o * in + k];
-        return pool.upload(t);
-      };
-      const HostTensor& sw = ws.get(d + "self_attn.in_proj_weight");
-      const HostTensor& sb = ws.get(d + "self_attn.in_proj_bias");
-      const HostTensor& cw = ws.get(d + "cross_attn.in_proj_weight");
-      const HostTensor& cb = ws.get(d + "cross_attn.in_proj_bias");
-      const int D = Dd_, F = (int)ws.get(d + "linear1.weight").dims[0];
-      fw_.D = D;
-      fw_.H = dh_;
-      fw_.F = F;
-      fw_.Wkv_t = tr(sw.data.data() + (size_t)D * D, 2 * D, D);
-      fw_.bkv = pool.upload(sb.data.data() + D, 2 * D);
-      fw_.Wo1_t = tr(ws.get(d + "self_attn.out_proj.weight").data.data(), D, D);
-      fw_.bo1 = pool.upload(ws.get(d + "self_attn.out_proj.bias").data);
-      fw_.Wq_t = tr(cw.data.data(), D, D);
-      fw_.bq = pool.upload(cb.data.data(), D);
-      fw_.Wo2_t = tr(ws.get(d + "cross_attn.out_proj.weight").data.data(), D, D);
-      fw_.bo2 = pool.upload(ws.get(d + "cross_attn.out_proj.bias").data);
-      fw_.W1_t = tr(ws.get(d + "linear1.weight").data.data(), F, D);
-      fw_.b1 = pool.upload(ws.get(d + "linear1.bias").data);
-      fw_.W2_t = tr(ws.get(d + "linear2.weight").data.data(), D, F);
-      fw_.b2 = pool.upload(ws.get(d + "linear2.bias").data);
+      auto hp = [&](const std::string& n) { return ws.get(d + n).data.data(); };
+      const HostTensor& l1 = ws.get(d + "linear1.weight");
+      const HostTensor& l2 = ws.get(d + "linear2.weight");
+      const int F = (int)l1.dims[0];
+      YMK_CHECK((int)l1.dims[1] == Dd_ && (int)l2.dims[0] == Dd_ && (int)l2.dims[1] == F, "decoder linear1 / linear2 shape");
+      YMK_CHECK((int)ws.get(d + "linear1.bias").numel() == F && (int)ws.get(d + "linear2.bias").numel() == Dd_ &&
+                    (int)ws.get(d + "self_attn.out_proj.weight").numel() == Dd_ * Dd_ &&
+                    (int)ws.get(d + "cross_attn.out_proj.weight").numel() == Dd_ * Dd_ &&
+                    (int)ws.get(d + "self_attn.out_proj.bias").numel() == Dd_ && (int)ws.get(d + "cross_attn.out_proj.bias").numel() == Dd_,
+                "decoder layer: out_proj / bias shapes");
+      const DecStepHostW hw{hp("self_attn.in_proj_weight"), hp("self_attn.in_proj_bias"), hp("self_attn.out_proj.weight"),
+                            hp("self_attn.out_proj.bias"), hp("cross_attn.in_proj_weight"), hp("cross_attn.in_proj_bias"),
+                            hp("cross_attn.out_proj.weight"), hp("cross_attn.out_proj.bias"), hp("linear1.weight"),
+                            hp("linear1.bias"), hp("linear2.weight"), hp("linear2.bias"), Dd_, dh_, F};
+      make_dec_step_weights(pool, hw, fw_);
     }
     lin1_ = make_linear(pool, ws, d + "linear1");
     lin2_ = make_linear(pool, ws, d + "linear2");

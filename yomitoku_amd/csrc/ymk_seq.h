@@ -49,6 +49,8 @@ void refine_prep(hipStream_t s, const int* raw, int ld_tok, int S, int bos_id, i
 void row_argmax(hipStream_t s, const float* logits, int rows, int C, int* out);
 void rep_cut(hipStream_t s, float* logits, long ld_b, int C, int S, const int* state, int eos_id, int B);
 void row_maxprob(hipStream_t s, const float* logits, int rows, int C, int* ids, float* probs);
+// dst[b][r][:] = src[r][:] for b < B (rows * D a multiple of 4, both 16 B aligned)
+void tile_rows(hipStream_t s, const float* src, int rows, int D, float* dst, int B);
 void fill_i32(hipStream_t s, int* p, int v, size_t n);
 
 }  // namespace ymk

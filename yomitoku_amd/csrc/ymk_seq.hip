@@ -684,7 +684,9 @@ __device__ __forceinline__ void row_reduce_256(const float* __restrict__ row, in
                                                float& sum) {
   const int t = threadIdx.x;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
+  // the thread's own first column: a row whose maximum is -inf then still reduces to column 0, as torch.argmax (a thread
+  // without a column keeps the sentinel, which loses every tie)
+  int bi = t < C ? t : 0x7fffffff;
   float v[ROW_RV];
   const bool in_regs = C <= 256 * ROW_RV;
   if (in_regs) {
