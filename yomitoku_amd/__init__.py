@@ -4,6 +4,9 @@
     analyzer = DocumentAnalyzer(configs={...}, device="cuda")
     results, ocr_vis, layout_vis = analyzer(img_bgr_uint8)
 
+    from yomitoku_amd import TableSemanticParser
+    tables, _, _ = TableSemanticParser(device="cuda")(img_bgr_uint8)   # grids and key-value items of forms and tables
+
 Importing the package does not load the HIP library; the first module construction does
 (`yomitoku_amd._lib.load()` raises if libymk_hip.so has not been built - there is no CPU fallback).
 """
@@ -18,7 +21,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 __version__ = "0.1.0"
 
 __all__ = ["DocumentAnalyzer", "OCR", "LayoutAnalyzer", "TextDetector", "TextRecognizer", "LayoutParser",
-           "TableStructureRecognizer"]
+           "TableStructureRecognizer", "TableSemanticParser"]
 
 
 def __getattr__(name):
@@ -42,4 +45,8 @@ def __getattr__(name):
         from .table_structure_recognizer import TableStructureRecognizer
 
         return TableStructureRecognizer
+    if name == "TableSemanticParser":
+        from .table_semantic_parser import TableSemanticParser
+
+        return TableSemanticParser
     raise AttributeError(name)

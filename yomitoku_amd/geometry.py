@@ -207,3 +207,16 @@ def adjacency_matrices(boxes_a, boxes_b, dist_threshold=15, overlap_ratio_th=0.1
     bottom &= ~((np.hypot(ax2 - bx1, ay2 - by1) < ignore_dist_threshold) | (np.hypot(ax1 - bx2, ay2 - by1) < ignore_dist_threshold))
     bottom &= soft((ax1, ay2), (ax2, ay2), (bx1, by1), (bx2, by1))
     return right, bottom
+
+
+# ---------------------------------------------------------------------------------------------- table semantic parser
+# what grid_parser.py / kv_parser.py call beyond the predicates above (utils/misc.py:270-274, :430-448 of the reference)
+def overlap_interval(i1, i2, j1, j2):
+    """Length of the overlap of [i1, i2] and [j1, j2] (0.0 when they are apart)."""
+    return _overlap_interval(i1, i2, j1, j2)
+
+
+def get_line_with_head(dag, head, dir_value):
+    """`head` and every node reachable from it along edges whose "dir" is `dir_value` (a row for "R", a column for "D"),
+    breadth first; `dag` is a yomitoku_amd.utils.graph.OrderedDiGraph."""
+    return dag.descendants_by(head, lambda d: d.get("dir") == dir_value)

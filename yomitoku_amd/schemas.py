@@ -153,3 +153,13 @@ class TableDetectorSchema(BaseSchema):
     cells: List[CellSchema]
     kv_regions: List[RegionSchema] = Field(default_factory=list)
     grid_regions: List[RegionSchema] = Field(default_factory=list)
+
+
+# ---- table semantic parser: the result types live in table_semantic_schemas.py (which builds on the classes above) and
+# are reachable from here as well, like every other schema
+def __getattr__(name):
+    from . import table_semantic_schemas
+
+    if name in table_semantic_schemas.__all__:
+        return getattr(table_semantic_schemas, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -228,6 +228,35 @@ class CellDetector(BaseModule):
             raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
         return outputs
 
+    def detect_pages(self, imgs, tables_per_page):
+        """`__call__` for several pages: the tables of ALL pages share forwards of up to MAX_TABLES_PER_FORWARD crops (images
+        of a batch are independent).  tables_per_page[k]: the table elements of imgs[k].  Returns [[TableDetectorSchema]], one
+        list per page, each what `__call__(imgs[k], tables_per_page[k])` returns."""
+        if self.visualize:
+            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
+        pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, self.device) for img in imgs]
+        jobs = [(k, table) for k, tables in enumerate(tables_per_page) for table in tables]
+        outputs = [[] for _ in pages]
+        oh, ow = (int(v) for v in self._cfg.data.img_size)
+        for start in range(0, len(jobs), self.MAX_TABLES_PER_FORWARD):
+            chunk = jobs[start : start + self.MAX_TABLES_PER_FORWARD]
+            batch = torch.empty((len(chunk), 3, oh, ow), dtype=torch.float32, device=pages[chunk[0][0]].device)
+            metas = []
+            for i, (k, table) in enumerate(chunk):
+                _, size, offset = imaging.rtdetr_tensor(pages[k], table.box, (oh, ow), out=batch[i])
+                metas.append({"size": size, "offset": offset})
+            preds = self.model(batch)
+            logits = preds["pred_logits"].cpu().numpy()
+            boxes = preds["pred_boxes"].cpu().numpy()
+            for i, (data, (k, table)) in enumerate(zip(metas, chunk)):
+                one = {"pred_logits": logits[i : i + 1], "pred_boxes": boxes[i : i + 1]}
+                cells, kv_regions, grid_regions = self.postprocess(one, data, table.box)
+                if len(cells) == 0:
+                    continue
+                outputs[k].append(TableDetectorSchema(id=None, box=table.box, role=table.role, cells=cells, kv_regions=kv_regions,
+                                                      grid_regions=grid_regions))
+        return outputs
+
 
 __all__ = ["CellDetector", "TableParserModelCatalog", "find_holes_as_rects", "calc_adjacent_holes_to_cells", "choose_role",
            "filter_contained_rectangles_with_category", "filter_contained_rectangles_across_categories", "logger"]
