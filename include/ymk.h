@@ -171,6 +171,41 @@ int ymk_crop_batch_levels(const unsigned char* const* level_pages, const int* le
 int ymk_halve_u8c3(const unsigned char* src_dev, int h, int w, unsigned char* dst_dev, int dst_h, int dst_w, void* stream);
 int ymk_crop_desc_size(void);
 
+/* ---- overlay rasteriser for visualize=True (yomitoku_amd/csrc/ymk_overlay.hip; replaces the cv2 / Pillow drawing of
+ * utils/visualizer.py on host copies of the page).  DESIGN.md, "Overlay rasteriser", has the drawing rules in full.
+ * ymk_draw_overlay: applies n commands IN COMMAND ORDER, in place, to canvas_dev: uint8 [h][w][3], 1 <= h, w <= 16383.  One block
+ *   per tile of ymk_overlay_tile() x ymk_overlay_tile() pixels, tiles row-major ((w + tile - 1) / tile per row).  The caller bins
+ *   the commands by bounding box: tile_offsets_dev int32 [tiles + 1] (ascending, [0] = 0, [tiles] = n_list), tile_cmds_dev int32
+ *   [n_list] = for each tile the indices of the commands that may cover one of its pixels, ascending.  A block stages its list in
+ *   LDS ymk_overlay_chunk() records at a time; a tile with an empty list is neither read nor written.  A list entry outside
+ *   [0, n), an unknown kind and a glyph byte outside [0, atlas_bytes) draw nothing.  Nothing is allocated and nothing waited for.
+ *   cmds_dev: n records of YMK_OVERLAY_CMD_WORDS int32 words (16-byte aligned), all coordinates in [-16383, 16383]:
+ *     word 0     kind: YMK_OVERLAY_SEG | YMK_OVERLAY_BOX | YMK_OVERLAY_GLYPH
+ *     words 1-3  colour in the canvas's channel order (B, G, R), 0..255
+ *     word 4     alpha 0..255 of SEG and BOX (GLYPH takes its alpha from the atlas)
+ *     SEG    words 5-9   x0, y0, x1, y1, t     a segment of thickness t with round caps: with d = P1 - P0, L2 = d.d, q = p - P0,
+ *                        u = q.d the pixel p is covered iff   L2 == 0 or u <= 0: 4 |q|^2 <= t^2;   u >= L2: 4 |p - P1|^2 <= t^2;
+ *                        otherwise 4 (q x d)^2 <= t^2 L2
+ *     BOX    words 5-12  ox1, oy1, ox2, oy2, ix1, iy1, ix2, iy2   covered iff inside the outer box and not inside the inner box
+ *                        (both inclusive; the inner box is empty when ix1 > ix2 or iy1 > iy2)
+ *     GLYPH  words 5-10  x, y, w, h, atlas_offset, pitch   alpha = atlas_dev[atlas_offset + (py - y) * pitch + (px - x)] for
+ *                        pixels in [x, x + w) x [y, y + h); atlas_dev: uint8 [atlas_bytes]
+ *   Blend of a covered pixel, per channel: dst = (colour * a + dst * (255 - a) + 127) / 255 (a = 255 overwrites, 0 leaves).
+ * ymk_heatmap_blend: prob_dev fp32 [mh][mw] blended over canvas_dev uint8 [h][w][3] in place, det_visualizer(vis_heatmap=True)
+ *   in integers: m = (uint8) trunc(clamp(p, 0, 1) * 255); per axis X = ((2 x + 1) * mw * 1024) / (2 w) - 512 clamped to
+ *   [0, (mw - 1) * 1024], taps X >> 10 and min(that + 1, mw - 1), weight X & 1023; v = (sum of the four weighted taps + 2^19)
+ *   >> 20; dst = (dst + jet_dev[v][channel] + 1) >> 1 with jet_dev: uint8 [256][3] (B, G, R). */
+#define YMK_OVERLAY_CMD_WORDS 16
+#define YMK_OVERLAY_SEG 0
+#define YMK_OVERLAY_BOX 1
+#define YMK_OVERLAY_GLYPH 2
+int ymk_draw_overlay(unsigned char* canvas_dev, int h, int w, const int* cmds_dev, int n, const int* tile_offsets_dev,
+                     const int* tile_cmds_dev, int n_list, const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream);
+int ymk_heatmap_blend(unsigned char* canvas_dev, int h, int w, const float* prob_dev, int mh, int mw, const unsigned char* jet_dev,
+                      void* stream);
+int ymk_overlay_tile(void);
+int ymk_overlay_chunk(void);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

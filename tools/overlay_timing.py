@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""What a visualize=True overlay costs, for profiles/visualize_overlay.json (run by hand on the GPU, not by the suite).
+
+    python tools/overlay_timing.py [--out FILE]
+
+One 1600 x 1200 page carrying 300 quads (closed polylines, t = 1), 300 labelled boxes (outline t = 2 + a 12 px label) and 300
+text lines of 20 characters (18 px).  Reported, each the median of 20 runs after 3 warm-ups, one process, nothing else on the card:
+  draw_overlay_device_ms   ymk_draw_overlay alone, HIP events around the launch
+  build_and_bin_host_ms    building the command list, the atlas and the per-tile lists on the host
+  render_wall_ms           Overlay.render on a device page: build + one H2D blob + clone + launch, host clock to a synchronise
+  d2h_ms                   the finished image to a host array
+  pillow_host_ms           Pillow's ImageDraw drawing the same content on a host copy of the page - how the reference draws
+Built-in font on both sides, so the glyph work is the same."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+H, W, N, CHARS = 1600, 1200, 300, 20
+RUNS, WARMUP = 20, 3
+
+
+def content(seed=0):
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    x, y = rng.integers(0, W - 260, N), rng.integers(20, H - 40, N)
+    bw, bh = rng.integers(60, 250, N), rng.integers(14, 32, N)
+    quads = np.stack([np.stack([x, y], 1), np.stack([x + bw, y], 1), np.stack([x + bw, y + bh], 1), np.stack([x, y + bh], 1)], 1)
+    bx, by = rng.integers(0, W - 400, N), rng.integers(20, H - 300, N)
+    boxes = np.stack([bx, by, bx + rng.integers(50, 400, N), by + rng.integers(30, 300, N)], 1)
+    alphabet = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
+    lines = ["".join(alphabet[int(k)] for k in rng.integers(0, len(alphabet), CHARS)) for _ in range(N)]
+    return quads, boxes, lines
+
+
+def build_overlay(quads, boxes, lines):
+    from yomitoku_amd.utils.visualizer import Overlay, load_font
+
+    ov = Overlay()
+    label, text = load_font(None, 12), load_font(None, 18)
+    ov.polyline(quads, True, (0, 255, 0), 1)
+    for k, b in enumerate(boxes.tolist()):
+        ov.rectangle(b, (255, 0, 255), 2)
+        ov.text((b[0], b[1]), f"paragraphs({k})", label, (255, 0, 0), anchor="ls")
+    for q, s in zip(quads.tolist(), lines):
+        ov.text((q[0][0], q[0][1] - 18), s, text, (0, 0, 255))
+    return ov
+
+
+def pillow_draw(page, quads, boxes, lines):
+    from PIL import Image, ImageDraw, ImageFont
+
+    img = Image.fromarray(page.copy())
+    draw = ImageDraw.Draw(img)
+    label, text = ImageFont.load_default(12), ImageFont.load_default(18)
+    for q in quads.tolist():
+        draw.line([tuple(p) for p in q] + [tuple(q[0])], fill=(0, 255, 0), width=1)
+    for k, b in enumerate(boxes.tolist()):
+        draw.rectangle(b, outline=(255, 0, 255), width=2)
+        draw.text((b[0], b[1]), f"paragraphs({k})", font=label, fill=(255, 0, 0), anchor="ls")
+    for q, s in zip(quads.tolist(), lines):
+        draw.text((q[0][0], q[0][1] - 18), s, font=text, fill=(0, 0, 255))
+    import numpy as np
+
+    return np.asarray(img)
+
+
+def median_ms(fn, sync=None):
+    out = []
+    for _ in range(RUNS + WARMUP):
+        if sync:
+            sync()
+        t0 = time.perf_counter()
+        fn()
+        if sync:
+            sync()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return round(statistics.median(out[WARMUP:]), 3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    import torch
+
+    from yomitoku_amd.utils.synth import synthetic_page
+    from yomitoku_amd.utils.visualizer import launch_staged, stage_commands
+
+    assert torch.cuda.is_available(), "overlay_timing.py measures on the GPU"
+    page = synthetic_page(0, H, W)
+    page_dev = torch.from_numpy(page).to("cuda:0")
+    quads, boxes, lines = content()
+    sync = torch.cuda.synchronize
+
+    ov = build_overlay(quads, boxes, lines)
+    data = ov.build(H, W)
+    canvas = page_dev.clone()
+    staged = stage_commands(canvas, data["cmds"], data["atlas"], lists=(data["tile_offsets"], data["tile_cmds"]))
+    kernel = []
+    for _ in range(RUNS + WARMUP):  # the same canvas again and again: the work per pixel does not depend on its colour
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        launch_staged(canvas, staged)
+        b.record()
+        b.synchronize()
+        kernel.append(a.elapsed_time(b))
+    per_tile = data["tile_offsets"][1:] - data["tile_offsets"][:-1]
+    result = {
+        "page": [H, W], "quads": N, "labelled_boxes": N, "text_lines": N, "chars_per_line": CHARS,
+        "commands": int(len(data["cmds"])), "list_entries": int(len(data["tile_cmds"])), "tiles": int(len(per_tile)),
+        "tiles_with_commands": int((per_tile > 0).sum()), "longest_tile_list": int(per_tile.max()), "atlas_bytes": int(data["atlas"].size),
+        "runs": RUNS, "warmup": WARMUP,
+        "draw_overlay_device_ms": round(statistics.median(kernel[WARMUP:]), 4),
+        "build_and_bin_host_ms": median_ms(lambda: build_overlay(quads, boxes, lines).build(H, W)),
+        "render_wall_ms": median_ms(lambda: build_overlay(quads, boxes, lines).render(page_dev), sync),
+        "d2h_ms": median_ms(lambda: canvas.cpu().numpy(), sync),
+        "pillow_host_ms": median_ms(lambda: pillow_draw(page, quads, boxes, lines)),
+        "device": torch.cuda.get_device_name(0),
+    }
+    text = json.dumps(result, indent=1)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()

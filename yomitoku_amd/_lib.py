@@ -53,6 +53,10 @@ SIGNATURES = {
     ),
     "ymk_halve_u8c3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "ymk_crop_desc_size": (c_int, []),
+    "ymk_draw_overlay": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "ymk_heatmap_blend": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_overlay_tile": (c_int, []),
+    "ymk_overlay_chunk": (c_int, []),
     "ymk_db_postprocess": (
         c_int,
         [c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,

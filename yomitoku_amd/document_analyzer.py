@@ -34,6 +34,11 @@ from .table_structure_recognizer import TableStructureRecognizer
 from .text_detector import TextDetector
 from .text_recognizer import TextRecognizer
 
+def _vis_to_host(vis):
+    """What a public call returns for `vis`: the device canvas of a visualize=True chain as np.ndarray (None stays None)."""
+    return vis if vis is None or isinstance(vis, np.ndarray) else vis.cpu().numpy()
+
+
 _USAGE = "configs must be a dict. See the https://kotaro-kinoshita.github.io/yomitoku/module/#config"
 
 
@@ -59,9 +64,9 @@ class OCR:
 
     def __call__(self, img):
         page = imaging.page_to_device(img, self.detector.device) if not isinstance(img, torch.Tensor) else img
-        det_outputs, vis = self.detector(page)
-        rec_outputs, vis = self.recognizer(page, det_outputs.points, vis=vis)
-        return OCRSchema(words=ocr_aggregate(det_outputs, rec_outputs)), vis
+        det_outputs, vis = self.detector._call(page, to_host=False)  # the overlay stays on the device inside the chain
+        rec_outputs, vis = self.recognizer._call(page, det_outputs.points, vis=vis, to_host=False)
+        return OCRSchema(words=ocr_aggregate(det_outputs, rec_outputs)), _vis_to_host(vis)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -77,13 +82,17 @@ class LayoutAnalyzer:
         self.table_structure_recognizer = TableStructureRecognizer(**ts_kwargs)
 
     def __call__(self, img):
+        return self._call(img)
+
+    def _call(self, img, to_host=True):
+        """`__call__`; to_host False leaves the overlay on the device (DocumentAnalyzer draws the reading order onto it)."""
         page = imaging.page_to_device(img, self.layout_parser.device) if not isinstance(img, torch.Tensor) else img
-        layout_results, vis = self.layout_parser(page)
+        layout_results, vis = self.layout_parser._call(page, to_host=False)
         table_boxes = [t.box for t in layout_results.tables]
-        table_results, vis = self.table_structure_recognizer(page, table_boxes, vis=vis)
+        table_results, vis = self.table_structure_recognizer._call(page, table_boxes, vis=vis, to_host=False)
         results = LayoutAnalyzerSchema(paragraphs=layout_results.paragraphs, tables=table_results,
                                        figures=layout_results.figures)
-        return results, vis
+        return results, _vis_to_host(vis) if to_host else vis
 
 
 # ---------------------------------------------------------------------------------------------- aggregation helpers
@@ -424,22 +433,33 @@ class DocumentAnalyzer:
             stream.synchronize()
         return out
 
+    def _vis_det(self, page, results_det):
+        """document_analyzer.py:613-617: the analyzer's own detection overlay (default colour, no heat map) - the canvas the
+        recogniser draws its strings onto.  Stays on the device."""
+        if not self.visualize:
+            return None
+        from .utils.visualizer import det_visualizer
+
+        return det_visualizer(page, results_det.points, to_host=False)
+
     def _detect_and_recognize(self, page):
-        results_det, _ = self.text_detector(page)
-        results_rec, ocr = self.text_recognizer(page, results_det.points, None)
+        results_det, _ = self.text_detector.detect(page)
+        results_rec, ocr = self.text_recognizer._call(page, results_det.points, self._vis_det(page, results_det), to_host=False)
         return results_det, results_rec, ocr
 
     def run(self, page):
+        """(results, ocr overlay, layout overlay); with visualize=True the overlays are device canvases (`__call__` brings them
+        to the host)."""
         if self.split_text_across_cells:
-            f_det = self._submit("ocr", self.text_detector, page)
-            f_lay = self._submit("layout", self.layout, page)
+            f_det = self._submit("ocr", self.text_detector.detect, page)
+            f_lay = self._submit("layout", self.layout._call, page, False)
             results_det, _ = f_det.result()
             results_layout, layout = f_lay.result()
             results_det = _split_text_across_cells(results_det, results_layout)
-            results_rec, ocr = self.text_recognizer(page, results_det.points, None)
+            results_rec, ocr = self.text_recognizer._call(page, results_det.points, self._vis_det(page, results_det), to_host=False)
         else:
             f_ocr = self._submit("ocr", self._detect_and_recognize, page)
-            f_lay = self._submit("layout", self.layout, page)
+            f_lay = self._submit("layout", self.layout._call, page, False)
             results_det, results_rec, ocr = f_ocr.result()
             results_layout, layout = f_lay.result()
         results_ocr = OCRSchema(words=ocr_aggregate(results_det, results_rec))
@@ -526,12 +546,11 @@ class DocumentAnalyzer:
         """`__call__` over a list of pages, `wave` pages at a time on the device.  Every page's result is what
         `__call__(img)` returns for it (pages never interact: batches are per-image independent, recogniser
         mini-batches are formed per page); what changes is how the launches are shared.  The two chains of a wave
-        run concurrently on their own HIP streams, as in `run`.  Returns [(DocumentAnalyzerSchema, None, None), ...].
+        run concurrently on their own HIP streams, as in `run`.  Returns [(DocumentAnalyzerSchema, ocr_vis, layout_vis), ...]
+        (the two images of `__call__` with visualize=True, else None).
         One wave at a time: `serve` is the throughput path (several waves in flight, failures isolated per page)."""
         from .serving import Wave
 
-        if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
         dev = self.text_detector.device
         out = []
         size = max(1, int(wave))
@@ -546,8 +565,35 @@ class DocumentAnalyzer:
             if self.split_text_across_cells:
                 self._stage_split(w)
                 self._submit("ocr", self._recognize_wave, w).result()
-            out.extend((self._stage_finish(w, k), None, None) for k in range(len(chunk)))
+            out.extend(self._with_overlays(w, k, self._stage_finish(w, k)) for k in range(len(chunk)))
         return out
+
+    def _with_overlays(self, wave, k, results):
+        """(results, ocr overlay, layout overlay) of page k of a finished wave: the images `__call__` returns for the page -
+        each module that was built with visualize=True draws what its own `__call__` draws, from the wave's per-page results.
+        (results, None, None) when nothing visualises."""
+        lp, ts = self.layout.layout_parser, self.layout.table_structure_recognizer
+        page = wave.pages[k]
+        ocr = self._vis_det(page, wave.dets[k])
+        if self.text_recognizer.visualize:
+            ocr = self.text_recognizer._visualize(page, wave.recs[k], ocr, to_host=False)
+        layout = None
+        if lp.visualize:
+            from .utils.visualizer import layout_visualizer
+
+            layout = layout_visualizer(wave.lay_parsed[k], page, to_host=False)
+        if ts.visualize:
+            layout = ts._visualize(page, wave.lays[k].tables, layout, to_host=False)
+        if self.visualize:
+            layout = self._vis_reading_order(page, layout, results)
+        return results, _vis_to_host(ocr), _vis_to_host(layout)
+
+    def _vis_reading_order(self, page, layout, results):
+        """document_analyzer.py:675-676: order numbers and arrows on the layout overlay (on a copy of the page when the layout
+        modules drew none)."""
+        from .utils.visualizer import reading_order_visualizer
+
+        return reading_order_visualizer(page if layout is None else layout, results, to_host=False)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
@@ -563,7 +609,8 @@ class DocumentAnalyzer:
         from .serving import PagePipeline
 
         if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
+            raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: a rendering stage in the page "
+                                      "pipeline is a change of its own (visualize=False only; __call__ and analyze_pages draw)")
         pipe = getattr(self, "_pipeline", None)
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
             if pipe is not None:
@@ -592,5 +639,5 @@ class DocumentAnalyzer:
         page = img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, dev)
         results, ocr, layout = self.run(page)
         if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
-        return results, ocr, layout
+            layout = self._vis_reading_order(page, layout, results)
+        return results, _vis_to_host(ocr), _vis_to_host(layout)

@@ -220,9 +220,16 @@ class LayoutParser(BaseModule):
         return self.pages_from_raw(self.forward_pages(imgs))
 
     def __call__(self, img):
+        return self._call(img)
+
+    def _call(self, img, to_host=True):
+        """`__call__`; to_host False leaves the overlay on the device (LayoutAnalyzer hands it to the table recogniser)."""
         ori_h, ori_w = img.shape[:2]
         preds = self.model(self.preprocess(img))
         results = self.postprocess(preds, (ori_h, ori_w))
+        vis = None
         if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
-        return results, None
+            from .utils.visualizer import device_page, layout_visualizer
+
+            vis = layout_visualizer(results, device_page(img, self.device), to_host=to_host)
+        return results, vis

@@ -168,6 +168,17 @@ class TableStructureRecognizer(BaseModule):
         return self.tables_from_raw(self.forward_tables(imgs, boxes_list), len(imgs))
 
     def __call__(self, img, table_boxes, vis=None):
+        return self._call(img, table_boxes, vis)
+
+    def _visualize(self, img, outputs, vis, to_host=True):
+        """table_structure_recognizer.py:280-288: every table's cells drawn onto `vis` (a host array or a device canvas), or
+        onto a copy of the page - all tables of the page in one launch."""
+        from .utils.visualizer import device_page, tables_visualizer
+
+        return tables_visualizer(device_page(img if vis is None else vis, self.device), outputs, to_host=to_host)
+
+    def _call(self, img, table_boxes, vis=None, to_host=True):
+        """`__call__`; to_host False leaves the overlay on the device."""
         outputs = []
         for start in range(0, len(table_boxes), self.MAX_TABLES_PER_FORWARD):
             batch, metas = self.preprocess(img, table_boxes[start : start + self.MAX_TABLES_PER_FORWARD])
@@ -178,5 +189,5 @@ class TableStructureRecognizer(BaseModule):
                 if table.n_row > 0 and table.n_col > 0:
                     outputs.append(table)
         if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
+            vis = self._visualize(img, outputs, vis, to_host)
         return outputs, vis

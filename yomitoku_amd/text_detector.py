@@ -162,11 +162,24 @@ class TextDetector(BaseModule):
         return self.extract_boxes(maps, [tuple(int(v) for v in p.shape[:2]) for p in pages])
 
     def __call__(self, img):
+        return self._call(img)
+
+    def detect(self, img):
+        """`__call__` without the overlay: (TextDetectorSchema, the network's output)."""
         ori_h, ori_w = img.shape[:2]
         tensor = self.preprocess(img)
         preds = self.model(tensor)
         quads, scores = self.postprocess(preds, (ori_h, ori_w))
-        results = TextDetectorSchema(points=quads, scores=scores)
+        return TextDetectorSchema(points=quads, scores=scores), preds
+
+    def _call(self, img, to_host=True):
+        """`__call__`; to_host False leaves the overlay on the device (the orchestrators hand it to the recogniser)."""
+        results, preds = self.detect(img)
+        quads = results.points
+        vis = None
         if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
-        return results, None
+            from .utils.visualizer import det_visualizer, device_page
+
+            vis = det_visualizer(device_page(img, self.device), quads, preds=preds, vis_heatmap=self._cfg.visualize.heatmap,
+                                 line_color=tuple(self._cfg.visualize.color[::-1]), to_host=to_host)
+        return results, vis

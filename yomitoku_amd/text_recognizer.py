@@ -440,6 +440,18 @@ class TextRecognizer(BaseModule):
         return self.finish_plan(self.forward_plan(self.plan_pages(imgs, points_list)))
 
     def __call__(self, img, points=None, vis=None):
+        return self._call(img, points, vis)
+
+    def _visualize(self, img, results, vis, to_host=True):
+        """text_recognizer.py:388-397: the strings drawn onto `vis` (a host array or a device canvas), or onto a copy of the page."""
+        from .utils.visualizer import device_page, rec_visualizer
+
+        return rec_visualizer(device_page(img if vis is None else vis, self.device), results, font_path=self._cfg.visualize.font,
+                              font_size=self._cfg.visualize.font_size, font_color=tuple(self._cfg.visualize.color[::-1]),
+                              to_host=to_host)
+
+    def _call(self, img, points=None, vis=None, to_host=True):
+        """`__call__`; to_host False leaves the overlay on the device."""
         batches, points, dataset, order = self.preprocess(img, points)
         if order is not None:
             sorted_points = [points[i] for i in order]
@@ -455,5 +467,5 @@ class TextRecognizer(BaseModule):
         preds, scores, directions = self._with_placeholders(dataset, points, preds, scores, directions)
         results = TextRecognizerSchema(contents=preds, scores=scores, points=points, directions=directions)
         if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
+            vis = self._visualize(img, results, vis, to_host)
         return results, vis
