@@ -31,6 +31,8 @@
 
 namespace ymk {
 
+// This file builds stand-alone against a copy of the product sources (build.sh) and records the kernel as the experiment ran
+// it, so it KEEPS its own copy of the scale and of the eight-wide cut; the product kernels share ymk_f16_planes.h.
 typedef _Float16 hf16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 hf16x8_t __attribute__((ext_vector_type(8)));
 typedef float hf32x2_t __attribute__((ext_vector_type(2)));

@@ -3,32 +3,8 @@
 #include "ymk_common.h"
 #include "ymk_decstep.h"
 #include "ymk_det.h"
+#include "ymk_entry.h"
 #include "ymk_seq.h"
-
-namespace ymk {
-const std::string& last_error();
-void dbnet_forward(Model* m, const float* x, int n, int h, int w, float* prob, hipStream_t s);
-void parseq_forward(Model* m, const float* x, int B, int W, float* logits, int* out_len, int* ar_steps, hipStream_t s);
-void parseq_forward_groups(Model* m, const float* const* x, const int* b, const int* w, int ng, float* logits, int* out_len,
-                           int* ar_steps, hipStream_t s);
-void parseq_dims(Model* m, int* num_steps, int* num_classes);
-Model* create_parseq();
-Model* create_rtdetr();
-void rtdetr_forward(Model* m, const float* x, int B, int H, int W, float* logits, float* boxes, hipStream_t s);
-void row_maxprob(hipStream_t s, const float* logits, int rows, int C, int* ids, float* probs);
-void prof_begin();
-void prof_end(double* ms, double* flop, int64_t* launches);
-double prof_bytes();
-int64_t prof_launch_table(double* ms, double* flop, double* bytes, double* products, int64_t capacity);
-bool gemm_takes_astat(int M, int K, const ConvW& w, bool with_res, int ld);
-bool conv_debug_option(const std::string& key, int value);
-bool parseq_debug_option(const std::string& key, int value);
-bool decstep_debug_option(const std::string& key, int value);
-bool conv_split_debug_option(const std::string& key, int value);
-bool conv_split_stat(const std::string& key, long long* value);
-bool parseq_stat(const std::string& key, long long* value);
-void amax_check_counters(long long* out4);
-}  // namespace ymk
 
 struct ymk_model {
   ymk::Model* impl = nullptr;

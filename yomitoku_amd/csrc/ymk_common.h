@@ -20,6 +20,7 @@
 namespace ymk {
 
 void set_error(const std::string& msg);
+const std::string& last_error();
 
 struct Error : public std::runtime_error {
   explicit Error(const std::string& m) : std::runtime_error(m) {}
@@ -91,7 +92,7 @@ struct Tensor {
   unsigned* amax = nullptr;  // record of max|x| over the tensor, filled by its producer (see above), or null
   // true: the values are stored as the two scaled fp16 planes the fp16-split kernels multiply with, not as fp32 - per pixel and
   // 32-channel slice 32 high halves then 32 low halves (128 bytes, where the fp32 form has its 32 floats: same size, same ld),
-  // scaled by the power of two that f16 scales derive from the record `amax` (which then holds the producer's BOUND, below).
+  // scaled by the power of two that f16_plane_scales (ymk_f16_planes.h) derives from the record `amax` (which then holds the producer's BOUND, below).
   // Only a k x k convolution on the LDS-DMA kernel reads such a tensor (conv_planes_pair_ok decides; ymk_conv_dma.hip).
   bool planes = false;
   size_t pixels() const { return (size_t)n * h * w; }

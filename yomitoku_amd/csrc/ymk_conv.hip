@@ -30,6 +30,7 @@
 #include <mutex>
 
 #include "ymk_conv_kernel.h"
+#include "ymk_entry.h"
 
 namespace ymk {
 
@@ -539,49 +540,8 @@ int64_t prof_launch_table(double* ms, double* flop, double* bytes, double* produ
   return n;
 }
 
-// open a timed span for one launch when profiling is on (returns the event pair to close it with)
-std::pair<hipEvent_t, hipEvent_t>* conv_prof_open(hipStream_t s, const ConvK& k, int BM, int BN, int grid, int ksplit) {
-  std::pair<hipEvent_t, hipEvent_t>* e = nullptr;
-  if (g_prof.on) {
-    std::lock_guard<std::mutex> lock(g_prof.mu);
-    if (g_prof.used == g_prof.ev.size()) {
-      std::pair<hipEvent_t, hipEvent_t> n;
-      YMK_HIP(hipEventCreate(&n.first));
-      YMK_HIP(hipEventCreate(&n.second));
-      g_prof.ev.push_back(n);
-    }
-    e = &g_prof.ev[g_prof.used++];
-    const int creal = k.mode == 0 ? k.C : 3;
-    const double fl = 2.0 * (double)k.M * (double)k.Cout * (double)(k.KH * k.KW * creal);
-    g_prof.flop += fl;
-    const double images = (double)k.M / ((double)k.OH * k.OW);
-    const double outs = (double)k.M * k.Cout;
-    const double by = 4.0 * (images * k.H * k.W * creal + (double)k.Cout * k.KH * k.KW * creal + outs * (k.res ? 2.0 : 1.0));
-    g_prof.bytes += by;
-    char buf[176];
-    snprintf(buf, sizeof buf, "M=%7d Cin=%4d Cout=%4d k=%dx%d s=%d d=%d res=%d tile=%dx%d ksplit=%d grid=%d", k.M, k.C, k.Cout,
-             k.KH, k.KW, k.stride, k.dil, k.res ? 1 : 0, BM, BN, ksplit, grid);
-    if (g_prof.desc.size() < g_prof.used) {
-      g_prof.desc.resize(g_prof.used);
-      g_prof.lflop.resize(g_prof.used);
-      g_prof.lbytes.resize(g_prof.used);
-      g_prof.lms.resize(g_prof.used);
-      g_prof.lprod.resize(g_prof.used);
-    }
-    g_prof.desc[g_prof.used - 1] = buf;
-    g_prof.lflop[g_prof.used - 1] = fl;
-    g_prof.lbytes[g_prof.used - 1] = by;
-    g_prof.lms[g_prof.used - 1] = 0.0;
-    // MFMA products behind one fp32-grade product: the split kernels tag their spans through `ksplit` (160 / 161: two fp16
-    // planes, 20 / 30: two / three bf16 planes); everything else is the exact fp32 MFMA
-    g_prof.lprod[g_prof.used - 1] = ksplit >= 160 ? 3.0 : (ksplit == 30 ? 6.0 : (ksplit == 20 ? 3.0 : 0.0));
-    YMK_HIP(hipEventRecord(e->first, s));
-  }
-  return e;
-}
-
-// the same for a launch that is not one convolution (the fused ViT MLP): description, algorithmic FLOPs and bytes, and the
-// MFMA products behind one fp32-grade product, as given
+// open a timed span when profiling is on (returns the event pair to close it with): the slot, its description, algorithmic
+// FLOPs and bytes, and the MFMA products behind one fp32-grade product, as given
 std::pair<hipEvent_t, hipEvent_t>* conv_prof_open_raw(hipStream_t s, const char* desc, double flops, double bytes, double products) {
   if (!g_prof.on) return nullptr;
   std::lock_guard<std::mutex> lock(g_prof.mu);
@@ -608,6 +568,22 @@ std::pair<hipEvent_t, hipEvent_t>* conv_prof_open_raw(hipStream_t s, const char*
   g_prof.lprod[g_prof.used - 1] = products;
   YMK_HIP(hipEventRecord(e->first, s));
   return e;
+}
+
+// the span of one convolution launch: the work and the traffic follow from the launch record
+std::pair<hipEvent_t, hipEvent_t>* conv_prof_open(hipStream_t s, const ConvK& k, int BM, int BN, int grid, int ksplit) {
+  if (!g_prof.on) return nullptr;
+  const int creal = k.mode == 0 ? k.C : 3;
+  const double fl = 2.0 * (double)k.M * (double)k.Cout * (double)(k.KH * k.KW * creal);
+  const double images = (double)k.M / ((double)k.OH * k.OW);
+  const double outs = (double)k.M * k.Cout;
+  const double by = 4.0 * (images * k.H * k.W * creal + (double)k.Cout * k.KH * k.KW * creal + outs * (k.res ? 2.0 : 1.0));
+  char buf[176];
+  snprintf(buf, sizeof buf, "M=%7d Cin=%4d Cout=%4d k=%dx%d s=%d d=%d res=%d tile=%dx%d ksplit=%d grid=%d", k.M, k.C, k.Cout,
+           k.KH, k.KW, k.stride, k.dil, k.res ? 1 : 0, BM, BN, ksplit, grid);
+  // MFMA products behind one fp32-grade product: the split kernels tag their spans through `ksplit` (160 / 161: two fp16
+  // planes, 20 / 30: two / three bf16 planes); everything else is the exact fp32 MFMA
+  return conv_prof_open_raw(s, buf, fl, by, ksplit >= 160 ? 3.0 : (ksplit == 30 ? 6.0 : (ksplit == 20 ? 3.0 : 0.0)));
 }
 
 template <int TM, int TN, int NW, int PF>
@@ -843,8 +819,6 @@ static bool conv2d_impl(hipStream_t s, const Tensor& in, const ConvW& w, const C
   return true;
 }
 
-int conv_split_route_with_planes(long M, int cout, int kpad, int taps, bool* auto_tile);  // ymk_conv_split.hip
-
 bool conv_planes_pair_ok(const Tensor& in, const ConvW& w1, const ConvArgs& a1, const ConvW& w2, const ConvArgs& a2) {
   if (conv_effective_split() != SPLIT_F16X2 || t_split_ctx == nullptr) return false;
   if (w1.mode != 0 || w2.mode != 0 || a1.epi != EPI_STORE || a2.epi != EPI_STORE || a1.res != nullptr) return false;
@@ -884,9 +858,6 @@ bool gemm_ln_fused(hipStream_t s, const float* X, int M, int K, int ldx, const f
   a.ln_eps = ln_eps;
   return conv2d_impl(s, in, w, a, o);
 }
-
-bool vit_mlp_split_launch(hipStream_t s, SplitCtx* ctx, float* x, int M, int ld, const float* ln_g, const float* ln_b, float ln_eps,
-                          float ln_bound, const ConvW& fc1, const ConvW& fc2);  // ymk_conv_split.hip
 
 bool vit_mlp_fused(hipStream_t s, float* x, int M, int ld, const float* ln_g, const float* ln_b, float ln_eps, float ln_bound, const ConvW& fc1,
                    const ConvW& fc2) {

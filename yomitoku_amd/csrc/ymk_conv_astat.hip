@@ -28,36 +28,11 @@
 #include <string>
 
 #include "ymk_conv_kernel.h"
+#include "ymk_entry.h"
 
 namespace ymk {
 
-typedef _Float16 as_hf16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 as_hf16x8_t __attribute__((ext_vector_type(8)));
-typedef float as_hf32x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void as_lds_void;
-
-__device__ __forceinline__ float2 astat_scales(unsigned amax_bits) {  // f16_scales of ymk_conv_split.hip
-  int e = (int)(amax_bits >> 23);
-  e = e < 27 ? 27 : (e > 227 ? 227 : e);
-  float2 r;
-  r.x = __uint_as_float((unsigned)(268 - e) << 23);
-  r.y = __uint_as_float((unsigned)(e - 14) << 23);
-  return r;
-}
-
-__device__ __forceinline__ void astat_split8(const f32x4 u, const f32x4 v, float sa, as_hf16x8_t& hi, as_hf16x8_t& lo) {
-  as_hf32x2_t x[4] = {{u.x, u.y}, {u.z, u.w}, {v.x, v.y}, {v.z, v.w}};
-  as_hf16x2_t h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    x[i] *= sa;
-    h[i] = __builtin_convertvector(x[i], as_hf16x2_t);
-    x[i] -= __builtin_convertvector(h[i], as_hf32x2_t);  // exact
-    l[i] = __builtin_convertvector(x[i], as_hf16x2_t);
-  }
-  hi = as_hf16x8_t{h[0].x, h[0].y, h[1].x, h[1].y, h[2].x, h[2].y, h[3].x, h[3].y};
-  lo = as_hf16x8_t{l[0].x, l[0].y, l[1].x, l[1].y, l[2].x, l[2].y, l[3].x, l[3].y};
-}
 
 // one column block of a wave (32 rows x 32 TN columns) out of the accumulators: scale / bias / residual / activation as
 // epilogue_tile does (same expression per value), through buffer descriptors with 32-bit offsets, four rows at a time -
@@ -187,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* _
   __shared__ __attribute__((aligned(16))) char lds[NST * B_STAGE];
 
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63, li = lane & 31, lh = lane >> 5;
-  const float2 sc = astat_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax, t)));
+  const float2 sc = f16_plane_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax, t)));
   const float sa = sc.x, inv_sa = sc.y;
   int tile_m, group = (int)blockIdx.y;
   if constexpr (RM) {
@@ -216,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* _
   const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
   const int m = m0 + 32 * wv + li;
   const unsigned row_off = m < p.M ? (unsigned)m * (unsigned)p.in_ld * 4u : OOB_OFFSET;
-  as_hf16x8_t ah[KT][2], al[KT][2];
+  f16x8 ah[KT][2], al[KT][2];
   {
     f32x4 u[KT][2], v[KT][2];
 #pragma unroll
@@ -263,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* _
           const int c = kt * 32 + s * 16 + lh * 8;
           const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.ln_g + c), g1 = *reinterpret_cast<const f32x4*>(p.ln_g + c + 4);
           const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.ln_b + c), b1 = *reinterpret_cast<const f32x4*>(p.ln_b + c + 4);
-          astat_split8(u[kt][s] * rstd * g0 + b0, v[kt][s] * rstd * g1 + b1, sa, ah[kt][s], al[kt][s]);
+          f16_split8(u[kt][s] * rstd * g0 + b0, v[kt][s] * rstd * g1 + b1, sa, ah[kt][s], al[kt][s]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -271,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* _
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) astat_split8(u[kt][s], v[kt][s], sa, ah[kt][s], al[kt][s]);
+        for (int s = 0; s < 2; ++s) f16_split8(u[kt][s], v[kt][s], sa, ah[kt][s], al[kt][s]);
     }
   }
 
@@ -331,11 +306,11 @@ __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* _
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const char* Bs = lds + st * B_STAGE + li * 128;
-        as_hf16x8_t bh[TN], bl[TN];
+        f16x8 bh[TN], bl[TN];
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
-          bh[b] = *reinterpret_cast<const as_hf16x8_t*>(Bs + b * 32 * 128 + (((s * 2 + lh) ^ bswz) * 16));
-          bl[b] = *reinterpret_cast<const as_hf16x8_t*>(Bs + b * 32 * 128 + (((4 + s * 2 + lh) ^ bswz) * 16));
+          bh[b] = *reinterpret_cast<const f16x8*>(Bs + b * 32 * 128 + (((s * 2 + lh) ^ bswz) * 16));
+          bl[b] = *reinterpret_cast<const f16x8*>(Bs + b * 32 * 128 + (((4 + s * 2 + lh) ^ bswz) * 16));
         }
 #pragma unroll
         for (int b = 0; b < TN; ++b) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[kt][s], bh[b], acc[b], 0, 0, 0);

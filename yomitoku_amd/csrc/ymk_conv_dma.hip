@@ -23,41 +23,13 @@
 
 namespace ymk {
 
-typedef _Float16 hf16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 hf16x8_t __attribute__((ext_vector_type(8)));
-typedef float hf32x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
-
-
-__device__ __forceinline__ float2 dma_f16_scales(unsigned amax_bits) {  // as f16_scales of ymk_conv_split.hip
-  int e = (int)(amax_bits >> 23);
-  e = e < 27 ? 27 : (e > 227 ? 227 : e);
-  float2 r;
-  r.x = __uint_as_float((unsigned)(268 - e) << 23);
-  r.y = __uint_as_float((unsigned)(e - 14) << 23);
-  return r;
-}
-
-// 8 fp32 (two 16-byte LDS slots), times the power of two sa -> hi and lo planes of 8 halves each
-__device__ __forceinline__ void split8(const f32x4 u, const f32x4 v, float sa, hf16x8_t& hi, hf16x8_t& lo) {
-  hf32x2_t x[4] = {{u.x, u.y}, {u.z, u.w}, {v.x, v.y}, {v.z, v.w}};
-  hf16x2_t h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    x[i] *= sa;
-    h[i] = __builtin_convertvector(x[i], hf16x2_t);
-    x[i] -= __builtin_convertvector(h[i], hf32x2_t);  // exact
-    l[i] = __builtin_convertvector(x[i], hf16x2_t);
-  }
-  hi = hf16x8_t{h[0].x, h[0].y, h[1].x, h[1].y, h[2].x, h[2].y, h[3].x, h[3].y};
-  lo = hf16x8_t{l[0].x, l[0].y, l[1].x, l[1].y, l[2].x, l[2].y, l[3].x, l[3].y};
-}
 
 // DMA_WAVES waves of 32 rows x BN columns (block tile 32 DMA_WAVES x BN), DMA_NST LDS stages of one 32-k tile, loads
 // DMA_NST - 1 tiles ahead.  <BN, 8, 3>: 256-row tiles, 144 KB, one block per CU.  <BN, 4, 2>: 128-row tiles, 68 KB, TWO blocks
 // per CU - another block's main loop covers a block's prologue and epilogue (what the short-K layers need).
-// APL: the ACTIVATIONS are fp16 planes in HBM already (Tensor::planes: the 128 bytes of a pixel's 32-channel slice are 32 high
-// halves then 32 low halves, written by the producing convolution's epilogue under the scale of the record p.amax): the
+// APL: the ACTIVATIONS are fp16 planes in HBM already (Tensor::planes, layout in ymk_f16_planes.h: the 128 bytes of a pixel's
+// 32-channel slice are 32 high halves then 32 low halves, written by the producing convolution's epilogue under p.amax): the
 // fragment read is two ds_read_b128 straight into the MFMA operands - no fp32 -> (h, l) conversion in the loop, where the fp32
 // form spends 12 VALU instructions per 16-k step and tap (6.8 VALU per MFMA on the 3 x 3 layers, the MFMA pipe 0.47 busy:
 // profiles/r04_conv_f16_short_k_pmc_pass*.csv).  Same DMA addressing, same swizzle, same products in the same order.
@@ -66,7 +38,7 @@ template <int BN, int DMA_WAVES, int DMA_NST, bool APL = false, bool OPL = false
 __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const uint4* __restrict__ wsplit, unsigned w_bytes) {
   constexpr int DMA_BM = 32 * DMA_WAVES, DMA_NT = 64 * DMA_WAVES;
   constexpr int TN = BN / 32;                 // 32-column MFMA tiles of a wave
-  constexpr int A_STAGE = DMA_BM * 128;       // bytes: BM rows x 32 fp32
+  constexpr int A_STAGE = DMA_BM * 128;       // bytes: BM rows x 32 fp32 (APL: x one plane slice, PLANE_SLICE_BYTES = the same 128)
   constexpr int B_STAGE = BN * 128;           // bytes: BN rows x 2 planes x 32 halves
   constexpr int STAGE_B = A_STAGE + B_STAGE;
   constexpr int BROWS = BN / DMA_WAVES;       // B rows a wave loads per K tile
@@ -80,7 +52,7 @@ __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const
   __shared__ __attribute__((aligned(16))) char lds[LDS_B];
 
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63, li = lane & 31, lh = lane >> 5;
-  const float2 sc = dma_f16_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax, t)));
+  const float2 sc = f16_plane_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax, t)));
   const float sa = sc.x, inv_sa = sc.y;
   int tile;
   {
@@ -179,21 +151,21 @@ __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const
     const char* As = lds + st * STAGE_B + arow * 128;
     const char* Bs = lds + st * STAGE_B + A_STAGE + li * 128;
     {
-      hf16x8_t ah, al;
+      f16x8 ah, al;
       if constexpr (APL) {  // k = 16 s + 8 lh .. + 7 of the slice: high halves in slots 0-3, low halves in slots 4-7
-        ah = *reinterpret_cast<const hf16x8_t*>(As + (((s * 2 + lh) ^ aswz) * 16));
-        al = *reinterpret_cast<const hf16x8_t*>(As + (((4 + s * 2 + lh) ^ aswz) * 16));
+        ah = *reinterpret_cast<const f16x8*>(As + (((s * 2 + lh) ^ aswz) * 16));
+        al = *reinterpret_cast<const f16x8*>(As + (((PLANE_LO_BYTES / 16 + s * 2 + lh) ^ aswz) * 16));
       } else {
         const int ca = s * 4 + lh * 2;
         const f32x4 u = *reinterpret_cast<const f32x4*>(As + ((ca ^ aswz) * 16));
         const f32x4 v = *reinterpret_cast<const f32x4*>(As + (((ca + 1) ^ aswz) * 16));
-        split8(u, v, sa, ah, al);
+        f16_split8(u, v, sa, ah, al);
       }
-      hf16x8_t bh[TN], bl[TN];
+      f16x8 bh[TN], bl[TN];
 #pragma unroll
       for (int b = 0; b < TN; ++b) {
-        bh[b] = *reinterpret_cast<const hf16x8_t*>(Bs + b * 32 * 128 + (((s * 2 + lh) ^ bswz) * 16));
-        bl[b] = *reinterpret_cast<const hf16x8_t*>(Bs + b * 32 * 128 + (((4 + s * 2 + lh) ^ bswz) * 16));
+        bh[b] = *reinterpret_cast<const f16x8*>(Bs + b * 32 * 128 + (((s * 2 + lh) ^ bswz) * 16));
+        bl[b] = *reinterpret_cast<const f16x8*>(Bs + b * 32 * 128 + (((4 + s * 2 + lh) ^ bswz) * 16));
       }
       // smallest terms first, term-major: consecutive MFMAs go to different accumulators
 #pragma unroll

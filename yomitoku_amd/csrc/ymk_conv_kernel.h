@@ -4,10 +4,9 @@
 #include <utility>
 
 #include "ymk_common.h"
+#include "ymk_f16_planes.h"
 
 namespace ymk {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvK {
   const float* in;
@@ -67,17 +66,6 @@ __device__ __forceinline__ float apply_act(float v, int act) {
   }
 }
 
-// max|x| bits -> {sa, 1 / sa}, sa the power of two that puts max|x| into [2^14, 2^15); both kept normal whatever the input
-// (the one definition behind f16_scales / dma_f16_scales / astat_scales of the three fp16 kernels)
-__device__ __forceinline__ float2 f16_plane_scales(unsigned amax_bits) {
-  int e = (int)(amax_bits >> 23);  // biased exponent, 0 .. 255
-  e = e < 27 ? 27 : (e > 227 ? 227 : e);
-  float2 r;
-  r.x = __uint_as_float((unsigned)(268 - e) << 23);  // 2^(14 - (e - 127))
-  r.y = __uint_as_float((unsigned)(e - 14) << 23);
-  return r;
-}
-
 constexpr int LDK = 36;  // padded K-tile row (floats)
 
 // ---- K-tile layout in LDS (conv_igemm OPT bit 1)
@@ -99,7 +87,6 @@ __device__ __forceinline__ int lds_slot(int row, int slot) {
 // beyond num_records, for which the hardware returns zeros - no branch, no select after the load,
 // so the loaded registers flow straight to ds_write and their wait can sit after the MFMAs.
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: stays in SSA registers
 constexpr unsigned OOB_OFFSET = 0xFFFFFFF0u;
 constexpr unsigned SPLITK_OOB_ROW = 0xC0000000u;  // conv_splitk: row base of a masked pixel (+ channel bytes, no wrap)
 
@@ -126,16 +113,15 @@ __device__ __forceinline__ void prefetch_residual(const ConvK& p, int m0, int n0
   }
 }
 
-// PL (fp16 kernels only): the outputs leave as the two fp16 planes of Tensor::planes instead of fp32 - 4 high halves and 4 low
-// halves per thread and row (two 8-byte stores where the fp32 form has one 16-byte store), scaled by the power of two of the
-// BOUND pl_a max|x_in| + pl_b, which is also what the output's record receives: the consumer derives the same scale from it.
+// PL (fp16 kernels only): the outputs leave as the two fp16 planes of Tensor::planes (ymk_f16_planes.h) instead of fp32 - 4 high
+// halves and 4 low halves per thread and row (two 8-byte stores where the fp32 form has one 16-byte store), scaled by the power
+// of two of the BOUND pl_a max|x_in| + pl_b, which is also what the output's record receives: the consumer derives the same
+// scale from it.
 // Plain stores with 16-byte channel groups only (the launcher checks: EPI_STORE, vec, no residual, out_ld == Cout % 32 == 0).
 template <int BM, int BN, int NT, bool PRE = false, int UNROLL = 4, bool PL = false>
 __device__ __forceinline__ void epilogue_tile(const ConvK& p, const float* Cs, int m0, int n0, int t, const float4* pre = nullptr) {
   constexpr int LDC = BN + 4;
   if constexpr (PL) {
-    typedef _Float16 ep_h2 __attribute__((ext_vector_type(2)));
-    typedef float ep_f2 __attribute__((ext_vector_type(2)));
     constexpr int TPR = BN / 4, RPP = NT / TPR;
     const int c4 = t % TPR, r0 = t / TPR;
     const int co = n0 + c4 * 4;
@@ -144,7 +130,7 @@ __device__ __forceinline__ void epilogue_tile(const ConvK& p, const float* Cs, i
     if (co < p.Cout) {
       const float4 sc = p.scale ? *reinterpret_cast<const float4*>(p.scale + co) : make_float4(1.f, 1.f, 1.f, 1.f);
       const float4 bi = p.bias ? *reinterpret_cast<const float4*>(p.bias + co) : make_float4(0.f, 0.f, 0.f, 0.f);
-      char* const obase = reinterpret_cast<char*>(p.out) + (size_t)(co >> 5) * 128 + (size_t)(co & 31) * 2;
+      char* const obase = plane_channel_ptr(reinterpret_cast<char*>(p.out), co);
 #pragma unroll 4
       for (int i = 0; i < EpiRows<BM, BN, NT>::NR; ++i) {
         const int row = r0 + RPP * i;
@@ -155,14 +141,11 @@ __device__ __forceinline__ void epilogue_tile(const ConvK& p, const float* Cs, i
         v.y = apply_act(v.y * sc.y + bi.y, p.act);
         v.z = apply_act(v.z * sc.z + bi.z, p.act);
         v.w = apply_act(v.w * sc.w + bi.w, p.act);
-        ep_f2 a = {v.x * so, v.y * so}, b = {v.z * so, v.w * so};
-        const ep_h2 ha = __builtin_convertvector(a, ep_h2), hb = __builtin_convertvector(b, ep_h2);
-        a -= __builtin_convertvector(ha, ep_f2);  // exact
-        b -= __builtin_convertvector(hb, ep_f2);
-        const ep_h2 la = __builtin_convertvector(a, ep_h2), lb = __builtin_convertvector(b, ep_h2);
+        uint2 hi, lo;
+        f16_split4(f32x2{v.x * so, v.y * so}, f32x2{v.z * so, v.w * so}, hi, lo);
         char* o = obase + (size_t)m * p.out_ld * 4;
-        *reinterpret_cast<uint2*>(o) = make_uint2(__builtin_bit_cast(unsigned, ha), __builtin_bit_cast(unsigned, hb));
-        *reinterpret_cast<uint2*>(o + 64) = make_uint2(__builtin_bit_cast(unsigned, la), __builtin_bit_cast(unsigned, lb));
+        *reinterpret_cast<uint2*>(o) = hi;
+        *reinterpret_cast<uint2*>(o + PLANE_LO_BYTES) = lo;
       }
     }
     if (p.amax_out) amax_commit(p.amax_out, bound_bits, t);
@@ -337,13 +320,24 @@ __device__ __forceinline__ void epilogue_direct(const ConvK& p, const f32x16 (&a
 
 // per-launch timing hooks (bench.py roofline leg), defined in ymk_conv.hip
 std::pair<hipEvent_t, hipEvent_t>* conv_prof_open(hipStream_t s, const ConvK& k, int BM, int BN, int grid, int ksplit);
+// the same for a launch that is not one convolution (the fused ViT MLP): description, algorithmic FLOPs and bytes, and the
+// MFMA products behind one fp32-grade product, as given
+std::pair<hipEvent_t, hipEvent_t>* conv_prof_open_raw(hipStream_t s, const char* desc, double flops, double bytes, double products);
 
 // split-operand path (ymk_conv_split.hip): true when the launch was taken.  code 2 / 3: bf16 planes (3 / 6 MFMAs per
 // product tile), SPLIT_F16X2: two scaled fp16 planes (3 MFMAs)
 bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* ctx);
+// for conv_planes_pair_ok: the route of a plain-store fp16-split launch that reads or writes planes; `auto_tile`: no tile is forced
+int conv_split_route_with_planes(long M, int cout, int kpad, int taps, bool* auto_tile);
+// the fused ViT MLP (ymk_vit_mlp.hip) behind vit_mlp_fused: panels, bounds, launch; false = nothing was launched
+bool vit_mlp_split_launch(hipStream_t s, SplitCtx* ctx, float* x, int M, int ld, const float* ln_g, const float* ln_b, float ln_eps,
+                          float ln_bound, const ConvW& fc1, const ConvW& fc2);
+// LDS-DMA kernel (ymk_conv_dma.hip); the caller has resolved the panel and the input's max|x| record
+bool conv2d_f16_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes, bool narrow, int rows);
 // A-stationary short-K 1 x 1 kernel (ymk_conv_astat.hip): false = this launch is not one it runs
 bool conv2d_f16_astat_can(const ConvK& k, size_t w_bytes);
 bool conv2d_f16_astat(hipStream_t s, ConvK& k, const void* planes, size_t w_bytes);
 int conv2d_f16_astat_columns(const ConvK& k);
+void astat_rowmax_dealt(int on);  // "rowmax_tile" 4: the row-max launch deals its column blocks to groups
 
 }  // namespace ymk

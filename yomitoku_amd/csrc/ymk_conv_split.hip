@@ -8,15 +8,14 @@
 //   bf16, 3 planes, 6 MFMAs  x_h y_h + (x_h y_m + x_m y_h) + (x_m y_m + x_h y_l + x_l y_h)   dropped terms <= 2^-23 |xy|
 //   bf16, 2 planes, 3 MFMAs  x_h y_h + (x_h y_l + x_l y_h)                                   dropped terms <= 2^-15 |xy|
 //   fp16, 2 planes, 3 MFMAs  the same three terms on 11-bit pieces                           dropped terms <= 2^-21 |xy|
-// fp16 pieces carry 22 of the 24 significand bits in the same 3 MFMAs that two bf16 planes need (16 bits), i.e. fp32-grade
-// products at 16 / 3 = 5.3 x the fp32 matrix rate: for K >= 64 the fp32 accumulation's own rounding (2^-24 of a partial sum
-// that is ~sqrt(K) products large) exceeds the 2^-21 per product.  What fp16 lacks is range, so the operands are scaled by
-// powers of two (exact): the activations by ONE scale per launch that puts max|x| of the input view into [2^14, 2^15) -
-// a pass over the input (k_absmax) ahead of the convolution, its result read by the kernel from device memory, no host
-// round trip -, the weights per output channel at panel-build time (row maximum into [2^14, 2^15); the inverse goes into the
-// epilogue's per-channel scale).  Elements more than 2^18 below the tensor's maximum lose low-plane bits gradually (fp16
-// subnormals); nothing overflows.  Accumulation is fp32 inside the MFMA (not an fmaf chain in k order: results agree
-// with the fp32 kernel to rounding, not bit for bit).
+// The fp16 form - pieces, scales, error analysis - is ymk_f16_planes.h, shared with every other fp16-split kernel: 22 of the 24
+// significand bits in the same 3 MFMAs that two bf16 planes need (16 bits), i.e. fp32-grade products at 16 / 3 = 5.3 x the
+// fp32 matrix rate.  What fp16 lacks is range, so the operands are scaled by powers of two (exact): the activations by ONE
+// scale per launch that puts max|x| of the input view into [2^14, 2^15) - a pass over the input (k_absmax) ahead of the
+// convolution, or the record its producer left, read by the kernel from device memory, no host round trip -, the weights per
+// output channel at panel-build time (row maximum into [2^14, 2^15); the inverse goes into the epilogue's per-channel scale).
+// Accumulation is fp32 inside the MFMA (not an fmaf chain in k order: results agree with the fp32 kernel to rounding, not
+// bit for bit).
 //
 // Data path: activations stay fp32 in HBM; a thread splits the 4 floats it stages into NS x 4 halves on the way to LDS
 // (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).  Weights are split once per (panel, format), the first time a launch asks, into
@@ -29,19 +28,18 @@
 #include <unordered_map>
 
 #include "ymk_conv_kernel.h"
+#include "ymk_entry.h"
+#include "ymk_vit_mlp.h"
 
 namespace ymk {
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // FMT 0: bf16 pieces, 1: fp16 pieces of the scaled operand
 template <int FMT> struct Half;
-template <> struct Half<0> { typedef bf16x2_t v2; typedef bf16x8_t v8; };
-template <> struct Half<1> { typedef f16x2_t v2; typedef f16x8_t v8; };
+template <> struct Half<0> { typedef bf16x8_t v8; };
+template <> struct Half<1> { typedef f16x8 v8; };
 
 template <int FMT>
 __device__ __forceinline__ f32x16 mfma16(const typename Half<FMT>::v8 a, const typename Half<FMT>::v8 b, const f32x16 c) {
@@ -49,28 +47,26 @@ __device__ __forceinline__ f32x16 mfma16(const typename Half<FMT>::v8 a, const t
   else return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
-// 4 floats (times sa, a power of two: exact) -> NS planes of 4 halves (8 B each)
+// 4 floats -> NS planes of 4 halves (8 B each): bf16 pieces, or the two fp16 planes of the values times sa (ymk_f16_planes.h)
 template <int FMT, int NS>
 __device__ __forceinline__ void split4(const f32x4 v, float sa, uint2* planes) {
-  typedef typename Half<FMT>::v2 h2;
-  f32x2_t a = {v.x, v.y}, b = {v.z, v.w};
-  if (FMT == 1) {
-    a *= sa;
-    b *= sa;
+  f32x2 a = {v.x, v.y}, b = {v.z, v.w};
+  if constexpr (FMT == 1) {
+    static_assert(NS == 2, "fp16 operands have two planes");
+    f16_split4(a * sa, b * sa, planes[0], planes[1]);
+    return;
   }
 #pragma unroll
   for (int pl = 0; pl < NS; ++pl) {
-    const h2 pa = __builtin_convertvector(a, h2), pb = __builtin_convertvector(b, h2);
+    const bf16x2_t pa = __builtin_convertvector(a, bf16x2_t), pb = __builtin_convertvector(b, bf16x2_t);
     planes[pl].x = __builtin_bit_cast(unsigned, pa);
     planes[pl].y = __builtin_bit_cast(unsigned, pb);
     if (pl + 1 < NS) {
-      a -= __builtin_convertvector(pa, f32x2_t);  // exact: the remainder of a round-to-nearest cut fits fp32
-      b -= __builtin_convertvector(pb, f32x2_t);
+      a -= __builtin_convertvector(pa, f32x2);  // exact: the remainder of a round-to-nearest cut fits fp32
+      b -= __builtin_convertvector(pb, f32x2);
     }
   }
 }
-
-__device__ __forceinline__ float2 f16_scales(unsigned amax_bits) { return f16_plane_scales(amax_bits); }  // ymk_conv_kernel.h
 
 // blocks of this shape a CU's 160 KB of LDS holds (at most 2 are asked for) -> minimum waves per SIMD for the register allocator
 template <int BM, int BN, int WM, int WN, int NS, int KS>
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(64 * WM * WN, (bf16_waves_per_simd<BM, BN, WM, WN, 
   const int t = threadIdx.x;
   float sa = 1.f, inv_sa = 1.f;
   if (FMT == 1) {
-    const float2 sc = f16_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax, t)));  // wave-uniform: scalar registers
+    const float2 sc = f16_plane_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax, t)));  // wave-uniform: scalar registers
     sa = sc.x;
     inv_sa = sc.y;
   }
@@ -430,7 +426,7 @@ __global__ void k_split_panel_f16(const float* __restrict__ w, unsigned short* _
   if ((t & 63) == 0) red[t >> 6] = m;
   __syncthreads();
   m = max(max(red[0], red[1]), max(red[2], red[3]));
-  const float2 sc = f16_scales(m);
+  const float2 sc = f16_plane_scales(m);
   for (int k = t; k < kpad; k += 256) {
     const int kt_src = k >> 5;
     int kk = k & 31;
@@ -440,10 +436,8 @@ __global__ void k_split_panel_f16(const float* __restrict__ w, unsigned short* _
       const int rem = kk & 15;
       kk = (kk & 16) | (((rem >> 2) & 1) << 3) | ((rem >> 3) << 2) | (rem & 3);
     }
-    float r = wr[k] * sc.x;
-    const _Float16 h = (_Float16)r;
-    r -= (float)h;
-    const _Float16 l = (_Float16)r;
+    _Float16 h, l;
+    f16_split1(wr[k], sc.x, h, l);
     unsigned short* o = out + (((size_t)row * (kpad >> 5) + kt) * 2) * 32 + kk;
     o[0] = __builtin_bit_cast(unsigned short, h);
     o[32] = __builtin_bit_cast(unsigned short, l);
@@ -733,19 +727,17 @@ static std::atomic<int> g_act_planes{1};
 // on 128 x 64, 36.3 / 44.4 / 55.5 on the wider tiles, 38.1 on (4), 28.2 on (0)
 static std::atomic<int> g_rowmax_tile{0};
 // launch counters since the process started (ymk_stat; tests assert that a route was really taken)
-static std::atomic<long long> g_n_astat{0}, g_n_ln_fused{0}, g_n_planes_read{0}, g_n_planes_written{0}, g_n_rowmax_wide{0};
-long long vit_mlp_fused_launches();
+static std::atomic<long long> g_n_astat{0}, g_n_ln_fused{0}, g_n_planes_read{0}, g_n_planes_written{0}, g_n_rowmax_wide{0}, g_n_mlp_fused{0};
 bool conv_split_stat(const std::string& key, long long* value) {
   if (key == "astat_launches") *value = g_n_astat.load();
   else if (key == "ln_fused_launches") *value = g_n_ln_fused.load();
   else if (key == "planes_read_launches") *value = g_n_planes_read.load();
   else if (key == "planes_written_launches") *value = g_n_planes_written.load();
   else if (key == "rowmax_wide_launches") *value = g_n_rowmax_wide.load();
-  else if (key == "mlp_fused_launches") *value = vit_mlp_fused_launches();
+  else if (key == "mlp_fused_launches") *value = g_n_mlp_fused.load();
   else return false;
   return true;
 }
-void astat_rowmax_dealt(int on);  // ymk_conv_astat.hip
 bool conv_split_debug_option(const std::string& key, int value) {
   if (key == "conv_split_tile") g_split_tile = value;
   else if (key == "amax_check") g_amax_check = value;
@@ -807,8 +799,6 @@ static void dispatch_f16(hipStream_t s, ConvK& k, const void* ws, int tile, bool
   }
 }
 
-bool conv2d_f16_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes, bool narrow, int rows);  // ymk_conv_dma.hip
-
 // ---- which kernel an fp16-split launch runs on: ONE rule, asked by conv2d_split for the launch itself and by
 // conv_planes_pair_ok (ymk_conv.hip) for a producer / consumer pair before either is launched
 //   none: not a launch that fills the chip (>= 256 tiles of 128 x 128, or - few - of 128 x 64): the exact fp32 paths keep it
@@ -861,7 +851,6 @@ static SplitRoute route_f16(const RouteQuery& q, int& tile, bool& narrow) {
   return ROUTE_STAGED;
 }
 
-// for conv_planes_pair_ok: the route of a plain-store fp16-split launch that reads or writes planes; `auto_tile`: no tile is forced
 int conv_split_route_with_planes(long M, int cout, int kpad, int taps, bool* auto_tile) {
   int tile = 0;
   bool narrow = false;
@@ -941,26 +930,6 @@ bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* c
 }
 
 // ---- the fused ViT MLP (ymk_vit_mlp.hip): planes of fc1 (standard) and fc2 (permuted), the bounds, the launch
-struct MlpK {  // as in ymk_vit_mlp.hip
-  const float* x;
-  float* out;
-  int M, ld;
-  const float *ln_g, *ln_b;
-  float ln_eps, ln_bound;
-  const uint4* w1;
-  unsigned w1_bytes;
-  const float *s1, *b1;
-  const uint4* w2;
-  unsigned w2_bytes;
-  const float *s2, *b2;
-  float g_bound;
-};
-bool vit_mlp_f16_launch(hipStream_t s, const MlpK& k, int D, int F);
-std::pair<hipEvent_t, hipEvent_t>* conv_prof_open_raw(hipStream_t s, const char* desc, double flops, double bytes, double products);
-
-static std::atomic<long long> g_n_mlp_fused{0};
-long long vit_mlp_fused_launches() { return g_n_mlp_fused.load(); }
-
 bool vit_mlp_split_launch(hipStream_t s, SplitCtx* ctx, float* x, int M, int ld, const float* ln_g, const float* ln_b, float ln_eps,
                           float ln_bound, const ConvW& fc1, const ConvW& fc2) {
   const int D = fc1.cin, F = fc1.cout;

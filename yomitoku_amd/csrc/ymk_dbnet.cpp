@@ -4,6 +4,7 @@
 // models/layers/dbnet_feature_attention.py:69-79,150-160 (adaptive scale fusion).
 // Weights arrive under the reference's state-dict names.
 #include "ymk_common.h"
+#include "ymk_entry.h"
 
 namespace ymk {
 

@@ -31,5 +31,6 @@ bool parseq_dec_step_supported(int D, int H, int F, int L, int NS);
 void parseq_dec_step(hipStream_t s, const DecStepW& W, const int* tok, int ld_tok, int step, float* skv, int NS,
                      const float* memkv, int L, const int* mem_off, const int* mem_len, float* out, const int* prev_not_done,
                      int B, const int* gid = nullptr, const int* gopen = nullptr, int ng = 1);
+bool decstep_debug_option(const std::string& key, int value);
 
 }  // namespace ymk

@@ -437,9 +437,6 @@ void crop_batch(hipStream_t s, const PageLevels& lv, const CropDesc* descs_dev, 
 
 // ------------------------------------------------------------------ C ABI
 #include "../../include/ymk.h"
-namespace ymk {
-void det_preprocess(hipStream_t s, const unsigned char* bgr, int h, int w, int oh, int ow, float* out);
-}
 extern "C" {
 int ymk_det_preprocess(const unsigned char* bgr_dev, int h, int w, int oh, int ow, float* x_dev, void* stream) {
   try {

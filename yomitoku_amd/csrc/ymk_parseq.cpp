@@ -22,6 +22,7 @@
 #include "ymk_common.h"
 #include "ymk_seq.h"
 #include "ymk_decstep.h"
+#include "ymk_entry.h"
 
 namespace ymk {
 

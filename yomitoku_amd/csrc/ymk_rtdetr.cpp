@@ -10,6 +10,7 @@
 //   - token rows are level-major (ymk_det.hip) so the per-token heads are single GEMMs over all images.
 #include "ymk_common.h"
 #include "ymk_det.h"
+#include "ymk_entry.h"
 #include "ymk_seq.h"
 
 namespace ymk {

@@ -2,12 +2,11 @@
 // RT-DETR AIFI / decoder): LayerNorm, position embedding, fp32-MFMA flash attention, a masked
 // small-query attention, and the on-device greedy-decode bookkeeping of PARSeq.
 #include "ymk_common.h"
+#include "ymk_f16_planes.h"
 #include "ymk_seq.h"
 
 namespace ymk {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -281,39 +280,13 @@ __global__ __launch_bounds__(256, 1) void k_flash_attn(AttnP p) {
 // ---------------------------------------------------------------- flash attention, fp16-split operands (round 4)
 // The same algorithm with both products on the 16-bit MFMA pipe, fp32-grade: S^T = K Q^T and O^T += V^T P^T multiply
 // fp32 operands as two scaled fp16 planes each (three v_mfma_f32_32x32x16_f16 per 16-k step: lo x hi, hi x lo, hi x hi -
-// ymk_conv_split.hip has the error analysis: products to 2^-21), fp32 accumulate, softmax arithmetic in fp32 as before.
+// ymk_f16_planes.h has the cut and its error analysis: products to 2^-21), fp32 accumulate, softmax arithmetic in fp32 as before.
 // Scales (powers of two, exact): q (times the softmax scale), k and v each by the one that puts the max|x| record of their
 // producer into [2^14, 2^15), P in (0, 1] by 2^14.  The D layout of S^T puts keys
 // (r & 3) + 8 (r >> 2) + 4 lh into register r of lane half lh: registers 8 j .. 8 j + 7 ARE the lane's eight k values of
 // 16-key step j of the P^T operand, provided V^T is gathered with the same key order - so P never leaves registers here
 // either.  32 x 32 x 16 MFMAs: 6 per 32-key sub-tile per 16 head dims of Q K^T ... 12 + 6 NDC instead of 4 HDR / 2 + 16 NDC
 // twice-as-long fp32 ones.
-typedef _Float16 ah16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 ah16x8 __attribute__((ext_vector_type(8)));
-typedef float af32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float2 attn_f16_scales(unsigned amax_bits) {  // as f16_scales of ymk_conv_split.hip
-  int e = (int)(amax_bits >> 23);
-  e = e < 27 ? 27 : (e > 227 ? 227 : e);
-  float2 r;
-  r.x = __uint_as_float((unsigned)(268 - e) << 23);
-  r.y = __uint_as_float((unsigned)(e - 14) << 23);
-  return r;
-}
-// 8 floats times the power of two sc -> hi / lo planes
-__device__ __forceinline__ void attn_split8(const float (&x)[8], float sc, ah16x8& hi, ah16x8& lo) {
-  ah16x2 h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    af32x2 v = {x[2 * i] * sc, x[2 * i + 1] * sc};
-    h[i] = __builtin_convertvector(v, ah16x2);
-    v -= __builtin_convertvector(h[i], af32x2);  // exact
-    l[i] = __builtin_convertvector(v, ah16x2);
-  }
-  hi = ah16x8{h[0].x, h[0].y, h[1].x, h[1].y, h[2].x, h[2].y, h[3].x, h[3].y};
-  lo = ah16x8{l[0].x, l[0].y, l[1].x, l[1].y, l[2].x, l[2].y, l[3].x, l[3].y};
-}
-
 template <int HD, int HDR = HD>
 __global__ __launch_bounds__(256, (HD <= 32 ? 3 : (HD <= 64 ? 2 : 1))) void k_flash_attn_f16(AttnP p) {
   constexpr int KT = 64;
@@ -346,15 +319,15 @@ __global__ __launch_bounds__(256, (HD <= 32 ? 3 : (HD <= 64 ? 2 : 1))) void k_fl
   }
   if ((int)blockIdx.x * 128 >= Lq) return;  // block-uniform: the grid is sized for the longest sample
 
-  const float2 cq = attn_f16_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax_q, t)));
-  const float2 ck = attn_f16_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax_k, t)));
-  const float2 cv = attn_f16_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax_v, t)));
+  const float2 cq = f16_plane_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax_q, t)));
+  const float2 ck = f16_plane_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax_k, t)));
+  const float2 cv = f16_plane_scales((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(p.amax_v, t)));
   const float s_q = cq.x, s_k = ck.x, s_v = cv.x;
   const float s_unscale = cq.y * ck.y;                // S = sacc / (s_q s_k)
   const float o_unscale = cv.y * (1.f / 16384.f);     // O = oacc / (s_v 2^14)
 
   // this lane's query row, times the softmax scale (<= 1: the launcher checks) and s_q, as planes: d = ks*16 + 8*lh + e
-  ah16x8 qh[NKS], ql[NKS];
+  f16x8 qh[NKS], ql[NKS];
   {
     const int qi = min(q0 + li, Lq - 1);
     const float* qr = qb + (size_t)qi * p.ldq;
@@ -363,7 +336,7 @@ __global__ __launch_bounds__(256, (HD <= 32 ? 3 : (HD <= 64 ? 2 : 1))) void k_fl
       const f32x4 a = *reinterpret_cast<const f32x4*>(qr + ks * 16 + lh * 8);
       const f32x4 c = *reinterpret_cast<const f32x4*>(qr + ks * 16 + lh * 8 + 4);
       const float x[8] = {a.x * p.scale, a.y * p.scale, a.z * p.scale, a.w * p.scale, c.x * p.scale, c.y * p.scale, c.z * p.scale, c.w * p.scale};
-      attn_split8(x, s_q, qh[ks], ql[ks]);
+      f16_split8(x, s_q, qh[ks], ql[ks]);
     }
   }
 
@@ -420,8 +393,8 @@ __global__ __launch_bounds__(256, (HD <= 32 ? 3 : (HD <= 64 ? 2 : 1))) void k_fl
         const f32x4 a = *reinterpret_cast<const f32x4*>(kr + ks * 16);
         const f32x4 c = *reinterpret_cast<const f32x4*>(kr + ks * 16 + 4);
         const float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-        ah16x8 kh, kl;
-        attn_split8(x, s_k, kh, kl);
+        f16x8 kh, kl;
+        f16_split8(x, s_k, kh, kl);
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[ks], sacc, 0, 0, 0);
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql[ks], sacc, 0, 0, 0);
         sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[ks], sacc, 0, 0, 0);
@@ -447,11 +420,11 @@ __global__ __launch_bounds__(256, (HD <= 32 ? 3 : (HD <= 64 ? 2 : 1))) void k_fl
       l_run = l_run * alpha + ps;
       m_run = m_new;
       // ---- P^T planes: registers 8 j .. 8 j + 7 are the lane's eight k values of 16-key step j
-      ah16x8 ph[2], pl[2];
+      f16x8 ph[2], pl[2];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const float x[8] = {sacc[8 * j], sacc[8 * j + 1], sacc[8 * j + 2], sacc[8 * j + 3], sacc[8 * j + 4], sacc[8 * j + 5], sacc[8 * j + 6], sacc[8 * j + 7]};
-        attn_split8(x, 16384.f, ph[j], pl[j]);
+        f16_split8(x, 16384.f, ph[j], pl[j]);
       }
       // ---- O^T[d][q] = alpha * O^T + V^T P^T: A = V^T (d = dc*32 + li; the same key order as P's registers)
 #pragma unroll
@@ -467,8 +440,8 @@ __global__ __launch_bounds__(256, (HD <= 32 ? 3 : (HD <= 64 ? 2 : 1))) void k_fl
             const int r = 8 * j + e;
             x[e] = vr[((r & 3) + 8 * (r >> 2)) * LDH];
           }
-          ah16x8 vh, vl;
-          attn_split8(x, s_v, vh, vl);
+          f16x8 vh, vl;
+          f16_split8(x, s_v, vh, vl);
           oacc[dc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, ph[j], oacc[dc], 0, 0, 0);
           oacc[dc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pl[j], oacc[dc], 0, 0, 0);
           oacc[dc] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, ph[j], oacc[dc], 0, 0, 0);

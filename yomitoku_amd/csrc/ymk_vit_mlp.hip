@@ -1,5 +1,5 @@
 // One launch for the MLP half of a ViT block on gfx950: x <- x + fc2(GELU(fc1(LayerNorm(x)))), fp16-split arithmetic (two scaled
-// fp16 planes per fp32 operand, three v_mfma_f32_32x32x16_f16 per product tile, fp32 accumulate - ymk_conv_split.hip), the
+// fp16 planes per fp32 operand, three v_mfma_f32_32x32x16_f16 per product tile, fp32 accumulate - ymk_f16_planes.h), the
 // hidden state never leaving the chip.  Replaces k_layernorm + the fc1 GEMM (GELU epilogue) + the fc2 GEMM (residual epilogue)
 // of timm's Block (models/layers/parseq_transformer.py:188-204: norm2 -> mlp.fc1 -> act -> mlp.fc2, drop-path identity at
 // inference), which wrote and re-read a [tokens][4 D] fp32 tensor per block: 1.05 GB each way at a wave's 342 624 tokens -
@@ -23,42 +23,11 @@
 #include <string>
 
 #include "ymk_conv_kernel.h"
+#include "ymk_vit_mlp.h"
 
 namespace ymk {
 
-typedef _Float16 mlp_h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 mlp_h8 __attribute__((ext_vector_type(8)));
-typedef float mlp_f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void mlp_lds_void;
-
-struct MlpK {
-  const float* x;   // [M][ld] token rows in
-  float* out;       // [M][ld] out (may be x)
-  int M, ld;
-  const float *ln_g, *ln_b;  // [D]
-  float ln_eps, ln_bound;    // LayerNorm epsilon; its static output bound (scale of the row planes)
-  const uint4* w1;           // fc1 planes [F^256][KT][2][32] halves (the standard fp16 panel: rows = hidden units)
-  unsigned w1_bytes;
-  const float *s1, *b1;      // [F]: epilogue scale (row's power of two taken back out) and bias of fc1
-  const uint4* w2;           // fc2 planes [D^256][F / 32][2][32] halves, hidden units of every 32-chunk in accumulator order
-  unsigned w2_bytes;
-  const float *s2, *b2;      // [D]
-  float g_bound;             // bound on |GELU(fc1(..))|: scale of the hidden planes
-};
-
-__device__ __forceinline__ void mlp_split8(const f32x4 u, const f32x4 v, float sa, mlp_h8& hi, mlp_h8& lo) {
-  mlp_f2 x[4] = {{u.x, u.y}, {u.z, u.w}, {v.x, v.y}, {v.z, v.w}};
-  mlp_h2 h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    x[i] *= sa;
-    h[i] = __builtin_convertvector(x[i], mlp_h2);
-    x[i] -= __builtin_convertvector(h[i], mlp_f2);  // exact
-    l[i] = __builtin_convertvector(x[i], mlp_h2);
-  }
-  hi = mlp_h8{h[0].x, h[0].y, h[1].x, h[1].y, h[2].x, h[2].y, h[3].x, h[3].y};
-  lo = mlp_h8{l[0].x, l[0].y, l[1].x, l[1].y, l[2].x, l[2].y, l[3].x, l[3].y};
-}
 
 // gelu_f32 (ymk_common.h) on four values at once, written on vectors so that the multiplies and fused multiply-adds become
 // packed instructions (v_pk_mul_f32 / v_pk_fma_f32: two values per issue slot); the same arithmetic per value.
@@ -86,21 +55,21 @@ __device__ __forceinline__ f32x4 gelu_f32x4(const f32x4 v) {
   return out;
 }
 
-__device__ __forceinline__ mlp_f2 gelu_f32x2(const mlp_f2 v) {  // the same on a pair
-  mlp_f2 z = {fabsf(v.x), fabsf(v.y)};
+__device__ __forceinline__ f32x2 gelu_f32x2(const f32x2 v) {  // the same on a pair
+  f32x2 z = {fabsf(v.x), fabsf(v.y)};
   z = z * 0.70710678118654752440f;
-  const mlp_f2 d = z * 0.39032074649205456f + 1.f;
-  const mlp_f2 t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-  mlp_f2 q = t * -0.22690855651422961f + 0.8816638035254636f;
+  const f32x2 d = z * 0.39032074649205456f + 1.f;
+  const f32x2 t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+  f32x2 q = t * -0.22690855651422961f + 0.8816638035254636f;
   q = q * t + -0.6277749224408846f;
   q = q * t + 0.6443424378640197f;
   q = q * t + 0.09342759526711675f;
   q = q * t + 0.23524963446014596f;
-  const mlp_f2 w = z * z * -1.4426950408889634f;
-  const mlp_f2 e = {__builtin_amdgcn_exp2f(w.x), __builtin_amdgcn_exp2f(w.y)};
-  const mlp_f2 r = 1.f - (t * q) * e;  // erf(|v| / sqrt 2)
-  const mlp_f2 hv = v * 0.5f;
-  return mlp_f2{fmaf(hv.x, copysignf(r.x, v.x), hv.x), fmaf(hv.y, copysignf(r.y, v.y), hv.y)};
+  const f32x2 w = z * z * -1.4426950408889634f;
+  const f32x2 e = {__builtin_amdgcn_exp2f(w.x), __builtin_amdgcn_exp2f(w.y)};
+  const f32x2 r = 1.f - (t * q) * e;  // erf(|v| / sqrt 2)
+  const f32x2 hv = v * 0.5f;
+  return f32x2{fmaf(hv.x, copysignf(r.x, v.x), hv.x), fmaf(hv.y, copysignf(r.y, v.y), hv.y)};
 }
 
 // KT = D / 32 (the model width in 32-channel tiles), NCH = F / 32 (hidden chunks)
@@ -159,7 +128,7 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
   }
 
   // ---- the wave's 32 rows: load, LayerNorm (as k_layernorm / conv_f16_astat<.., LN>), planes
-  mlp_h8 xh[KT][2], xl[KT][2];
+  f16x8 xh[KT][2], xl[KT][2];
   {
     const size_t in_bytes = (size_t)p.M * (size_t)p.ld * 4;
     const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, (unsigned)in_bytes, 0x00020000);
@@ -203,7 +172,7 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
         const int c = kt * 32 + s * 16 + lh * 8;
         const f32x4 g0 = *reinterpret_cast<const f32x4*>(p.ln_g + c), g1 = *reinterpret_cast<const f32x4*>(p.ln_g + c + 4);
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(p.ln_b + c), b1 = *reinterpret_cast<const f32x4*>(p.ln_b + c + 4);
-        mlp_split8(u[kt][s] * rstd * g0 + b0, v[kt][s] * rstd * g1 + b1, sx.x, xh[kt][s], xl[kt][s]);
+        f16_split8(u[kt][s] * rstd * g0 + b0, v[kt][s] * rstd * g1 + b1, sx.x, xh[kt][s], xl[kt][s]);
       }
   }
 
@@ -222,26 +191,26 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
   // (what the compiler does left to itself: the first forms of this kernel, 1015-1048 us) stalls every MFMA for one.
   static_assert(KT % 3 == 0, "slots of three k-steps / three column tiles");
   constexpr int S1 = 2 * KT / 3, S2 = 2 * KT / 3, NSLOT = S1 + S2;  // 4 + 4 at KT = 6
-  auto load_slot = [&](int j, int slot1, int slot2, mlp_h8 (&f)[6]) {
+  auto load_slot = [&](int j, int slot1, int slot2, f16x8 (&f)[6]) {
     if (j < S1) {
       const char* W1s = lds + slot1 * W1_B + li * 128;
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         const int step = 3 * j + u, kt = step >> 1, s = step & 1;
-        f[2 * u] = *reinterpret_cast<const mlp_h8*>(W1s + kt * 4096 + (((s * 2 + lh) ^ swz) * 16));
-        f[2 * u + 1] = *reinterpret_cast<const mlp_h8*>(W1s + kt * 4096 + (((4 + s * 2 + lh) ^ swz) * 16));
+        f[2 * u] = *reinterpret_cast<const f16x8*>(W1s + kt * 4096 + (((s * 2 + lh) ^ swz) * 16));
+        f[2 * u + 1] = *reinterpret_cast<const f16x8*>(W1s + kt * 4096 + (((4 + s * 2 + lh) ^ swz) * 16));
       }
     } else {
       const char* W2s = lds + RING2 + slot2 * W2_B + li * 128;
       const int jj = j - S1, s = jj / (KT / 3), ct0 = 3 * (jj % (KT / 3));
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
-        f[2 * u] = *reinterpret_cast<const mlp_h8*>(W2s + (ct0 + u) * 4096 + (((s * 2 + lh) ^ swz) * 16));
-        f[2 * u + 1] = *reinterpret_cast<const mlp_h8*>(W2s + (ct0 + u) * 4096 + (((4 + s * 2 + lh) ^ swz) * 16));
+        f[2 * u] = *reinterpret_cast<const f16x8*>(W2s + (ct0 + u) * 4096 + (((s * 2 + lh) ^ swz) * 16));
+        f[2 * u + 1] = *reinterpret_cast<const f16x8*>(W2s + (ct0 + u) * 4096 + (((4 + s * 2 + lh) ^ swz) * 16));
       }
     }
   };
-  auto mfma_slot = [&](int j, const mlp_h8 (&f)[6], f32x16& h0, f32x16& h1, f32x16& h2, const mlp_h8 (&gh)[2], const mlp_h8 (&gl)[2]) {
+  auto mfma_slot = [&](int j, const f16x8 (&f)[6], f32x16& h0, f32x16& h1, f32x16& h2, const f16x8 (&gh)[2], const f16x8 (&gl)[2]) {
     if (j < S1) {
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
@@ -267,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
   //   fc1 ring (2 slots): slab k is read at iteration k - 1, DMA-ed at iteration k - 2 into the slot slab k - 2 left at k - 3
   //   fc2 ring (3 slots): slab k is read at iteration k + 1, DMA-ed at iteration k - 1 into the slot slab k - 3 left at k - 2
   f32x16 c0, c1, c2;    // the three accumulators of the CURRENT chunk's first product
-  mlp_h8 ph[2], pl[2];  // planes of the PREVIOUS chunk's hidden values (zero before the first chunk: its product adds nothing)
+  f16x8 ph[2], pl[2];  // planes of the PREVIOUS chunk's hidden values (zero before the first chunk: its product adds nothing)
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -279,7 +248,7 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
     for (int r = 0; r < 16; ++r) c0[r] = c1[r] = c2[r] = 0.f;
 #pragma unroll
     for (int j = 0; j < S1; ++j) {
-      mlp_h8 f[6];
+      f16x8 f[6];
       load_slot(j, 0, 0, f);
       mfma_slot(j, f, c0, c1, c2, ph, pl);
     }
@@ -293,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
     __builtin_amdgcn_s_barrier();
     if (c + 2 < NCH) issue1(c + 2, s1n ^ 1);
     if (c + 1 < NCH) issue2(c + 1, s2n);
-    mlp_h8 fa[2][6];
+    f16x8 fa[2][6];
     load_slot(0, s1n, s2p, fa[0]);
     // pre-activations of chunk c: register r of lane (li, lh) is hidden unit (r & 3) + 8 (r >> 2) + 4 lh
     f32x4 v[4], a[4];
@@ -309,18 +278,18 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
     f32x16 n0, n1, n2;
 #pragma unroll
     for (int r = 0; r < 16; ++r) n0[r] = n1[r] = n2[r] = 0.f;
-    mlp_h8 gh[2], gl[2];
+    f16x8 gh[2], gl[2];
 #pragma unroll
     for (int j = 0; j < NSLOT; ++j) {
       if (j + 1 < NSLOT) load_slot(j + 1, s1n, s2p, fa[(j + 1) & 1]);  // (the last iteration multiplies a stale fc1 slab: no branch)
       mfma_slot(j, fa[j & 1], n0, n1, n2, ph, pl);
       {  // GELU of two of the sixteen values per slot (packed pairs); the plane cut once eight are through
         const int g = j >> 1, e0 = 2 * (j & 1);
-        const mlp_f2 pair = gelu_f32x2(mlp_f2{v[g][e0], v[g][e0 + 1]});
+        const f32x2 pair = gelu_f32x2(f32x2{v[g][e0], v[g][e0 + 1]});
         a[g][e0] = pair.x;
         a[g][e0 + 1] = pair.y;
-        if (j == NSLOT / 2 - 1) mlp_split8(a[0], a[1], sg.x, gh[0], gl[0]);
-        if (j == NSLOT - 1) mlp_split8(a[2], a[3], sg.x, gh[1], gl[1]);
+        if (j == NSLOT / 2 - 1) f16_split8(a[0], a[1], sg.x, gh[0], gl[0]);
+        if (j == NSLOT - 1) f16_split8(a[2], a[3], sg.x, gh[1], gl[1]);
       }
 #pragma unroll
       for (int i = 0; i < 9; ++i) {  // inside a slot: an MFMA, then its share of the slot's VALU work
@@ -345,7 +314,7 @@ __global__ __launch_bounds__(256, 1) void k_vit_mlp_f16(MlpK p) {
     f32x16 d0, d1, d2;
 #pragma unroll
     for (int j = S1; j < NSLOT; ++j) {
-      mlp_h8 f[6];
+      f16x8 f[6];
       load_slot(j, 0, s2p, f);
       mfma_slot(j, f, d0, d1, d2, ph, pl);
     }
