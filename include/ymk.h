@@ -253,8 +253,9 @@ int ymk_prof_begin(void);
  *                        -1 = unset: models run their default (16), ymk_op_conv2d exact fp32.  Also set for a whole process by
  *                        the environment variable YMK_CONV_SPLIT (yomitoku_amd/_lib.py).
  *   "conv_split_tile" (0) tile shape of that path for A/B runs: 0 = by format, 1 = 128 x 64, 2 = 256 x 128 (16 waves),
- *                        3 = 128 x 128 (16 waves), 4 = 128 x 128 (8 waves), 11 = 256 x 256 (16 waves; two planes);
- *                        5-10 / 12-14 (bf16 only): 64-k stages, loads two stages ahead, stores threaded through the MFMAs
+ *                        3 = 128 x 128 (16 waves), 4 = 128 x 128 (8 waves), 11 = 256 x 256 (16 waves; two planes); two fp16
+ *                        planes only: 20 / 21 = the LDS-DMA kernel (256- / 128-row tiles), 30 = the A-stationary kernel ("astat"
+ *                        below).  Accepted: 0, 1, 2, 3, 4, 11, 20, 21, 30; any other value is an error and changes nothing
  *   "gemm_row_limit" (0) > 0: linear layers cut their rows into chunks of at most this many (rounded down to 1024s) - the chunking
  *                        that keeps an A operand view below the 4 GiB a buffer descriptor addresses, forced at test sizes
  *   "astat" (1)          1: chip-filling pointwise layers with K <= 192 and Cout > 64 run on the A-stationary kernel (K = 256 stays on

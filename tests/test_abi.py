@@ -44,6 +44,16 @@ def test_debug_options_exist_and_their_documented_defaults_agree():
     for key, default in (("conv_fast", _lib.CONV_FAST_DEFAULT), ("conv_variant", 0), ("no_splitk", 0), ("splitk_force", -1),
                          ("conv_split", -1), ("conv_split_tile", 0), ("prof_dump", 0), ("dec_rows", 0), ("parseq_no_rowmax", 0), ("amax_check", 0), ("rowmax_tile", 0), ("astat", 1), ("act_planes", 1), ("ar_publish", 1)):
         assert lib.ymk_debug_option(key.encode(), default) == 0, key
+    # "conv_split_tile" takes the selectors the routing code knows and nothing else: a retired or mistyped one is an error,
+    # never a run of the default tile under another label
+    try:
+        for tile in (0, 1, 2, 3, 4, 11, 20, 21, 30):
+            assert lib.ymk_debug_option(b"conv_split_tile", tile) == 0, tile
+        for tile in (5, 10, 12, 14, 99):
+            assert lib.ymk_debug_option(b"conv_split_tile", tile) != 0, tile
+            assert lib.ymk_last_error(), tile
+    finally:
+        assert lib.ymk_debug_option(b"conv_split_tile", 0) == 0
     src = open(os.path.join(ROOT, "yomitoku_amd", "csrc", "ymk_conv.hip")).read()
     assert int(re.search(r"g_conv_fast\{(\d+)\}", src).group(1)) == _lib.CONV_FAST_DEFAULT
     header = open(os.path.join(ROOT, "include", "ymk.h")).read()

@@ -85,7 +85,10 @@ def run(shape, variant, inputs, reps=REPS):
     extras = dict(kv.split("=") for kv in extra.split(";") if kv)
     force = -1
     split, split_tile = 0, 0
-    if vnum.startswith("b"):  # "b<ns>[t<tile>]": bf16-split operands (ymk_conv_bf16.hip), ns planes, tile shape selector
+    # "b<ns>[t<tile>]": split operands (ymk_conv_split.hip), "conv_split" code ns (2 / 3 bf16 planes, 16 = two fp16 planes) and
+    # "conv_split_tile" selector: 0 = automatic, 1 = 128 x 64, 2 = 256 x 128, 3 = 128 x 128 x 16 waves, 4 = 128 x 128 x 8 waves,
+    # 11 = 256 x 256; fp16 only: 20 / 21 the LDS-DMA kernel, 30 the A-stationary kernel.  Any other tile is refused by the library
+    if vnum.startswith("b"):
         body, _, tl = vnum[1:].partition("t")
         split, split_tile, vnum = int(body), int(tl or 0), "0"
     _lib.debug_option("conv_split", split)

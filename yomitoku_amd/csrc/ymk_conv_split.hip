@@ -18,11 +18,14 @@
 // bit for bit).
 //
 // Data path: activations stay fp32 in HBM; a thread splits the 4 floats it stages into NS x 4 halves on the way to LDS
-// (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).  Weights are split once per (panel, format), the first time a launch asks, into
-// panels [Cout^128][K tiles][NS][32], so a K tile's B rows are copied to LDS verbatim.  LDS row = NS x 64 B + 16 B pad
+// (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).  Weights are split once per (panel, format) at ymk_model_finalize (SplitCtx::prebuild;
+// SplitCtx::panels is the counted fallback for a pair first asked for inside a forward) into panels
+// [Cout^128][K tiles][NS][32], so a K tile's B rows are copied to LDS verbatim.  LDS row = NS x 64 B + 16 B pad
 // (conflict-free ds_read_b128: row stride 36 or 52 dwords = 4 x odd), one ds_read_b128 per (32-row tile, plane, 16-k
 // step) feeds v_mfma_f32_32x32x16_{bf16,f16}: lane l holds row l & 31, k = 8 (l >> 5) .. + 7 of the step, for A and B alike.
+#include <algorithm>
 #include <atomic>
+#include <iterator>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
@@ -69,26 +72,24 @@ __device__ __forceinline__ void split4(const f32x4 v, float sa, uint2* planes) {
 }
 
 // blocks of this shape a CU's 160 KB of LDS holds (at most 2 are asked for) -> minimum waves per SIMD for the register allocator
-template <int BM, int BN, int WM, int WN, int NS, int KS>
-constexpr int bf16_waves_per_simd() {
-  constexpr int lds = 2 * (BM + BN) * (KS * NS * 64 + 16);
+template <int BM, int BN, int WM, int WN, int NS>
+constexpr int split_waves_per_simd() {
+  constexpr int lds = 2 * (BM + BN) * (NS * 64 + 16);
   constexpr int blocks = 2 * lds <= 160 * 1024 ? 2 : 1;
   return blocks * 64 * WM * WN / 256;
 }
 
-// KS: 32-k tiles per LDS stage (a stage = one barrier interval: KS = 2 halves the barriers per k and doubles the MFMAs a wave
-// issues between them); PF: stages the global loads run ahead of the MFMAs (2 = two register sets, as conv_igemm's PF).
+// The register-staged kernel: BM x BN tile, WM x WN waves, NS planes of format FMT.  A stage is one 32-k tile in one of two
+// LDS buffers; the global loads of tile st + 1 are issued ahead of the MFMAs of tile st and held in registers (one set), then
+// split and written to the other buffer behind them - one barrier per K tile.
 // OPL (fp16 form): the epilogue writes fp16 planes (epilogue_tile<.., PL>, Tensor::planes).
-template <int BM, int BN, int WM, int WN, int NS, int KS, int PF, int FMT, bool OPL = false>
-__global__ __launch_bounds__(64 * WM * WN, (bf16_waves_per_simd<BM, BN, WM, WN, NS, KS>())) void conv_igemm_split(ConvK p, const uint4* __restrict__ wsplit) {
+template <int BM, int BN, int WM, int WN, int NS, int FMT, bool OPL = false>
+__global__ __launch_bounds__(64 * WM * WN, (split_waves_per_simd<BM, BN, WM, WN, NS>())) void conv_igemm_split(ConvK p, const uint4* __restrict__ wsplit) {
   typedef typename Half<FMT>::v8 h8;
-  static_assert(PF >= 1 && PF <= 3, "prefetch: 1 = one stage ahead, 2 = two ahead, 3 = two ahead with the LDS stores threaded through the MFMAs");
-  constexpr int NSET = PF == 1 ? 1 : 2;  // register sets of staged loads
   constexpr int NT = 64 * WM * WN;
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TM = WTM / 32, TN = WTN / 32;
-  constexpr int TILEB = NS * 64;               // bytes of one 32-k tile of a row: NS planes of 32 bf16
-  constexpr int ROWB = KS * TILEB + 16;        // bytes of an LDS row: KS tiles + pad (row stride = 4 x odd dwords)
+  constexpr int ROWB = NS * 64 + 16;           // bytes of an LDS row: NS planes of 32 halves + pad (row stride = 4 x odd dwords)
   constexpr int STAGE_B = (BM + BN) * ROWB;    // bytes of one stage
   constexpr int RPP = NT / 8;                  // A rows staged per pass (8 threads x 16 B of fp32 per 32-k row)
   constexpr int APASS = BM / RPP;
@@ -141,8 +142,7 @@ __global__ __launch_bounds__(64 * WM * WN, (bf16_waves_per_simd<BM, BN, WM, WN, 
       iw0[i] = 0;
     }
   }
-  const int ktiles = p.Kpad >> 5;   // a multiple of KS (the launcher checks)
-  const int nstages = ktiles / KS;
+  const int ktiles = p.Kpad >> 5;
   // B pieces of this thread: piece q = t + NT * j of the tile's BN x PPR, row-major
   const uint4* wsrc[BPASS];
   int boff[BPASS];  // byte offset inside the B half of a stage, or -1 past the tile
@@ -156,71 +156,65 @@ __global__ __launch_bounds__(64 * WM * WN, (bf16_waves_per_simd<BM, BN, WM, WN, 
   }
 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
-  f32x4 ra[NSET][KS][APASS];
-  uint4 rb[NSET][KS][BPASS];
+  f32x4 ra[APASS];
+  uint4 rb[1][BPASS];  // (the [1] is for the compiler: as a flat array the three-plane kernels come out with another register allocation)
   int cur_kh = 0, cur_kw = 0, cur_cc = 0;
   unsigned voff[APASS];
 #pragma unroll
   for (int i = 0; i < APASS; ++i) voff[i] = OOB_OFFSET;
 
-  // stage st (K tiles st * KS .. + KS - 1) -> register set `set`; the tap cursor walks K tile by K tile
-  auto load_stage = [&](int st, int set) {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (FMT == 1 ? (cur_cc == 0 || p.KH * p.KW > 1) : cur_cc == 0) {  // wave-uniform: a new filter tap (fp16 panels: every K tile of a k x k layer)
-        const int dh = cur_kh * p.dil, dw = cur_kw * p.dil;
-#pragma unroll
-        for (int i = 0; i < APASS; ++i) {
-          const int ih = ih0[i] + dh, iw = iw0[i] + dw;
-          const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-          const unsigned off = ((unsigned)(pixb[i] + ih * p.W + iw) * (unsigned)p.in_ld + (unsigned)(colq * 4)) * 4u;
-          voff[i] = ok ? off : OOB_OFFSET;
-        }
-      }
-      const bool chan_ok = cur_cc * 32 + colq * 4 < p.C;
-      const int soff = cur_cc * 128;
+  // K tile st -> the staging registers; the tap cursor walks K tile by K tile
+  auto load_stage = [&](int st) {
+    if (FMT == 1 ? (cur_cc == 0 || p.KH * p.KW > 1) : cur_cc == 0) {  // wave-uniform: a new filter tap (fp16 panels: every K tile of a k x k layer)
+      const int dh = cur_kh * p.dil, dw = cur_kw * p.dil;
 #pragma unroll
       for (int i = 0; i < APASS; ++i) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(chan_ok ? voff[i] : OOB_OFFSET), soff, 0);
-        ra[set][ks][i] = __builtin_bit_cast(f32x4, v);
+        const int ih = ih0[i] + dh, iw = iw0[i] + dw;
+        const bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+        const unsigned off = ((unsigned)(pixb[i] + ih * p.W + iw) * (unsigned)p.in_ld + (unsigned)(colq * 4)) * 4u;
+        voff[i] = ok ? off : OOB_OFFSET;
       }
-      if (FMT == 1) {  // channel-major panels: the taps of one channel slice back to back
-        if (++cur_kw == p.KW) {
-          cur_kw = 0;
-          if (++cur_kh == p.KH) {
-            cur_kh = 0;
-            ++cur_cc;
-          }
-        }
-      } else if (++cur_cc == p.ctiles) {
-        cur_cc = 0;
-        if (++cur_kw == p.KW) {
-          cur_kw = 0;
-          ++cur_kh;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < BPASS; ++j) rb[set][ks][j] = wsrc[j][(size_t)(st * KS + ks) * PPR];
     }
+    const bool chan_ok = cur_cc * 32 + colq * 4 < p.C;
+    const int soff = cur_cc * 128;
+#pragma unroll
+    for (int i = 0; i < APASS; ++i) {
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(chan_ok ? voff[i] : OOB_OFFSET), soff, 0);
+      ra[i] = __builtin_bit_cast(f32x4, v);
+    }
+    if (FMT == 1) {  // channel-major panels: the taps of one channel slice back to back
+      if (++cur_kw == p.KW) {
+        cur_kw = 0;
+        if (++cur_kh == p.KH) {
+          cur_kh = 0;
+          ++cur_cc;
+        }
+      }
+    } else if (++cur_cc == p.ctiles) {
+      cur_cc = 0;
+      if (++cur_kw == p.KW) {
+        cur_kw = 0;
+        ++cur_kh;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < BPASS; ++j) rb[0][j] = wsrc[j][(size_t)st * PPR];
   };
 
-  auto store_stage = [&](int buf, int set) {
+  auto store_stage = [&](int buf) {
     char* As = lds + buf * STAGE_B;
     char* Bs = As + BM * ROWB;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
+    for (int i = 0; i < APASS; ++i) {
+      uint2 pl[NS];
+      split4<FMT, NS>(ra[i], sa, pl);
+      char* row = As + (rowb + RPP * i) * ROWB + colq * 8;
 #pragma unroll
-      for (int i = 0; i < APASS; ++i) {
-        uint2 pl[NS];
-        split4<FMT, NS>(ra[set][ks][i], sa, pl);
-        char* row = As + (rowb + RPP * i) * ROWB + ks * TILEB + colq * 8;
-#pragma unroll
-        for (int q = 0; q < NS; ++q) *reinterpret_cast<uint2*>(row + q * 64) = pl[q];
-      }
-#pragma unroll
-      for (int j = 0; j < BPASS; ++j)
-        if (boff[j] >= 0) *reinterpret_cast<uint4*>(Bs + boff[j] + ks * TILEB) = rb[set][ks][j];
+      for (int q = 0; q < NS; ++q) *reinterpret_cast<uint2*>(row + q * 64) = pl[q];
     }
+#pragma unroll
+    for (int j = 0; j < BPASS; ++j)
+      if (boff[j] >= 0) *reinterpret_cast<uint4*>(Bs + boff[j]) = rb[0][j];
   };
 
   const int wv = t >> 6, lane = t & 63;
@@ -245,128 +239,36 @@ __global__ __launch_bounds__(64 * WM * WN, (bf16_waves_per_simd<BM, BN, WM, WN, 
     const char* As = lds + buf * STAGE_B + (wm * WTM + li) * ROWB + lh * 16;
     const char* Bs = lds + buf * STAGE_B + BM * ROWB + (wn * WTN + li) * ROWB + lh * 16;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
+    for (int s = 0; s < 2; ++s) {  // two 16-k steps per 32-k tile
+      h8 fa[TM][NS], fb[TN][NS];
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {  // two 16-k steps per 32-k tile
-        h8 fa[TM][NS], fb[TN][NS];
+      for (int a = 0; a < TM; ++a)
 #pragma unroll
-        for (int a = 0; a < TM; ++a)
+        for (int q = 0; q < NS; ++q) fa[a][q] = *reinterpret_cast<const h8*>(As + a * 32 * ROWB + q * 64 + s * 32);
 #pragma unroll
-          for (int q = 0; q < NS; ++q) fa[a][q] = *reinterpret_cast<const h8*>(As + a * 32 * ROWB + ks * TILEB + q * 64 + s * 32);
+      for (int b = 0; b < TN; ++b)
 #pragma unroll
-        for (int b = 0; b < TN; ++b)
+        for (int q = 0; q < NS; ++q) fb[b][q] = *reinterpret_cast<const h8*>(Bs + b * 32 * ROWB + q * 64 + s * 32);
+      // term-major: consecutive MFMAs go to different accumulators whenever a wave owns more than one 32 x 32 tile
 #pragma unroll
-          for (int q = 0; q < NS; ++q) fb[b][q] = *reinterpret_cast<const h8*>(Bs + b * 32 * ROWB + ks * TILEB + q * 64 + s * 32);
-        // term-major: consecutive MFMAs go to different accumulators whenever a wave owns more than one 32 x 32 tile
-#pragma unroll
-        for (int tm = 0; tm < NTERM; ++tm)
-#pragma unroll
-          for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < TN; ++b)
-              acc[a][b] = mfma16<FMT>(fa[a][TA[T0 + tm]], fb[b][TB[T0 + tm]], acc[a][b]);
-      }
-  };
-
-  // PF == 3: the same MFMAs with the next stage's conversion + LDS stores slotted between them, one chunk (one A pass: split
-  // + NS ds_write_b64, or one B piece: ds_write_b128) every `stride` MFMAs, pinned by scheduling fences.  A wave issues in
-  // order and an MFMA occupies the matrix pipe for 32 cycles: the few VALU / DS instructions behind it ride in its shadow
-  // instead of forming a separate phase between the last MFMA and the barrier (the staged data was loaded a whole stage
-  // earlier, so no chunk waits on memory).
-  auto compute_store = [&](int buf, int sbuf, int set, auto do_store) {
-    constexpr bool STORE = decltype(do_store)::value;
-    const char* As = lds + buf * STAGE_B + (wm * WTM + li) * ROWB + lh * 16;
-    const char* Bs = lds + buf * STAGE_B + BM * ROWB + (wn * WTN + li) * ROWB + lh * 16;
-    char* SA = lds + sbuf * STAGE_B;
-    char* SB = SA + BM * ROWB;
-    constexpr int NCH = KS * (APASS + BPASS);
-    constexpr int NM = KS * 2 * NTERM * TM * TN;
-    constexpr int STRIDE = NM / NCH > 0 ? NM / NCH : 1;
-    auto chunk = [&](int c) {
-      const int ks = c / (APASS + BPASS), r = c - ks * (APASS + BPASS);
-      if (r < APASS) {
-        uint2 pl[NS];
-        split4<FMT, NS>(ra[set][ks][r], sa, pl);
-        char* row = SA + (rowb + RPP * r) * ROWB + ks * TILEB + colq * 8;
-#pragma unroll
-        for (int q = 0; q < NS; ++q) *reinterpret_cast<uint2*>(row + q * 64) = pl[q];
-      } else {
-        const int j = r - APASS;
-        if (boff[j] >= 0) *reinterpret_cast<uint4*>(SB + boff[j] + ks * TILEB) = rb[set][ks][j];
-      }
-    };
-    int mi = 0;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        h8 fa[TM][NS], fb[TN][NS];
+      for (int tm = 0; tm < NTERM; ++tm)
 #pragma unroll
         for (int a = 0; a < TM; ++a)
 #pragma unroll
-          for (int q = 0; q < NS; ++q) fa[a][q] = *reinterpret_cast<const h8*>(As + a * 32 * ROWB + ks * TILEB + q * 64 + s * 32);
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-          for (int q = 0; q < NS; ++q) fb[b][q] = *reinterpret_cast<const h8*>(Bs + b * 32 * ROWB + ks * TILEB + q * 64 + s * 32);
-#pragma unroll
-        for (int tm = 0; tm < NTERM; ++tm)
-#pragma unroll
-          for (int a = 0; a < TM; ++a)
-#pragma unroll
-            for (int b = 0; b < TN; ++b) {
-              acc[a][b] = mfma16<FMT>(fa[a][TA[T0 + tm]], fb[b][TB[T0 + tm]], acc[a][b]);
-              if (STORE && mi % STRIDE == STRIDE - 1 && mi / STRIDE < NCH) {
-                __builtin_amdgcn_sched_barrier(0);
-                chunk(mi / STRIDE);
-                __builtin_amdgcn_sched_barrier(0);
-              }
-              ++mi;
-            }
-      }
-    if (STORE) {
-#pragma unroll
-      for (int c = NM / STRIDE; c < NCH; ++c) chunk(c);  // more chunks than MFMA slots (short stages): the rest at the end
+          for (int b = 0; b < TN; ++b)
+            acc[a][b] = mfma16<FMT>(fa[a][TA[T0 + tm]], fb[b][TB[T0 + tm]], acc[a][b]);
     }
   };
 
-  load_stage(0, 0);
-  store_stage(0, 0);
-  if (PF >= 2 && nstages > 1) load_stage(1, 1);
+  load_stage(0);
+  store_stage(0);
   __syncthreads();
-  if (PF == 3) {
-    for (int st = 0; st < nstages; st += 2) {
-      if (st + 2 < nstages) load_stage(st + 2, 0);
-      if (st + 1 < nstages) compute_store(0, 1, NSET - 1, std::true_type{});
-      else compute_store(0, 1, NSET - 1, std::false_type{});
-      __syncthreads();
-      if (st + 1 >= nstages) break;
-      if (st + 3 < nstages) load_stage(st + 3, NSET - 1);
-      if (st + 2 < nstages) compute_store(1, 0, 0, std::true_type{});
-      else compute_store(1, 0, 0, std::false_type{});
-      __syncthreads();
-    }
-  } else if (PF == 1) {
-    for (int st = 0; st < nstages; ++st) {
-      const int buf = st & 1;
-      if (st + 1 < nstages) load_stage(st + 1, 0);
-      compute(buf);
-      if (st + 1 < nstages) store_stage(buf ^ 1, 0);
-      __syncthreads();
-    }
-  } else {
-    // stage s travels in register set s & 1: loaded at the top of step s - 2, written to LDS[s & 1] at the end of step s - 1
-    for (int st = 0; st < nstages; st += 2) {
-      if (st + 2 < nstages) load_stage(st + 2, 0);
-      compute(0);
-      if (st + 1 < nstages) store_stage(1, NSET - 1);
-      __syncthreads();
-      if (st + 1 >= nstages) break;
-      if (st + 3 < nstages) load_stage(st + 3, NSET - 1);
-      compute(1);
-      if (st + 2 < nstages) store_stage(0, 0);
-      __syncthreads();
-    }
+  for (int st = 0; st < ktiles; ++st) {
+    const int buf = st & 1;
+    if (st + 1 < ktiles) load_stage(st + 1);
+    compute(buf);
+    if (st + 1 < ktiles) store_stage(buf ^ 1);
+    __syncthreads();
   }
 
   float* Cs = reinterpret_cast<float*>(lds);
@@ -677,12 +579,8 @@ static void amax_verify(hipStream_t s, const ConvK& k, SplitCtx* ctx) {
   }
 }
 
-template <int FMT, int BM, int BN, int WM, int WN, int NS, int KS = 1, int PF = 1, bool OPL = false>
-static void launch_split(hipStream_t s, ConvK& k, const void* wsplit, SplitCtx* ctx = nullptr) {
-  if (KS > 1 && (k.Kpad >> 5) % KS != 0) {  // a stage holds KS whole K tiles: odd tile counts take the one-tile form
-    launch_split<FMT, BM, BN, WM, WN, NS, 1, PF, OPL>(s, k, wsplit, ctx);
-    return;
-  }
+template <int FMT, int BM, int BN, int WM, int WN, int NS, bool OPL = false>
+static void launch_split(hipStream_t s, ConvK& k, const void* wsplit, SplitCtx* ctx) {
   const int mt = (k.M + BM - 1) / BM, nt = (k.Cout + BN - 1) / BN;
   k.ntiles_n = nt;
   auto* e = conv_prof_open(s, k, BM, BN, mt * nt, (FMT ? 160 : 10 * NS));
@@ -691,20 +589,19 @@ static void launch_split(hipStream_t s, ConvK& k, const void* wsplit, SplitCtx* 
   } else if (FMT == 1 && g_amax_check.load(std::memory_order_relaxed)) {
     amax_verify(s, k, ctx);
   }
-  hipLaunchKernelGGL((conv_igemm_split<BM, BN, WM, WN, NS, KS, PF, FMT, OPL>), dim3(mt * nt), dim3(64 * WM * WN), 0, s, k,
+  hipLaunchKernelGGL((conv_igemm_split<BM, BN, WM, WN, NS, FMT, OPL>), dim3(mt * nt), dim3(64 * WM * WN), 0, s, k,
                      reinterpret_cast<const uint4*>(wsplit));
   if (e) YMK_HIP(hipEventRecord(e->second, s));
 }
 
-// tile shapes, ymk_debug_option("conv_split_tile", v): 0 = the measured best per format (profiles/
-// r03_conv_sweep_bf16_split*.txt); for A/B runs
-//   1 = 128 x 64, 8 waves          2 = 256 x 128, 16 waves        3 = 128 x 128, 16 waves        4 = 128 x 128, 8 waves
-//   5 = 128 x 128, 16 waves, 64-k stages              6 = the same, loads two stages ahead
-//   7 = 128 x 128, 8 waves, 64-k stages, two ahead    8 = 256 x 128, 16 waves, 32-k stages, two ahead
-//   9 = 128 x 128, 8 waves, 32-k stages, two ahead   10 = 128 x 128, 16 waves, 32-k stages, two ahead
-//   11 = 256 x 256, 16 waves (64 x 64 per wave), two planes
-//   12 / 13 / 14 = 128 x 128 x 16 waves / 256 x 128 x 16 waves / 128 x 128 x 8 waves with the stores threaded through the MFMAs
-// (bf16 only; the fp16 form keeps the shapes that won there: 0 / 3 = 128 x 128 x 16 waves, 1 = 128 x 64, 2 = 256 x 128, 11)
+// ymk_debug_option("conv_split_tile", v), for A/B runs; any other value is refused (SPLIT_TILES):
+//   0 = the measured best per format (profiles/r03_conv_sweep_bf16_split*.txt): 256 x 128 for three bf16 planes, else 128 x 128 x 16 waves
+//   shapes of the register-staged kernel (dispatch_staged), every format:
+//     1 = 128 x 64, 8 waves        2 = 256 x 128, 16 waves        3 = 128 x 128, 16 waves        4 = 128 x 128, 8 waves
+//     11 = 256 x 256, 16 waves (64 x 64 per wave) with two planes and Cout >= 256, else as 3
+//   other kernels, fp16 form only (the bf16 forms run as 3): 20 / 21 = the LDS-DMA kernel with 256- / 128-row tiles, 30 = the
+//     A-stationary kernel for every launch it can run (route_f16)
+static constexpr int SPLIT_TILES[] = {0, 1, 2, 3, 4, 11, 20, 21, 30};
 static std::atomic<int> g_split_tile{0};
 // ... or, for the calling thread only, a ConvSplitTileScope (single-operator entry points: the process-wide word would
 // reroute forwards that other threads have in flight)
@@ -739,7 +636,13 @@ bool conv_split_stat(const std::string& key, long long* value) {
   return true;
 }
 bool conv_split_debug_option(const std::string& key, int value) {
-  if (key == "conv_split_tile") g_split_tile = value;
+  if (key == "conv_split_tile") {
+    const bool known_tile = std::find(std::begin(SPLIT_TILES), std::end(SPLIT_TILES), value) != std::end(SPLIT_TILES);
+    std::string accepted;
+    for (int v : SPLIT_TILES) accepted += " " + std::to_string(v);
+    YMK_CHECK(known_tile, "conv_split_tile " + std::to_string(value) + " is no selector; accepted:" + accepted);
+    g_split_tile = value;
+  }
   else if (key == "amax_check") g_amax_check = value;
   else if (key == "astat") g_astat = value;
   else if (key == "act_planes") g_act_planes = value;
@@ -751,51 +654,28 @@ bool conv_split_debug_option(const std::string& key, int value) {
   return true;
 }
 
-template <int NS>
-static void dispatch_bf16(hipStream_t s, ConvK& k, const void* ws, int tile, bool narrow) {
+// the tile shapes of the register-staged kernel, for every format (FMT 0: NS bf16 planes, 1: two fp16 planes)
+template <int FMT, int NS>
+static void dispatch_staged(hipStream_t s, ConvK& k, const void* ws, int tile, bool narrow, SplitCtx* ctx) {
+  if constexpr (FMT == 1) {
+    if (k.out_planes) {  // plane-writing epilogues exist for the two shapes the automatic choice uses
+      if (narrow) launch_split<1, 128, 64, 4, 2, 2, true>(s, k, ws, ctx);
+      else launch_split<1, 128, 128, 4, 4, 2, true>(s, k, ws, ctx);
+      return;
+    }
+  }
   if (narrow) {
-    launch_split<0, 128, 64, 4, 2, NS>(s, k, ws);
+    launch_split<FMT, 128, 64, 4, 2, NS>(s, k, ws, ctx);
     return;
   }
   switch (tile) {
-    case 2: launch_split<0, 256, 128, 4, 4, NS>(s, k, ws); break;
-    case 4: launch_split<0, 128, 128, 4, 2, NS>(s, k, ws); break;
-    // 64-k stages of three planes do not fit the CU's LDS (205 KB): those selectors keep 32-k stages there
-    case 5: launch_split<0, 128, 128, 4, 4, NS, NS == 2 ? 2 : 1, 1>(s, k, ws); break;
-    case 6: launch_split<0, 128, 128, 4, 4, NS, NS == 2 ? 2 : 1, 2>(s, k, ws); break;
-    case 7: launch_split<0, 128, 128, 4, 2, NS, NS == 2 ? 2 : 1, 2>(s, k, ws); break;
-    case 8: launch_split<0, 256, 128, 4, 4, NS, 1, 2>(s, k, ws); break;
-    case 9: launch_split<0, 128, 128, 4, 2, NS, 1, 2>(s, k, ws); break;
-    case 10: launch_split<0, 128, 128, 4, 4, NS, 1, 2>(s, k, ws); break;
-    case 12: launch_split<0, 128, 128, 4, 4, NS, 1, 3>(s, k, ws); break;
-    case 13: launch_split<0, 256, 128, 4, 4, NS, 1, 3>(s, k, ws); break;
-    case 14: launch_split<0, 128, 128, 4, 2, NS, 1, 3>(s, k, ws); break;
+    case 2: launch_split<FMT, 256, 128, 4, 4, NS>(s, k, ws, ctx); break;
+    case 4: launch_split<FMT, 128, 128, 4, 2, NS>(s, k, ws, ctx); break;
     case 11:  // 256 x 256, 16 waves of 64 x 64 (two planes only: three do not fit the LDS); Cout < 256 keeps 128-wide tiles
-      if (NS == 2 && k.Cout >= 256) launch_split<0, 256, 256, 4, 4, 2>(s, k, ws);
-      else launch_split<0, 128, 128, 4, 4, NS>(s, k, ws);
+      if (NS == 2 && k.Cout >= 256) launch_split<FMT, 256, 256, 4, 4, 2>(s, k, ws, ctx);
+      else launch_split<FMT, 128, 128, 4, 4, NS>(s, k, ws, ctx);
       break;
-    default: launch_split<0, 128, 128, 4, 4, NS>(s, k, ws); break;
-  }
-}
-
-static void dispatch_f16(hipStream_t s, ConvK& k, const void* ws, int tile, bool narrow, SplitCtx* ctx) {
-  if (k.out_planes) {  // plane-writing epilogues exist for the two shapes the automatic choice uses
-    if (narrow) launch_split<1, 128, 64, 4, 2, 2, 1, 1, true>(s, k, ws, ctx);
-    else launch_split<1, 128, 128, 4, 4, 2, 1, 1, true>(s, k, ws, ctx);
-    return;
-  }
-  if (narrow) {
-    launch_split<1, 128, 64, 4, 2, 2>(s, k, ws, ctx);
-    return;
-  }
-  switch (tile) {
-    case 2: launch_split<1, 256, 128, 4, 4, 2>(s, k, ws, ctx); break;
-    case 4: launch_split<1, 128, 128, 4, 2, 2>(s, k, ws, ctx); break;
-    case 11:
-      if (k.Cout >= 256) launch_split<1, 256, 256, 4, 4, 2>(s, k, ws, ctx);
-      else launch_split<1, 128, 128, 4, 4, 2>(s, k, ws, ctx);
-      break;
-    default: launch_split<1, 128, 128, 4, 4, 2>(s, k, ws, ctx); break;
+    default: launch_split<FMT, 128, 128, 4, 4, NS>(s, k, ws, ctx); break;
   }
 }
 
@@ -919,11 +799,11 @@ bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* c
   if (code == SPLIT_F16X2) {
     k.scale = pn.scale;
     if (rowmax && !narrow) ++g_n_rowmax_wide;
-    dispatch_f16(s, k, pn.planes, tile, narrow, ctx);
+    dispatch_staged<1, 2>(s, k, pn.planes, tile, narrow, ctx);
   } else if (code == 2) {
-    dispatch_bf16<2>(s, k, pn.planes, tile, narrow);
+    dispatch_staged<0, 2>(s, k, pn.planes, tile, narrow, ctx);
   } else {
-    dispatch_bf16<3>(s, k, pn.planes, tile, narrow);
+    dispatch_staged<0, 3>(s, k, pn.planes, tile, narrow, ctx);
   }
   YMK_HIP(hipGetLastError());
   return true;
