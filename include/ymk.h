@@ -206,6 +206,36 @@ int ymk_heatmap_blend(unsigned char* canvas_dev, int h, int w, const float* prob
 int ymk_overlay_tile(void);
 int ymk_overlay_chunk(void);
 
+/* ---- a wave of canvases in two calls (DocumentAnalyzer.serve(overlays=True)): text laid out and commands culled on the device.
+ * The canvases of a wave - uint8 [h][w][3] each, of differing sizes - lie in ONE device buffer; cmds_dev holds the records of all
+ * of them (layout and rules as above), each canvas's commands contiguous and in drawing order.  canvases_dev / table_dev: int64
+ * [n_canvases][YMK_OVERLAY_CANVAS_WORDS] = byte offset of the canvas in the buffer, h, w, first command, command count, first
+ * tile (the canvases' tiles are numbered one canvas after the other, row-major inside a canvas).  An entry that does not fit
+ * (1 <= h, w <= 16383, the bytes inside the buffer, the commands inside [0, n_cmds)) is ignored, never trusted.
+ * ymk_overlay_layout: (1) text runs -> GLYPH records.  The host reserves one record per character (kind, colour filled in) and
+ *   gives runs_dev: int32 [n_runs][YMK_OVERLAY_RUN_WORDS] = first slot, first code index, count, pen x, pen y, direction (0
+ *   horizontal, 1 vertical), vertical step, 0; codes_dev: int32 [n_codes] glyph ids; glyphs_dev: int32 [n_glyphs]
+ *   [YMK_OVERLAY_GLYPH_WORDS] = atlas offset, w, h, x offset, y offset, advance.  Character i of a run gets words 5..10 = clamp(pen
+ *   + offsets) to [-16383, 16383], w, h, atlas offset, pitch w, with the pen at (pen x + the advances of characters 0..i-1, pen y),
+ *   vertical: (pen x, pen y + i * step).  A character whose glyph is empty (w or h 0) or whose id lies outside [0, n_glyphs) gets
+ *   kind -1 (draws nothing; it still advances the pen by its advance, 0 for an unknown id).  A run whose slots or codes fall
+ *   outside the arrays is skipped.  (2) bounds_dev: int16 [n_cmds][4] = every command's inclusive bounding box x0, y0, x1, y1 (SEG:
+ *   the end points' box grown by (t + 1) / 2; BOX: the outer box; GLYPH: x .. x + w - 1, y .. y + h - 1) clipped to its canvas;
+ *   (1, 1, 0, 0) - x1 < x0 - for a command that covers none of its canvas.  Commands no canvas entry names are not written.
+ * ymk_draw_overlay_pages: ONE launch, a block per tile (total_tiles = the sum over the canvases).  A block finds its canvas in
+ *   the table, tests ymk_overlay_cull_pass() bounding boxes of that canvas at a time against its tile, keeps the hits in command
+ *   order and applies them as ymk_draw_overlay does; a tile without hits is neither read nor written.  The result equals
+ *   ymk_draw_overlay per canvas with the caller's per-tile lists.  No atomics, nothing allocated, nothing waited for. */
+#define YMK_OVERLAY_RUN_WORDS 8
+#define YMK_OVERLAY_GLYPH_WORDS 6
+#define YMK_OVERLAY_CANVAS_WORDS 6
+int ymk_overlay_layout(int* cmds_dev, int n_cmds, int16_t* bounds_dev, const int* runs_dev, int n_runs, const int* codes_dev,
+                       int n_codes, const int* glyphs_dev, int n_glyphs, const int64_t* canvases_dev, int n_canvases, void* stream);
+int ymk_draw_overlay_pages(unsigned char* canvases_dev, int64_t canvas_bytes, const int64_t* table_dev, int n_canvases,
+                           int64_t total_tiles, const int* cmds_dev, int n_cmds, const int16_t* bounds_dev,
+                           const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream);
+int ymk_overlay_cull_pass(void);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

@@ -2,6 +2,7 @@
 """What a visualize=True overlay costs, for profiles/visualize_overlay.json (run by hand on the GPU, not by the suite).
 
     python tools/overlay_timing.py [--out FILE]
+    python tools/overlay_timing.py --wave [--out FILE]    the wave renderer, for profiles/visualize_overlay_wave.json (wave_leg)
 
 One 1600 x 1200 page carrying 300 quads (closed polylines, t = 1), 300 labelled boxes (outline t = 2 + a 12 px label) and 300
 text lines of 20 characters (18 px).  Reported, each the median of 20 runs after 3 warm-ups, one process, nothing else on the card:
@@ -39,10 +40,10 @@ def content(seed=0):
     return quads, boxes, lines
 
 
-def build_overlay(quads, boxes, lines):
+def build_overlay(quads, boxes, lines, recorder=None):
     from yomitoku_amd.utils.visualizer import Overlay, load_font
 
-    ov = Overlay()
+    ov = (recorder or Overlay)()
     label, text = load_font(None, 12), load_font(None, 18)
     ov.polyline(quads, True, (0, 255, 0), 1)
     for k, b in enumerate(boxes.tolist()):
@@ -84,10 +85,97 @@ def median_ms(fn, sync=None):
     return round(statistics.median(out[WARMUP:]), 3)
 
 
+WAVE_PAGES = 16
+
+
+def wave_leg(out_path):
+    """serve(overlays=True)'s renderer on a wave of WAVE_PAGES such pages x 2 canvases (every canvas carries the whole content):
+      layout_device_ms / draw_pages_device_ms   ymk_overlay_layout / ymk_draw_overlay_pages for the WAVE, HIP events around each call
+      record_and_build_host_ms_per_page         the run recorder + build_wave for the wave, per page (two canvases)
+      render_wave_wall_ms                       render_wave: clone, blob, both launches, D2H of all canvases, owned copies
+    next to the per-page path's own rows re-measured in the same process (one launch and one host build per CANVAS)."""
+    import torch
+
+    from yomitoku_amd import _lib
+    from yomitoku_amd.utils import visualizer as V
+    from yomitoku_amd.utils.synth import synthetic_page
+
+    assert torch.cuda.is_available(), "overlay_timing.py measures on the GPU"
+    lib = _lib.load()
+    page_dev = torch.from_numpy(synthetic_page(0, H, W)).to("cuda:0")
+    quads, boxes, lines = content()
+    sync = torch.cuda.synchronize
+    n_canvases = 2 * WAVE_PAGES
+
+    def record():
+        return [build_overlay(quads, boxes, lines, V.RunOverlay) for _ in range(n_canvases)]
+
+    V.build_wave(record()[:1], [(H, W)])  # the glyphs enter the store once per process
+    sizes = [(H, W)] * n_canvases
+    data = V.build_wave(record(), sizes)
+    buf = torch.empty(data["bytes"], dtype=torch.uint8, device="cuda:0")
+    for off in data["table"][:, 0].tolist():
+        buf[off : off + H * W * 3] = page_dev.reshape(-1)
+    staged = V.draw_wave(buf, record(), sizes)
+    stream = _lib.current_stream_ptr()
+
+    def timed(fn, name, call_args):
+        out = []
+        for _ in range(RUNS + WARMUP):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            _lib.check(fn(*call_args, stream), name)
+            b.record()
+            b.synchronize()
+            out.append(a.elapsed_time(b))
+        return round(statistics.median(out[WARMUP:]), 4)
+
+    # the per-page path, one canvas: the rows of profiles/visualize_overlay.json again, same process
+    ov = build_overlay(quads, boxes, lines)
+    one = ov.build(H, W)
+    canvas = page_dev.clone()
+    staged_one = V.stage_commands(canvas, one["cmds"], one["atlas"], lists=(one["tile_offsets"], one["tile_cmds"]))
+    kernel = []
+    for _ in range(RUNS + WARMUP):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        V.launch_staged(canvas, staged_one)
+        b.record()
+        b.synchronize()
+        kernel.append(a.elapsed_time(b))
+    slot = [None]
+    result = {
+        "page": [H, W], "wave_pages": WAVE_PAGES, "canvases": n_canvases, "commands_per_canvas": int(len(data["cmds"]) // n_canvases),
+        "commands": int(len(data["cmds"])), "text_runs": int(len(data["runs"])), "characters": int(len(data["codes"])),
+        "tiles": int(data["tiles"]), "runs": RUNS, "warmup": WARMUP,
+        "layout_device_ms": timed(lib.ymk_overlay_layout, "ymk_overlay_layout", staged["layout_args"]),
+        "draw_pages_device_ms": timed(lib.ymk_draw_overlay_pages, "ymk_draw_overlay_pages", staged["draw_args"]),
+        "record_and_build_host_ms_per_page": round(median_ms(lambda: V.build_wave(record(), sizes)) / WAVE_PAGES, 3),
+        "render_wave_wall_ms": median_ms(lambda: V.render_wave([page_dev] * n_canvases, record(), slot), sync),
+        "per_page_path_same_process": {
+            "draw_overlay_device_ms_per_canvas": round(statistics.median(kernel[WARMUP:]), 4),
+            "build_and_bin_host_ms_per_canvas": median_ms(lambda: build_overlay(quads, boxes, lines).build(H, W)),
+            "render_wall_ms_per_canvas": median_ms(lambda: build_overlay(quads, boxes, lines).render(page_dev), sync),
+        },
+        "device": torch.cuda.get_device_name(0),
+    }
+    result["draw_pages_device_ms_per_canvas"] = round(result["draw_pages_device_ms"] / n_canvases, 4)
+    result["layout_device_ms_per_canvas"] = round(result["layout_device_ms"] / n_canvases, 4)
+    text = json.dumps(result, indent=1)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
+    ap.add_argument("--wave", action="store_true", help="the wave renderer of serve(overlays=True): profiles/visualize_overlay_wave.json")
     args = ap.parse_args()
+    if args.wave:
+        return wave_leg(args.out)
     import torch
 
     from yomitoku_amd.utils.synth import synthetic_page

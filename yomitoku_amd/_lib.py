@@ -57,6 +57,9 @@ SIGNATURES = {
     "ymk_heatmap_blend": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ymk_overlay_tile": (c_int, []),
     "ymk_overlay_chunk": (c_int, []),
+    "ymk_overlay_layout": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "ymk_draw_overlay_pages": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ymk_overlay_cull_pass": (c_int, []),
     "ymk_db_postprocess": (
         c_int,
         [c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,

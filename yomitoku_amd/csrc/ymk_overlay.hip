@@ -121,6 +121,223 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay(unsigned char* __re
   }
 }
 
+// ---- a wave of canvases in one launch (DocumentAnalyzer.serve(overlays=True)) -------------------------------------------------
+//
+//   k_overlay_layout       one wavefront per text run: the pen of character i is the run's pen plus the exclusive prefix sum of
+//                          the advances before it (horizontal) or plus i steps (vertical); the scan runs OV_SCAN characters at a
+//                          time with a carry.  Writes words 5..10 of the run's GLYPH slots, kind -1 into a slot whose character
+//                          has no pixels.
+//   k_overlay_bounds       every command's inclusive bounding box clipped to ITS canvas, four int16 (1, 1, 0, 0 = covers nothing).
+//   k_draw_overlay_pages   one block per tile of ANY canvas of the wave.  No host binning: the block culls its canvas's commands
+//                          against its tile OV_THREADS boxes at a time, compacts the hits IN COMMAND ORDER into an LDS ring
+//                          (64-bit ballot + popcount prefix) and applies them through the chunk loop of k_draw_overlay.  Culling
+//                          by the clipped box is bin_commands' predicate and the order inside a tile is command order, so the
+//                          canvas equals what k_draw_overlay draws from the host's lists.
+constexpr int OV_SCAN = 64;                // characters per scan step: one per lane of a wavefront
+constexpr int OV_RING = 512;               // hit ring: at most OV_CHUNK - 1 pending hits + OV_THREADS new ones
+constexpr int OV_COORD = 16383;
+static_assert(OV_RING >= OV_CHUNK + OV_THREADS && (OV_RING & (OV_RING - 1)) == 0, "ring holds a pass on top of a partial chunk");
+static_assert(OV_THREADS % 64 == 0, "the compaction counts per 64-lane wavefront");
+
+__device__ __forceinline__ int clamp_coord(long long v) {
+  return (int)(v < -OV_COORD ? -OV_COORD : (v > OV_COORD ? OV_COORD : v));
+}
+
+__global__ __launch_bounds__(OV_SCAN) void k_overlay_layout(int* __restrict__ cmds, int n_cmds, const int* __restrict__ runs,
+                                                            int n_runs, const int* __restrict__ codes, int n_codes,
+                                                            const int* __restrict__ glyphs, int n_glyphs) {
+  const int r = blockIdx.x;
+  if (r >= n_runs) return;
+  const int* run = runs + (size_t)r * YMK_OVERLAY_RUN_WORDS;
+  const long long slot0 = run[0], code0 = run[1], count = run[2];
+  const long long pen_x = run[3], pen_y = run[4];
+  const bool vertical = run[5] != 0;
+  const long long step = run[6];
+  // a run that points outside the slot or code arrays is skipped, not trusted (block-uniform)
+  if (count <= 0 || slot0 < 0 || code0 < 0 || slot0 + count > n_cmds || code0 + count > n_codes) return;
+  const int lane = threadIdx.x;
+  long long carry = 0;  // sum of the advances of the characters before this step
+  for (long long base = 0; base < count; base += OV_SCAN) {
+    const long long i = base + lane;
+    const bool live = i < count;
+    int off = 0, gw = 0, gh = 0, ox = 0, oy = 0, adv = 0;
+    bool known = false;
+    if (live) {
+      const int id = codes[code0 + i];
+      if (id >= 0 && id < n_glyphs) {
+        const int* g = glyphs + (size_t)id * YMK_OVERLAY_GLYPH_WORDS;
+        off = g[0], gw = g[1], gh = g[2], ox = g[3], oy = g[4], adv = g[5];
+        known = true;
+      }
+    }
+    int incl = adv;  // inclusive scan over the wavefront
+#pragma unroll
+    for (int d = 1; d < OV_SCAN; d <<= 1) {
+      const int up = __shfl_up(incl, d, OV_SCAN);
+      if (lane >= d) incl += up;
+    }
+    const int total = __shfl(incl, OV_SCAN - 1, OV_SCAN);
+    if (live) {
+      int* c = cmds + (size_t)(slot0 + i) * OV_WORDS;
+      if (known && gw > 0 && gh > 0) {
+        const long long x = vertical ? pen_x : pen_x + carry + (incl - adv);
+        const long long y = vertical ? pen_y + i * step : pen_y;
+        c[5] = clamp_coord(x + ox);
+        c[6] = clamp_coord(y + oy);
+        c[7] = gw;
+        c[8] = gh;
+        c[9] = off;
+        c[10] = gw;
+      } else {
+        c[0] = -1;  // a space, or an id outside the table: a record that draws nothing
+#pragma unroll
+        for (int k = 5; k <= 10; ++k) c[k] = 0;
+      }
+    }
+    carry += total;
+  }
+}
+
+// canvas table entry: YMK_OVERLAY_CANVAS_WORDS int64 = byte offset, h, w, first command, command count, first tile
+struct OvCanvas {
+  long long offset, h, w, first, count, tile0;
+};
+
+__device__ __forceinline__ bool canvas_ok(const OvCanvas& cv, long long canvas_bytes, int n_cmds) {
+  if (!(cv.h > 0 && cv.w > 0 && cv.h <= OV_COORD && cv.w <= OV_COORD)) return false;
+  return cv.offset >= 0 && cv.offset <= canvas_bytes - cv.h * cv.w * 3 && cv.first >= 0 && cv.first <= n_cmds && cv.count >= 0 &&
+         cv.count <= n_cmds - cv.first && cv.tile0 >= 0;
+}
+
+__global__ __launch_bounds__(256) void k_overlay_bounds(const int* __restrict__ cmds, int n_cmds, short* __restrict__ bounds,
+                                                        const long long* __restrict__ table, int n_canvases) {
+  const int ci = blockIdx.y;
+  if (ci >= n_canvases) return;
+  const OvCanvas cv = reinterpret_cast<const OvCanvas*>(table)[ci];
+  if (!canvas_ok(cv, 0x7fffffffffffffffLL, n_cmds)) return;
+  for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < cv.count; k += (long long)gridDim.x * blockDim.x) {
+    const int* c = cmds + (size_t)(cv.first + k) * OV_WORDS;
+    int x0 = 1, y0 = 1, x1 = 0, y1 = 0;
+    const int kind = c[0];
+    if (kind == YMK_OVERLAY_SEG) {
+      const int pad = (c[9] + 1) / 2;  // t >= 0: a segment reaches t / 2 from its axis
+      x0 = min(c[5], c[7]) - pad, y0 = min(c[6], c[8]) - pad, x1 = max(c[5], c[7]) + pad, y1 = max(c[6], c[8]) + pad;
+    } else if (kind == YMK_OVERLAY_BOX) {
+      x0 = c[5], y0 = c[6], x1 = c[7], y1 = c[8];
+    } else if (kind == YMK_OVERLAY_GLYPH) {
+      x0 = c[5], y0 = c[6], x1 = c[5] + c[7] - 1, y1 = c[6] + c[8] - 1;
+    }
+    x0 = max(x0, 0), y0 = max(y0, 0), x1 = min(x1, (int)cv.w - 1), y1 = min(y1, (int)cv.h - 1);
+    if (x0 > x1 || y0 > y1) x0 = 1, y0 = 1, x1 = 0, y1 = 0;
+    short* b = bounds + (size_t)(cv.first + k) * 4;
+    b[0] = (short)x0, b[1] = (short)y0, b[2] = (short)x1, b[3] = (short)y1;
+  }
+}
+
+__global__ __launch_bounds__(OV_THREADS) void k_draw_overlay_pages(unsigned char* __restrict__ canvases, long long canvas_bytes,
+                                                                   const long long* __restrict__ table, int n_canvases,
+                                                                   const int* __restrict__ cmds, int n_cmds,
+                                                                   const short* __restrict__ bounds,
+                                                                   const unsigned char* __restrict__ atlas, long long atlas_bytes) {
+  __shared__ __attribute__((aligned(16))) int s_cmd[OV_CHUNK * OV_WORDS];
+  __shared__ int s_hits[OV_RING];
+  __shared__ int s_wave[OV_THREADS / 64];
+  // the canvas this tile belongs to: the table is a few dozen entries, every thread walks it (uniform, scalar loads)
+  const long long tile = blockIdx.x;
+  OvCanvas cv;
+  int tiles_x = 0;
+  bool found = false;
+  for (int ci = 0; ci < n_canvases && !found; ++ci) {
+    cv = reinterpret_cast<const OvCanvas*>(table)[ci];
+    if (!canvas_ok(cv, canvas_bytes, n_cmds)) continue;
+    tiles_x = (int)((cv.w + OV_TILE - 1) / OV_TILE);
+    const long long tiles = (long long)tiles_x * ((cv.h + OV_TILE - 1) / OV_TILE);
+    found = tile >= cv.tile0 && tile - cv.tile0 < tiles;
+  }
+  if (!found || cv.count == 0) return;  // block-uniform
+  const int h = (int)cv.h, w = (int)cv.w;
+  const int local = (int)(tile - cv.tile0);
+  const int tx0 = (local % tiles_x) * OV_TILE, ty0 = (local / tiles_x) * OV_TILE;
+  const int tx1 = tx0 + OV_TILE - 1, ty1 = ty0 + OV_TILE - 1;
+  const int px0 = tx0 + (threadIdx.x % (OV_TILE / OV_PX)) * OV_PX;
+  const int py = ty0 + threadIdx.x / (OV_TILE / OV_PX);
+  const bool row_in = py < h;
+  unsigned char* row = canvases + cv.offset + ((size_t)(row_in ? py : 0) * w) * 3;
+  const int* ccmds = cmds + (size_t)cv.first * OV_WORDS;
+  const short4* cbounds = reinterpret_cast<const short4*>(bounds) + cv.first;
+  const int count = (int)cv.count, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int pix[OV_PX][3];
+  bool loaded = false;
+  int head = 0, tail = 0;  // ring positions (block-uniform, only ever grow)
+  for (int base = 0; base < count; base += OV_THREADS) {
+    {
+      const int k = base + threadIdx.x;
+      bool hit = false;
+      if (k < count) {
+        const short4 b = cbounds[k];
+        hit = b.x <= b.z && b.x <= tx1 && b.z >= tx0 && b.y <= ty1 && b.w >= ty0;
+      }
+      const unsigned long long mask = __ballot(hit);
+      if (lane == 0) s_wave[wv] = __popcll(mask);
+      __syncthreads();
+      int before = 0, all = 0;
+#pragma unroll
+      for (int v = 0; v < OV_THREADS / 64; ++v) {
+        const int cnt = s_wave[v];
+        before += v < wv ? cnt : 0;
+        all += cnt;
+      }
+      if (hit) s_hits[(tail + before + __popcll(mask & ((1ull << lane) - 1ull))) & (OV_RING - 1)] = k;
+      tail += all;
+      __syncthreads();  // the hits are visible; s_wave may be rewritten by the next pass
+    }
+    const bool last = base + OV_THREADS >= count;
+    while (tail - head >= OV_CHUNK || (last && head < tail)) {
+      const int n_chunk = min(OV_CHUNK, tail - head);
+      if (!loaded) {  // the first hit of this tile: only now is the canvas read
+        loaded = true;
+#pragma unroll
+        for (int k = 0; k < OV_PX; ++k) {
+          const bool in = row_in && px0 + k < w;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) pix[k][ch] = in ? (int)row[(size_t)(px0 + k) * 3 + ch] : 0;
+        }
+      }
+      __syncthreads();  // the previous chunk has been read by every thread
+      {
+        const int rec = threadIdx.x / 4, quarter = threadIdx.x % 4;
+        if (rec < n_chunk) {
+          const int id = s_hits[(head + rec) & (OV_RING - 1)];  // in [0, count) by construction
+          reinterpret_cast<int4*>(s_cmd + rec * OV_WORDS)[quarter] = reinterpret_cast<const int4*>(ccmds + (size_t)id * OV_WORDS)[quarter];
+        }
+      }
+      __syncthreads();
+      for (int i = 0; i < n_chunk; ++i) {
+        const int* c = s_cmd + i * OV_WORDS;
+        const int cb = c[1], cg = c[2], cr = c[3];
+#pragma unroll
+        for (int k = 0; k < OV_PX; ++k) {
+          const int a = overlay_alpha(c, px0 + k, py, atlas, atlas_bytes);
+          if (a > 0) {
+            pix[k][0] = blend_u8(pix[k][0], cb, a);
+            pix[k][1] = blend_u8(pix[k][1], cg, a);
+            pix[k][2] = blend_u8(pix[k][2], cr, a);
+          }
+        }
+      }
+      head += n_chunk;
+    }
+  }
+  if (!loaded || !row_in) return;  // a tile without hits has neither read nor written a canvas byte
+#pragma unroll
+  for (int k = 0; k < OV_PX; ++k) {
+    if (px0 + k < w) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) row[(size_t)(px0 + k) * 3 + ch] = (unsigned char)pix[k][ch];
+    }
+  }
+}
+
 __device__ __forceinline__ int quantise_prob(float p) {
   p = fminf(fmaxf(p, 0.f), 1.f);
   return (int)(unsigned char)(int)(p * 255.f);  // truncation, as ndarray.astype(np.uint8) of a value in [0, 255]
@@ -170,6 +387,58 @@ int ymk_draw_overlay(unsigned char* canvas_dev, int h, int w, const int* cmds_de
     const dim3 grid((w + ymk::OV_TILE - 1) / ymk::OV_TILE, (h + ymk::OV_TILE - 1) / ymk::OV_TILE);
     hipLaunchKernelGGL(ymk::k_draw_overlay, grid, dim3(ymk::OV_THREADS), 0, (hipStream_t)stream, canvas_dev, h, w, cmds_dev, n,
                        tile_offsets_dev, tile_cmds_dev, n_list, atlas_dev, (long long)atlas_bytes);
+    YMK_HIP(hipGetLastError());
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_overlay_cull_pass(void) { return ymk::OV_THREADS; }
+
+int ymk_overlay_layout(int* cmds_dev, int n_cmds, int16_t* bounds_dev, const int* runs_dev, int n_runs, const int* codes_dev,
+                       int n_codes, const int* glyphs_dev, int n_glyphs, const int64_t* canvases_dev, int n_canvases, void* stream) {
+  try {
+    YMK_CHECK(n_cmds >= 0 && n_runs >= 0 && n_codes >= 0 && n_glyphs >= 0 && n_canvases >= 0 && n_canvases <= 65535, "bad argument");
+    if (n_cmds == 0) return 0;
+    YMK_CHECK(cmds_dev && bounds_dev, "null command / bounds pointer");
+    YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0 && ((uintptr_t)bounds_dev & 7) == 0 && ((uintptr_t)canvases_dev & 7) == 0,
+              "command records must be 16-byte, bounds and the canvas table 8-byte aligned");
+    if (n_runs > 0) {
+      YMK_CHECK(runs_dev && (codes_dev || n_codes == 0) && (glyphs_dev || n_glyphs == 0), "null run / code / glyph pointer");
+      hipLaunchKernelGGL(ymk::k_overlay_layout, dim3(n_runs), dim3(ymk::OV_SCAN), 0, (hipStream_t)stream, cmds_dev, n_cmds, runs_dev,
+                         n_runs, codes_dev, n_codes, glyphs_dev, n_glyphs);
+      YMK_HIP(hipGetLastError());
+    }
+    if (n_canvases > 0) {
+      YMK_CHECK(canvases_dev, "null canvas table");
+      const int gx = std::min(std::max((n_cmds + 255) / 256, 1), 256);
+      hipLaunchKernelGGL(ymk::k_overlay_bounds, dim3(gx, n_canvases), dim3(256), 0, (hipStream_t)stream, cmds_dev, n_cmds,
+                         (short*)bounds_dev, (const long long*)canvases_dev, n_canvases);
+      YMK_HIP(hipGetLastError());
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_draw_overlay_pages(unsigned char* canvases_dev, int64_t canvas_bytes, const int64_t* table_dev, int n_canvases,
+                           int64_t total_tiles, const int* cmds_dev, int n_cmds, const int16_t* bounds_dev,
+                           const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream) {
+  try {
+    YMK_CHECK(canvas_bytes >= 0 && n_canvases >= 0 && total_tiles >= 0 && total_tiles <= 0x7fffffffLL && n_cmds >= 0 &&
+                  atlas_bytes >= 0, "bad argument");
+    if (n_canvases == 0 || total_tiles == 0 || n_cmds == 0) return 0;
+    YMK_CHECK(canvases_dev && table_dev && cmds_dev && bounds_dev, "null canvas / table / command / bounds pointer");
+    YMK_CHECK(atlas_dev || atlas_bytes == 0, "null atlas with a non-zero size");
+    YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0 && ((uintptr_t)bounds_dev & 7) == 0 && ((uintptr_t)table_dev & 7) == 0,
+              "command records must be 16-byte, bounds and the canvas table 8-byte aligned");
+    hipLaunchKernelGGL(ymk::k_draw_overlay_pages, dim3((unsigned)total_tiles), dim3(ymk::OV_THREADS), 0, (hipStream_t)stream,
+                       canvases_dev, (long long)canvas_bytes, (const long long*)table_dev, n_canvases, cmds_dev, n_cmds,
+                       (const short*)bounds_dev, atlas_dev, (long long)atlas_bytes);
     YMK_HIP(hipGetLastError());
     return 0;
   } catch (const std::exception& e) {

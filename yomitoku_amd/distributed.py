@@ -404,6 +404,9 @@ class ShardedServer:
         from the node's PageDealer; "static": source i belongs to rank i % world, known up front."""
         if assign not in ("dynamic", "static"):
             raise ValueError(f"assign must be 'dynamic' or 'static', got {assign!r}")
+        if serve_kwargs.get("overlays"):
+            raise NotImplementedError("overlays=True is not supported by serve_sharded: the ranks' images are not gathered "
+                                      "(DocumentAnalyzer.serve(..., overlays=True) draws on one GPU)")
         serve_kwargs.setdefault("rec_lanes", self.budget["rec_lanes"])
         self._jobs += 1  # run() is called by every rank for every job: the job number is the same everywhere
         if assign == "static":

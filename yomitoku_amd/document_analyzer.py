@@ -355,6 +355,7 @@ class DocumentAnalyzer:
         # without a subclass that re-states the stage bodies (bench.py; tests/test_serving_gpu.py holds the hook to
         # "identity in, identical results out")
         self.handover = None
+        self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
 
     # ---- aggregation (:487-601)
     def aggregate(self, ocr_res, layout_res, img=None):
@@ -526,6 +527,45 @@ class DocumentAnalyzer:
         results_ocr = OCRSchema(words=ocr_aggregate(wave.dets[k], wave.recs[k]))
         return DocumentAnalyzerSchema(**self.aggregate(results_ocr, wave.lays[k], img=wave.imgs[k]))
 
+    def _page_drawings(self, wave, k, results):
+        """The two drawings of page k of a finished wave, recorded for the wave renderer: what `_with_overlays` draws with
+        every visualize flag on - the detection quads and the recognised strings; the layout boxes, the table cells and the
+        reading order."""
+        from .utils import visualizer as V
+
+        ocr, layout = V.RunOverlay(), V.RunOverlay()
+        V._det_commands(ocr, wave.dets[k].points)
+        cfg = self.text_recognizer._cfg.visualize
+        V._rec_commands(ocr, wave.recs[k], V.load_font(cfg.font, cfg.font_size), cfg.font_size, tuple(cfg.color[::-1]))
+        V._layout_commands(layout, wave.lay_parsed[k])
+        for table in wave.lays[k].tables:
+            V._table_commands(layout, table)
+        V._page_order_commands(layout, results)
+        return ocr, layout
+
+    def _stage_render(self, wave, results):
+        """serve(overlays=True): per page of the wave (ocr overlay, layout overlay) as owned host arrays, an exception for a
+        page whose drawing raised, None for a page that had already failed.  All canvases of the wave are drawn by two
+        launches on the calling thread's stream and come back through the wave slot's pinned buffer."""
+        from .utils.visualizer import render_wave
+
+        out = [None] * len(wave)
+        live, drawings = [], []
+        for k in range(len(wave)):
+            if isinstance(results[k], BaseException):
+                continue
+            try:
+                drawings.extend(self._page_drawings(wave, k, results[k]))
+                live.append(k)
+            except Exception as exc:  # noqa: BLE001 - only this page fails
+                out[k] = exc
+        if live:
+            pinned = self._render_pinned.setdefault(wave.ring, [None])
+            images = render_wave([wave.pages[k] for k in live for _ in range(2)], drawings, pinned)
+            for j, k in enumerate(live):
+                out[k] = (images[2 * j], images[2 * j + 1])
+        return out
+
     def _recognize_wave(self, wave):
         self._stage_crops(wave)
         self._stage_recognize(wave)
@@ -595,7 +635,8 @@ class DocumentAnalyzer:
 
         return reading_order_visualizer(page if layout is None else layout, results, to_host=False)
 
-    def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2):
+    def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
+              overlays: bool = False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -605,12 +646,18 @@ class DocumentAnalyzer:
         affected (cli/main.py:555-564).  `defer_full_gc`: postpone CPython's generation-2 garbage collections until
         the job is done (a full pass holds the GIL for 100+ ms with a few hundred results alive and stalls every stage).
         `with_source`: (source index, frame index, entry) triples, for callers that write one output per file page.
-        `rec_lanes`: recogniser forwards in flight (2: a second PARSeq handle with the same weights; serving.py)."""
+        `rec_lanes`: recogniser forwards in flight (2: a second PARSeq handle with the same weights; serving.py).
+        `overlays`: a property of the job, not of the analyzer - True: a page's entry is (schema, ocr overlay, layout overlay),
+        the two images `analyze_pages` returns for the page when everything was built with visualize=True (detection quads and
+        recognised strings; layout boxes, table cells, reading order; no heat map), as uint8 H x W x 3 arrays the caller owns.
+        They are drawn on the device by a render stage of the pipeline - text layout, per-tile culling and all canvases of a
+        wave in two launches ("Overlay rasteriser") - that only the waves of such a job visit."""
         from .serving import PagePipeline
 
         if self.visualize:
-            raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: a rendering stage in the page "
-                                      "pipeline is a change of its own (visualize=False only; __call__ and analyze_pages draw)")
+            raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: build the analyzer with "
+                                      "visualize=False and ask per job, serve(..., overlays=True) (__call__ and analyze_pages "
+                                      "draw with visualize=True)")
         pipe = getattr(self, "_pipeline", None)
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
             if pipe is not None:
@@ -618,7 +665,7 @@ class DocumentAnalyzer:
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
             pipe.rec_lanes_asked = int(rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, release the extra recogniser handles and - `release_models` - the device memory of the
@@ -628,6 +675,7 @@ class DocumentAnalyzer:
         if pipe is not None:
             pipe.close()
             self._pipeline = None
+        self._render_pinned.clear()
         self.text_recognizer.close_replicas()
         if release_models:
             for module in (self.text_detector, self.text_recognizer, self.layout.layout_parser, self.layout.table_structure_recognizer):

@@ -14,6 +14,7 @@ leaves the device mostly idle, so `DocumentAnalyzer.serve` runs the page loop as
     tables          layout boxes (host), table-structure forward over all table crops            HIP stream
     cells           row / column / span filters, cell grids                                      host
     finish          word -> cell / paragraph aggregation and reading order, per page             host
+    render          serve(overlays=True) only: both overlay images of every page of the wave      HIP stream
 
 The host halves are their own stages on purpose: a thread that owns a network only ever launches - it never sits in box
 logic or string decoding while its stream runs dry (measured: with crop planning / decode inside the recognise stage
@@ -25,6 +26,11 @@ model handle is only ever used by one thread, which is what include/ymk.h asks f
 stream fit the eight hardware queues the package asks the HIP runtime for.  Wave k + 1 is in the detector while wave k decodes text and its tables are parsed; up to `in_flight`
 waves are between upload and aggregation (a ring of pinned map buffers per wave slot), which bounds host and device
 memory.
+
+`render` is not one of the nine: its thread and stream are started by the first job that asks for overlays, and only the
+waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all canvases
+of a wave (two per page) with two launches (utils/visualizer.py: render_wave); a job without overlays runs exactly the stages
+above.
 
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
 process while holding the GIL - measured 100-180 ms with the results of a few hundred pages alive, six times in a
@@ -65,11 +71,12 @@ class Wave:
     """The pages that share device batches, and what the stages have produced for them so far."""
 
     __slots__ = ("seq", "ids", "imgs", "pages", "ring", "uploaded", "maps", "sizes", "dets", "rec_plan", "recs", "lay_raw",
-                 "lay_parsed", "tab_raw", "lays", "error", "failed_stage", "layout_done", "joined", "retry", "job")
+                 "lay_parsed", "tab_raw", "lays", "error", "failed_stage", "layout_done", "joined", "retry", "job", "results")
 
     def __init__(self, seq=0, ids=(), imgs=(), pages=(), ring=0, uploaded=None, retry=False, job=None):
         self.seq, self.ids, self.imgs, self.pages, self.ring, self.uploaded = seq, list(ids), list(imgs), list(pages), ring, uploaded
         self.job = job  # the serve() call this wave belongs to: a late wave of an aborted job must not write into the next one
+        self.results = None  # per page, what `finish` made of it (schema or exception): only kept for the render stage
         self.sizes = [tuple(int(v) for v in p.shape[:2]) for p in self.pages]
         self.maps = self.dets = self.rec_plan = self.recs = self.lay_raw = self.lay_parsed = self.tab_raw = self.lays = None
         self.error: Optional[BaseException] = None
@@ -89,8 +96,9 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0):
+    def __init__(self, n_hint=0, overlays=False):
         self.results = {}
+        self.overlays = bool(overlays)  # entries are (schema, ocr overlay, layout overlay): the waves visit the render stage
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -179,6 +187,8 @@ class PagePipeline:
         self._seq = 0
         self.trace = None  # a list: every stage appends (stage, wave seq, pages, t_start, t_end) - tools/serve_trace.py
         self._serve_lock = threading.Lock()
+        self._render_q: "queue.Queue" = queue.Queue()
+        self._render_thread = None  # started by the first job that asks for overlays
         a = analyzer
         # (stage, function, launches on the GPU?, next stages); the recognise chain and the layout chain join in `finish`
         plan = (("detect", a._stage_detect, True, ("boxes",)), ("boxes", self._boxes, False, ("crops",)),
@@ -252,6 +262,55 @@ class PagePipeline:
             if wave.error is None:
                 a._stage_split(wave)
 
+    def _render_loop(self):
+        """The render stage: waves of overlays jobs, after aggregation.  Turns every page's schema into (schema, ocr overlay,
+        layout overlay); a page whose drawing fails - or every page of the wave, when the launches fail - gets the exception."""
+        stream = None
+        if self._gpu:
+            torch.cuda.set_device(self.device)
+            stream = torch.cuda.Stream(device=self.device)
+        while True:
+            wave = self._render_q.get()
+            if wave is _STOP:
+                return
+            t_start = time.perf_counter()
+            job, results = wave.job, wave.results
+            try:
+                try:
+                    if stream is not None:
+                        with torch.cuda.stream(stream):
+                            stream.wait_event(wave.uploaded)
+                            images = self.analyzer._stage_render(wave, results)
+                            stream.synchronize()
+                    else:
+                        images = self.analyzer._stage_render(wave, results)
+                except BaseException as exc:  # noqa: BLE001 - delivered to the pages' result slots
+                    logger.error("wave %d failed in the render stage: %s: %s", wave.seq, type(exc).__name__, exc)
+                    images = [exc] * len(wave)
+                    if stream is not None:
+                        try:
+                            stream.synchronize()  # nothing may still read the wave's pages when the slot goes back
+                        except Exception:  # noqa: BLE001
+                            pass
+                for k, idx in enumerate(wave.ids):
+                    if isinstance(results[k], BaseException):
+                        job.results[idx] = results[k]
+                    elif isinstance(images[k], BaseException):
+                        logger.error("page %d failed in the render stage: %s: %s", idx, type(images[k]).__name__, images[k])
+                        job.results[idx] = images[k]
+                    else:
+                        job.results[idx] = (results[k],) + tuple(images[k])
+                if self.trace is not None:
+                    self.trace.append(("render", wave.seq, len(wave), t_start, time.perf_counter()))
+            finally:
+                wave.results = None
+                self._release(wave)
+
+    def _start_render(self):
+        if self._render_thread is None or not self._render_thread.is_alive():
+            self._render_thread = threading.Thread(target=self._render_loop, name="ymk-render", daemon=True)
+            self._render_thread.start()
+
     def _release(self, wave):
         job = wave.job
         wave.pages = wave.maps = wave.rec_plan = None  # the device pages, the pinned map views and the crop tensors go back
@@ -273,12 +332,19 @@ class PagePipeline:
                              wave.error)
                 job.results[wave.ids[0]] = wave.error
         else:
+            done = []
             for k, idx in enumerate(wave.ids):
                 try:
-                    job.results[idx] = self.analyzer._stage_finish(wave, k)
+                    done.append(self.analyzer._stage_finish(wave, k))
                 except Exception as exc:  # noqa: BLE001 - aggregation is per page: only this page fails
                     logger.error("page %d failed in aggregation: %s: %s", idx, type(exc).__name__, exc)
-                    job.results[idx] = exc
+                    done.append(exc)
+            if job.overlays:  # the render stage writes the entries and hands the slot back
+                wave.results = done
+                self._render_q.put(wave)
+                return
+            for idx, entry in zip(wave.ids, done):
+                job.results[idx] = entry
         self._release(wave)
 
     # ------------------------------------------------------------------ caller side
@@ -310,15 +376,21 @@ class PagePipeline:
         self._q["detect"].put(wave)
         self._q["layout"].put(wave)
 
-    def serve(self, sources: Iterable, with_source: bool = False) -> List:
+    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
-        caller that writes `<file>_p<page>.json` per page needs (cli/main.py:122-137)."""
+        caller that writes `<file>_p<page>.json` per page needs (cli/main.py:122-137).
+        overlays=True: a page's entry is (DocumentAnalyzerSchema, ocr overlay, layout overlay) - the two uint8 H x W x 3 images
+        `analyze_pages` returns for the page with visualize=True everywhere, as arrays the caller owns; a failed page's entry
+        stays the bare exception.  The waves of such a job pass through the render stage, whose thread the first such job
+        starts; a job without overlays runs what it always ran."""
         from .data.functions import load_image
 
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job()
+            job = self._job = _Job(overlays=overlays)
+            if job.overlays:
+                self._start_render()
             n = 0
             origin = []  # page id -> (source index, frame index)
             pend_ids, pend_imgs = [], []
@@ -404,3 +476,7 @@ class PagePipeline:
                 q.put(_STOP)
         for t in self._threads:
             t.join(timeout=10)
+        if self._render_thread is not None:
+            self._render_q.put(_STOP)
+            self._render_thread.join(timeout=10)
+            self._render_thread = None

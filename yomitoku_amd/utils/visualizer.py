@@ -11,6 +11,11 @@ The overlays are equivalent in content to the reference's (same elements, colour
 points), not byte-identical: OpenCV's Hershey font and Bresenham rules are replaced by the rules of include/ymk.h and by
 Pillow glyphs.  Colour tuples are applied to the canvas's channels in the order given, as cv2 and ImageDraw do.
 
+`DocumentAnalyzer.serve(overlays=True)` draws the same content another way (the second half of this file): text is recorded
+as runs and laid out by ymk_overlay_layout, and ymk_draw_overlay_pages culls per tile and draws all canvases of a wave of pages
+in one launch - no per-character loop and no binning on the host.  The CONTENT of each drawing is written once, in the
+`_xxx_commands(ov, ...)` helpers, for both recorders (Overlay, RunOverlay).
+
 The five functions keep the reference's names and arguments and return np.ndarray; `img` may also be a device tensor, and
 `to_host=False` (not in the reference) returns the device canvas instead, which is how the modules chain overlays without a
 round trip through the host.
@@ -294,11 +299,10 @@ class Overlay:
         self._heatmap = prob
 
     # ---- build + launch
-    def build(self, h: int, w: int, tile=None):
-        """The launch's host data: {"cmds": int32 [n][16], "atlas": uint8 [bytes], "tile_offsets", "tile_cmds"}."""
-        tile = overlay_tile() if tile is None else int(tile)
+    def _clamped(self):
+        """The recorded commands, int64 [n][16]: every coordinate clipped into [-16383, 16383] (the range the kernel's 64-bit
+        products are sized for), colours into 0..255."""
         cmds = np.concatenate(self._chunks, axis=0) if self._chunks else np.zeros((0, CMD_WORDS), dtype=np.int64)
-        # every coordinate into [-16383, 16383] (the range the kernel's 64-bit products are sized for), colours into 0..255
         kind = cmds[:, 0:1]
         words = np.arange(CMD_WORDS)[None, :]
         coord = ((kind == SEG) & (words >= 5) & (words <= 8)) | ((kind == BOX) & (words >= 5) & (words <= 12)) \
@@ -307,6 +311,12 @@ class Overlay:
         cmds[:, 1:4] = np.clip(cmds[:, 1:4], 0, 255)
         seg_t = cmds[:, 0] == SEG
         cmds[seg_t, 9] = np.clip(cmds[seg_t, 9], 0, COORD_MAX)
+        return cmds
+
+    def build(self, h: int, w: int, tile=None):
+        """The launch's host data: {"cmds": int32 [n][16], "atlas": uint8 [bytes], "tile_offsets", "tile_cmds"}."""
+        tile = overlay_tile() if tile is None else int(tile)
+        cmds = self._clamped()
         sizes = np.array([m.size for m in self._masks], dtype=np.int64)
         starts = np.cumsum(sizes) - sizes
         atlas = np.concatenate([m.reshape(-1) for m in self._masks]) if self._masks else np.zeros(0, dtype=np.uint8)
@@ -410,28 +420,40 @@ def det_visualizer(img, quads, preds=None, vis_heatmap=False, line_color=(0, 255
     if vis_heatmap:
         binary = preds["binary"] if isinstance(preds, dict) else preds
         ov.heatmap(binary[0] if binary.ndim == 4 else binary)
-    ov.polyline(np.asarray(quads, dtype=np.int64).reshape(-1, 4, 2), True, line_color, 1)
+    _det_commands(ov, quads, line_color)
     return _finish(ov, img, to_host)
+
+
+def _det_commands(ov, quads, line_color=(0, 255, 0)):
+    ov.polyline(np.asarray(quads, dtype=np.int64).reshape(-1, 4, 2), True, line_color, 1)
 
 
 def rec_visualizer(img, outputs, font_path, font_size=12, font_color=(255, 0, 0), to_host=True):
     """utils/visualizer.py:207-250: every recognised line next to its quad - horizontal lines start at quad[0] + (0, -font_size),
     vertical lines at quad[0] + (-font_size, 0) and run downwards."""
     ov = Overlay()
-    font = load_font(font_path, font_size)
+    _rec_commands(ov, outputs, load_font(font_path, font_size), font_size, font_color)
+    return _finish(ov, img, to_host)
+
+
+def _rec_commands(ov, outputs, font, font_size, font_color):
     for pred, quad, direction in zip(outputs.contents, outputs.points, outputs.directions):
         x, y = int(quad[0][0]), int(quad[0][1])
         if direction == "vertical":
             ov.text((x - font_size, y), pred, font, font_color, direction="vertical")
         else:
             ov.text((x, y - font_size), pred, font, font_color)
-    return _finish(ov, img, to_host)
 
 
 def layout_visualizer(results, img, to_host=True):
     """utils/visualizer.py:99-125: per category the PALETTE colour, an outline of t = 2 and the label `category(role)` in the
     built-in font at 12 px with its baseline at (x1, y1)."""
     ov = Overlay()
+    _layout_commands(ov, results)
+    return _finish(ov, img, to_host)
+
+
+def _layout_commands(ov, results):
     font = load_font(None, 12)
     for idx, (category, preds) in enumerate(results.model_dump().items()):
         color = PALETTE[idx % len(PALETTE)]
@@ -440,7 +462,6 @@ def layout_visualizer(results, img, to_host=True):
             x1, y1, x2, y2 = (int(v) for v in element["box"])
             ov.rectangle((x1, y1, x2, y2), color, 2)
             ov.text((x1, y1), category + ("" if role is None else f"({role})"), font, color, anchor="ls")
-    return _finish(ov, img, to_host)
 
 
 def table_visualizer(img, table, to_host=True):
@@ -486,9 +507,347 @@ def reading_order_visualizer(img, results, line_color=(0, 0, 255), tip_size=10, 
     """utils/visualizer.py:11-78: the order number of every paragraph, table and figure at its centre (24 px) and an arrow of
     t = 2 from each element's centre to the next one's."""
     ov = Overlay()
+    _page_order_commands(ov, results, line_color, tip_size, visualize_figure_letter)
+    return _finish(ov, img, to_host)
+
+
+def _page_order_commands(ov, results, line_color=(0, 0, 255), tip_size=10, visualize_figure_letter=False):
     elements = sorted(results.paragraphs + results.tables + results.figures, key=lambda e: e.order)
     _reading_order_commands(ov, elements, line_color, tip_size)
     if visualize_figure_letter:
         for figure in results.figures:
             _reading_order_commands(ov, figure.paragraphs, (0, 255, 0), 5)
-    return _finish(ov, img, to_host)
+
+
+# ------------------------------------------------------------------------------- a wave of canvases (serve(overlays=True))
+# The per-page path above spends its time on the host: a Python loop per character and a sort over the per-tile lists
+# (DESIGN.md "Overlay rasteriser").  Here the host records text as RUNS and reserves one command slot per character;
+# ymk_overlay_layout places the glyphs and computes every command's clipped bounding box, ymk_draw_overlay_pages culls per
+# tile and draws all canvases of a wave in one launch (include/ymk.h).
+RUN_WORDS, GLYPH_WORDS, CANVAS_WORDS = 8, 6, 6  # YMK_OVERLAY_RUN_WORDS / _GLYPH_WORDS / _CANVAS_WORDS
+PEN_MAX = 1 << 30  # pens are int32 on the device; a pen this far out has left the clamp range for good
+
+
+class GlyphStore:
+    """Glyph table and atlas of every font drawn through the wave path: glyph id -> (atlas offset, w, h, x offset, y offset,
+    advance), ids and offsets handed out once and never moved (append-only).  The host mirror serves the code point -> glyph id
+    lookup (`ids`: one searchsorted per font; a code point seen for the first time goes through `glyph_of`); `tensors` keeps a
+    device copy up to date.  A device tensor is only ever appended to past what earlier launches can reference, and replaced -
+    never resized - when it is full, so a wave in flight stays valid as long as it holds the tensors it launched with."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._fonts = {}                                    # font key -> (sorted code points int64, glyph ids int32)
+        self._table = np.zeros((256, GLYPH_WORDS), np.int32)
+        self._atlas = np.zeros(1 << 16, np.uint8)
+        self.n_glyphs = 0
+        self.atlas_bytes = 0
+        self._dev = {}                                      # device -> [table tensor, rows uploaded, atlas tensor, bytes uploaded]
+
+    @staticmethod
+    def _lookup(entry, codes):
+        cps, gids = entry
+        if len(cps) == 0:
+            return np.full(len(codes), -1, np.int32), np.zeros(len(codes), bool)
+        pos = np.minimum(np.searchsorted(cps, codes), len(cps) - 1)
+        return gids[pos], cps[pos] == codes
+
+    def ids(self, font, codes):
+        """Glyph ids (int32) of the code points `codes` (integer array) in `font` (what load_font returned)."""
+        font_obj, fkey = font
+        codes = np.asarray(codes, dtype=np.int64)
+        with self._lock:
+            entry = self._fonts.get(fkey) or (np.zeros(0, np.int64), np.zeros(0, np.int32))
+            gids, hit = self._lookup(entry, codes)
+            if not hit.all():
+                entry = self._fonts[fkey] = self._append(font_obj, fkey, entry, np.unique(codes[~hit]))
+                gids, hit = self._lookup(entry, codes)
+            return gids
+
+    def _append(self, font_obj, fkey, entry, missing):
+        """Slow path: rasterise the code points `missing` (sorted, unique) and append them to the table and the atlas."""
+        new_ids = []
+        for cp in missing.tolist():
+            mask, ox, oy, advance = glyph_of(font_obj, fkey, chr(cp))
+            gh, gw = mask.shape
+            if self.n_glyphs == len(self._table):
+                self._table = np.concatenate([self._table, np.zeros_like(self._table)])
+            while self.atlas_bytes + mask.size > len(self._atlas):
+                self._atlas = np.concatenate([self._atlas, np.zeros_like(self._atlas)])
+            self._table[self.n_glyphs] = (self.atlas_bytes, gw, gh, ox, oy, advance)
+            self._atlas[self.atlas_bytes : self.atlas_bytes + mask.size] = mask.reshape(-1)
+            new_ids.append(self.n_glyphs)
+            self.n_glyphs += 1
+            self.atlas_bytes += mask.size
+        cps = np.concatenate([entry[0], missing])
+        gids = np.concatenate([entry[1], np.asarray(new_ids, np.int32)])
+        order = np.argsort(cps, kind="stable")
+        return cps[order], gids[order]
+
+    def host(self):
+        """(glyph table int32 [n][6], atlas uint8 [bytes]) as they stand."""
+        with self._lock:
+            return self._table[: self.n_glyphs].copy(), self._atlas[: self.atlas_bytes].copy()
+
+    def tensors(self, device):
+        """(table tensor, n_glyphs, atlas tensor, atlas_bytes) on `device`, holding everything `ids` has handed out so far."""
+        import torch
+
+        device = torch.device(device)
+        with self._lock:
+            st = self._dev.get(device)
+            if st is None:
+                st = self._dev[device] = [None, 0, None, 0]
+            if st[1] < self.n_glyphs or st[3] < self.atlas_bytes or st[0] is None:
+                with torch.cuda.device(device):
+                    if st[0] is None or st[0].shape[0] < self.n_glyphs:  # full: a new tensor; the old one lives on with its waves
+                        st[0], st[1] = torch.zeros((len(self._table), GLYPH_WORDS), dtype=torch.int32, device=device), 0
+                    if st[2] is None or st[2].shape[0] < self.atlas_bytes:
+                        st[2], st[3] = torch.zeros(len(self._atlas), dtype=torch.uint8, device=device), 0
+                    if st[1] < self.n_glyphs:
+                        st[0][st[1] : self.n_glyphs].copy_(torch.from_numpy(self._table[st[1] : self.n_glyphs].copy()))
+                    if st[3] < self.atlas_bytes:
+                        st[2][st[3] : self.atlas_bytes].copy_(torch.from_numpy(self._atlas[st[3] : self.atlas_bytes].copy()))
+                    st[1], st[3] = self.n_glyphs, self.atlas_bytes
+                    torch.cuda.current_stream().synchronize()  # rare (a glyph seen for the first time): visible to every stream
+            return st[0], st[1], st[2], st[3]
+
+
+_STORE = GlyphStore()
+
+
+def glyph_store() -> GlyphStore:
+    """The process's glyph store."""
+    return _STORE
+
+
+class RunOverlay(Overlay):
+    """Overlay's drawing methods for the wave path.  `text` records a RUN - first slot, pen, direction, font, string - and
+    reserves one GLYPH slot per character; the records of those slots (kind, colour) are written for all runs at once when the
+    wave is built (np.repeat), and the device lays the characters out.  A single rectangle is recorded as plain integers.
+    There is no per-character work on the host and no array is made per call.  `text` returns None (the pen's end is only
+    known on the device); `glyph` and `heatmap` are not part of the wave path."""
+
+    def __init__(self):
+        super().__init__()
+        self._n = 0
+        self._at = []     # first slot of every block of self._chunks
+        self._boxes = []  # (slot, r, g, b, alpha, eight BOX words) of rectangles given as four numbers
+        self._runs = []   # (first slot, count, pen x, pen y, vertical, step, font, string, colour)
+
+    def _push(self, kind, color, alpha, params):
+        before = len(self._chunks)
+        super()._push(kind, color, alpha, params)
+        if len(self._chunks) > before:
+            self._at.append(self._n)
+            self._n += len(self._chunks[-1])
+
+    def __len__(self):
+        return self._n
+
+    def glyph(self, *args, **kwargs):
+        raise NotImplementedError("RunOverlay draws text through runs; free-standing masks go through Overlay")
+
+    def heatmap(self, prob):
+        raise NotImplementedError("the wave path draws no heat map")
+
+    def render(self, page, device=None):
+        raise NotImplementedError("a RunOverlay is drawn with its wave: render_wave / draw_wave")
+
+    def build(self, h, w, tile=None):
+        raise NotImplementedError("a RunOverlay is built with its wave: build_wave")
+
+    def rectangle(self, box, color, thickness=1, alpha=255):
+        if int(thickness) < 0 or np.ndim(box) != 1 or np.ndim(color) != 1:
+            return super().rectangle(box, color, thickness, alpha)
+        xa, ya, xb, yb = (int(v) for v in box)  # Overlay.rectangle for one box, in plain integers
+        x1, x2, y1, y2 = min(xa, xb), max(xa, xb), min(ya, yb), max(ya, yb)
+        t = int(thickness)
+        g, s = t // 2, (t + 1) // 2
+        self._boxes.append((self._n, int(color[0]), int(color[1]), int(color[2]), min(max(int(alpha), 0), 255),
+                            x1 - g, y1 - g, x2 + g, y2 + g, x1 + s, y1 + s, x2 - s, y2 - s))
+        self._n += 1
+
+    def text(self, xy, string, font, color, direction="horizontal", anchor="la"):
+        n = len(string)
+        if n == 0:
+            return None
+        font_obj = font[0]
+        pen_x, pen_y = int(xy[0]), int(xy[1])
+        if anchor == "ls":
+            pen_y -= int(font_obj.getmetrics()[0])
+        self._runs.append((self._n, n, min(max(pen_x, -PEN_MAX), PEN_MAX), min(max(pen_y, -PEN_MAX), PEN_MAX),
+                           direction == "vertical", int(font_obj.size), font, string, color))
+        self._n += n
+        return None
+
+    def _clamped(self):
+        """The records of this drawing, int64 [n][16], clamped as Overlay's; the text slots carry kind, colour and alpha."""
+        self._chunks, blocks, at = [], self._chunks, self._at
+        try:
+            if self._boxes:
+                boxes = np.asarray(self._boxes, dtype=np.int64)
+                rec = np.zeros((len(boxes), CMD_WORDS), dtype=np.int64)
+                rec[:, 0] = BOX
+                rec[:, 1:13] = boxes[:, 1:]
+                blocks, at = blocks + [rec], at + [boxes[:, 0]]
+            self._chunks = blocks
+            drawn = super()._clamped()  # every block that is not text, in the order of `blocks`
+        finally:
+            self._chunks = self._chunks[: len(self._at)]
+        out = np.zeros((self._n, CMD_WORDS), dtype=np.int64)
+        if len(drawn):
+            out[np.concatenate([np.arange(len(b)) + a if np.ndim(a) == 0 else a for b, a in zip(blocks, at)])] = drawn
+        if self._runs:
+            first = np.asarray([r[0] for r in self._runs], dtype=np.int64)
+            counts = np.asarray([r[1] for r in self._runs], dtype=np.int64)
+            colours = np.clip(np.asarray([r[8] for r in self._runs], dtype=np.int64).reshape(-1, 3), 0, 255)
+            slots = np.repeat(first - (np.cumsum(counts) - counts), counts) + np.arange(int(counts.sum()))
+            out[slots, 0] = GLYPH
+            out[slots, 1:4] = np.repeat(colours, counts, axis=0)
+            out[slots, 4] = 255
+        return out
+
+
+def build_wave(drawings, sizes, offsets=None, store=None):
+    """Host data of one wave: `drawings` - one RunOverlay per canvas - on canvases of `sizes` [(h, w)] that start at byte
+    `offsets` of the canvas buffer (default: packed, each on a 16-byte boundary).
+    {"cmds" int32 [n][16], "table" int64 [canvases][6], "runs" int32 [runs][8], "codes" int32 [characters], "tiles", "bytes"}."""
+    store = _STORE if store is None else store
+    tile = overlay_tile()
+    table = np.zeros((len(drawings), CANVAS_WORDS), dtype=np.int64)
+    parts, runs, strings, fonts, font_of_run = [], [], [], {}, []
+    first = tiles = at = 0
+    for ci, (ov, (h, w)) in enumerate(zip(drawings, sizes)):
+        h, w = int(h), int(w)
+        if offsets is None:
+            off, at = at, at + -(-(h * w * 3) // 16) * 16
+        else:
+            off = int(offsets[ci])
+            at = max(at, off + h * w * 3)
+        table[ci] = (off, h, w, first, len(ov), tiles)
+        if len(ov):
+            parts.append(ov._clamped())
+        for slot, n, pen_x, pen_y, vertical, step, font, string, _ in ov._runs:
+            runs.append((first + slot, 0, n, pen_x, pen_y, int(vertical), step, 0))
+            strings.append(string)
+            font_of_run.append(fonts.setdefault(font[1], (len(fonts), font))[0])
+        first += len(ov)
+        tiles += -(-h // tile) * -(-w // tile)
+    cmds = np.concatenate(parts, axis=0).astype(np.int32) if parts else np.zeros((0, CMD_WORDS), dtype=np.int32)
+    runs = np.asarray(runs, dtype=np.int32).reshape(-1, RUN_WORDS)
+    # every string of the wave as code points in one pass; glyph ids by one sorted lookup per font
+    points = np.frombuffer("".join(strings).encode("utf-32-le", "surrogatepass"), dtype="<u4").astype(np.int64)
+    codes = np.zeros(len(points), dtype=np.int32)
+    if len(runs):
+        counts = runs[:, 2].astype(np.int64)
+        runs[:, 1] = np.cumsum(counts) - counts
+        which = np.repeat(np.asarray(font_of_run, dtype=np.int64), counts)
+        for fi, font in fonts.values():
+            sel = which == fi
+            codes[sel] = store.ids(font, points[sel])
+    return {"cmds": cmds, "table": table, "runs": runs, "codes": codes, "tiles": tiles, "bytes": at}
+
+
+def launch_wave(canvas_buf, cmds, table, runs=None, codes=None, glyphs=None, atlas=None):
+    """Two library calls on the current stream, in place on `canvas_buf` (a contiguous 1-D uint8 device tensor that holds the
+    canvases `table` describes): ymk_overlay_layout, ymk_draw_overlay_pages.  cmds / table / runs / codes: host arrays as
+    build_wave returns them, uploaded as ONE blob; glyphs / atlas: the glyph table and the atlas, device tensors (GlyphStore.
+    tensors) or host arrays (uploaded with the blob).  Returns a dict that keeps every device buffer of the launches alive
+    ("cmds_dev" int32 [n][16] and "bounds_dev" int16 [n][4] are what the layout call wrote)."""
+    import torch
+
+    from .. import _lib
+
+    lib = _lib.load()
+    if not (isinstance(canvas_buf, torch.Tensor) and canvas_buf.is_cuda and canvas_buf.dtype == torch.uint8 and canvas_buf.ndim == 1
+            and canvas_buf.is_contiguous()):
+        raise ValueError("overlay: the canvas buffer must be a contiguous 1-D uint8 device tensor")
+    tile = int(lib.ymk_overlay_tile())
+    cmds = np.ascontiguousarray(np.asarray(cmds, dtype=np.int32).reshape(-1, CMD_WORDS))
+    table = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, CANVAS_WORDS))
+    runs = np.zeros((0, RUN_WORDS), np.int32) if runs is None else np.ascontiguousarray(np.asarray(runs, dtype=np.int32).reshape(-1, RUN_WORDS))
+    codes = np.zeros(0, np.int32) if codes is None else np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+    total_tiles = 0
+    for off, h, w, first, count, tile0 in table.tolist():  # the kernels ignore an entry that does not fit; here it is a caller's bug
+        if not (0 < h <= COORD_MAX and 0 < w <= COORD_MAX and 0 <= off and off + h * w * 3 <= canvas_buf.numel()
+                and 0 <= first and 0 <= count and first + count <= len(cmds) and tile0 == total_tiles):
+            raise ValueError("overlay: the canvas table does not match the canvas buffer, the commands or the tile numbering")
+        total_tiles += -(-h // tile) * -(-w // tile)
+    host = {"cmds": cmds, "table": table, "runs": runs, "codes": codes}
+    dev_glyphs = isinstance(glyphs, torch.Tensor)
+    if not dev_glyphs:
+        host["glyphs"] = np.zeros((0, GLYPH_WORDS), np.int32) if glyphs is None else np.ascontiguousarray(np.asarray(glyphs, dtype=np.int32).reshape(-1, GLYPH_WORDS))
+        host["atlas"] = np.zeros(0, np.uint8) if atlas is None else np.ascontiguousarray(atlas, dtype=np.uint8).reshape(-1)
+    starts, size = {}, 0
+    for name, part in host.items():  # every section starts on a 16-byte boundary
+        starts[name] = size
+        size += -(-part.nbytes // 16) * 16
+    blob = np.zeros(max(size, 16), dtype=np.uint8)
+    for name, part in host.items():
+        blob[starts[name] : starts[name] + part.nbytes] = part.view(np.uint8).reshape(-1)
+    out = {"n": len(cmds), "tiles": total_tiles}
+    with torch.cuda.device(canvas_buf.device):
+        blob_dev = out["blob"] = torch.from_numpy(blob).to(canvas_buf.device)  # one H2D copy, ordered before the launches
+        base = blob_dev.data_ptr()
+        if dev_glyphs:
+            out["glyphs"], out["atlas"] = glyphs, atlas
+            n_glyphs, atlas_bytes = int(glyphs.shape[0]), int(atlas.numel()) if atlas is not None else 0
+            glyphs_ptr, atlas_ptr = glyphs.data_ptr(), atlas.data_ptr() if atlas_bytes else None
+        else:
+            n_glyphs, atlas_bytes = len(host["glyphs"]), int(host["atlas"].size)
+            glyphs_ptr, atlas_ptr = base + starts["glyphs"], base + starts["atlas"] if atlas_bytes else None
+        n = len(cmds)
+        out["cmds_dev"] = blob_dev[starts["cmds"] : starts["cmds"] + cmds.nbytes].view(torch.int32).view(-1, CMD_WORDS)
+        bounds = out["bounds_dev"] = torch.zeros((n, 4), dtype=torch.int16, device=canvas_buf.device)
+        stream = _lib.current_stream_ptr()
+        # the two calls' arguments up to the stream (tools/overlay_timing.py times each call on its own)
+        out["layout_args"] = (base + starts["cmds"], n, bounds.data_ptr(), base + starts["runs"], len(runs), base + starts["codes"],
+                              len(codes), glyphs_ptr, n_glyphs, base + starts["table"], len(table))
+        out["draw_args"] = (canvas_buf.data_ptr(), canvas_buf.numel(), base + starts["table"], len(table), total_tiles,
+                            base + starts["cmds"], n, bounds.data_ptr(), atlas_ptr, atlas_bytes)
+        if n:
+            _lib.check(lib.ymk_overlay_layout(*out["layout_args"], stream), "ymk_overlay_layout")
+            _lib.check(lib.ymk_draw_overlay_pages(*out["draw_args"], stream), "ymk_draw_overlay_pages")
+    return out
+
+
+def draw_wave(canvas_buf, drawings, sizes, offsets=None, store=None):
+    """`drawings` (one RunOverlay per canvas) onto the canvases of `sizes` inside `canvas_buf`, in place on the current stream."""
+    store = _STORE if store is None else store
+    data = build_wave(drawings, sizes, offsets, store)
+    glyphs, n_glyphs, atlas, atlas_bytes = store.tensors(canvas_buf.device)  # after build_wave: it may have added glyphs
+    out = launch_wave(canvas_buf, data["cmds"], data["table"], data["runs"], data["codes"], glyphs[:n_glyphs], atlas[:atlas_bytes])
+    out["store"] = (glyphs, atlas)
+    return out
+
+
+def render_wave(pages, drawings, pinned=None, store=None):
+    """One canvas per entry of `pages` (uint8 H x W x 3 device tensors; a page may appear several times, it is never drawn
+    on) with the RunOverlay of the same index drawn over it: one batched clone into a canvas buffer, one blob upload, the
+    two launches, one copy of all canvases to pinned memory, one wait for the stream.  Returns owned np.ndarrays.
+    `pinned`: a one-element list the caller keeps per wave slot; its pinned buffer is reused while it is large enough."""
+    import torch
+
+    sizes = [(int(p.shape[0]), int(p.shape[1])) for p in pages]
+    for p in pages:
+        if not (p.is_cuda and p.dtype == torch.uint8 and p.ndim == 3 and p.shape[2] == 3):
+            raise ValueError("overlay: a page must be a uint8 H x W x 3 device tensor")
+    data_bytes = [h * w * 3 for h, w in sizes]
+    offsets = np.cumsum([0] + [-(-b // 16) * 16 for b in data_bytes])
+    total = int(offsets[-1])
+    device = pages[0].device
+    with torch.cuda.device(device):
+        buf = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+        views = [buf[int(o) : int(o) + b].view(h, w, 3) for o, b, (h, w) in zip(offsets, data_bytes, sizes)]
+        torch._foreach_copy_(views, [p.contiguous() for p in pages])
+        staged = draw_wave(buf, drawings, sizes, offsets[:-1], store)
+        pinned = [None] if pinned is None else pinned
+        if pinned[0] is None or pinned[0].numel() < buf.numel():
+            pinned[0] = torch.empty(buf.numel(), dtype=torch.uint8, pin_memory=True)
+        host = pinned[0][: buf.numel()]
+        host.copy_(buf, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        del staged
+        arr = host.numpy()
+        return [arr[int(o) : int(o) + b].reshape(h, w, 3).copy() for o, b, (h, w) in zip(offsets, data_bytes, sizes)]
