@@ -180,7 +180,8 @@ int ymk_crop_desc_size(void);
  *   LDS ymk_overlay_chunk() records at a time; a tile with an empty list is neither read nor written.  A list entry outside
  *   [0, n), an unknown kind and a glyph byte outside [0, atlas_bytes) draw nothing.  Nothing is allocated and nothing waited for.
  *   cmds_dev: n records of YMK_OVERLAY_CMD_WORDS int32 words (16-byte aligned), all coordinates in [-16383, 16383]:
- *     word 0     kind: YMK_OVERLAY_SEG | YMK_OVERLAY_BOX | YMK_OVERLAY_GLYPH
+ *     word 0     kind: YMK_OVERLAY_SEG | _BOX | _GLYPH | _RBOX | _FLUSH, or-ed with YMK_OVERLAY_TO_LAYER or not; a word with any
+ *                bit outside 0x1ff set (-1 among them) draws nothing
  *     words 1-3  colour in the canvas's channel order (B, G, R), 0..255
  *     word 4     alpha 0..255 of SEG and BOX (GLYPH takes its alpha from the atlas)
  *     SEG    words 5-9   x0, y0, x1, y1, t     a segment of thickness t with round caps: with d = P1 - P0, L2 = d.d, q = p - P0,
@@ -190,7 +191,19 @@ int ymk_crop_desc_size(void);
  *                        (both inclusive; the inner box is empty when ix1 > ix2 or iy1 > iy2)
  *     GLYPH  words 5-10  x, y, w, h, atlas_offset, pitch   alpha = atlas_dev[atlas_offset + (py - y) * pitch + (px - x)] for
  *                        pixels in [x, x + w) x [y, y + h); atlas_dev: uint8 [atlas_bytes]
- *   Blend of a covered pixel, per channel: dst = (colour * a + dst * (255 - a) + 127) / 255 (a = 255 overwrites, 0 leaves).
+ *     RBOX   words 5-9   x1, y1, x2, y2, r     a filled box with round corners: r' = min(r, (x2 - x1) / 2, (y2 - y1) / 2), cx =
+ *                        clamp(px, x1 + r', x2 - r'), cy likewise; covered iff inside the box and (px - cx)^2 + (py - cy)^2 <= r'^2
+ *     FLUSH  words 5-9   x1, y1, x2, y2, keep255   see "layer"; word 4 is its alpha, the colour words are unused
+ *   Blend of a covered pixel, per channel: dst = blend(dst, colour, a) = (colour * a + dst * (255 - a) + 127) / 255 (a = 255
+ *   overwrites, 0 leaves).
+ *   Layer: every pixel has, for the length of one call, a LAYER next to it: a colour and a coverage cov, both 0 at the start.  A
+ *   SEG, BOX, GLYPH or RBOX record with YMK_OVERLAY_TO_LAYER set leaves the canvas alone; where its coverage is a > 0 it paints the
+ *   layer: cov == 0: colour = the record's, cov = a; else colour = blend(colour, the record's, a) per channel and cov = blend(cov,
+ *   255, a).  FLUSH composites the layer over the canvas, once per pixel however many records painted it: for a pixel inside its
+ *   box with cov > 0, e = (cov * alpha + 127) / 255 and dst = blend(dst, layer colour, e) per channel - except, with keep255 != 0,
+ *   a channel whose layer colour is exactly 255, which is left alone - and every pixel inside the box gets cov = 0.  Pixels
+ *   outside the box keep their layer; a layer never flushed is dropped; a FLUSH with YMK_OVERLAY_TO_LAYER set draws nothing.  The
+ *   bounding box of an RBOX and of a FLUSH is its box, and a record directed into the layer has the bounds of its kind.
  * ymk_heatmap_blend: prob_dev fp32 [mh][mw] blended over canvas_dev uint8 [h][w][3] in place, det_visualizer(vis_heatmap=True)
  *   in integers: m = (uint8) trunc(clamp(p, 0, 1) * 255); per axis X = ((2 x + 1) * mw * 1024) / (2 w) - 512 clamped to
  *   [0, (mw - 1) * 1024], taps X >> 10 and min(that + 1, mw - 1), weight X & 1023; v = (sum of the four weighted taps + 2^19)
@@ -199,6 +212,10 @@ int ymk_crop_desc_size(void);
 #define YMK_OVERLAY_SEG 0
 #define YMK_OVERLAY_BOX 1
 #define YMK_OVERLAY_GLYPH 2
+#define YMK_OVERLAY_RBOX 3
+#define YMK_OVERLAY_FLUSH 4
+#define YMK_OVERLAY_KIND_MASK 0xff
+#define YMK_OVERLAY_TO_LAYER 0x100
 int ymk_draw_overlay(unsigned char* canvas_dev, int h, int w, const int* cmds_dev, int n, const int* tile_offsets_dev,
                      const int* tile_cmds_dev, int n_list, const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream);
 int ymk_heatmap_blend(unsigned char* canvas_dev, int h, int w, const float* prob_dev, int mh, int mw, const unsigned char* jet_dev,
@@ -220,7 +237,8 @@ int ymk_overlay_chunk(void);
  *   vertical: (pen x, pen y + i * step).  A character whose glyph is empty (w or h 0) or whose id lies outside [0, n_glyphs) gets
  *   kind -1 (draws nothing; it still advances the pen by its advance, 0 for an unknown id).  A run whose slots or codes fall
  *   outside the arrays is skipped.  (2) bounds_dev: int16 [n_cmds][4] = every command's inclusive bounding box x0, y0, x1, y1 (SEG:
- *   the end points' box grown by (t + 1) / 2; BOX: the outer box; GLYPH: x .. x + w - 1, y .. y + h - 1) clipped to its canvas;
+ *   the end points' box grown by (t + 1) / 2; BOX: the outer box; RBOX, FLUSH: the box; GLYPH: x .. x + w - 1, y .. y + h - 1;
+ *   with or without the layer flag) clipped to its canvas;
  *   (1, 1, 0, 0) - x1 < x0 - for a command that covers none of its canvas.  Commands no canvas entry names are not written.
  * ymk_draw_overlay_pages: ONE launch, a block per tile (total_tiles = the sum over the canvases).  A block finds its canvas in
  *   the table, tests ymk_overlay_cull_pass() bounding boxes of that canvas at a time against its tile, keeps the hits in command

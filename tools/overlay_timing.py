@@ -3,6 +3,7 @@
 
     python tools/overlay_timing.py [--out FILE]
     python tools/overlay_timing.py --wave [--out FILE]    the wave renderer, for profiles/visualize_overlay_wave.json (wave_leg)
+    python tools/overlay_timing.py --tables [--out FILE]  a form page with tinted tables, as parse_pages(overlays=True) draws it (tables_leg)
 
 One 1600 x 1200 page carrying 300 quads (closed polylines, t = 1), 300 labelled boxes (outline t = 2 + a 12 px label) and 300
 text lines of 20 characters (18 px).  Reported, each the median of 20 runs after 3 warm-ups, one process, nothing else on the card:
@@ -169,13 +170,120 @@ def wave_leg(out_path):
     print(text)
 
 
+def form_results(seed=0):
+    """What TableSemanticParser returns for a dense form, without running the networks: 4 tables of 12 x 6 cells (the first row
+    headers, every cell sharing its border rows and columns with its neighbours), a kv item per cell of the first data column,
+    one grid and its graph per table, a word per cell."""
+    from types import SimpleNamespace as NS
+
+    from yomitoku_amd.utils.graph import OrderedDiGraph
+
+    tables, dags, words = [], [], []
+    rows, cols, cw, ch = 12, 6, 90, 28
+    for t in range(4):
+        ox, oy = 40 + (t % 2) * 580, 60 + (t // 2) * 760
+        cells, dag = {}, OrderedDiGraph()
+        for r in range(rows):
+            for c in range(cols):
+                b = [ox + c * cw, oy + r * ch, ox + (c + 1) * cw, oy + (r + 1) * ch]
+                cid = f"r{r}c{c}"
+                cells[cid] = NS(id=cid, box=b, role="header" if r == 0 else ("empty" if (r + c) % 5 == 0 else "cell"), contents="")
+                dag.add_node(cid, bbox=b)
+                words.append(NS(points=[[b[0] + 4, b[1] + 6], [b[2] - 4, b[1] + 6], [b[2] - 4, b[3] - 4], [b[0] + 4, b[3] - 4]],
+                                content=f"w{t}{r}{c}", direction="horizontal"))
+        for r in range(rows):
+            for c in range(cols):
+                if c + 1 < cols:
+                    dag.add_edge(f"r{r}c{c}", f"r{r}c{c + 1}", dir="R")
+                    dag.add_edge(f"r{r}c{c + 1}", f"r{r}c{c}", dir="L")
+                if r + 1 < rows:
+                    dag.add_edge(f"r{r}c{c}", f"r{r + 1}c{c}", dir="D")
+                    dag.add_edge(f"r{r + 1}c{c}", f"r{r}c{c}", dir="U")
+        box = [ox, oy, ox + cols * cw, oy + rows * ch]
+        cells["grp0"] = NS(id="grp0", box=box, role="group", contents="")
+        kv = [NS(id=f"kv{r}", key=[f"r{r}c0"], value=f"r{r}c1") for r in range(1, rows)]
+        tables.append(NS(id=f"t{t}", box=box, cells=cells, kv_items=kv, grids=[NS(box=box)]))
+        dags.append(dag)
+    paragraphs = [NS(id=f"p{k}", box=[40 + 290 * k, 20, 300 + 290 * k, 50]) for k in range(4)]
+    return NS(tables=tables, paragraphs=paragraphs, words=words), dags
+
+
+def tables_leg(out_path):
+    """The render step of TableSemanticParser.parse_pages(overlays=True) for a wave of WAVE_PAGES form pages (form_results), two
+    canvases per page, through the functions parse_pages calls (the drawings' content helpers on RunOverlay, build_wave, the
+    two launches):
+      draw_pages_device_ms               ymk_draw_overlay_pages for the WAVE, HIP events around the call
+      record_and_build_host_ms_per_page  recording both drawings of a page + its share of build_wave
+      layer_records / flushes            how many records of a layout canvas paint the layer, and how many flushes composite it"""
+    import torch
+
+    from yomitoku_amd import _lib
+    from yomitoku_amd.utils import visualizer as V
+    from yomitoku_amd.utils.synth import synthetic_page
+
+    assert torch.cuda.is_available(), "overlay_timing.py measures on the GPU"
+    lib = _lib.load()
+    page_dev = torch.from_numpy(synthetic_page(0, H, W)).to("cuda:0")
+    results, dags = form_results()
+    font = V.load_font(None, 12)
+
+    def record():
+        out = []
+        for _ in range(WAVE_PAGES):
+            layout, ocr = V.RunOverlay(), V.RunOverlay()
+            V._semantic_layout_commands(layout, results, dags)
+            V._semantic_ocr_commands(ocr, results, font, 12, (255, 0, 0))
+            out += [layout, ocr]
+        return out
+
+    n_canvases = 2 * WAVE_PAGES
+    sizes = [(H, W)] * n_canvases
+    V.build_wave(record()[:2], sizes[:2])  # the glyphs enter the store once per process
+    data = V.build_wave(record(), sizes)
+    buf = torch.empty(data["bytes"], dtype=torch.uint8, device="cuda:0")
+    for off in data["table"][:, 0].tolist():
+        buf[off : off + H * W * 3] = page_dev.reshape(-1)
+    staged = V.draw_wave(buf, record(), sizes)
+    stream = _lib.current_stream_ptr()
+    times = []
+    for _ in range(RUNS + WARMUP):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        _lib.check(lib.ymk_draw_overlay_pages(*staged["draw_args"], stream), "ymk_draw_overlay_pages")
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    first = data["table"][0]
+    layout_cmds = data["cmds"][int(first[3]) : int(first[3]) + int(first[4])]
+    result = {
+        "page": [H, W], "wave_pages": WAVE_PAGES, "canvases": n_canvases, "tables_per_page": len(results.tables),
+        "cells_per_page": sum(len(t.cells) for t in results.tables), "words_per_page": len(results.words),
+        "commands": int(len(data["cmds"])), "layout_canvas_commands": int(len(layout_cmds)),
+        "layer_records": int(((layout_cmds[:, 0] & V.TO_LAYER) != 0).sum()), "flushes": int((layout_cmds[:, 0] == V.FLUSH).sum()),
+        "runs": RUNS, "warmup": WARMUP,
+        "draw_pages_device_ms": round(statistics.median(times[WARMUP:]), 4),
+        "record_and_build_host_ms_per_page": round(median_ms(lambda: V.build_wave(record(), sizes)) / WAVE_PAGES, 3),
+        "device": torch.cuda.get_device_name(0),
+    }
+    result["draw_pages_device_ms_per_canvas"] = round(result["draw_pages_device_ms"] / n_canvases, 4)
+    text = json.dumps(result, indent=1)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--wave", action="store_true", help="the wave renderer of serve(overlays=True): profiles/visualize_overlay_wave.json")
+    ap.add_argument("--tables", action="store_true", help="a form page with tinted tables: profiles/visualize_table_overlays.json")
     args = ap.parse_args()
     if args.wave:
         return wave_leg(args.out)
+    if args.tables:
+        return tables_leg(args.out)
     import torch
 
     from yomitoku_amd.utils.synth import synthetic_page

@@ -10,6 +10,11 @@
 //   k_heatmap_blend    det_visualizer(vis_heatmap=True) (utils/visualizer.py:81-91 of the reference) in integers: the
 //                      probability map quantised to uint8, a fixed-point bilinear sample, a 256-entry jet table, a 50 % blend.
 //
+//   The layer ("Overlay rasteriser", "Layer"): next to its PX canvas pixels a thread keeps a LAYER for the same pixels,
+//   a colour and a coverage packed into one register per pixel.  A record with YMK_OVERLAY_TO_LAYER in word 0 paints the layer
+//   instead of the canvas; YMK_OVERLAY_FLUSH composites the layer over the canvas ONCE and clears it.  overlay_apply is the one
+//   per-record loop of both draw kernels.
+//
 // Every coverage test is exact integer arithmetic ("Overlay rasteriser"): coordinates lie in [-16383, 16383], so
 // squared lengths stay below 2^32 and the products compared stay below 2^63; the factor 4 of `4 c <= T` is moved to the right
 // as an integer division (c integer: 4 c <= T  <=>  c <= T / 4 for T >= 0).
@@ -25,26 +30,27 @@ constexpr int OV_THREADS = OV_TILE * OV_TILE / OV_PX;    // 256
 constexpr int OV_CHUNK = 64;                             // command records staged in LDS at a time
 constexpr int OV_WORDS = YMK_OVERLAY_CMD_WORDS;          // int32 words per record
 static_assert(OV_WORDS == 16, "the staging loop moves a record as four int4");
+static_assert(OV_PX == 4, "a thread's layer is four packed registers");
 static_assert(OV_CHUNK * OV_WORDS / 4 == OV_THREADS, "one int4 per thread stages a chunk");
 
 __device__ __forceinline__ int blend_u8(int dst, int colour, int a) { return (colour * a + dst * (255 - a) + 127) / 255; }
 
-// coverage (0..255; 0 = not covered) of command `c` at pixel (px, py)
-__device__ __forceinline__ int overlay_alpha(const int* __restrict__ c, int px, int py, const unsigned char* __restrict__ atlas,
-                                             long long atlas_bytes) {
-  const int kind = c[0];
+// coverage (0..255; 0 = not covered) of command `c` of kind `kind` (word 0 without its flag) at pixel (px, py)
+__device__ __forceinline__ int overlay_alpha(int kind, const int* __restrict__ c, int px, int py,
+                                             const unsigned char* __restrict__ atlas, long long atlas_bytes) {
   if (kind == YMK_OVERLAY_SEG) {
-    const long long x0 = c[5], y0 = c[6], x1 = c[7], y1 = c[8], t = c[9];
-    const long long dx = x1 - x0, dy = y1 - y0, qx = px - x0, qy = py - y0;
-    const long long l2 = dx * dx + dy * dy, u = qx * dx + qy * dy, t2 = t * t;
+    // coordinates lie in [-16383, 16383] and pixels in [0, 16383): differences fit 32 bits, every product is widened to 64
+    const int x0 = c[5], y0 = c[6], x1 = c[7], y1 = c[8], t = c[9];
+    const int dx = x1 - x0, dy = y1 - y0, qx = px - x0, qy = py - y0;
+    const long long l2 = (long long)dx * dx + (long long)dy * dy, u = (long long)qx * dx + (long long)qy * dy, t2 = (long long)t * t;
     bool in;
     if (l2 == 0 || u <= 0) {
-      in = qx * qx + qy * qy <= t2 / 4;
+      in = (long long)qx * qx + (long long)qy * qy <= t2 / 4;
     } else if (u >= l2) {
-      const long long ex = px - x1, ey = py - y1;
-      in = ex * ex + ey * ey <= t2 / 4;
+      const int ex = px - x1, ey = py - y1;
+      in = (long long)ex * ex + (long long)ey * ey <= t2 / 4;
     } else {
-      const long long cr = qx * dy - qy * dx;  // |cr| < 2^32: cr * cr < 2^63 (|q|, |d| <= 32766 sqrt 2)
+      const long long cr = (long long)qx * dy - (long long)qy * dx;  // |cr| < 2^32: cr * cr < 2^63 (|q|, |d| <= 32766 sqrt 2)
       in = cr * cr <= (t2 * l2) / 4;
     }
     return in ? c[4] : 0;
@@ -60,7 +66,80 @@ __device__ __forceinline__ int overlay_alpha(const int* __restrict__ c, int px, 
     const long long at = (long long)c[9] + (long long)gy * c[10] + gx;
     return at >= 0 && at < atlas_bytes ? (int)atlas[at] : 0;  // a record that points outside the atlas draws nothing
   }
+  if (kind == YMK_OVERLAY_RBOX) {
+    const int x1 = c[5], y1 = c[6], x2 = c[7], y2 = c[8];
+    if (px < x1 || px > x2 || py < y1 || py > y2) return 0;
+    const int r = max(min(min(c[9], (x2 - x1) / 2), (y2 - y1) / 2), 0);
+    const int ex = px - min(max(px, x1 + r), x2 - r), ey = py - min(max(py, y1 + r), y2 - r);  // |ex|, |ey| <= r <= 16383
+    return ex * ex + ey * ey <= r * r ? c[4] : 0;
+  }
   return 0;
+}
+
+// the layer of one pixel in one register: colour channel ch in bits 8 ch .. 8 ch + 7, coverage in bits 24 .. 31
+__device__ __forceinline__ unsigned layer_pack(int c0, int c1, int c2, int cov) {
+  return (unsigned)(c0 & 255) | (unsigned)(c1 & 255) << 8 | (unsigned)(c2 & 255) << 16 | (unsigned)(cov & 255) << 24;
+}
+
+// Records s_cmd[0 .. count) applied in order to the thread's PX canvas pixels and to their layer.  Every branch on a record's
+// word is wave-uniform (the record is an LDS broadcast); only the coverage of a pixel diverges.
+__device__ __forceinline__ void overlay_apply(const int* __restrict__ s_cmd, int count, int (&pix)[OV_PX][3], unsigned (&layer)[OV_PX],
+                                              int px0, int py, const unsigned char* __restrict__ atlas, long long atlas_bytes) {
+  for (int i = 0; i < count; ++i) {
+    // the same address in every lane: an LDS broadcast.  The words are moved to scalar registers, so whatever depends on the
+    // record alone (a segment's direction and squared length, a rounded box's radius) is computed once per wave
+    int c[13];
+#pragma unroll
+    for (int j = 0; j < 13; ++j) c[j] = __builtin_amdgcn_readfirstlane(s_cmd[i * OV_WORDS + j]);
+    const int word0 = c[0];
+    if (word0 & ~(YMK_OVERLAY_KIND_MASK | YMK_OVERLAY_TO_LAYER)) continue;  // -1 (an empty glyph) and any other stray bit
+    const int kind = word0 & YMK_OVERLAY_KIND_MASK;
+    const bool to_layer = (word0 & YMK_OVERLAY_TO_LAYER) != 0;
+    if (kind == YMK_OVERLAY_FLUSH) {
+      if (to_layer || py < c[6] || py > c[8]) continue;
+      const int alpha = c[4];
+      const bool keep255 = c[9] != 0;
+#pragma unroll
+      for (int k = 0; k < OV_PX; ++k) {
+        if (px0 + k < c[5] || px0 + k > c[7]) continue;
+        const unsigned l = layer[k];
+        layer[k] = 0;
+        const int cov = (int)(l >> 24);
+        if (cov == 0) continue;
+        const int e = (cov * alpha + 127) / 255;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const int colour = (int)(l >> (8 * ch)) & 255;
+          if (!(keep255 && colour == 255)) pix[k][ch] = blend_u8(pix[k][ch], colour, e);
+        }
+      }
+      continue;
+    }
+    const int cb = c[1], cg = c[2], cr = c[3];
+    if (!to_layer) {
+#pragma unroll
+      for (int k = 0; k < OV_PX; ++k) {
+        const int a = overlay_alpha(kind, c, px0 + k, py, atlas, atlas_bytes);
+        if (a > 0) {
+          pix[k][0] = blend_u8(pix[k][0], cb, a);
+          pix[k][1] = blend_u8(pix[k][1], cg, a);
+          pix[k][2] = blend_u8(pix[k][2], cr, a);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < OV_PX; ++k) {
+        const int a = overlay_alpha(kind, c, px0 + k, py, atlas, atlas_bytes);
+        if (a > 0) {
+          const unsigned l = layer[k];
+          const int cov = (int)(l >> 24);
+          layer[k] = cov == 0 ? layer_pack(cb, cg, cr, a)
+                              : layer_pack(blend_u8((int)(l & 255), cb, a), blend_u8((int)(l >> 8) & 255, cg, a),
+                                           blend_u8((int)(l >> 16) & 255, cr, a), blend_u8(cov, 255, a));
+        }
+      }
+    }
+  }
 }
 
 __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay(unsigned char* __restrict__ canvas, int h, int w,
@@ -77,6 +156,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay(unsigned char* __re
   const bool row_in = py < h;
   unsigned char* row = canvas + ((size_t)(row_in ? py : 0) * w) * 3;
   int pix[OV_PX][3];
+  unsigned layer[OV_PX] = {0, 0, 0, 0};  // dropped when the tile ends, flushed or not
 #pragma unroll
   for (int k = 0; k < OV_PX; ++k) {
     const bool in = row_in && px0 + k < w;
@@ -97,19 +177,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay(unsigned char* __re
       }
     }
     __syncthreads();
-    for (int i = 0; i < count; ++i) {
-      const int* c = s_cmd + i * OV_WORDS;  // the same address in every lane: an LDS broadcast
-      const int cb = c[1], cg = c[2], cr = c[3];
-#pragma unroll
-      for (int k = 0; k < OV_PX; ++k) {
-        const int a = overlay_alpha(c, px0 + k, py, atlas, atlas_bytes);
-        if (a > 0) {
-          pix[k][0] = blend_u8(pix[k][0], cb, a);
-          pix[k][1] = blend_u8(pix[k][1], cg, a);
-          pix[k][2] = blend_u8(pix[k][2], cr, a);
-        }
-      }
-    }
+    overlay_apply(s_cmd, count, pix, layer, px0, py, atlas, atlas_bytes);
   }
   if (!row_in) return;
 #pragma unroll
@@ -218,11 +286,11 @@ __global__ __launch_bounds__(256) void k_overlay_bounds(const int* __restrict__ 
   for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < cv.count; k += (long long)gridDim.x * blockDim.x) {
     const int* c = cmds + (size_t)(cv.first + k) * OV_WORDS;
     int x0 = 1, y0 = 1, x1 = 0, y1 = 0;
-    const int kind = c[0];
+    const int kind = c[0] & ~(YMK_OVERLAY_KIND_MASK | YMK_OVERLAY_TO_LAYER) ? -1 : c[0] & YMK_OVERLAY_KIND_MASK;  // flagged: the bounds of its kind
     if (kind == YMK_OVERLAY_SEG) {
       const int pad = (c[9] + 1) / 2;  // t >= 0: a segment reaches t / 2 from its axis
       x0 = min(c[5], c[7]) - pad, y0 = min(c[6], c[8]) - pad, x1 = max(c[5], c[7]) + pad, y1 = max(c[6], c[8]) + pad;
-    } else if (kind == YMK_OVERLAY_BOX) {
+    } else if (kind == YMK_OVERLAY_BOX || kind == YMK_OVERLAY_RBOX || kind == YMK_OVERLAY_FLUSH) {
       x0 = c[5], y0 = c[6], x1 = c[7], y1 = c[8];
     } else if (kind == YMK_OVERLAY_GLYPH) {
       x0 = c[5], y0 = c[6], x1 = c[5] + c[7] - 1, y1 = c[6] + c[8] - 1;
@@ -262,11 +330,13 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay_pages(unsigned char
   const int px0 = tx0 + (threadIdx.x % (OV_TILE / OV_PX)) * OV_PX;
   const int py = ty0 + threadIdx.x / (OV_TILE / OV_PX);
   const bool row_in = py < h;
-  unsigned char* row = canvases + cv.offset + ((size_t)(row_in ? py : 0) * w) * 3;
+  // byte offset of the thread's first pixel in the canvas buffer: recomputed where it is used, not held over the command loop
+  auto first_byte = [&]() { return cv.offset + ((long long)(row_in ? py : 0) * w + px0) * 3; };
   const int* ccmds = cmds + (size_t)cv.first * OV_WORDS;
   const short4* cbounds = reinterpret_cast<const short4*>(bounds) + cv.first;
   const int count = (int)cv.count, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int pix[OV_PX][3];
+  unsigned layer[OV_PX] = {0, 0, 0, 0};
   bool loaded = false;
   int head = 0, tail = 0;  // ring positions (block-uniform, only ever grow)
   for (int base = 0; base < count; base += OV_THREADS) {
@@ -300,7 +370,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay_pages(unsigned char
         for (int k = 0; k < OV_PX; ++k) {
           const bool in = row_in && px0 + k < w;
 #pragma unroll
-          for (int ch = 0; ch < 3; ++ch) pix[k][ch] = in ? (int)row[(size_t)(px0 + k) * 3 + ch] : 0;
+          for (int ch = 0; ch < 3; ++ch) pix[k][ch] = in ? (int)canvases[first_byte() + k * 3 + ch] : 0;
         }
       }
       __syncthreads();  // the previous chunk has been read by every thread
@@ -312,19 +382,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay_pages(unsigned char
         }
       }
       __syncthreads();
-      for (int i = 0; i < n_chunk; ++i) {
-        const int* c = s_cmd + i * OV_WORDS;
-        const int cb = c[1], cg = c[2], cr = c[3];
-#pragma unroll
-        for (int k = 0; k < OV_PX; ++k) {
-          const int a = overlay_alpha(c, px0 + k, py, atlas, atlas_bytes);
-          if (a > 0) {
-            pix[k][0] = blend_u8(pix[k][0], cb, a);
-            pix[k][1] = blend_u8(pix[k][1], cg, a);
-            pix[k][2] = blend_u8(pix[k][2], cr, a);
-          }
-        }
-      }
+      overlay_apply(s_cmd, n_chunk, pix, layer, px0, py, atlas, atlas_bytes);
       head += n_chunk;
     }
   }
@@ -333,7 +391,7 @@ __global__ __launch_bounds__(OV_THREADS) void k_draw_overlay_pages(unsigned char
   for (int k = 0; k < OV_PX; ++k) {
     if (px0 + k < w) {
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) row[(size_t)(px0 + k) * 3 + ch] = (unsigned char)pix[k][ch];
+      for (int ch = 0; ch < 3; ++ch) canvases[first_byte() + k * 3 + ch] = (unsigned char)pix[k][ch];
     }
   }
 }

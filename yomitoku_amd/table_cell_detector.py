@@ -224,16 +224,12 @@ class CellDetector(BaseModule):
                     continue
                 outputs.append(TableDetectorSchema(id=None, box=table.box, role=table.role, cells=cells, kv_regions=kv_regions,
                                                    grid_regions=grid_regions))
-        if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
-        return outputs
+        return outputs  # `visualize` is stored and draws nothing, as in the reference (utils/visualizer.py has cell_detector_visualizer)
 
     def detect_pages(self, imgs, tables_per_page):
         """`__call__` for several pages: the tables of ALL pages share forwards of up to MAX_TABLES_PER_FORWARD crops (images
         of a batch are independent).  tables_per_page[k]: the table elements of imgs[k].  Returns [[TableDetectorSchema]], one
         list per page, each what `__call__(imgs[k], tables_per_page[k])` returns."""
-        if self.visualize:
-            raise NotImplementedError("visualisation is out of scope of the MI355X path (visualize=False only)")
         pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, self.device) for img in imgs]
         jobs = [(k, table) for k, tables in enumerate(tables_per_page) for table in tables]
         outputs = [[] for _ in pages]

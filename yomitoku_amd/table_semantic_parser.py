@@ -4,11 +4,16 @@ column headers) and key-value items - the consumer of CellDetector's cells, `kv_
     parser = TableSemanticParser(configs={...}, device="cuda")
     results, _, _ = parser(img_bgr_uint8)          # TableSemanticParserSchema
     results.to_dict() / .to_structured() / .to_simple() / .to_csv(outdir)
+    results, vis_layout, vis_ocr = parser(img_bgr_uint8, overlays=True)   # + the reference's two pictures, uint8 H x W x 3
 
 Same constructor keys (`table_detector`, `table_cell_parser`, `text_detector`, `text_recognizer`), same `__call__`
 arguments and the same result for the same model outputs.  What differs from the reference:
 
-  * `visualize` defaults to False (the reference: True) and True raises NotImplementedError, as in every module of this path;
+  * the pictures are a property of the CALL, as in `DocumentAnalyzer.serve(overlays=True)`: `parser(img, overlays=True)` and
+    `parse_pages(imgs, overlays=True)` return the reference's layout picture (tables and paragraphs boxed and labelled, cells
+    tinted by role, key -> value arrows, grid boxes, grid graphs) and its OCR picture, drawn on the device from the page that was
+    uploaded for the networks (utils/visualizer.py; the page itself is never drawn on).  The constructor's `visualize` defaults
+    to False (the reference: True) and True still raises NotImplementedError;
   * the page is uploaded once and the device page is shared by the four modules; the text chain (DBNet -> PARSeq) and the table
     chain (RT-DETRv2 table detector -> RT-DETRv2 cell detector) run side by side on two HIP streams, like the two chains of
     DocumentAnalyzer (the reference runs the two detectors side by side and the rest in sequence; the results are the same);
@@ -16,7 +21,7 @@ arguments and the same result for the same model outputs.  What differs from the
   * `aggregate` assigns words to cells from one words x cells overlap matrix instead of a double loop (same assignment).
 
 Everything after the four networks is host logic on at most a few hundred boxes per table (`semantic_stage`): no kernel.
-Not restated: the visualisers, and the helpers of the reference's module that nothing on its call path uses
+Not restated: the helpers of the reference's module that nothing on its call path uses
 (`_weakly_cluster_nodes_with_graph`, `is_grid_cluster`, `_get_cluster_nodes`, `drop_single_out_edge_by_type`, `replace_edge_type`).
 """
 
@@ -40,7 +45,8 @@ from .table_semantic_schemas import TableSemanticContentsSchema, TableSemanticPa
 from .text_detector import TextDetector
 from .text_recognizer import TextRecognizer
 
-_NO_VIS = "visualisation is out of scope of the MI355X path (visualize=False only)"
+_NO_VIS = ("the constructor's visualize flag is not supported (visualize=False only): ask for the pictures per call, "
+           "parser(img, overlays=True) / parse_pages(imgs, overlays=True)")
 _VALUE_ROLES = ("cell", "header", "empty")
 
 
@@ -210,6 +216,13 @@ def overlap_ratio_matrix(boxes_a, boxes_b):
     return np.where(hit, ratio, 0.0)
 
 
+def _owned_host_image(canvas):
+    """A device canvas as an array the caller owns: one D2H copy into a freshly allocated array."""
+    out = np.empty(tuple(canvas.shape), dtype=np.uint8)
+    torch.from_numpy(out).copy_(canvas)
+    return out
+
+
 class TableSemanticParser:
     merge_same_column_values = False  # True: grid columns under the same innermost header cell become one column
     visualize = False
@@ -311,8 +324,9 @@ class TableSemanticParser:
         return OCRSchema(words=ocr_aggregate(results_det, results_rec)), results_table, paragraphs
 
     # ---- everything after the networks
-    def _parse_table(self, table, cells, grid_only, kv_only):
-        """(grids, kv items, {id: cell} the items refer to) of one detected table; `cells`: its cells by id."""
+    def _parse_table(self, table, cells, grid_only, kv_only, dags=None):
+        """(grids, kv items, {id: cell} the items refer to) of one detected table; `cells`: its cells by id.  `dags`: a list
+        that every parsed grid's graph is appended to."""
         value_cells = [c for c in table.cells if c.role in _VALUE_ROLES]
         grid_regions = [] if kv_only else list(table.grid_regions)
         kv_regions = [] if grid_only else list(table.kv_regions)
@@ -328,6 +342,8 @@ class TableSemanticParser:
                 continue
             grids.append(result[0])
             used.update(result[1])
+            if dags is not None:
+                dags.append(result[2])
             claimed.update(c.id for c in region_cells)
         remaining = [c for c in value_cells if c.id not in claimed]  # what no grid claimed is read as key-value items
         if remaining:
@@ -338,9 +354,10 @@ class TableSemanticParser:
             used.update(kv_cells)
         return grids, kv_items, used
 
-    def semantic_stage(self, results_ocr, results_table, paragraphs, template=None, grid_only=False, kv_only=False):
+    def semantic_stage(self, results_ocr, results_table, paragraphs, template=None, grid_only=False, kv_only=False, dags=None):
         """`run_models`' results -> TableSemanticParserSchema: words into cells and paragraphs, grids and kv items per table
-        (or, with `template`, the template's), ids by position."""
+        (or, with `template`, the template's), ids by position.  `dags`: a list that the graph of every parsed grid is appended
+        to, in table order (what dag_visualizer draws; the kv graph is not handed out, as in the reference)."""
         for table in results_table:
             self.aggregate(results_ocr, table.cells)
         self.aggregate(results_ocr, paragraphs)
@@ -349,7 +366,7 @@ class TableSemanticParser:
             cells = {cell.id: cell for cell in table.cells}
             info = {"id": f"t{k}", "box": table.box, "cells": {}, "style": "border", "kv_items": [], "grids": []}
             if template is None:
-                info["grids"], info["kv_items"], used = self._parse_table(table, cells, grid_only, kv_only)
+                info["grids"], info["kv_items"], used = self._parse_table(table, cells, grid_only, kv_only, dags)
                 info["cells"].update(used)
             for cell in cells.values():
                 info["cells"].setdefault(cell.id, cell)
@@ -363,14 +380,36 @@ class TableSemanticParser:
             results.load_template_json(template)
         return results
 
-    def __call__(self, img, template=None, id=None, grid_only=False, kv_only=False):
+    # ---- overlays=True: the reference's two pictures, per call
+    def _drawings(self, results, dags, recorder):
+        """(layout drawing, ocr drawing) of one page's results, recorded on two `recorder()`s."""
+        from .utils import visualizer as V
+
+        layout, ocr = recorder(), recorder()
+        V._semantic_layout_commands(layout, results, dags)
+        cfg = self.text_recognizer._cfg.visualize
+        V._semantic_ocr_commands(ocr, results, V.load_font(cfg.font, cfg.font_size), cfg.font_size, tuple(cfg.color[::-1]))
+        return layout, ocr
+
+    def __call__(self, img, template=None, id=None, grid_only=False, kv_only=False, overlays=False):
         """`img`: uint8 H x W x 3 BGR page.  `template`: path of a template JSON (save_template_json) whose kv items and grids
         replace the parsed ones; `grid_only` / `kv_only`: ignore the predicted kv / grid regions; `id`: accepted and unused, as in
-        the reference.  Returns (TableSemanticParserSchema, None, None)."""
+        the reference.  Returns (TableSemanticParserSchema, None, None); with `overlays=True` (TableSemanticParserSchema, layout
+        picture, OCR picture), two uint8 H x W x 3 arrays the caller owns, each one launch over a device copy of the page."""
         if self.visualize:
             raise NotImplementedError(_NO_VIS)
-        results_ocr, results_table, paragraphs = self.run_models(img)
-        return self.semantic_stage(results_ocr, results_table, paragraphs, template, grid_only, kv_only), None, None
+        if not overlays:
+            results_ocr, results_table, paragraphs = self.run_models(img)
+            return self.semantic_stage(results_ocr, results_table, paragraphs, template, grid_only, kv_only), None, None
+        from .utils import visualizer as V
+
+        page = img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, self.text_detector.device)
+        dags = []
+        results = self.semantic_stage(*self.run_models(page), template, grid_only, kv_only, dags=dags)
+        with torch.cuda.device(page.device):
+            layout, ocr = self._drawings(results, dags, V.Overlay)
+            vis_layout, vis_ocr = layout.render(page), ocr.render(page)  # each a clone of the page: the D2H below is the only copy out
+            return results, _owned_host_image(vis_layout), _owned_host_image(vis_ocr)
 
     # ---- several pages per call
     def _ocr_pages(self, pages):
@@ -382,24 +421,37 @@ class TableSemanticParser:
         tables = [self._handed_tables(k, list(l.tables)) for k, l in enumerate(layouts)]
         return layouts, self.cell_detector.detect_pages(pages, tables)
 
-    def parse_pages(self, imgs, wave: int = 8, template=None, grid_only=False, kv_only=False):
+    def parse_pages(self, imgs, wave: int = 8, template=None, grid_only=False, kv_only=False, overlays=False):
         """`__call__` over a list of pages, `wave` pages at a time on the device: DBNet and the table detector run over the
         pages of a wave, PARSeq over the lines of all its pages, the cell detector over the tables of all its pages in chunks of
         CellDetector.MAX_TABLES_PER_FORWARD.  Pages never interact, so every page's result is what `__call__` returns for it.
-        Returns [TableSemanticParserSchema], in page order."""
+        Returns [TableSemanticParserSchema], in page order; with `overlays=True` [(TableSemanticParserSchema, layout picture,
+        OCR picture)]: all canvases of a wave, two per page, are drawn by the wave renderer (utils/visualizer.py: render_wave)."""
         if self.visualize:
             raise NotImplementedError(_NO_VIS)
-        dev = self.text_detector.device
+        from .utils.visualizer import RunOverlay, render_wave
+
         out = []
         size = max(1, int(wave))
+        pinned = [None]  # the pinned buffer the canvases come back through: this call's, reused by its waves
         for start in range(0, len(imgs), size):
+            dev = self.text_detector.device
             pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, dev) for img in imgs[start : start + size]]
             f_ocr = self._submit("ocr", self._ocr_pages, pages)
             f_tab = self._submit("layout", self._tables_and_cells_pages, pages)
             dets, recs = f_ocr.result()
             layouts, tables = f_tab.result()
+            drawings = []
             for det, rec, layout, page_tables in zip(dets, recs, layouts, tables):
-                out.append(self.semantic_stage(*self._hand_over(det, rec, layout, page_tables), template, grid_only, kv_only))
+                dags = [] if overlays else None
+                out.append(self.semantic_stage(*self._hand_over(det, rec, layout, page_tables), template, grid_only, kv_only, dags=dags))
+                if overlays:
+                    drawings.extend(self._drawings(out[-1], dags, RunOverlay))
+            if overlays:
+                with torch.cuda.device(pages[0].device):
+                    images = render_wave([p for p in pages for _ in range(2)], drawings, pinned)
+                for k in range(len(pages)):
+                    out[start + k] = (out[start + k], images[2 * k], images[2 * k + 1])
         return out
 
     def close(self):

@@ -1,4 +1,4 @@
-"""visualize=True: the reference's overlays (utils/visualizer.py:11-250) drawn on the device.
+"""visualize=True: the reference's overlays (utils/visualizer.py:11-295, table_semantic_parser.py:308-620) drawn on the device.
 
 The reference draws with OpenCV and Pillow on host copies of the page.  Here a drawing is an ordered list of fixed-size int32
 commands - thick segments, boxes with an optional hole, glyph blits - that ONE launch of ymk_draw_overlay applies to a device
@@ -16,13 +16,18 @@ as runs and laid out by ymk_overlay_layout, and ymk_draw_overlay_pages culls per
 in one launch - no per-character loop and no binning on the host.  The CONTENT of each drawing is written once, in the
 `_xxx_commands(ov, ...)` helpers, for both recorders (Overlay, RunOverlay).
 
-The five functions keep the reference's names and arguments and return np.ndarray; `img` may also be a device tensor, and
+The table-semantic parser's drawings (`cell_detector_visualizer`, `cell_id_visualizer`, `kv_items_visualizer`, `dag_visualizer`)
+need two things more: a tint that is composited ONCE however many cells cover a pixel - commands recorded inside
+`with ov.layer():` paint a per-pixel layer, `ov.flush(alpha)` blends it over the canvas - and a rounded filled box.
+
+The nine functions keep the reference's names and arguments and return np.ndarray; `img` may also be a device tensor, and
 `to_host=False` (not in the reference) returns the device canvas instead, which is how the modules chain overlays without a
 round trip through the host.
 """
 
 from __future__ import annotations
 
+import contextlib
 import logging
 import os
 import threading
@@ -32,7 +37,8 @@ import numpy as np
 logger = logging.getLogger(__name__)
 
 CMD_WORDS = 16  # YMK_OVERLAY_CMD_WORDS
-SEG, BOX, GLYPH = 0, 1, 2  # YMK_OVERLAY_SEG / _BOX / _GLYPH
+SEG, BOX, GLYPH, RBOX, FLUSH = 0, 1, 2, 3, 4  # YMK_OVERLAY_SEG / _BOX / _GLYPH / _RBOX / _FLUSH
+KIND_MASK, TO_LAYER = 0xFF, 0x100  # YMK_OVERLAY_KIND_MASK / _TO_LAYER: word 0 = kind | flag
 COORD_MAX = 16383
 
 # constants.py:9-32
@@ -61,17 +67,24 @@ def jet_table() -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------------------------------- binning
+def _kinds(word0):
+    """The kind in word 0 without the layer flag; -1 for a word with a bit outside 0x1ff (a record that draws nothing)."""
+    word0 = np.asarray(word0, dtype=np.int64)
+    return np.where((word0 & ~(KIND_MASK | TO_LAYER)) != 0, -1, word0 & KIND_MASK)
+
+
 def command_bounds(cmds: np.ndarray):
     """Inclusive bounding box (x0, y0, x1, y1; int64 arrays) of every command; x1 < x0 for one that covers nothing."""
     c = np.asarray(cmds, dtype=np.int64).reshape(-1, CMD_WORDS)
-    kind = c[:, 0]
+    kind = _kinds(c[:, 0])  # a record directed into the layer has the bounds of its kind
     pad = (c[:, 9] + 1) // 2  # a segment reaches t / 2 from its axis
     seg = (np.minimum(c[:, 5], c[:, 7]) - pad, np.minimum(c[:, 6], c[:, 8]) - pad,
            np.maximum(c[:, 5], c[:, 7]) + pad, np.maximum(c[:, 6], c[:, 8]) + pad)
     box = (c[:, 5], c[:, 6], c[:, 7], c[:, 8])
     glyph = (c[:, 5], c[:, 6], c[:, 5] + c[:, 7] - 1, c[:, 6] + c[:, 8] - 1)
     none = (np.ones_like(kind), np.ones_like(kind), np.zeros_like(kind), np.zeros_like(kind))
-    return tuple(np.where(kind == SEG, s, np.where(kind == BOX, b, np.where(kind == GLYPH, g, e)))
+    boxed = (kind == BOX) | (kind == RBOX) | (kind == FLUSH)
+    return tuple(np.where(kind == SEG, s, np.where(boxed, b, np.where(kind == GLYPH, g, e)))
                  for s, b, g, e in zip(seg, box, glyph, none))
 
 
@@ -184,21 +197,54 @@ class Overlay:
         self._mask_index = {}
         self._chars = {}      # (font key, character) -> (mask index or -1, x offset, y offset, advance, width, height)
         self._heatmap = None
+        self._flag = 0        # TO_LAYER inside `with ov.layer():`
+        self._pending = []    # the blocks pushed into the layer since the last flush
         self.canvas = None
 
     def __len__(self):
         return sum(len(c) for c in self._chunks)
 
+    # ---- the layer
+    @contextlib.contextmanager
+    def layer(self):
+        """Everything pushed inside `with ov.layer():` paints the layer instead of the canvas (include/ymk.h); `flush`
+        composites what was painted over the canvas once."""
+        before, self._flag = self._flag, TO_LAYER
+        try:
+            yield self
+        finally:
+            self._flag = before
+
+    def flush(self, alpha, keep255=False):
+        """ONE FLUSH record over the union of the bounds of the layer commands since the previous flush (nothing when there
+        are none): the layer is blended over the canvas at `alpha`, each pixel once however many commands painted it.
+        keep255: a channel whose layer colour is exactly 255 keeps the canvas's byte."""
+        pending, self._pending = self._pending, []
+        if not pending:
+            return
+        x0, y0, x1, y1 = command_bounds(np.concatenate(pending, axis=0))
+        live = (x0 <= x1) & (y0 <= y1)
+        if not live.any():
+            return
+        before, self._flag = self._flag, 0  # the flush itself is never directed into the layer
+        try:
+            self._push(FLUSH, (0, 0, 0), alpha, [[int(x0[live].min()), int(y0[live].min()), int(x1[live].max()), int(y1[live].max()),
+                                                   int(bool(keep255))]])
+        finally:
+            self._flag = before
+
     # ---- primitives
     def _push(self, kind, color, alpha, params):
         params = np.asarray(params, dtype=np.int64).reshape(-1, np.shape(params)[-1])
         rec = np.zeros((len(params), CMD_WORDS), dtype=np.int64)
-        rec[:, 0] = kind
+        rec[:, 0] = kind | self._flag
         rec[:, 1:4] = np.asarray(color, dtype=np.int64).reshape(-1, 3)  # clamped with the coordinates, once, in build()
         rec[:, 4] = min(max(int(alpha), 0), 255)
         rec[:, 5 : 5 + params.shape[1]] = params
         if len(rec):
             self._chunks.append(rec)
+            if self._flag:
+                self._pending.append(rec)
 
     def segment(self, p0, p1, color, thickness=1, alpha=255):
         """Thick segment(s) with round caps; p0, p1: (x, y) or arrays [k][2]."""
@@ -239,6 +285,14 @@ class Overlay:
         outer = np.stack([x1, y1, x2, y2], axis=1)
         hole = np.tile(np.array([1, 1, 0, 0], dtype=np.int64), (len(outer), 1))  # ix1 > ix2: no hole
         self._push(BOX, color, alpha, np.concatenate([outer, hole], axis=1))
+
+    def rounded_fill(self, box, radius, color, alpha=255):
+        """Filled rectangle(s) (x1, y1, x2, y2), both corners included, with corners of `radius` (clamped to half the shorter
+        side by the rule of include/ymk.h), blended with `alpha`."""
+        b = np.asarray(box, dtype=np.int64).reshape(-1, 4)
+        x1, x2 = np.minimum(b[:, 0], b[:, 2]), np.maximum(b[:, 0], b[:, 2])
+        y1, y2 = np.minimum(b[:, 1], b[:, 3]), np.maximum(b[:, 1], b[:, 3])
+        self._push(RBOX, color, alpha, np.stack([x1, y1, x2, y2, np.full_like(x1, int(radius))], axis=1))
 
     def arrow(self, p0, p1, color, thickness=1, tip=10.0, alpha=255):
         """cv2.arrowedLine: the shaft, then two strokes of length `tip` (pixels) from p1 at +-45 degrees around the reversed
@@ -303,14 +357,14 @@ class Overlay:
         """The recorded commands, int64 [n][16]: every coordinate clipped into [-16383, 16383] (the range the kernel's 64-bit
         products are sized for), colours into 0..255."""
         cmds = np.concatenate(self._chunks, axis=0) if self._chunks else np.zeros((0, CMD_WORDS), dtype=np.int64)
-        kind = cmds[:, 0:1]
+        kind = _kinds(cmds[:, 0:1])  # with or without the layer flag
         words = np.arange(CMD_WORDS)[None, :]
         coord = ((kind == SEG) & (words >= 5) & (words <= 8)) | ((kind == BOX) & (words >= 5) & (words <= 12)) \
-            | ((kind == GLYPH) & (words >= 5) & (words <= 6))
+            | ((kind == GLYPH) & (words >= 5) & (words <= 6)) | (((kind == RBOX) | (kind == FLUSH)) & (words >= 5) & (words <= 8))
         cmds = np.where(coord, np.clip(cmds, -COORD_MAX, COORD_MAX), cmds)
         cmds[:, 1:4] = np.clip(cmds[:, 1:4], 0, 255)
-        seg_t = cmds[:, 0] == SEG
-        cmds[seg_t, 9] = np.clip(cmds[seg_t, 9], 0, COORD_MAX)
+        length = (kind[:, 0] == SEG) | (kind[:, 0] == RBOX)  # word 9 of both is a length (thickness, radius), not a coordinate
+        cmds[length, 9] = np.clip(cmds[length, 9], 0, COORD_MAX)
         return cmds
 
     def build(self, h: int, w: int, tile=None):
@@ -320,7 +374,7 @@ class Overlay:
         sizes = np.array([m.size for m in self._masks], dtype=np.int64)
         starts = np.cumsum(sizes) - sizes
         atlas = np.concatenate([m.reshape(-1) for m in self._masks]) if self._masks else np.zeros(0, dtype=np.uint8)
-        is_glyph = cmds[:, 0] == GLYPH
+        is_glyph = _kinds(cmds[:, 0]) == GLYPH
         if is_glyph.any():
             cmds[is_glyph, 9] = starts[cmds[is_glyph, 9]]
         offsets, lists = bin_commands(cmds, h, w, tile)
@@ -519,6 +573,159 @@ def _page_order_commands(ov, results, line_color=(0, 0, 255), tip_size=10, visua
             _reading_order_commands(ov, figure.paragraphs, (0, 255, 0), 5)
 
 
+# --------------------------------------------------------------------------------- the table-semantic parser's drawings
+CELL_COLORS = {"cell": (255, 128, 0), "empty": (255, 0, 255), "header": (0, 255, 0), "group": (255, 255, 0)}
+UNKNOWN_ROLE_COLOR = (200, 200, 200)
+TINTED_ROLES = ("cell", "empty", "header")
+
+
+def _cell_commands(ov, cells, groups=None):
+    """cell_detector_visualizer's first image on `ov` (and, with `groups`, its second on that recorder): the cell / empty /
+    header boxes go opaquely into the layer - a later cell overwrites an earlier one where they overlap or share a border row -
+    and ONE flush blends the layer over the page at 77 / 255, leaving the channels whose tint is 255 alone (the reference
+    compares its fill image with 255 per channel).  Then the outlines, t = 2, in the role's colour."""
+    cells = list(cells)
+    with ov.layer():
+        for cell in cells:
+            if cell.role in TINTED_ROLES:
+                ov.fill([int(v) for v in cell.box], CELL_COLORS[cell.role])
+    ov.flush(77, keep255=True)
+    for cell in cells:
+        target = groups if cell.role == "group" else ov
+        if target is not None:
+            target.rectangle([int(v) for v in cell.box], CELL_COLORS.get(cell.role, UNKNOWN_ROLE_COLOR), 2)
+
+
+def cell_detector_visualizer(img1, img2, cells, to_host=True):
+    """utils/visualizer.py:155-204: (img1 with the cells tinted by role and outlined, img2 with the outlines of the group cells)."""
+    cells = list(cells)
+    ov1, ov2 = Overlay(), Overlay()
+    _cell_commands(ov1, cells, ov2)
+    return _finish(ov1, img1, to_host), _finish(ov2, img2, to_host)
+
+
+def _link_commands(ov, box_u, box_v, direction, color):
+    """One arrow of t = 2 from box_u to box_v, centre to centre - but on the axis ACROSS the contact both ends move to the
+    middle of the band the two boxes share, so a link to a spanning cell stays horizontal / vertical.  direction "R" / "D":
+    the contact is known; None: a horizontal link when the boxes share rows and their centres differ in x (compared as
+    integers), else a vertical one when they share columns.  The tip is min(0.2, 12 / length) of the arrow's length, the ratio
+    taken from the exact centres and applied, as cv2.arrowedLine does, to the length between the integer end points."""
+    cx1, cy1 = (box_u[0] + box_u[2]) / 2, (box_u[1] + box_u[3]) / 2
+    cx2, cy2 = (box_v[0] + box_v[2]) / 2, (box_v[1] + box_v[3]) / 2
+    y_lo, y_hi = max(box_u[1], box_v[1]), min(box_u[3], box_v[3])
+    x_lo, x_hi = max(box_u[0], box_v[0]), min(box_u[2], box_v[2])
+    if direction is None:
+        direction = "R" if y_lo < y_hi and int(cx1) != int(cx2) else "D"
+    if direction == "R" and y_lo < y_hi:
+        cy1 = cy2 = (y_lo + y_hi) / 2
+    elif direction == "D" and x_lo < x_hi:
+        cx1 = cx2 = (x_lo + x_hi) / 2
+    length = max(1.0, float(np.hypot(cx2 - cx1, cy2 - cy1)))
+    p0, p1 = (int(cx1), int(cy1)), (int(cx2), int(cy2))
+    ov.arrow(p0, p1, color, 2, tip=min(0.2, 12.0 / length) * float(np.hypot(p1[0] - p0[0], p1[1] - p0[1])))
+
+
+def _kv_commands(ov, table):
+    cells = table.cells
+    for kv in table.kv_items:
+        keys = [kv.key] if isinstance(kv.key, str) else list(kv.key)
+        chain = [k for k in keys if k in cells] + ([kv.value] if kv.value in cells else [])
+        for u, v in zip(chain, chain[1:]):
+            _link_commands(ov, cells[u].box, cells[v].box, None, (0, 255, 0))
+
+
+def kv_items_visualizer(table, img, to_host=True):
+    """table_semantic_parser.py:537-577: every kv item's chain key[0] -> ... -> value as green arrows between the cells."""
+    ov = Overlay()
+    _kv_commands(ov, table)
+    return _finish(ov, img, to_host)
+
+
+def _dag_commands(ov, dag):
+    for u, v, attrs in dag.edges():  # OrderedDiGraph: (u, v, attributes)
+        if attrs["dir"] in ("L", "U"):
+            continue
+        right = attrs["dir"] == "R"
+        _link_commands(ov, dag.nodes[u]["bbox"], dag.nodes[v]["bbox"], "R" if right else "D", (0, 255, 0) if right else (255, 0, 0))
+
+
+def dag_visualizer(dag, img, to_host=True):
+    """table_semantic_parser.py:580-620: the grid graph's R edges (0, 255, 0) and D edges (255, 0, 0); L and U are their mirrors."""
+    ov = Overlay()
+    _dag_commands(ov, dag)
+    return _finish(ov, img, to_host)
+
+
+def text_box(font, string):
+    """(left, top, right, bottom), right and bottom excluded, of `string` drawn horizontally with the pen at (0, 0) under the
+    text rule above: the union of the placed glyph boxes; (0, 0, 0, 0) for a string without pixels."""
+    font_obj, fkey = font
+    pen, boxes = 0, []
+    for ch in string:
+        mask, ox, oy, advance = glyph_of(font_obj, fkey, ch)
+        if mask.size:
+            boxes.append((pen + ox, oy, pen + ox + mask.shape[1], oy + mask.shape[0]))
+        pen += advance
+    if not boxes:
+        return 0, 0, 0, 0
+    return min(b[0] for b in boxes), min(b[1] for b in boxes), max(b[2] for b in boxes), max(b[3] for b in boxes)
+
+
+def _cell_id_commands(ov, tables, font, font_size):
+    pad = radius = max(2, font_size // 5)
+    for table in tables:
+        cells = table.cells.values() if isinstance(table.cells, dict) else table.cells
+        for cell in cells:
+            if cell.role == "group" or cell.id is None:
+                continue
+            label = str(cell.id)
+            left, top, right, bottom = text_box(font, label)
+            bx, by = int(cell.box[0]) + 2, int(cell.box[1]) + 2
+            ov.rounded_fill((bx, by, bx + right - left + 2 * pad, by + bottom - top + 2 * pad), radius, (40, 40, 40), alpha=200)
+            ov.text((bx + pad - left, by + pad - top), label, font, (255, 255, 255))
+
+
+def cell_id_visualizer(img, tables, font_path, font_size=None, to_host=True):
+    """utils/visualizer.py:254-295: the id of every non-group cell as a chip - a rounded dark box at alpha 200 with the id in
+    white - at the cell's top-left corner + (2, 2)."""
+    page = device_page(img)
+    font_size = max(14, int(page.shape[1]) // 75) if font_size is None else int(font_size)
+    ov = Overlay()
+    _cell_id_commands(ov, tables, load_font(font_path, font_size), font_size)
+    return _finish(ov, page, to_host)
+
+
+def _semantic_layout_commands(ov, results, dags=()):
+    """TableSemanticParser's layout image (table_semantic_parser.py:795-830, :986-989): tables, then paragraphs, boxed in green
+    with their id; per table the tinted cells (a flush of its own), its kv arrows and its grid boxes; the grid graphs."""
+    font = load_font(None, 19)  # cv2.putText at scale 0.8
+    for prefix, elements in (("Table", results.tables), ("Paragraph", results.paragraphs)):
+        for element in elements:
+            x1, y1, x2, y2 = (int(v) for v in element.box)
+            ov.rectangle((x1, y1, x2, y2), (0, 255, 0), 2)
+            ov.text((x1, y1 - 10), f"{prefix}: {element.id}", font, (255, 0, 0), anchor="ls")
+    for table in results.tables:
+        _cell_commands(ov, table.cells.values())
+        _kv_commands(ov, table)
+        for grid in table.grids:
+            ov.rectangle([int(v) for v in grid.box], (255, 0, 0), 3)
+    for dag in dags:
+        _dag_commands(ov, dag)
+
+
+def _semantic_ocr_commands(ov, results, font, font_size, font_color):
+    """TableSemanticParser's OCR image (table_semantic_parser.py:335-387): per word its quad, closed, in green, then its text
+    placed as rec_visualizer places a line."""
+    for word in results.words:
+        quad = np.asarray(word.points).astype(np.int32)
+        ov.polyline(quad.reshape(4, 2), True, (0, 255, 0), 1)
+        x, y = int(quad[0][0]), int(quad[0][1])
+        if word.direction == "vertical":
+            ov.text((x - font_size, y), word.content, font, font_color, direction="vertical")
+        else:
+            ov.text((x, y - font_size), word.content, font, font_color)
+
+
 # ------------------------------------------------------------------------------- a wave of canvases (serve(overlays=True))
 # The per-page path above spends its time on the host: a Python loop per character and a sort over the per-tile lists
 # (DESIGN.md "Overlay rasteriser").  Here the host records text as RUNS and reserves one command slot per character;
@@ -658,7 +865,7 @@ class RunOverlay(Overlay):
         raise NotImplementedError("a RunOverlay is built with its wave: build_wave")
 
     def rectangle(self, box, color, thickness=1, alpha=255):
-        if int(thickness) < 0 or np.ndim(box) != 1 or np.ndim(color) != 1:
+        if int(thickness) < 0 or np.ndim(box) != 1 or np.ndim(color) != 1 or self._flag:
             return super().rectangle(box, color, thickness, alpha)
         xa, ya, xb, yb = (int(v) for v in box)  # Overlay.rectangle for one box, in plain integers
         x1, x2, y1, y2 = min(xa, xb), max(xa, xb), min(ya, yb), max(ya, yb)
@@ -672,6 +879,8 @@ class RunOverlay(Overlay):
         n = len(string)
         if n == 0:
             return None
+        if self._flag:  # flush needs the bounds of what was painted; a run's are only known on the device
+            raise NotImplementedError("RunOverlay: text cannot be directed into the layer")
         font_obj = font[0]
         pen_x, pen_y = int(xy[0]), int(xy[1])
         if anchor == "ls":
