@@ -71,12 +71,13 @@ class Wave:
     """The pages that share device batches, and what the stages have produced for them so far."""
 
     __slots__ = ("seq", "ids", "imgs", "pages", "ring", "uploaded", "maps", "sizes", "dets", "rec_plan", "recs", "lay_raw",
-                 "lay_parsed", "tab_raw", "lays", "error", "failed_stage", "layout_done", "joined", "retry", "job", "results")
+                 "lay_parsed", "tab_raw", "lays", "error", "failed_stage", "layout_done", "joined", "retry", "job", "results", "dags")
 
     def __init__(self, seq=0, ids=(), imgs=(), pages=(), ring=0, uploaded=None, retry=False, job=None):
         self.seq, self.ids, self.imgs, self.pages, self.ring, self.uploaded = seq, list(ids), list(imgs), list(pages), ring, uploaded
         self.job = job  # the serve() call this wave belongs to: a late wave of an aborted job must not write into the next one
         self.results = None  # per page, what `finish` made of it (schema or exception): only kept for the render stage
+        self.dags = None  # TableSemanticParser, overlays jobs: per page the grid graphs `finish` parsed, for the render stage
         self.sizes = [tuple(int(v) for v in p.shape[:2]) for p in self.pages]
         self.maps = self.dets = self.rec_plan = self.recs = self.lay_raw = self.lay_parsed = self.tab_raw = self.lays = None
         self.error: Optional[BaseException] = None
@@ -96,8 +97,9 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False):
+    def __init__(self, n_hint=0, overlays=False, options=None):
         self.results = {}
+        self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, ocr overlay, layout overlay): the waves visit the render stage
         self.cond = threading.Condition()
         self.outstanding = 0
@@ -376,7 +378,7 @@ class PagePipeline:
         self._q["detect"].put(wave)
         self._q["layout"].put(wave)
 
-    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False) -> List:
+    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -384,11 +386,13 @@ class PagePipeline:
         overlays=True: a page's entry is (DocumentAnalyzerSchema, ocr overlay, layout overlay) - the two uint8 H x W x 3 images
         `analyze_pages` returns for the page with visualize=True everywhere, as arrays the caller owns; a failed page's entry
         stays the bare exception.  The waves of such a job pass through the render stage, whose thread the first such job
-        starts; a job without overlays runs what it always ran."""
+        starts; a job without overlays runs what it always ran.
+        options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
+        pipeline does not look at it."""
         from .data.functions import load_image
 
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job(overlays=overlays)
+            job = self._job = _Job(overlays=overlays, options=options)
             if job.overlays:
                 self._start_render()
             n = 0

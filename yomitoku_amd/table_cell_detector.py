@@ -19,7 +19,7 @@ import torch
 from . import _lib, imaging
 from .base import BaseModelCatalog, BaseModule, load_config
 from .configs import TableCellParserRTDETRv2Config
-from .geometry import adjacency_matrices, calc_iou, containment_matrix, filter_by_flag, is_contained
+from .geometry import adjacency_matrices, calc_iou, containment_matrix, filter_by_flag
 from .layout_parser import RTDETRPostProcessor, load_local_checkpoint
 from .nets import RTDETRv2
 from .schemas import CellSchema, RegionSchema, TableDetectorSchema
@@ -33,30 +33,27 @@ class TableParserModelCatalog(BaseModelCatalog):
 
 def filter_contained_rectangles_with_category(category_elements, ignore_categories=()):
     """Per category, of two boxes one of which lies (80 %) inside the other, keep the INNER one; when they contain each
-    other the larger one stays (what table_cell_detector.py:41-75 does - its comment says the opposite; the code is
-    what is mirrored.  Note the direction differs from the layout filter, which keeps the outer box)."""
+    other the larger one stays, the later one among equal areas (what table_cell_detector.py:41-75 does - its comment says
+    the opposite; the code is what is mirrored.  Note the direction differs from the layout filter, which keeps the outer
+    box).  The reference's pair loop only ever clears flags, so its result does not depend on the visiting order: one
+    containment matrix per category gives the same flags.  A form's table has a few hundred cells - tens of thousands of
+    pairs - and as a Python loop this filter was the longest stage of `TableSemanticParser.serve`."""
     for category, elements in category_elements.items():
-        if category in ignore_categories:
+        if category in ignore_categories or len(elements) < 2:
             continue
         boxes = [e["box"] for e in elements]
-        keep = [True] * len(boxes)
-        for i, box_i in enumerate(boxes):
-            for j in range(i + 1, len(boxes)):
-                box_j = boxes[j]
-                ij = is_contained(box_i, box_j)
-                ji = is_contained(box_j, box_i)
-                if ij and ji:
-                    area_i = (box_i[2] - box_i[0]) * (box_i[3] - box_i[1])
-                    area_j = (box_j[2] - box_j[0]) * (box_j[3] - box_j[1])
-                    if area_i > area_j:
-                        keep[j] = False
-                    else:
-                        keep[i] = False
-                elif ij:
-                    keep[i] = False
-                elif ji:
-                    keep[j] = False
-        category_elements[category] = filter_by_flag(elements, keep)
+        n = len(boxes)
+        inside = containment_matrix(boxes, boxes, 0.8)  # inside[i][j]: box j lies in box i
+        np.fill_diagonal(inside, False)
+        raw = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+        area = (raw[:, 2] - raw[:, 0]) * (raw[:, 3] - raw[:, 1])
+        mutual = inside & inside.T
+        holds = inside & ~mutual  # i holds j and not the other way round: the outer box i goes
+        # a mutual pair (p < q) loses q when area_p > area_q and p otherwise.  Seen from i: it goes against an earlier box
+        # with a larger area, and against a later box whose area is not smaller
+        later = np.arange(n)[:, None] > np.arange(n)[None, :]
+        loses = mutual & np.where(later, area[None, :] > area[:, None], ~(area[:, None] > area[None, :]))
+        category_elements[category] = filter_by_flag(elements, (~(holds | loses).any(axis=1)).tolist())
     return category_elements
 
 
@@ -226,32 +223,47 @@ class CellDetector(BaseModule):
                                                    grid_regions=grid_regions))
         return outputs  # `visualize` is stored and draws nothing, as in the reference (utils/visualizer.py has cell_detector_visualizer)
 
-    def detect_pages(self, imgs, tables_per_page):
-        """`__call__` for several pages: the tables of ALL pages share forwards of up to MAX_TABLES_PER_FORWARD crops (images
-        of a batch are independent).  tables_per_page[k]: the table elements of imgs[k].  Returns [[TableDetectorSchema]], one
-        list per page, each what `__call__(imgs[k], tables_per_page[k])` returns."""
+    def forward_tables(self, imgs, tables_per_page):
+        """The device half of `detect_pages`: the table crops of ALL pages fill shared forwards of at most
+        MAX_TABLES_PER_FORWARD crops.  tables_per_page[k]: the table elements of imgs[k].  Returns [(page index, table element,
+        logits 1 x Q x C, boxes 1 x Q x 4, meta)] per table, host arrays, in page / table order - what `tables_from_raw` turns
+        into TableDetectorSchemas on the host."""
         pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, self.device) for img in imgs]
-        jobs = [(k, table) for k, tables in enumerate(tables_per_page) for table in tables]
-        outputs = [[] for _ in pages]
         oh, ow = (int(v) for v in self._cfg.data.img_size)
-        for start in range(0, len(jobs), self.MAX_TABLES_PER_FORWARD):
-            chunk = jobs[start : start + self.MAX_TABLES_PER_FORWARD]
-            batch = torch.empty((len(chunk), 3, oh, ow), dtype=torch.float32, device=pages[chunk[0][0]].device)
-            metas = []
-            for i, (k, table) in enumerate(chunk):
-                _, size, offset = imaging.rtdetr_tensor(pages[k], table.box, (oh, ow), out=batch[i])
-                metas.append({"size": size, "offset": offset})
+        self.model.reserve_once(self.MAX_TABLES_PER_FORWARD, oh, ow, self.device)  # any table count: no reallocation later (once per live handle)
+        flat = [(k, table) for k, tables in enumerate(tables_per_page) for table in tables]
+        raw = []
+        # forwards of EQUAL size: 10 crops run as 5 + 5, not 8 + 2 - a batch of two leaves most of the chip idle
+        n_fwd = max(1, -(-len(flat) // self.MAX_TABLES_PER_FORWARD))
+        per = -(-len(flat) // n_fwd) if flat else 1
+        for start in range(0, len(flat), per):
+            chunk = flat[start : start + per]
+            batch, metas = imaging.rtdetr_batch_tensor(pages, [(k, table.box) for k, table in chunk], (oh, ow))  # every crop of the forward in one launch
             preds = self.model(batch)
-            logits = preds["pred_logits"].cpu().numpy()
-            boxes = preds["pred_boxes"].cpu().numpy()
-            for i, (data, (k, table)) in enumerate(zip(metas, chunk)):
-                one = {"pred_logits": logits[i : i + 1], "pred_boxes": boxes[i : i + 1]}
-                cells, kv_regions, grid_regions = self.postprocess(one, data, table.box)
-                if len(cells) == 0:
-                    continue
-                outputs[k].append(TableDetectorSchema(id=None, box=table.box, role=table.role, cells=cells, kv_regions=kv_regions,
-                                                      grid_regions=grid_regions))
+            logits, boxes = imaging.to_host(preds["pred_logits"], preds["pred_boxes"])
+            for i, ((k, table), data) in enumerate(zip(chunk, metas)):
+                raw.append((k, table, logits[i : i + 1], boxes[i : i + 1], data))
+        return raw
+
+    def tables_from_raw(self, raw, n_pages):
+        """The host half: post-processor, containment filters, holes and roles per table; per page the list
+        `__call__(imgs[k], tables_per_page[k])` returns (tables without cells dropped)."""
+        outputs = [[] for _ in range(n_pages)]
+        for k, table, logits, boxes, data in raw:
+            cells, kv_regions, grid_regions = self.postprocess({"pred_logits": logits, "pred_boxes": boxes}, data, table.box)
+            if len(cells) == 0:
+                continue
+            outputs[k].append(TableDetectorSchema(id=None, box=table.box, role=table.role, cells=cells, kv_regions=kv_regions,
+                                                  grid_regions=grid_regions))
         return outputs
+
+    def detect_pages(self, imgs, tables_per_page):
+        """`__call__` for several pages: shared forwards over the table crops of all pages (images of a batch are
+        independent), then the host box logic.  Returns [[TableDetectorSchema]], one list per page, each what
+        `__call__(imgs[k], tables_per_page[k])` returns."""
+        if len(imgs) == 0:  # nothing to reserve a workspace for
+            return []
+        return self.tables_from_raw(self.forward_tables(imgs, tables_per_page), len(imgs))
 
 
 __all__ = ["CellDetector", "TableParserModelCatalog", "find_holes_as_rects", "calc_adjacent_holes_to_cells", "choose_role",

@@ -17,7 +17,10 @@ arguments and the same result for the same model outputs.  What differs from the
   * the page is uploaded once and the device page is shared by the four modules; the text chain (DBNet -> PARSeq) and the table
     chain (RT-DETRv2 table detector -> RT-DETRv2 cell detector) run side by side on two HIP streams, like the two chains of
     DocumentAnalyzer (the reference runs the two detectors side by side and the rest in sequence; the results are the same);
-  * `parse_pages(imgs)`: several pages through shared forwards;
+  * `parse_pages(imgs)`: several pages through shared forwards, one wave at a time;
+  * `serve(sources)`: the throughput path - the parser as the analyzer of the page pipeline (serving.py): several waves in
+    flight, the host stages on threads of their own, a failing page isolated; `template`, `grid_only`, `kv_only` and `overlays`
+    per job.  `distributed.ShardedServer` / `serve_sharded` take a `make_analyzer` that returns a parser;
   * `aggregate` assigns words to cells from one words x cells overlap matrix instead of a double loop (same assignment).
 
 Everything after the four networks is host logic on at most a few hundred boxes per table (`semantic_stage`): no kernel.
@@ -226,6 +229,7 @@ def _owned_host_image(canvas):
 class TableSemanticParser:
     merge_same_column_values = False  # True: grid columns under the same innermost header cell become one column
     visualize = False
+    split_text_across_cells = False  # the page pipeline asks its analyzer (serving.py); the reference's parser has no such option
 
     def __init__(self, configs={}, device="cuda", visualize=False, workspace_reuse=False):
         if not isinstance(configs, dict):
@@ -249,6 +253,7 @@ class TableSemanticParser:
         # `handover`: None, or an object whose `tables(page index, [Element])` sees - and may replace - the table boxes that the
         # table detector hands to the cell detector (measurements and tests with seeded weights, whose detections are noise)
         self.handover = None
+        self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
 
     _submit = DocumentAnalyzer._submit        # needs _pool, _streams, concurrent_chains, chain_priority, text_detector.device
     _on_stream = DocumentAnalyzer._on_stream
@@ -454,8 +459,113 @@ class TableSemanticParser:
                     out[start + k] = (out[start + k], images[2 * k], images[2 * k + 1])
         return out
 
+    # ---- the stage protocol of the page pipeline (yomitoku_amd/serving.py: one thread per stage, HIP stream for those that
+    # launch).  The OCR chain is DocumentAnalyzer's on this parser's detector and recogniser (the three stages that touch
+    # nothing else are borrowed; detect and boxes are restated without the analyzer's hand-over hooks, which the parser does
+    # not have); the table chain ends in the cell detector's two halves; `finish` is what `__call__` does after the networks.
+    def _stage_detect(self, wave):
+        """DBNet forwards over same-size pages of the wave; the maps come back into the wave slot's pinned buffers."""
+        wave.maps = self.text_detector.forward_pages(wave.pages, ring=wave.ring)
+
+    def _stage_boxes(self, wave):
+        """DB box extraction (C++, GIL released), the pages of the wave concurrently."""
+        wave.dets = self.text_detector.extract_boxes(wave.maps, wave.sizes)
+
+    _stage_crops = DocumentAnalyzer._stage_crops          # needs text_recognizer
+    _stage_recognize = DocumentAnalyzer._stage_recognize  # (wave, lane): the recogniser handle of the lane
+    _stage_decode = DocumentAnalyzer._stage_decode
+
+    def _stage_layout(self, wave):
+        """One RT-DETRv2 table-detector forward over the pages (device half)."""
+        wave.lay_raw = self.layout_parser.forward_pages(wave.pages)
+
+    def _stage_tables(self, wave):
+        """Table boxes on the host (shown to the hand-over under the page's position in the job), then the cell detector's
+        forwards over all table crops of the wave."""
+        wave.lay_parsed = self.layout_parser.pages_from_raw(wave.lay_raw)
+        wave.lay_raw = None
+        tables = [self._handed_tables(idx, list(l.tables)) for idx, l in zip(wave.ids, wave.lay_parsed)]
+        wave.tab_raw = self.cell_detector.forward_tables(wave.pages, tables)
+
+    def _stage_cells(self, wave):
+        """The cell detector's box logic on the host: per page its [TableDetectorSchema]."""
+        wave.lays = self.cell_detector.tables_from_raw(wave.tab_raw, len(wave.pages))
+        wave.tab_raw = None
+
+    def _stage_finish(self, wave, k):
+        """Page k of the wave -> TableSemanticParserSchema, with the job's template / grid_only / kv_only: what `__call__` does
+        after the networks.  An overlays job keeps the page's grid graphs on the wave for the render stage."""
+        job = wave.job
+        options = getattr(job, "options", None) or {}
+        dags = [] if getattr(job, "overlays", False) else None
+        handed = self._hand_over(wave.dets[k], wave.recs[k], wave.lay_parsed[k], wave.lays[k])
+        results = self.semantic_stage(*handed, options.get("template"), options.get("grid_only", False), options.get("kv_only", False), dags=dags)
+        if dags is not None:
+            if wave.dags is None:
+                wave.dags = [None] * len(wave)
+            wave.dags[k] = dags
+        return results
+
+    def _stage_render(self, wave, results):
+        """serve(overlays=True): per page of the wave (layout picture, OCR picture) as owned host arrays - the order `__call__`
+        returns them in -, an exception for a page whose drawing raised, None for a page that had already failed.  All
+        canvases of the wave are drawn by the wave renderer on the calling thread's stream and come back through the wave
+        slot's pinned buffer."""
+        from .utils.visualizer import RunOverlay, render_wave
+
+        out = [None] * len(wave)
+        live, drawings = [], []
+        for k in range(len(wave)):
+            if isinstance(results[k], BaseException):
+                continue
+            try:
+                drawings.extend(self._drawings(results[k], wave.dags[k], RunOverlay))
+                live.append(k)
+            except Exception as exc:  # noqa: BLE001 - only this page fails
+                out[k] = exc
+        wave.dags = None
+        if live:
+            pinned = self._render_pinned.setdefault(wave.ring, [None])
+            images = render_wave([wave.pages[k] for k in live for _ in range(2)], drawings, pinned)
+            for j, k in enumerate(live):
+                out[k] = (images[2 * j], images[2 * j + 1])
+        return out
+
+    def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
+              overlays: bool = False, template=None, grid_only=False, kv_only=False):
+        """The multi-page entry point, as `DocumentAnalyzer.serve`: host pages (uint8 H x W x 3 BGR arrays) and / or image file
+        paths in, one entry per page out, in page order, through the stage pipeline of yomitoku_amd/serving.py - `wave` pages
+        per device batch, up to `in_flight` waves between upload and the semantic stage, every host stage (table boxes, the
+        cell detector's box logic, the semantic stage) on a thread of its own, so that the networks of the next waves run
+        while this wave's cells and grids are worked out.  A page's entry is its TableSemanticParserSchema - equal to
+        `__call__(img, template, grid_only=..., kv_only=...)[0]` - or, when the page (or its file) failed, the exception
+        object; the other pages are not affected.  `with_source`: (source index, frame index, entry) triples.  `overlays`:
+        a page's entry is (schema, layout picture, OCR picture), the two pictures of `__call__(img, overlays=True)` as uint8
+        H x W x 3 arrays the caller owns, drawn by the pipeline's render stage; a failed page's entry stays the exception.
+        `template`, `grid_only`, `kv_only`, `overlays` are properties of the JOB: they travel with it and the next job starts
+        without them.  `defer_full_gc`, `rec_lanes`: see `DocumentAnalyzer.serve`."""
+        from .serving import PagePipeline
+
+        if self.visualize:
+            raise NotImplementedError(_NO_VIS)
+        pipe = getattr(self, "_pipeline", None)
+        if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
+            if pipe is not None:
+                pipe.close()
+            pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
+            pipe.rec_lanes_asked = int(rec_lanes)
+        pipe.defer_full_gc = bool(defer_full_gc)
+        options = {"template": template, "grid_only": bool(grid_only), "kv_only": bool(kv_only)}
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options)
+
     def close(self):
-        """Release the device memory of the four nets (a net rebuilds its handle when it is called again)."""
+        """Stop the pipeline threads, drop the render buffers and release the device memory of the four nets (a net rebuilds
+        its handle when it is called again)."""
+        pipe = getattr(self, "_pipeline", None)
+        if pipe is not None:
+            pipe.close()
+            self._pipeline = None
+        self._render_pinned.clear()
         self.text_recognizer.close_replicas()
         for module in (self.text_detector, self.text_recognizer, self.layout_parser, self.cell_detector):
             module.model.close()
