@@ -312,3 +312,28 @@ def test_sources_are_pulled_only_when_a_wave_slot_is_free():
     assert max(ahead) <= (2 + 1 + 1) * 2, max(ahead)
     assert pipe.serve(iter([])) == [] and pipe.serve(feed(4))[-1][0] == 3  # the slots all came back (an exact multiple of the wave too)
     pipe.close()
+
+
+@pytest.mark.parametrize("good", [3, 0, 2], ids=["mid-wave", "before-the-first-page", "on-a-wave-boundary"])
+def test_a_source_iterator_that_raises_gives_its_wave_slot_back(good):
+    """serve() holds a wave slot while it pulls the wave's sources.  A source that raises (distributed.PageDealer.pull is a
+    generator over a TCP store) must not take the slot with it: with in_flight=1 the next job would wait for it for ever.
+    `good` pages come first: 3 = one wave launched and one page pending, 0 = nothing pulled yet, 2 = exactly one wave (the slot
+    for the next is held with nothing pending).  The next job runs on a daemon thread so that a regression fails, not hangs."""
+    pipe = PagePipeline(StubAnalyzer(), wave=2, in_flight=1)
+
+    def feed():
+        for i in range(good):
+            yield page(i)
+        raise ConnectionError("store gone")
+
+    with pytest.raises(ConnectionError, match="store gone"):
+        pipe.serve(feed())
+    out = []
+    t = threading.Thread(target=lambda: out.extend(pipe.serve([page(4), page(5)])), daemon=True)
+    t.start()
+    t.join(10)
+    assert not t.is_alive(), "the job after a failed source is still waiting for a wave slot"
+    assert [o[0] for o in out] == [0, 1] and [o[1] for o in out] == [(4 + 1000) * 2, (5 + 1000) * 2]  # its two pages, in order
+    assert pipe._rings.qsize() == 1
+    pipe.close()

@@ -98,3 +98,25 @@ def test_parse_pages_equals_per_page_calls(parser, page, single):
     for one, many in zip(singles, multi):
         _assert_same_schema(one, many.model_dump())
     assert parser.parse_pages([]) == []
+
+
+@pytest.mark.parametrize("overlays", [False, True], ids=["plain", "overlays"])
+def test_parse_pages_across_chunk_boundaries(parser, page, overlays):
+    """Three pages with wave=2: two chunks, the second ragged - the smallest input whose pages' indices in the call differ from
+    their indices in the wave (the stage methods run over a Wave per chunk; `finish` and the renderer index it by position).
+    Every entry is the per-page `__call__`'s, to the tolerances above; the pictures are equal byte for byte (an integer
+    rasteriser over the same integer boxes and strings)."""
+    from tests.test_pipeline_gpu import _assert_same_schema
+
+    flipped = np.ascontiguousarray(page[:, ::-1])
+    want = [parser(img, overlays=overlays) for img in (page, flipped)]
+    multi = parser.parse_pages([page, flipped, page], wave=2, overlays=overlays)
+    assert len(multi) == 3
+    for (one, vis_layout, vis_ocr), many in zip(want + want[:1], multi):
+        if overlays:
+            many, many_layout, many_ocr = many
+            assert many_layout.shape == page.shape and many_layout.dtype == np.uint8
+            assert np.array_equal(many_layout, vis_layout) and np.array_equal(many_ocr, vis_ocr)
+        _assert_same_schema(one.model_dump(), many.model_dump())
+    if overlays:
+        assert not np.array_equal(multi[0][1], multi[1][1]) and not np.array_equal(multi[0][1], page)  # something was drawn

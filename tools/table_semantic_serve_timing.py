@@ -28,8 +28,8 @@ PAGES, HEIGHT, WIDTH = 64, 1600, 1200
 
 
 class TrueTables:
-    """The hand-over of both legs.  `serve` shows a page under its position in the job; `parse_pages` under its position in the
-    wave, one call per page in page order - there the calls are counted."""
+    """The hand-over of both legs.  `serve` and `parse_pages` show a page under its position in the job (`parse_pages` of older
+    commits: in the wave), one call per page in page order - for `parse_pages` the calls are counted, which holds for both."""
 
     def __init__(self, boxes_per_page, by_call_order):
         self.boxes, self.by_call_order, self.calls = boxes_per_page, by_call_order, 0

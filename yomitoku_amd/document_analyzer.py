@@ -10,11 +10,8 @@ with its own HIP stream), as in document_analyzer.py:622-669.
 
 from __future__ import annotations
 
-import os
-
 import math
 import re
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -30,6 +27,7 @@ from .schemas import (
     OCRSchema,
     ParagraphSchema,
 )
+from .serving import StageAnalyzer
 from .table_structure_recognizer import TableStructureRecognizer
 from .text_detector import TextDetector
 from .text_recognizer import TextRecognizer
@@ -309,16 +307,7 @@ def _split_text_across_cells(results_det, results_layout):
 
 
 # ---------------------------------------------------------------------------------------------- DocumentAnalyzer
-def _chain_priorities():
-    spec = os.environ.get("YMK_CHAIN_PRIORITY", "")  # e.g. "layout:-1,ocr:0" (measurement knob)
-    out = {}
-    for item in filter(None, spec.split(",")):
-        name, _, value = item.partition(":")
-        out[name.strip()] = int(value)
-    return out
-
-
-class DocumentAnalyzer:
+class DocumentAnalyzer(StageAnalyzer):
     def __init__(self, configs={}, device="cuda", visualize=False, ignore_meta=False, reading_order="auto",
                  split_text_across_cells=False, ignore_ruby=False, ruby_threshold=2.0, workspace_reuse=False):
         # workspace_reuse: every network plans its workspace so that dead activations share bytes (include/ymk.h,
@@ -340,22 +329,14 @@ class DocumentAnalyzer:
         self.split_text_across_cells = split_text_across_cells
         self.ignore_ruby = ignore_ruby
         self.ruby_threshold = ruby_threshold
-        self._pool = ThreadPoolExecutor(max_workers=2)
-        self._streams = {}
-        # False: the two chains run one after the other on the caller's thread and stream (profiling: a kernel's
-        # timing then brackets that kernel alone); results are the same either way
-        self.concurrent_chains = True
-        # HIP stream priority per chain (0 = default, -1 = high).  Measured on the analyzer bench: raising either chain
-        # LOWERS the throughput (66.9 -> 62.3 layout high, 64.2 ocr high), so the default is no priority
-        self.chain_priority = _chain_priorities()
-        # `handover`: an object with any of maps / boxes / layout_raw / table_boxes / layouts (yomitoku_amd.testing.Handover) that
-        # sees - and may replace - what one stage of the multi-page paths hands to the next, AFTER the stage has produced it at
-        # full cost.  None (always, outside measurements): the stages hand over what they computed.  It exists so that a
-        # throughput measurement with seeded weights (whose detections are noise) can feed realistic unit counts downstream
-        # without a subclass that re-states the stage bodies (bench.py; tests/test_serving_gpu.py holds the hook to
-        # "identity in, identical results out")
-        self.handover = None
-        self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
+        # `handover`: an object with any of maps / boxes / layout_raw / table_boxes / layouts (yomitoku_amd.testing.Handover);
+        # it exists so that a throughput measurement with seeded weights can feed realistic unit counts downstream without a
+        # subclass that re-states the stage bodies (bench.py; tests/test_serving_gpu.py holds the hook to "identity in,
+        # identical results out")
+        self._init_chains()
+
+    def _nets(self):
+        return self.text_detector, self.text_recognizer, self.layout.layout_parser, self.layout.table_structure_recognizer
 
     # ---- aggregation (:487-601)
     def aggregate(self, ocr_res, layout_res, img=None):
@@ -409,31 +390,6 @@ class DocumentAnalyzer:
             "words": ocr_res.words,
         }
 
-    # ---- the two concurrent chains, each on its own HIP stream
-    def _submit(self, name, fn, *args):
-        """A chain as a future: on its own thread + HIP stream, or - concurrent_chains False - run right here."""
-        if self.concurrent_chains:
-            return self._pool.submit(self._on_stream, name, fn, *args)
-        from concurrent.futures import Future
-
-        f = Future()
-        try:
-            f.set_result(fn(*args))
-        except BaseException as exc:  # noqa: BLE001 - delivered by f.result(), like a pool future
-            f.set_exception(exc)
-        return f
-
-    def _on_stream(self, name, fn, *args):
-        dev = self.text_detector.device
-        stream = self._streams.get(name)
-        if stream is None:
-            stream = self._streams[name] = torch.cuda.Stream(device=dev, priority=self.chain_priority.get(name, 0))
-        stream.wait_stream(torch.cuda.default_stream(dev))  # the page upload was issued there
-        with torch.cuda.stream(stream):
-            out = fn(*args)
-            stream.synchronize()
-        return out
-
     def _vis_det(self, page, results_det):
         """document_analyzer.py:613-617: the analyzer's own detection overlay (default colour, no heat map) - the canvas the
         recogniser draws its strings onto.  Stays on the device."""
@@ -471,38 +427,8 @@ class DocumentAnalyzer:
     # batch-1 RT-DETR / PARSeq launches are grid-starved and every page pays its own greedy-decode loop).  The stages of
     # a wave (yomitoku_amd.serving.Wave) are separate methods: `analyze_pages` runs them as two concurrent chains,
     # `serve` as a pipeline with one thread and HIP stream per stage.
-    def _handed(self, what, wave, value):
-        fn = getattr(self.handover, what, None) if self.handover is not None else None
-        return value if fn is None else fn(wave, value)
-
-    def _stage_detect(self, wave):
-        """DBNet forwards over same-size pages of the wave; the maps come back into the wave slot's pinned buffers."""
-        wave.maps = self._handed("maps", wave, self.text_detector.forward_pages(wave.pages, ring=wave.ring))
-
-    def _stage_boxes(self, wave):
-        """DB box extraction (C++, GIL released), the pages of the wave concurrently."""
-        wave.dets = self._handed("boxes", wave, self.text_detector.extract_boxes(wave.maps, wave.sizes))
-
     def _stage_split(self, wave):
         wave.dets = [_split_text_across_cells(d, l) for d, l in zip(wave.dets, wave.lays)]
-
-    def _stage_crops(self, wave):
-        """Per-page mini-batches (bucketing, width budget) and the crop kernels that build their tensors."""
-        wave.rec_plan = self.text_recognizer.plan_pages(wave.pages, [d.points for d in wave.dets])
-
-    def _stage_recognize(self, wave, lane=0):
-        """One grouped PARSeq forward over the mini-batches of all pages of the wave, on the recogniser handle of `lane`
-        (serve keeps two forwards in flight: TextRecognizer.replica_model); with `rec_orientation_fallback` the decode
-        happens here too, because the retry runs further forwards."""
-        self.text_recognizer.forward_plan(wave.rec_plan, self.text_recognizer.replica_model(lane))
-        if self.text_recognizer.rec_orientation_fallback:
-            self._stage_decode(wave)
-
-    def _stage_decode(self, wave):
-        """Token decode and un-permutation on the host."""
-        if wave.recs is None:
-            wave.recs = self.text_recognizer.finish_plan(wave.rec_plan)
-            wave.rec_plan = None
 
     def _stage_layout(self, wave):
         """One RT-DETRv2 layout forward over the pages (device half)."""
@@ -543,45 +469,6 @@ class DocumentAnalyzer:
         V._page_order_commands(layout, results)
         return ocr, layout
 
-    def _stage_render(self, wave, results):
-        """serve(overlays=True): per page of the wave (ocr overlay, layout overlay) as owned host arrays, an exception for a
-        page whose drawing raised, None for a page that had already failed.  All canvases of the wave are drawn by two
-        launches on the calling thread's stream and come back through the wave slot's pinned buffer."""
-        from .utils.visualizer import render_wave
-
-        out = [None] * len(wave)
-        live, drawings = [], []
-        for k in range(len(wave)):
-            if isinstance(results[k], BaseException):
-                continue
-            try:
-                drawings.extend(self._page_drawings(wave, k, results[k]))
-                live.append(k)
-            except Exception as exc:  # noqa: BLE001 - only this page fails
-                out[k] = exc
-        if live:
-            pinned = self._render_pinned.setdefault(wave.ring, [None])
-            images = render_wave([wave.pages[k] for k in live for _ in range(2)], drawings, pinned)
-            for j, k in enumerate(live):
-                out[k] = (images[2 * j], images[2 * j + 1])
-        return out
-
-    def _recognize_wave(self, wave):
-        self._stage_crops(wave)
-        self._stage_recognize(wave)
-        self._stage_decode(wave)
-
-    def _layout_wave(self, wave):
-        self._stage_layout(wave)
-        self._stage_tables(wave)
-        self._stage_cells(wave)
-
-    def _ocr_wave(self, wave):
-        self._stage_detect(wave)
-        self._stage_boxes(wave)
-        if not self.split_text_across_cells:
-            self._recognize_wave(wave)
-
     def analyze_pages(self, imgs, wave: int = 8):
         """`__call__` over a list of pages, `wave` pages at a time on the device.  Every page's result is what
         `__call__(img)` returns for it (pages never interact: batches are per-image independent, recogniser
@@ -589,23 +476,11 @@ class DocumentAnalyzer:
         run concurrently on their own HIP streams, as in `run`.  Returns [(DocumentAnalyzerSchema, ocr_vis, layout_vis), ...]
         (the two images of `__call__` with visualize=True, else None).
         One wave at a time: `serve` is the throughput path (several waves in flight, failures isolated per page)."""
-        from .serving import Wave
-
-        dev = self.text_detector.device
         out = []
         size = max(1, int(wave))
         for start in range(0, len(imgs), size):
-            chunk = imgs[start : start + size]
-            pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, dev) for img in chunk]
-            w = Wave(start // size, range(start, start + len(chunk)), chunk, pages)
-            f_ocr = self._submit("ocr", self._ocr_wave, w)
-            f_lay = self._submit("layout", self._layout_wave, w)
-            f_ocr.result()
-            f_lay.result()
-            if self.split_text_across_cells:
-                self._stage_split(w)
-                self._submit("ocr", self._recognize_wave, w).result()
-            out.extend(self._with_overlays(w, k, self._stage_finish(w, k)) for k in range(len(chunk)))
+            w = self._run_wave(imgs[start : start + size], start)
+            out.extend(self._with_overlays(w, k, self._stage_finish(w, k)) for k in range(len(w)))
         return out
 
     def _with_overlays(self, wave, k, results):
@@ -652,34 +527,11 @@ class DocumentAnalyzer:
         recognised strings; layout boxes, table cells, reading order; no heat map), as uint8 H x W x 3 arrays the caller owns.
         They are drawn on the device by a render stage of the pipeline - text layout, per-tile culling and all canvases of a
         wave in two launches ("Overlay rasteriser") - that only the waves of such a job visit."""
-        from .serving import PagePipeline
-
         if self.visualize:
             raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: build the analyzer with "
                                       "visualize=False and ask per job, serve(..., overlays=True) (__call__ and analyze_pages "
                                       "draw with visualize=True)")
-        pipe = getattr(self, "_pipeline", None)
-        if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
-            if pipe is not None:
-                pipe.close()
-            pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
-            pipe.rec_lanes_asked = int(rec_lanes)
-        pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source, overlays=overlays)
-
-    def close(self, release_models: bool = True):
-        """Stop the pipeline threads, release the extra recogniser handles and - `release_models` - the device memory of the
-        four nets (weights and the reserved workspaces: tens of GB per analyzer).  The analyzer stays usable: a net rebuilds
-        its handle from the state dict it holds the next time it is called."""
-        pipe = getattr(self, "_pipeline", None)
-        if pipe is not None:
-            pipe.close()
-            self._pipeline = None
-        self._render_pinned.clear()
-        self.text_recognizer.close_replicas()
-        if release_models:
-            for module in (self.text_detector, self.text_recognizer, self.layout.layout_parser, self.layout.table_structure_recognizer):
-                module.model.close()
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays)
 
     def __call__(self, img):
         self.img = img

@@ -42,7 +42,11 @@ previous thresholds come back when the job ends).
 Failure isolation: a stage that raises marks its wave failed; the pages of a failed wave are re-run as single-page
 waves through the same pipeline, and a page that fails alone gets the exception object as its result - the job goes
 on (the reference's per-file `except: log, continue`).  Results equal `DocumentAnalyzer.__call__` page by page
-(tests/test_serving_gpu.py)."""
+(tests/test_serving_gpu.py).
+
+What the pipeline asks of an analyzer is written down in `StageAnalyzer` (below), the base class of DocumentAnalyzer and
+TableSemanticParser: it holds the chain plumbing, the OCR chain and the render stage once, each analyzer adds its table chain,
+`finish` and the drawings of a page."""
 
 from __future__ import annotations
 
@@ -55,11 +59,13 @@ import sys
 import threading
 import time
 from collections import deque
+from concurrent.futures import Future, ThreadPoolExecutor
 from typing import Iterable, List, Optional
 
 import numpy as np
 import torch
 
+from . import imaging
 from .data.staging import PageStager
 
 logger = logging.getLogger(__name__)
@@ -153,6 +159,27 @@ def _switch_interval(seconds):
                 _switch_saved = None
 
 
+def _run_stage(stream, wave, fn, *args):
+    """One stage visit: `fn(*args)` on `stream` after the wave's upload, waited for.  The one place that guards device memory: when
+    the stage raises, kernels it already queued may still read the wave's pages / pinned maps / crops, which the caller is about
+    to hand back with the slot - they are drained first (best effort: the device may be the problem), then the exception goes
+    on.  `stream` None (a host stage, or the host-only pipeline): the plain call."""
+    if stream is None:
+        return fn(*args)
+    try:
+        with torch.cuda.stream(stream):
+            stream.wait_event(wave.uploaded)
+            out = fn(*args)
+            stream.synchronize()
+        return out
+    except BaseException:
+        try:
+            stream.synchronize()
+        except Exception:  # noqa: BLE001
+            pass
+        raise
+
+
 class PagePipeline:
     def __init__(self, analyzer, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, stage_priority=None,
                  rec_lanes: int = 2):
@@ -169,6 +196,7 @@ class PagePipeline:
         self.switch_interval = float(os.environ.get("YMK_SWITCH_INTERVAL", 2e-4))
         self.stage_priority = dict(stage_priority or {})
         rec = getattr(analyzer, "text_recognizer", None)
+        self.rec_lanes_asked = int(rec_lanes)  # what the caller asked for: an analyzer's serve() rebuilds the pipeline when it changes
         self.rec_lanes = 1 if getattr(rec, "rec_orientation_fallback", False) else max(1, int(os.environ.get("YMK_REC_LANES", rec_lanes)))
         for item in filter(None, os.environ.get("YMK_STAGE_PRIORITY", "").split(",")):
             name, _, value = item.partition(":")
@@ -228,22 +256,9 @@ class PagePipeline:
             if wave.error is None or name == "finish":
                 t_start = time.perf_counter()
                 try:
-                    if stream is not None:
-                        with torch.cuda.stream(stream):
-                            stream.wait_event(wave.uploaded)
-                            fn(wave)
-                            stream.synchronize()
-                    else:
-                        fn(wave)
+                    _run_stage(stream, wave, fn, wave)
                 except BaseException as exc:  # noqa: BLE001 - delivered to the page's result slot
                     wave.fail(name, exc)
-                    if stream is not None:
-                        # kernels the failed stage already queued may still read the wave's pages / pinned maps / crops, which
-                        # the finish stage is about to hand back: drain them first (best effort - the device may be the problem)
-                        try:
-                            stream.synchronize()
-                        except Exception:  # noqa: BLE001
-                            pass
                     if name == "finish":  # cannot happen short of a bug in _finish itself: never lose a page or a slot
                         for idx in wave.ids:
                             wave.job.results.setdefault(idx, exc)
@@ -279,21 +294,10 @@ class PagePipeline:
             job, results = wave.job, wave.results
             try:
                 try:
-                    if stream is not None:
-                        with torch.cuda.stream(stream):
-                            stream.wait_event(wave.uploaded)
-                            images = self.analyzer._stage_render(wave, results)
-                            stream.synchronize()
-                    else:
-                        images = self.analyzer._stage_render(wave, results)
+                    images = _run_stage(stream, wave, self.analyzer._stage_render, wave, results)
                 except BaseException as exc:  # noqa: BLE001 - delivered to the pages' result slots
                     logger.error("wave %d failed in the render stage: %s: %s", wave.seq, type(exc).__name__, exc)
                     images = [exc] * len(wave)
-                    if stream is not None:
-                        try:
-                            stream.synchronize()  # nothing may still read the wave's pages when the slot goes back
-                        except Exception:  # noqa: BLE001
-                            pass
                 for k, idx in enumerate(wave.ids):
                     if isinstance(results[k], BaseException):
                         job.results[idx] = results[k]
@@ -431,38 +435,43 @@ class PagePipeline:
             # work from a shared counter (distributed.PageDealer) - a rank must not claim pages it has no room for yet, or the
             # end of a sharded job is as ragged as a static deal.  (A slot held while nothing is pending is given back below.)
             it = enumerate(sources)
-            while True:
-                if not pend_ids and held[0] is None:
-                    drain_retries()
-                    t_wait = time.perf_counter()
-                    held[0] = self._rings.get()
-                    held[1] = time.perf_counter() - t_wait
-                try:
-                    si, src = next(it)
-                except StopIteration:
-                    break
-                if isinstance(src, np.ndarray):
-                    frames = [src]
-                else:
+            try:
+                while True:
+                    if not pend_ids and held[0] is None:
+                        drain_retries()
+                        t_wait = time.perf_counter()
+                        held[0] = self._rings.get()
+                        held[1] = time.perf_counter() - t_wait
                     try:
-                        frames = list(load_image(src))
-                    except Exception as exc:  # noqa: BLE001 - cli/main.py:555-564: log, go on with the next file
-                        logger.error("cannot load %s: %s: %s", src, type(exc).__name__, exc)
-                        job.results[n] = exc
-                        origin.append((si, 0))
+                        si, src = next(it)
+                    except StopIteration:
+                        break
+                    if isinstance(src, np.ndarray):
+                        frames = [src]
+                    else:
+                        try:
+                            frames = list(load_image(src))
+                        except Exception as exc:  # noqa: BLE001 - cli/main.py:555-564: log, go on with the next file
+                            logger.error("cannot load %s: %s: %s", src, type(exc).__name__, exc)
+                            job.results[n] = exc
+                            origin.append((si, 0))
+                            n += 1
+                            continue
+                    for fi, frame in enumerate(frames):
+                        origin.append((si, fi))
+                        pend_ids.append(n)
+                        pend_imgs.append(frame)
                         n += 1
-                        continue
-                for fi, frame in enumerate(frames):
-                    origin.append((si, fi))
-                    pend_ids.append(n)
-                    pend_imgs.append(frame)
-                    n += 1
-                    if len(pend_ids) == self.wave:
-                        flush()
-            flush()
-            if held[0] is not None:  # the source list ended on a wave boundary
-                self._rings.put(held[0])
-                held[0] = None
+                        if len(pend_ids) == self.wave:
+                            flush()
+                flush()
+            finally:
+                # the source list ended on a wave boundary - or the source iterator raised (a generator over a network store,
+                # KeyboardInterrupt): the exception goes to the caller, the slot goes back first, or `in_flight` such failures
+                # would block every later job.  Waves already launched finish on their own and release theirs (_release)
+                if held[0] is not None:
+                    self._rings.put(held[0])
+                    held[0] = None
             while True:
                 drain_retries()
                 with job.cond:
@@ -484,3 +493,193 @@ class PagePipeline:
             self._render_q.put(_STOP)
             self._render_thread.join(timeout=10)
             self._render_thread = None
+
+
+def _chain_priorities():
+    spec = os.environ.get("YMK_CHAIN_PRIORITY", "")  # e.g. "layout:-1,ocr:0" (measurement knob)
+    out = {}
+    for item in filter(None, spec.split(",")):
+        name, _, value = item.partition(":")
+        out[name.strip()] = int(value)
+    return out
+
+
+class StageAnalyzer:
+    """What `PagePipeline` asks of its analyzer, and the part of it that DocumentAnalyzer and TableSemanticParser share.  The
+    pipeline is duck-typed (the tests drive it with stubs); a real analyzer derives from this class and adds its table chain.
+
+    Attributes the pipeline reads: `text_detector.device`, `text_recognizer` (its `rec_orientation_fallback` forces one
+    recogniser lane) and `split_text_across_cells` (True: `boxes` waits for the wave's `cells`, then calls `_stage_split(wave)`).
+
+    Stage methods, each called with the `Wave` by the stage's one thread (GPU: on that thread's HIP stream, after the wave's
+    upload; the stream is waited for before the wave moves on):
+
+        stage      launches  reads                                  writes              defined
+        detect     GPU       pages, ring                            maps                here
+        boxes      host      maps, sizes                            dets                here
+        crops      GPU       pages, dets                            rec_plan            here
+        recognize  GPU       rec_plan; called (wave, lane)          rec_plan            here
+        decode     host      rec_plan                               recs, rec_plan=None here
+        layout     GPU       pages                                  lay_raw             subclass
+        tables     GPU       pages, lay_raw, ids (hand-over)        lay_parsed, tab_raw subclass
+        cells      host      tab_raw, lay_parsed                    lays                subclass
+
+    `_stage_finish(wave, k)` (host, subclass) returns page k's schema from dets / recs / lay_parsed / lays / imgs and the job
+    (`wave.job.options`, `wave.job.overlays`); `_stage_render(wave, results)` (GPU, here; overlays jobs only) returns per page
+    the two pictures, from `_page_drawings(wave, k, results)` (subclass) and `wave.pages`.  `_nets()` (subclass): the modules
+    whose `model.close()` releases the analyzer's device memory.
+
+    `handover`: None, or an object that sees - and may replace - what one stage hands to the next, AFTER the stage has
+    produced it at full cost (`_handed`; yomitoku_amd.testing.Handover): measurements and tests with seeded weights, whose
+    detections are noise.  A hook the object lacks - or a data attribute of that name - passes the value through."""
+
+    split_text_across_cells = False
+
+    def _init_chains(self):
+        """The constructors' shared part: the two chains of a page or wave (OCR; layout / tables) run on one thread and HIP
+        stream each; `concurrent_chains` False runs them one after the other on the caller's thread and stream (profiling: a
+        kernel's timing then brackets that kernel alone; same results)."""
+        self._pool = ThreadPoolExecutor(max_workers=2)
+        self._streams = {}
+        self.concurrent_chains = True
+        # HIP stream priority per chain (0 = default, -1 = high).  Measured on the analyzer bench: raising either chain
+        # LOWERS the throughput (66.9 -> 62.3 layout high, 64.2 ocr high), so the default is no priority
+        self.chain_priority = _chain_priorities()
+        self.handover = None
+        self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
+        self._pipeline = None
+
+    # ---- the two concurrent chains, each on its own HIP stream
+    def _submit(self, name, fn, *args):
+        """A chain as a future: on its own thread + HIP stream, or - concurrent_chains False - run right here."""
+        if self.concurrent_chains:
+            return self._pool.submit(self._on_stream, name, fn, *args)
+        f = Future()
+        try:
+            f.set_result(fn(*args))
+        except BaseException as exc:  # noqa: BLE001 - delivered by f.result(), like a pool future
+            f.set_exception(exc)
+        return f
+
+    def _on_stream(self, name, fn, *args):
+        dev = self.text_detector.device
+        stream = self._streams.get(name)
+        if stream is None:
+            stream = self._streams[name] = torch.cuda.Stream(device=dev, priority=self.chain_priority.get(name, 0))
+        stream.wait_stream(torch.cuda.default_stream(dev))  # the page upload was issued there
+        with torch.cuda.stream(stream):
+            out = fn(*args)
+            stream.synchronize()
+        return out
+
+    def _handed(self, what, wave, value):
+        fn = getattr(self.handover, what, None)  # a hook is a method: an attribute of that name that holds data is none
+        return fn(wave, value) if callable(fn) else value
+
+    # ---- the OCR chain
+    def _stage_detect(self, wave):
+        """DBNet forwards over same-size pages of the wave; the maps come back into the wave slot's pinned buffers."""
+        wave.maps = self._handed("maps", wave, self.text_detector.forward_pages(wave.pages, ring=wave.ring))
+
+    def _stage_boxes(self, wave):
+        """DB box extraction (C++, GIL released), the pages of the wave concurrently."""
+        wave.dets = self._handed("boxes", wave, self.text_detector.extract_boxes(wave.maps, wave.sizes))
+
+    def _stage_crops(self, wave):
+        """Per-page mini-batches (bucketing, width budget) and the crop kernels that build their tensors."""
+        wave.rec_plan = self.text_recognizer.plan_pages(wave.pages, [d.points for d in wave.dets])
+
+    def _stage_recognize(self, wave, lane=0):
+        """One grouped PARSeq forward over the mini-batches of all pages of the wave, on the recogniser handle of `lane`
+        (serve keeps two forwards in flight: TextRecognizer.replica_model); with `rec_orientation_fallback` the decode
+        happens here too, because the retry runs further forwards."""
+        self.text_recognizer.forward_plan(wave.rec_plan, self.text_recognizer.replica_model(lane))
+        if self.text_recognizer.rec_orientation_fallback:
+            self._stage_decode(wave)
+
+    def _stage_decode(self, wave):
+        """Token decode and un-permutation on the host."""
+        if wave.recs is None:
+            wave.recs = self.text_recognizer.finish_plan(wave.rec_plan)
+            wave.rec_plan = None
+
+    def _stage_render(self, wave, results, pinned=None):
+        """Overlays: per page of the wave its two pictures as owned host arrays, in the order `_page_drawings` records them;
+        an exception for a page whose drawing raised, None for a page that had already failed.  All canvases of the wave are
+        drawn by the wave renderer (utils/visualizer.py: render_wave) on the calling thread's stream and come back through
+        `pinned` - by default the wave slot's pinned buffer."""
+        from .utils.visualizer import render_wave
+
+        out = [None] * len(wave)
+        live, drawings = [], []
+        for k in range(len(wave)):
+            if isinstance(results[k], BaseException):
+                continue
+            try:
+                drawings.extend(self._page_drawings(wave, k, results[k]))
+                live.append(k)
+            except Exception as exc:  # noqa: BLE001 - only this page fails
+                out[k] = exc
+        wave.dags = None
+        if live:
+            if pinned is None:
+                pinned = self._render_pinned.setdefault(wave.ring, [None])
+            images = render_wave([wave.pages[k] for k in live for _ in range(2)], drawings, pinned)
+            for j, k in enumerate(live):
+                out[k] = (images[2 * j], images[2 * j + 1])
+        return out
+
+    # ---- one wave at a time (`analyze_pages`, `parse_pages`): the same stage methods as two concurrent chains
+    def _recognize_wave(self, wave):
+        self._stage_crops(wave)
+        self._stage_recognize(wave)
+        self._stage_decode(wave)
+
+    def _layout_wave(self, wave):
+        self._stage_layout(wave)
+        self._stage_tables(wave)
+        self._stage_cells(wave)
+
+    def _ocr_wave(self, wave):
+        self._stage_detect(wave)
+        self._stage_boxes(wave)
+        if not self.split_text_across_cells:
+            self._recognize_wave(wave)
+
+    def _run_wave(self, imgs, start, job=None):
+        """`imgs` (pages `start`... of a call) uploaded and through every stage before `finish`: the finished Wave."""
+        dev = self.text_detector.device
+        pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, dev) for img in imgs]
+        wave = Wave(ids=range(start, start + len(imgs)), imgs=imgs, pages=pages, job=job)
+        f_ocr = self._submit("ocr", self._ocr_wave, wave)
+        f_lay = self._submit("layout", self._layout_wave, wave)
+        f_ocr.result()
+        f_lay.result()
+        if self.split_text_across_cells:
+            self._stage_split(wave)
+            self._submit("ocr", self._recognize_wave, wave).result()
+        return wave
+
+    # ---- the pipeline of this analyzer
+    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None):
+        """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
+        pipe = self._pipeline
+        if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
+            if pipe is not None:
+                pipe.close()
+            pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
+        pipe.defer_full_gc = bool(defer_full_gc)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options)
+
+    def close(self, release_models: bool = True):
+        """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -
+        the device memory of the four nets (weights and the reserved workspaces: tens of GB per analyzer).  The analyzer stays
+        usable: a net rebuilds its handle from the state dict it holds the next time it is called."""
+        if self._pipeline is not None:
+            self._pipeline.close()
+            self._pipeline = None
+        self._render_pinned.clear()
+        self.text_recognizer.close_replicas()
+        if release_models:
+            for module in self._nets():
+                module.model.close()

@@ -30,19 +30,20 @@ Not restated: the helpers of the reference's module that nothing on its call pat
 
 from __future__ import annotations
 
-from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import imaging
-from .document_analyzer import _USAGE, DocumentAnalyzer, _chain_priorities, ocr_aggregate
+from .document_analyzer import _USAGE, ocr_aggregate
 from .geometry import is_contained, quad_to_xyxy
 from .grid_parser import parse_grid_from_bottom_up
 from .kv_parser import parse_kv_items
 from .layout_parser import LayoutParser
 from .reading_order import prediction_reading_order
 from .schemas import Element, OCRSchema, ParagraphSchema
+from .serving import StageAnalyzer
 from .table_cell_detector import CellDetector
 from .table_semantic_schemas import TableSemanticContentsSchema, TableSemanticParserSchema
 from .text_detector import TextDetector
@@ -226,10 +227,9 @@ def _owned_host_image(canvas):
     return out
 
 
-class TableSemanticParser:
+class TableSemanticParser(StageAnalyzer):
     merge_same_column_values = False  # True: grid columns under the same innermost header cell become one column
     visualize = False
-    split_text_across_cells = False  # the page pipeline asks its analyzer (serving.py); the reference's parser has no such option
 
     def __init__(self, configs={}, device="cuda", visualize=False, workspace_reuse=False):
         if not isinstance(configs, dict):
@@ -244,19 +244,12 @@ class TableSemanticParser:
         self.text_recognizer = TextRecognizer(**kwargs["text_recognizer"])
         self.visualize = visualize
         self.merge_same_column_values = False
-        # the two chains, as in DocumentAnalyzer: one thread and HIP stream each; False runs them one after the other on the
-        # caller's thread and stream (same results)
-        self._pool = ThreadPoolExecutor(max_workers=2)
-        self._streams = {}
-        self.concurrent_chains = True
-        self.chain_priority = _chain_priorities()
         # `handover`: None, or an object whose `tables(page index, [Element])` sees - and may replace - the table boxes that the
         # table detector hands to the cell detector (measurements and tests with seeded weights, whose detections are noise)
-        self.handover = None
-        self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
+        self._init_chains()
 
-    _submit = DocumentAnalyzer._submit        # needs _pool, _streams, concurrent_chains, chain_priority, text_detector.device
-    _on_stream = DocumentAnalyzer._on_stream
+    def _nets(self):
+        return self.text_detector, self.text_recognizer, self.layout_parser, self.cell_detector
 
     # ---- words into cells
     def aggregate(self, ocr_res, cells, overlap_th=0.2):
@@ -417,64 +410,35 @@ class TableSemanticParser:
             return results, _owned_host_image(vis_layout), _owned_host_image(vis_ocr)
 
     # ---- several pages per call
-    def _ocr_pages(self, pages):
-        dets = self.text_detector.detect_pages(pages)
-        return dets, self.text_recognizer.recognize_pages(pages, [d.points for d in dets])
-
-    def _tables_and_cells_pages(self, pages):
-        layouts = self.layout_parser.parse_pages(pages)
-        tables = [self._handed_tables(k, list(l.tables)) for k, l in enumerate(layouts)]
-        return layouts, self.cell_detector.detect_pages(pages, tables)
-
     def parse_pages(self, imgs, wave: int = 8, template=None, grid_only=False, kv_only=False, overlays=False):
-        """`__call__` over a list of pages, `wave` pages at a time on the device: DBNet and the table detector run over the
-        pages of a wave, PARSeq over the lines of all its pages, the cell detector over the tables of all its pages in chunks of
+        """`__call__` over a list of pages, `wave` pages at a time on the device, through the stage methods `serve` runs (the two
+        chains of a wave side by side, then `finish` per page): DBNet and the table detector run over the pages of a wave,
+        PARSeq over the lines of all its pages, the cell detector over the tables of all its pages in chunks of
         CellDetector.MAX_TABLES_PER_FORWARD.  Pages never interact, so every page's result is what `__call__` returns for it.
+        `handover.tables(k, ...)` sees a page under its index in `imgs`, as in `serve` (not its index in the wave).
         Returns [TableSemanticParserSchema], in page order; with `overlays=True` [(TableSemanticParserSchema, layout picture,
         OCR picture)]: all canvases of a wave, two per page, are drawn by the wave renderer (utils/visualizer.py: render_wave)."""
         if self.visualize:
             raise NotImplementedError(_NO_VIS)
-        from .utils.visualizer import RunOverlay, render_wave
-
+        job = SimpleNamespace(options={"template": template, "grid_only": grid_only, "kv_only": kv_only}, overlays=bool(overlays))
         out = []
         size = max(1, int(wave))
         pinned = [None]  # the pinned buffer the canvases come back through: this call's, reused by its waves
         for start in range(0, len(imgs), size):
-            dev = self.text_detector.device
-            pages = [img if isinstance(img, torch.Tensor) else imaging.page_to_device(img, dev) for img in imgs[start : start + size]]
-            f_ocr = self._submit("ocr", self._ocr_pages, pages)
-            f_tab = self._submit("layout", self._tables_and_cells_pages, pages)
-            dets, recs = f_ocr.result()
-            layouts, tables = f_tab.result()
-            drawings = []
-            for det, rec, layout, page_tables in zip(dets, recs, layouts, tables):
-                dags = [] if overlays else None
-                out.append(self.semantic_stage(*self._hand_over(det, rec, layout, page_tables), template, grid_only, kv_only, dags=dags))
-                if overlays:
-                    drawings.extend(self._drawings(out[-1], dags, RunOverlay))
+            w = self._run_wave(imgs[start : start + size], start, job)
+            results = [self._stage_finish(w, k) for k in range(len(w))]
             if overlays:
-                with torch.cuda.device(pages[0].device):
-                    images = render_wave([p for p in pages for _ in range(2)], drawings, pinned)
-                for k in range(len(pages)):
-                    out[start + k] = (out[start + k], images[2 * k], images[2 * k + 1])
+                with torch.cuda.device(w.pages[0].device):
+                    images = self._stage_render(w, results, pinned)
+                for k, pictures in enumerate(images):
+                    if isinstance(pictures, BaseException):
+                        raise pictures
+                    results[k] = (results[k],) + pictures
+            out.extend(results)
         return out
 
-    # ---- the stage protocol of the page pipeline (yomitoku_amd/serving.py: one thread per stage, HIP stream for those that
-    # launch).  The OCR chain is DocumentAnalyzer's on this parser's detector and recogniser (the three stages that touch
-    # nothing else are borrowed; detect and boxes are restated without the analyzer's hand-over hooks, which the parser does
-    # not have); the table chain ends in the cell detector's two halves; `finish` is what `__call__` does after the networks.
-    def _stage_detect(self, wave):
-        """DBNet forwards over same-size pages of the wave; the maps come back into the wave slot's pinned buffers."""
-        wave.maps = self.text_detector.forward_pages(wave.pages, ring=wave.ring)
-
-    def _stage_boxes(self, wave):
-        """DB box extraction (C++, GIL released), the pages of the wave concurrently."""
-        wave.dets = self.text_detector.extract_boxes(wave.maps, wave.sizes)
-
-    _stage_crops = DocumentAnalyzer._stage_crops          # needs text_recognizer
-    _stage_recognize = DocumentAnalyzer._stage_recognize  # (wave, lane): the recogniser handle of the lane
-    _stage_decode = DocumentAnalyzer._stage_decode
-
+    # ---- the stage protocol of the page pipeline (serving.py: StageAnalyzer, which holds the OCR chain).  The table chain
+    # ends in the cell detector's two halves; `finish` is what `__call__` does after the networks.
     def _stage_layout(self, wave):
         """One RT-DETRv2 table-detector forward over the pages (device half)."""
         wave.lay_raw = self.layout_parser.forward_pages(wave.pages)
@@ -506,30 +470,12 @@ class TableSemanticParser:
             wave.dags[k] = dags
         return results
 
-    def _stage_render(self, wave, results):
-        """serve(overlays=True): per page of the wave (layout picture, OCR picture) as owned host arrays - the order `__call__`
-        returns them in -, an exception for a page whose drawing raised, None for a page that had already failed.  All
-        canvases of the wave are drawn by the wave renderer on the calling thread's stream and come back through the wave
-        slot's pinned buffer."""
-        from .utils.visualizer import RunOverlay, render_wave
+    def _page_drawings(self, wave, k, results):
+        """(layout drawing, ocr drawing) of page k - the order `__call__` returns the pictures in -, from the grid graphs that
+        `finish` kept on the wave."""
+        from .utils.visualizer import RunOverlay
 
-        out = [None] * len(wave)
-        live, drawings = [], []
-        for k in range(len(wave)):
-            if isinstance(results[k], BaseException):
-                continue
-            try:
-                drawings.extend(self._drawings(results[k], wave.dags[k], RunOverlay))
-                live.append(k)
-            except Exception as exc:  # noqa: BLE001 - only this page fails
-                out[k] = exc
-        wave.dags = None
-        if live:
-            pinned = self._render_pinned.setdefault(wave.ring, [None])
-            images = render_wave([wave.pages[k] for k in live for _ in range(2)], drawings, pinned)
-            for j, k in enumerate(live):
-                out[k] = (images[2 * j], images[2 * j + 1])
-        return out
+        return self._drawings(results, wave.dags[k], RunOverlay)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, template=None, grid_only=False, kv_only=False):
@@ -544,28 +490,7 @@ class TableSemanticParser:
         H x W x 3 arrays the caller owns, drawn by the pipeline's render stage; a failed page's entry stays the exception.
         `template`, `grid_only`, `kv_only`, `overlays` are properties of the JOB: they travel with it and the next job starts
         without them.  `defer_full_gc`, `rec_lanes`: see `DocumentAnalyzer.serve`."""
-        from .serving import PagePipeline
-
         if self.visualize:
             raise NotImplementedError(_NO_VIS)
-        pipe = getattr(self, "_pipeline", None)
-        if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
-            if pipe is not None:
-                pipe.close()
-            pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
-            pipe.rec_lanes_asked = int(rec_lanes)
-        pipe.defer_full_gc = bool(defer_full_gc)
         options = {"template": template, "grid_only": bool(grid_only), "kv_only": bool(kv_only)}
-        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options)
-
-    def close(self):
-        """Stop the pipeline threads, drop the render buffers and release the device memory of the four nets (a net rebuilds
-        its handle when it is called again)."""
-        pipe = getattr(self, "_pipeline", None)
-        if pipe is not None:
-            pipe.close()
-            self._pipeline = None
-        self._render_pinned.clear()
-        self.text_recognizer.close_replicas()
-        for module in (self.text_detector, self.text_recognizer, self.layout_parser, self.cell_detector):
-            module.model.close()
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options)
