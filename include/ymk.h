@@ -254,6 +254,56 @@ int ymk_draw_overlay_pages(unsigned char* canvases_dev, int64_t canvas_bytes, co
                            const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream);
 int ymk_overlay_cull_pass(void);
 
+/* ---- baseline JPEG encoder for a wave of pages (yomitoku_amd/csrc/ymk_jpeg.hip; DocumentAnalyzer.serve(jpeg=...) and
+ * yomitoku_amd/jpeg.py).  DESIGN.md, "JPEG encoder", has the file format and the pixel rules; every stage is integer arithmetic
+ * and equals tests/jpeg_ref.py byte for byte.  Pages: uint8 [h][w][3] (B G R; 4:2:0, MCU 16 x 16, six blocks Y0 Y1 Y2 Y3 Cb Cr)
+ * or uint8 [h][w] (one component, MCU 8 x 8), rows contiguous, 1 <= h, w <= 16383; a restart interval is one MCU row.
+ * Page table: blob_dev, int32 words on the device (16-byte aligned), blob_words of them: n_pages records of
+ *   YMK_JPEG_PAGE_WORDS words, then whatever the records point to.
+ *     words 0-1   page address, low / high          words 2-4   h, w, channels (1 | 3)
+ *     words 5-7   first MCU, first block, first restart interval of the page (the pages' are numbered one after the other)
+ *     words 8-9   byte offset of the page's file in out_dev, low / high           word 10  capacity of that file in bytes
+ *     word 11-12  BYTE offset in the blob and length of the file's header (ymk_jpeg_header)
+ *     word 13     WORD offset in the blob of the page's 128 quantisation values (ymk_jpeg_quant_tables)      words 14-15  0
+ *   A record that does not fit (sizes, indices beyond the totals passed, offsets beyond the blob or out_bytes) is ignored, never
+ *   trusted: its page gets length -1.
+ * Scratch and output are the caller's; ymk_jpeg_scratch_bytes sizes them from HOST arrays h, w, channels: sizes6_out = total
+ *   MCUs, blocks, intervals, then the bytes of coef_dev (int16 [blocks][64], 16-byte aligned), of stream_dev (the unstuffed scan:
+ *   YMK_JPEG_BLOCK_STREAM_BYTES per block - a block's worst case - big-endian 32-bit words, an interval's words starting at
+ *   its first block's) and of intervals_dev (int32 [intervals][2] = bytes, bytes after FF -> FF 00).
+ * ymk_jpeg_quant_tables: the 64 luminance, then the 64 chrominance values for `quality` (1..100, IJG rule), zig-zag order; HOST.
+ * ymk_jpeg_header: SOI, APP0, DQT, SOF0, DHT, DRI, SOS of such a file into the HOST buffer `out`; returns its length, -1 on error.
+ * ymk_jpeg_coefficients: pages -> coef_dev, zig-zag, scan order; one wave per MCU.
+ * ymk_jpeg_entropy: coef_dev -> stream_dev + intervals_dev; one wave per interval (bit lengths, wave prefix sum, Huffman bits, pad).
+ * ymk_jpeg_compact: lengths_dev int32 [n_pages]: header + stuffed intervals + RSTm + EOI laid out at the page's offset and the
+ *   file's length - or -1, and NOT ONE BYTE of the page's output written, when the file would exceed the page's capacity.
+ * ymk_jpeg_encode_pages: the three stages in order on `stream`.  Nothing is allocated, nothing waited for. */
+#define YMK_JPEG_PAGE_WORDS 16
+#define YMK_JPEG_BLOCK_STREAM_BYTES 208
+int ymk_jpeg_page_words(void);
+int ymk_jpeg_quant_tables(int quality, int* zigzag128_out);
+int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out, int capacity);
+int ymk_jpeg_scratch_bytes(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes6_out);
+int ymk_jpeg_coefficients(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int16_t* coef_dev,
+                          int64_t total_blocks, void* stream);
+int ymk_jpeg_entropy(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
+                     uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, int64_t total_intervals, void* stream);
+int ymk_jpeg_compact(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* stream_dev, int64_t stream_bytes,
+                     int64_t total_blocks, const int* intervals_dev, int64_t total_intervals, unsigned char* out_dev, int64_t out_bytes,
+                     int* lengths_dev, void* stream);
+int ymk_jpeg_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
+                          int64_t total_intervals, int16_t* coef_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
+                          unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream);
+/* ymk_pil_resize_u8: Pillow's two-pass 8-bit resample (as ymk_pil_resize_to_chw: 22-bit coefficients, 1 << 21 bias, clip to
+ *   uint8 between the passes) for n images in one launch, written as uint8 [oh][ow][C] in the source's channel order.  blob_dev:
+ *   n records of YMK_PIL_RESIZE_U8_WORDS int32 words {source address low, high; H; W; C (1 | 3); oh; ow; ksize_x; ksize_y; word
+ *   offsets in the blob of xbounds [ow][2], xcoefs [ow][ksize_x], ybounds, ycoefs; destination address low, high; 0}, then the
+ *   tables.  A pixel whose taps leave the source, or whose tables leave the blob, is not written.  max_oh, max_ow: the largest
+ *   output of the launch. */
+#define YMK_PIL_RESIZE_U8_WORDS 16
+int ymk_pil_resize_u8_record_words(void);
+int ymk_pil_resize_u8(const int* blob_dev, int64_t blob_words, int n, int max_oh, int max_ow, void* stream);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

@@ -1,0 +1,282 @@
+"""Host checks of the JPEG path (no GPU): the definition tests/jpeg_ref.py against Pillow, the Lanczos coefficient tables, the
+PDF writer's handling of finished JPEG files, and the `jpeg=` argument's validation.
+
+The device encoder (tests/test_jpeg_gpu.py) must equal the definition byte for byte, so what is shown here of the definition's
+files - they open, carry libjpeg's tables, and lose no quality against libjpeg's own - holds for the device's files."""
+import io
+import os
+import re
+import zlib
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+from PIL import Image
+
+from tests import jpeg_ref
+from yomitoku_amd import imaging
+from yomitoku_amd.utils.searchable_pdf import searchable_pdf_bytes
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def synthetic_page(h, w, seed=0, grey=False):
+    """A smooth background, a few dark bars like text lines, and mild seeded noise: B G R (or grey) uint8."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    base = 200 + 40 * np.sin(xx / 37.0) * np.cos(yy / 53.0)
+    base[(yy % 24 < 6) & (xx % 97 < 60)] = 40
+    planes = [np.clip(base * f + rng.normal(0, 3, (h, w)), 0, 255).astype(np.uint8) for f in ((1.0,) if grey else (0.9, 1.0, 0.95))]
+    return planes[0] if grey else np.stack(planes, -1)
+
+
+def pillow_jpeg(page, quality, **kwargs):
+    image = Image.fromarray(page if page.ndim == 2 else np.ascontiguousarray(page[:, :, ::-1]))
+    out = io.BytesIO()
+    image.save(out, "JPEG", quality=quality, **kwargs)
+    return out.getvalue()
+
+
+def decoded(data):
+    image = Image.open(io.BytesIO(data))
+    image.load()
+    arr = np.asarray(image)
+    return image, (arr if arr.ndim == 2 else arr[:, :, ::-1])
+
+
+def psnr(a, b):
+    mse = np.mean((a.astype(np.float64) - b.astype(np.float64)) ** 2)
+    return 10 * np.log10(255.0 ** 2 / mse)
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 3), (16, 16, 3), (17, 33, 3), (40, 200, 3), (9, 23), (48, 160, 3)])
+def test_the_definitions_files_open_in_pillow_with_the_right_size_and_mode(shape):
+    page = synthetic_page(shape[0], shape[1], seed=3, grey=len(shape) == 2)
+    image, _ = decoded(jpeg_ref.encode(page, 85))
+    assert image.size == (shape[1], shape[0]) and image.mode == ("L" if len(shape) == 2 else "RGB") and image.format == "JPEG"
+
+
+@pytest.mark.parametrize("quality", [60, 80, 85])
+def test_quantisation_tables_are_libjpegs(quality):
+    page = synthetic_page(32, 48, seed=1)
+    mine = Image.open(io.BytesIO(jpeg_ref.encode(page, quality)))
+    theirs = Image.open(io.BytesIO(pillow_jpeg(page, quality)))
+    assert {k: list(v) for k, v in mine.quantization.items()} == {k: list(v) for k, v in theirs.quantization.items()}
+    grey = synthetic_page(32, 48, seed=1, grey=True)
+    assert ({k: list(v) for k, v in Image.open(io.BytesIO(jpeg_ref.encode(grey, quality))).quantization.items()} ==
+            {k: list(v) for k, v in Image.open(io.BytesIO(pillow_jpeg(grey, quality))).quantization.items()})
+
+
+def test_decoded_quality_is_that_of_pillows_own_420_save(capsys):
+    """PSNR of the decoded file against the source, next to Pillow's own 4:2:0 save at the same quality.
+
+    The definition follows libjpeg's rules (colour tables, alternating-bias 2 x 2 chroma mean, `islow` DCT, rounded
+    division), and where every component has an even number of blocks in both directions the FILE equals Pillow's
+    `save(quality=q, restart_marker_rows=1)` byte for byte - measured on a CPU with Pillow 12.2 (libjpeg-turbo): equal at
+    32 x 48, 48 x 160, 1200 x 1600 and every grey size tried, different only in the blocks libjpeg fills with a neighbour's DC
+    instead of replicated pixels (17 x 33, 120 x 160 noise).  Measured PSNR differences (definition minus Pillow) on the two
+    pages below at qualities 60 / 80 / 85: 0.000 dB each (golden crop 47.085 dB at 85; synthetic 35.218 / 36.871 / 37.179 dB) -
+    the golden crop's margins are flat, so even its odd block row and column come out byte-equal.  The allowed shortfall is
+    0.1 dB: what a page with busy edges may lose in its replicated blocks stays below that, while a wrong rounding rule costs
+    more (a truncating quantiser loses over 1 dB)."""
+    golden = np.asarray(Image.open(os.path.join(ROOT, "tests", "golden", "test_page.jpg")).convert("RGB"))[:, :, ::-1]
+    golden = np.ascontiguousarray(golden[: min(golden.shape[0], 600), : min(golden.shape[1], 800)])
+    equal = []
+    for name, page in (("golden", golden), ("synthetic", synthetic_page(240, 320, seed=7))):
+        for quality in (60, 80, 85):
+            mine = jpeg_ref.encode(page, quality)
+            theirs = pillow_jpeg(page, quality, subsampling="4:2:0")
+            a, b = psnr(decoded(mine)[1], page), psnr(decoded(theirs)[1], page)
+            equal.append(mine == pillow_jpeg(page, quality, restart_marker_rows=1))
+            with capsys.disabled():
+                print(f"\n{name} {page.shape[1]}x{page.shape[0]} q{quality}: definition {a:.3f} dB, Pillow {b:.3f} dB, "
+                      f"{len(mine)} / {len(theirs)} bytes, byte-equal to Pillow with restart rows: {equal[-1]}")
+            assert a >= b - 0.1, (name, quality, a, b)
+
+
+def test_the_file_equals_pillows_where_block_counts_are_even():
+    """Reported, and held here for the sizes the serving path meets most (both sides multiples of 16): the definition's file IS
+    Pillow's `save(quality=q, restart_marker_rows=1)`."""
+    for shape, quality in (((32, 48, 3), 85), ((48, 160, 3), 60), ((40, 24), 80)):
+        page = synthetic_page(shape[0], shape[1], seed=5, grey=len(shape) == 2)
+        assert jpeg_ref.encode(page, quality) == pillow_jpeg(page, quality, restart_marker_rows=1), shape
+
+
+def test_huffman_tables_are_annex_k_as_pillow_writes_them():
+    """The DHT segments of the definition's header are those of a Pillow file (libjpeg's standard tables)."""
+    page = synthetic_page(16, 16)
+    tables = []
+    for data in (jpeg_ref.encode(page, 85), pillow_jpeg(page, 85)):
+        head, found = data[: data.index(b"\xff\xda")], []
+        for m in re.finditer(rb"\xff\xc4", head):
+            n = int.from_bytes(head[m.start() + 2 : m.start() + 4], "big")
+            found.append(head[m.start() + 4 : m.start() + 2 + n])
+        tables.append(b"".join(found))
+    assert tables[0] == tables[1] and len(tables[0]) == 4 * 17 + 12 + 12 + 162 + 162
+
+
+def _lanczos_resize(img, ow, oh):
+    """Pillow's two 8-bit passes with the tables of imaging.pil_lanczos_coeffs, in NumPy."""
+    h, w = img.shape[:2]
+    xb, xk, _ = imaging.pil_lanczos_coeffs(w, ow)
+    yb, yk, _ = imaging.pil_lanczos_coeffs(h, oh)
+    a = img.reshape(h, w, -1).astype(np.int64)
+    tmp = np.zeros((h, ow, a.shape[2]), np.int64)
+    for x in range(ow):
+        m, n = xb[x]
+        tmp[:, x] = np.clip(((a[:, m : m + n] * xk[x, :n, None].astype(np.int64)).sum(1) + (1 << 21)) >> 22, 0, 255)
+    out = np.zeros((oh, ow, a.shape[2]), np.int64)
+    for y in range(oh):
+        m, n = yb[y]
+        out[y] = np.clip(((tmp[m : m + n] * yk[y, :n, None, None].astype(np.int64)).sum(0) + (1 << 21)) >> 22, 0, 255)
+    return out.astype(np.uint8).reshape((oh, ow) + img.shape[2:])
+
+
+@pytest.mark.parametrize("size", [(150, 195), (77, 100), (120, 156), (200, 260)])
+def test_lanczos_tables_reproduce_pillows_resize_bit_for_bit(size):
+    img = np.random.default_rng(11).integers(0, 256, (208, 160, 3), dtype=np.uint8)
+    want = np.asarray(Image.fromarray(img).resize(size, Image.LANCZOS))
+    assert np.array_equal(_lanczos_resize(img, *size), want)
+
+
+# ------------------------------------------------------------------------------------------------ the PDF writer
+def _doc():
+    from yomitoku_amd.schemas import DocumentAnalyzerSchema, ParagraphSchema, WordPrediction
+
+    word = WordPrediction(points=[[100, 40], [300, 40], [300, 80], [100, 80]], content="invoice", direction="horizontal", rec_score=0.9,
+                          det_score=0.9)
+    para = ParagraphSchema(box=[90, 30, 310, 90], contents="invoice", direction="horizontal", order=0, role=None)
+    return DocumentAnalyzerSchema(paragraphs=[para], tables=[], figures=[], words=[word])
+
+
+def _objects(pdf):
+    return re.findall(rb"\d+ 0 obj\n(.*?)\nendobj", pdf, re.S)
+
+
+def _image_streams(pdf):
+    out = []
+    for body in _objects(pdf):
+        m = re.match(rb"<< /Type /XObject /Subtype /Image /Width (\d+) /Height (\d+) /ColorSpace /(\w+) .*? /Length (\d+) >>\nstream\n", body, re.S)
+        if m:
+            out.append((int(m.group(1)), int(m.group(2)), m.group(3).decode(), body[m.end() : m.end() + int(m.group(4))]))
+    return out
+
+
+def _text_matrices(pdf):
+    out = []
+    for body in _objects(pdf):
+        m = re.match(rb"<<\s+/Filter /FlateDecode /Length (\d+) >>\nstream\n", body)
+        if m:
+            text = zlib.decompress(body[m.end() : m.end() + int(m.group(1))])
+            out += [tuple(float(v) for v in t.split()[:6]) for t in re.findall(rb"([-\d. ]+) Tm", text)]
+    return out
+
+
+def test_pdf_embeds_an_encoded_jpeg_as_it_is():
+    doc = _doc()
+    page = synthetic_page(120, 400, seed=2)
+    colour = SimpleNamespace(data=b"\xff\xd8 not even a jpeg \xff\xd9", width=150, height=45, grey=False, scale=0.375)
+    grey = SimpleNamespace(data=jpeg_ref.encode(synthetic_page(120, 400, grey=True), 85), width=400, height=120, grey=True, scale=1.0)
+    pdf = searchable_pdf_bytes([colour, grey], [doc, doc], image_quality="low")
+    streams = _image_streams(pdf)
+    assert [(s[0], s[1], s[2]) for s in streams] == [(150, 45, "DeviceRGB"), (400, 120, "DeviceGray")]
+    assert streams[0][3] == colour.data and streams[1][3] == grey.data
+    assert pdf.count(b"/MediaBox [0 0 150 45]") == 1 and pdf.count(b"/MediaBox [0 0 400 120]") == 1
+    half, full = _text_matrices(pdf)
+    # the word's x (100) scaled by the object's scale - 37.5, a fraction the schema's integer boxes could not hold - and truncated
+    assert half[4] == pytest.approx(37.0) and full[4] == pytest.approx(100.0)
+    # arrays behave as before, alone and next to an encoded entry
+    before = searchable_pdf_bytes([page], [doc], "high")
+    assert _image_streams(before)[0][3] == pillow_jpeg(page, 85)
+    mixed = searchable_pdf_bytes([page, grey], [doc, doc], "high")
+    assert [s[3] for s in _image_streams(mixed)] == [pillow_jpeg(page, 85), grey.data]
+    alone = searchable_pdf_bytes([page], [doc], "high")
+    assert alone == before
+
+
+def test_host_arrays_shrunk_by_a_fraction_keep_their_text_layer():
+    """The host path at a scale that leaves fractions (1600 wide, "low": 1500 / 1600): the writer used to raise here, because
+    the scaled boxes were assigned back into the schema, whose boxes are integers.  The image is Pillow's own shrunk file and
+    the word lands at its scaled, truncated place."""
+    page = synthetic_page(120, 1600, seed=6)
+    pdf = searchable_pdf_bytes([page], [_doc()], "low")
+    small = Image.fromarray(np.ascontiguousarray(page[:, :, ::-1])).resize((1500, 112), Image.LANCZOS)
+    data = io.BytesIO()
+    small.save(data, "JPEG", quality=60)
+    assert _image_streams(pdf) == [(1500, 112, "DeviceRGB", data.getvalue())]
+    (matrix,) = _text_matrices(pdf)
+    assert matrix[4] == pytest.approx(93.0)  # x1 = 100 * 0.9375 = 93.75, truncated as poly2rect does
+
+
+def test_the_real_encoded_jpeg_class_is_recognised_by_the_writer():
+    from yomitoku_amd.jpeg import EncodedJpeg
+    from yomitoku_amd.utils.searchable_pdf import _is_encoded
+
+    assert _is_encoded(EncodedJpeg(b"x", 1, 1, False, 1.0)) and EncodedJpeg(b"x", 1, 1, True).scale == 1.0
+    assert not _is_encoded(np.zeros((2, 2, 3), np.uint8)) and not _is_encoded(Image.new("RGB", (2, 2)))
+
+
+# ------------------------------------------------------------------------------------------------ the switch
+def test_an_unknown_preset_is_refused_before_a_page_is_read():
+    from yomitoku_amd.document_analyzer import DocumentAnalyzer
+    from yomitoku_amd.jpeg import encode_jpeg_pages
+    from yomitoku_amd.serving import PagePipeline
+
+    def sources():
+        raise AssertionError("a source was read")
+        yield
+
+    with pytest.raises(ValueError, match="nope"):
+        DocumentAnalyzer.serve(SimpleNamespace(visualize=False), sources(), jpeg="nope")
+    from tests.test_serving import StubAnalyzer
+
+    pipe = PagePipeline(StubAnalyzer(), wave=2, in_flight=1)
+    try:
+        with pytest.raises(ValueError, match="nope"):
+            pipe.serve(sources(), jpeg="nope")
+    finally:
+        pipe.close()
+    with pytest.raises(ValueError, match="nope"):
+        encode_jpeg_pages([np.zeros((8, 8, 3), np.uint8)], "nope")
+
+
+def test_sharded_serving_refuses_jpeg():
+    from yomitoku_amd.distributed import ShardedServer
+
+    server = ShardedServer.__new__(ShardedServer)  # no process group: the refusal comes before anything is served
+    with pytest.raises(NotImplementedError, match="jpeg"):
+        server.serve_local([np.zeros((8, 8, 3), np.uint8)], jpeg="high")
+
+
+def test_jpeg_jobs_visit_the_render_stage_and_plain_jobs_do_not():
+    """Stub stages on the host: (schema, file) pairs in page order, quads with overlays, a page failing in the encoder fails
+    alone, and a job without `jpeg` right after runs no render visit."""
+    from tests.test_serving import StubAnalyzer, page
+
+    class Stub(StubAnalyzer):
+        def _stage_render(self, wave, results):
+            return [None if isinstance(r, BaseException) else (np.zeros((1, 1, 3), np.uint8), np.ones((1, 1, 3), np.uint8)) for r in results]
+
+        def _stage_jpeg(self, wave, results):
+            assert wave.job.jpeg == "low"
+            return [None if isinstance(r, BaseException) else (ValueError("no room") if img[0, 1, 0] == 77 else (("file", wave.ids[k]),))
+                    for k, (r, img) in enumerate(zip(results, wave.imgs))]
+
+    from yomitoku_amd.serving import PagePipeline
+
+    pipe = PagePipeline(Stub(), wave=4, in_flight=2)
+    try:
+        pages = [page(i) for i in range(6)]
+        pages[3][0, 1, 0] = 77
+        pipe.trace = []
+        out = pipe.serve(pages, jpeg="low")
+        assert isinstance(out[3], ValueError)
+        assert [(o[0][0], o[1]) for i, o in enumerate(out) if i != 3] == [(i, ("file", i)) for i in range(6) if i != 3]
+        assert all(len(o) == 2 for i, o in enumerate(out) if i != 3) and "render" in {t[0] for t in pipe.trace}
+        both = pipe.serve([page(i) for i in range(3)], overlays=True, jpeg="low")
+        assert all(len(o) == 4 and o[3] == ("file", i) and isinstance(o[1], np.ndarray) for i, o in enumerate(both))
+        pipe.trace = []
+        plain = pipe.serve([page(i) for i in range(3)])
+        assert [o[0] for o in plain] == [0, 1, 2] and "render" not in {t[0] for t in pipe.trace}
+    finally:
+        pipe.close()

@@ -60,6 +60,18 @@ SIGNATURES = {
     "ymk_overlay_layout": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "ymk_draw_overlay_pages": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "ymk_overlay_cull_pass": (c_int, []),
+    "ymk_jpeg_page_words": (c_int, []),
+    "ymk_jpeg_quant_tables": (c_int, [c_int, POINTER(c_int)]),
+    "ymk_jpeg_header": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int]),
+    "ymk_jpeg_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_jpeg_coefficients": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    "ymk_jpeg_entropy": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "ymk_jpeg_compact": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                 c_void_p]),
+    "ymk_jpeg_encode_pages": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                      c_void_p, c_int64, c_void_p, c_void_p]),
+    "ymk_pil_resize_u8_record_words": (c_int, []),
+    "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (
         c_int,
         [c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,

@@ -1,0 +1,748 @@
+// Baseline JPEG encoder for a wave of pages resident in HBM (DocumentAnalyzer.serve(jpeg=...), yomitoku_amd/jpeg.py), and the
+// uint8 form of the Pillow resample that shrinks a page first.  DESIGN.md, "JPEG encoder", has the pixel rules and the format;
+// tests/jpeg_ref.py is the definition every stage equals byte for byte.  All arithmetic is integer.
+//
+//   k_jpeg_coefficients   one wave per MCU (16 x 16 pixels of a colour page, 8 x 8 of a grey one), four MCUs per block.  The MCU's
+//                         rows come in as 16-byte loads into LDS (an edge MCU, or a page whose rows are not 16-byte aligned: byte
+//                         loads with the coordinates clamped = edge replication), are converted to Y Cb Cr, the chroma averaged
+//                         2 x 2, and the six 8 x 8 blocks go through libjpeg's `islow` DCT - 8 lanes per block, one row, then one
+//                         column each - and the quantiser.  Output: zig-zag int16 [block][64] in scan order.
+//   k_jpeg_entropy        one wave per restart interval (= one MCU row).  64 blocks at a time: their coefficients staged in LDS,
+//                         each lane sizes ITS block (DC predictor = the previous block of the component, 0 at the start of the
+//                         interval), a wave prefix sum turns the sizes into bit positions, the words the chunk will touch are
+//                         zeroed, and each lane writes its block's codes.  A lane shares at most its first and its last 32-bit
+//                         word with a neighbour: those two go out with atomicOr, the words in between with plain stores.  Then
+//                         the pad bits, and a count of the FF bytes: the interval's record is (bytes, bytes after stuffing).
+//   k_jpeg_compact        one wave per interval again: the stuffed lengths of the page's intervals summed (the file's length, and
+//                         this interval's place in it), the header copied by interval 0, the interval copied with FF -> FF 00
+//                         (a count per lane and a wave prefix sum give every lane its place), RSTm or EOI behind it.  A file that
+//                         does not fit the page's capacity is not written at all; its length stays -1.
+//   k_pil_resize_u8       k_pil_resize_batch (ymk_image.hip) with uint8 [oh][ow][C] outputs of differing sizes.
+//
+// Nothing is allocated and nothing waited for; no workgroup waits for another (the three stages are three launches).
+#include "ymk_common.h"
+
+#include "../../include/ymk.h"
+
+namespace ymk {
+
+constexpr int JP_REC = YMK_JPEG_PAGE_WORDS;
+constexpr int JP_BLOCK_WORDS = YMK_JPEG_BLOCK_STREAM_BYTES / 4;  // 32-bit words of the unstuffed stream reserved per block
+constexpr int JP_WAVES = 4;                                      // MCUs per block of k_jpeg_coefficients
+static_assert(YMK_JPEG_BLOCK_STREAM_BYTES % 4 == 0 && YMK_JPEG_BLOCK_STREAM_BYTES * 8 >= 22 + 63 * 26,
+              "a block's worst case: a 11 + 11 bit DC and 63 AC symbols of 16 + 10 bits");
+
+// ------------------------------------------------------------------------------------------------ tables (Annex K)
+struct HuffSpec {
+  unsigned char bits[16];   // codes of each length 1..16
+  unsigned char vals[162];  // symbols in code order
+  int n;
+};
+constexpr HuffSpec DC_LUMA = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12};
+constexpr HuffSpec DC_CHROMA = {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12};
+constexpr HuffSpec AC_LUMA = {
+    {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    162};
+constexpr HuffSpec AC_CHROMA = {
+    {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    162};
+
+// symbol -> code | length << 16 (Annex C's canonical assignment); 0 for a symbol the table does not have
+struct HuffLut {
+  unsigned e[256];
+};
+constexpr HuffLut make_lut(const HuffSpec& s) {
+  HuffLut t{};
+  unsigned code = 0;
+  int k = 0;
+  for (int len = 1; len <= 16; ++len) {
+    for (int i = 0; i < s.bits[len - 1]; ++i) t.e[s.vals[k++]] = code++ | (unsigned)len << 16;
+    code <<= 1;
+  }
+  return t;
+}
+// [0] luminance, [1] chrominance; the twelve DC entries follow the 256 AC entries of a table
+struct HuffLuts {
+  unsigned e[2][256 + 16];
+};
+constexpr HuffLuts make_luts() {
+  HuffLuts t{};
+  const HuffLut ac0 = make_lut(AC_LUMA), ac1 = make_lut(AC_CHROMA), dc0 = make_lut(DC_LUMA), dc1 = make_lut(DC_CHROMA);
+  for (int i = 0; i < 256; ++i) t.e[0][i] = ac0.e[i], t.e[1][i] = ac1.e[i];
+  for (int i = 0; i < 16; ++i) t.e[0][256 + i] = dc0.e[i], t.e[1][256 + i] = dc1.e[i];
+  return t;
+}
+__constant__ HuffLuts c_luts = make_luts();
+
+constexpr unsigned char ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__constant__ unsigned char c_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+constexpr unsigned char LUMA_Q[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40, 57,
+                                      69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,
+                                      81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92,  95,  98,  112, 100, 103, 99};
+constexpr unsigned char CHROMA_Q[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                        99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                        99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+
+// the IJG quality rule; out: zig-zag order, luminance then chrominance
+static void quant_tables(int quality, int* out128) {
+  const int q = std::min(std::max(quality, 1), 100);
+  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+  for (int t = 0; t < 2; ++t)
+    for (int k = 0; k < 64; ++k) {
+      const int base = (t ? CHROMA_Q : LUMA_Q)[ZIGZAG[k]];
+      out128[t * 64 + k] = std::min(std::max((base * scale + 50) / 100, 1), 255);
+    }
+}
+
+static void put_segment(std::vector<unsigned char>& out, int marker, const std::vector<unsigned char>& payload) {
+  out.push_back(0xff);
+  out.push_back((unsigned char)marker);
+  out.push_back((unsigned char)((payload.size() + 2) >> 8));
+  out.push_back((unsigned char)((payload.size() + 2) & 255));
+  out.insert(out.end(), payload.begin(), payload.end());
+}
+
+// SOI, APP0, DQT, SOF0, DHT, DRI, SOS: everything before the scan's first byte
+static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quality) {
+  int q[128];
+  quant_tables(quality, q);
+  std::vector<unsigned char> out = {0xff, 0xd8};
+  put_segment(out, 0xe0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
+  for (int t = 0; t < (grey ? 1 : 2); ++t) {
+    std::vector<unsigned char> p = {(unsigned char)t};
+    for (int k = 0; k < 64; ++k) p.push_back((unsigned char)q[t * 64 + k]);
+    put_segment(out, 0xdb, p);
+  }
+  std::vector<unsigned char> sof = {8, (unsigned char)(h >> 8), (unsigned char)(h & 255), (unsigned char)(w >> 8), (unsigned char)(w & 255)};
+  if (grey) {
+    sof.insert(sof.end(), {1, 1, 0x11, 0});
+  } else {
+    sof.insert(sof.end(), {3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
+  }
+  put_segment(out, 0xc0, sof);
+  const HuffSpec* specs[4] = {&DC_LUMA, &AC_LUMA, &DC_CHROMA, &AC_CHROMA};
+  const unsigned char ids[4] = {0x00, 0x10, 0x01, 0x11};
+  for (int t = 0; t < (grey ? 2 : 4); ++t) {
+    std::vector<unsigned char> p = {ids[t]};
+    p.insert(p.end(), specs[t]->bits, specs[t]->bits + 16);
+    p.insert(p.end(), specs[t]->vals, specs[t]->vals + specs[t]->n);
+    put_segment(out, 0xc4, p);
+  }
+  const int mcus = grey ? (w + 7) / 8 : (w + 15) / 16;
+  put_segment(out, 0xdd, {(unsigned char)(mcus >> 8), (unsigned char)(mcus & 255)});
+  if (grey) {
+    put_segment(out, 0xda, {1, 1, 0x00, 0, 63, 0});
+  } else {
+    put_segment(out, 0xda, {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+  }
+  return out;
+}
+
+// ------------------------------------------------------------------------------------------------ the page table
+struct JpegLimits {
+  long long blob_words, total_mcus, total_blocks, total_intervals, out_bytes;  // out_bytes < 0: the stage writes no output
+};
+struct JpegPage {
+  const unsigned char* src;
+  int h, w, ch, mcu_w, mcu_h, per;  // per: blocks per MCU
+  long long first_mcu, first_block, first_interval, out_off;
+  int capacity, hdr_off, hdr_len, q_off;
+};
+// Record p, checked against the limits: a record that does not fit is no page (never trusted).
+__device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const JpegLimits& lim, int p, JpegPage& g) {
+  const int* r = blob + (size_t)p * JP_REC;
+  g.src = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)r[1] << 32) | (unsigned long long)(unsigned)r[0]);
+  g.h = r[2], g.w = r[3], g.ch = r[4];
+  if (g.src == nullptr || g.h < 1 || g.w < 1 || g.h > 16383 || g.w > 16383 || (g.ch != 1 && g.ch != 3)) return false;
+  const int m = g.ch == 3 ? 16 : 8;
+  g.per = g.ch == 3 ? 6 : 1;
+  g.mcu_w = (g.w + m - 1) / m, g.mcu_h = (g.h + m - 1) / m;
+  g.first_mcu = r[5], g.first_block = r[6], g.first_interval = r[7];
+  g.out_off = (long long)(((unsigned long long)(unsigned)r[9] << 32) | (unsigned long long)(unsigned)r[8]);
+  g.capacity = r[10], g.hdr_off = r[11], g.hdr_len = r[12], g.q_off = r[13];
+  const long long mcus = (long long)g.mcu_w * g.mcu_h;
+  if (g.first_mcu < 0 || g.first_block < 0 || g.first_interval < 0 || g.first_mcu + mcus > lim.total_mcus ||
+      g.first_block + mcus * g.per > lim.total_blocks || g.first_interval + g.mcu_h > lim.total_intervals)
+    return false;
+  if (g.q_off < 0 || (long long)g.q_off + 128 > lim.blob_words) return false;
+  if (g.hdr_off < 0 || g.hdr_len < 0 || (long long)g.hdr_off + g.hdr_len > lim.blob_words * 4) return false;
+  if (lim.out_bytes >= 0 && (g.capacity < 0 || g.out_off < 0 || g.out_off + g.capacity > lim.out_bytes)) return false;
+  return true;
+}
+// the page whose MCUs (by_interval false) / restart intervals (true) contain global index `idx`, or -1
+__device__ __forceinline__ int jpeg_find(const int* __restrict__ blob, const JpegLimits& lim, int n_pages, long long idx, bool by_interval,
+                                         JpegPage& g) {
+  for (int p = 0; p < n_pages; ++p) {
+    if (!jpeg_page(blob, lim, p, g)) continue;
+    const long long first = by_interval ? g.first_interval : g.first_mcu;
+    const long long count = by_interval ? g.mcu_h : (long long)g.mcu_w * g.mcu_h;
+    if (idx >= first && idx < first + count) return p;
+  }
+  return -1;
+}
+
+// ------------------------------------------------------------------------------------------------ coefficients
+// libjpeg's jfdctint.c (`islow`), one pass over eight values `stride` apart: CONST_BITS 13, PASS1_BITS 2
+template <bool FIRST>
+__device__ __forceinline__ void fdct_pass(int* d, int stride) {
+  constexpr int F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137,
+                F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
+  constexpr int SH = FIRST ? 11 : 15, RND = 1 << (SH - 1);
+  const int d0 = d[0], d1 = d[stride], d2 = d[2 * stride], d3 = d[3 * stride], d4 = d[4 * stride], d5 = d[5 * stride],
+            d6 = d[6 * stride], d7 = d[7 * stride];
+  int t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  if (FIRST) {
+    d[0] = (t10 + t11) * 4;
+    d[4 * stride] = (t10 - t11) * 4;
+  } else {
+    d[0] = (t10 + t11 + 2) >> 2;
+    d[4 * stride] = (t10 - t11 + 2) >> 2;
+  }
+  int z1 = (t12 + t13) * F0541;
+  d[2 * stride] = (z1 + t13 * F0765 + RND) >> SH;
+  d[6 * stride] = (z1 - t12 * F1847 + RND) >> SH;
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * F1175;
+  t4 *= F0298, t5 *= F2053, t6 *= F3072, t7 *= F1501;
+  z1 *= -F0899, z2 *= -F2562;
+  z3 = z3 * -F1961 + z5, z4 = z4 * -F0390 + z5;
+  d[7 * stride] = (t4 + z1 + z3 + RND) >> SH;
+  d[5 * stride] = (t5 + z2 + z4 + RND) >> SH;
+  d[3 * stride] = (t6 + z2 + z3 + RND) >> SH;
+  d[stride] = (t7 + z1 + z4 + RND) >> SH;
+}
+
+__global__ __launch_bounds__(JP_WAVES * 64) void k_jpeg_coefficients(const int* __restrict__ blob, JpegLimits lim, int n_pages,
+                                                                     short* __restrict__ coef) {
+  __shared__ __align__(16) unsigned char s_raw[JP_WAVES][16 * 48];  // the MCU's pixels, B G R
+  __shared__ short s_chroma[JP_WAVES][2][256];                      // Cb, Cr at full resolution
+  __shared__ int s_blk[JP_WAVES][6][64];                            // Y0 Y1 Y2 Y3 Cb Cr, samples - 128, then the DCT in place
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long mcu = (long long)blockIdx.x * JP_WAVES + wave;
+  JpegPage g;
+  const bool ok = mcu < lim.total_mcus && jpeg_find(blob, lim, n_pages, mcu, false, g) >= 0;  // the same in all lanes of a wave
+  const bool colour = ok && g.ch == 3, grey = ok && g.ch == 1;
+  int mx = 0, my = 0;
+  if (ok) {
+    const long long local = mcu - g.first_mcu;
+    my = (int)(local / g.mcu_w), mx = (int)(local % g.mcu_w);
+  }
+  if (colour) {
+    const int x0 = mx * 16, y0 = my * 16;
+    const size_t pitch = (size_t)g.w * 3;
+    const bool whole = x0 + 16 <= g.w && y0 + 16 <= g.h && (pitch & 15) == 0 && ((uintptr_t)g.src & 15) == 0;
+    if (whole) {
+      if (lane < 48) {  // 16 rows of 48 bytes: three 16-byte loads per row, adjacent lanes on adjacent segments
+        const int row = lane / 3, seg = lane % 3;
+        const uint4 v = *reinterpret_cast<const uint4*>(g.src + (size_t)(y0 + row) * pitch + (size_t)x0 * 3 + seg * 16);
+        *reinterpret_cast<uint4*>(&s_raw[wave][row * 48 + seg * 16]) = v;
+      }
+    } else {
+      for (int i = lane; i < 256; i += 64) {
+        const int sy = min(y0 + (i >> 4), g.h - 1), sx = min(x0 + (i & 15), g.w - 1);
+        const unsigned char* px = g.src + (size_t)sy * pitch + (size_t)sx * 3;
+        s_raw[wave][i * 3] = px[0], s_raw[wave][i * 3 + 1] = px[1], s_raw[wave][i * 3 + 2] = px[2];
+      }
+    }
+  }
+  __syncthreads();
+  if (colour) {
+    for (int i = lane; i < 256; i += 64) {
+      const int b = s_raw[wave][i * 3], gr = s_raw[wave][i * 3 + 1], r = s_raw[wave][i * 3 + 2];
+      const int y = (19595 * r + 38470 * gr + 7471 * b + 32768) >> 16;
+      const int cb = (-11059 * r - 21709 * gr + 32768 * b + (128 << 16) + 32767) >> 16;
+      const int cr = (32768 * r - 27439 * gr - 5329 * b + (128 << 16) + 32767) >> 16;
+      const int py = i >> 4, px = i & 15;
+      s_blk[wave][(py >> 3) * 2 + (px >> 3)][(py & 7) * 8 + (px & 7)] = y - 128;
+      s_chroma[wave][0][i] = (short)cb;
+      s_chroma[wave][1][i] = (short)cr;
+    }
+  } else if (grey) {
+    const int sy = min(my * 8 + (lane >> 3), g.h - 1), sx = min(mx * 8 + (lane & 7), g.w - 1);
+    s_blk[wave][0][lane] = (int)g.src[(size_t)sy * g.w + sx] - 128;
+  }
+  __syncthreads();
+  if (colour) {
+    const int cy = lane >> 3, cx = lane & 7, at = cy * 32 + cx * 2;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const short* s = s_chroma[wave][c];
+      s_blk[wave][4 + c][lane] = ((s[at] + s[at + 1] + s[at + 16] + s[at + 17] + 1 + (cx & 1)) >> 2) - 128;  // MCUs are 8 chroma columns wide
+    }
+  }
+  __syncthreads();
+  const int nb = ok ? g.per : 0;
+  if (lane < nb * 8) fdct_pass<true>(&s_blk[wave][lane >> 3][(lane & 7) * 8], 1);
+  __syncthreads();
+  if (lane < nb * 8) fdct_pass<false>(&s_blk[wave][lane >> 3][lane & 7], 8);
+  __syncthreads();
+  if (ok) {
+    const int* qt = blob + g.q_off;
+    const long long first = g.first_block + (mcu - g.first_mcu) * g.per;
+    for (int b = 0; b < nb; ++b) {
+      const int v = s_blk[wave][b][c_zigzag[lane]];
+      const int d = min(max(qt[(b >= 4 ? 64 : 0) + lane], 1), 255) * 8;
+      int c = (abs(v) + d / 2) / d;
+      c = v < 0 ? -c : c;
+      c = min(max(c, lane == 0 ? -1024 : -1023), 1023);
+      coef[(size_t)(first + b) * 64 + lane] = (short)c;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ entropy
+constexpr int EN_PITCH = 66;  // shorts between the staged blocks of two lanes: 33 words, so 32 lanes read 32 banks
+
+struct BitWriter {
+  unsigned* out;  // the interval's words, most significant bit first
+  int w;          // next word
+  unsigned long long acc;
+  int n;          // bits of `acc` in use (< 32 between calls); the first word starts with the neighbour's bits as zeros
+  bool first;
+  __device__ __forceinline__ void put(unsigned code, int len) {
+    acc = (acc << len) | code;
+    n += len;
+    if (n >= 32) {
+      n -= 32;
+      const unsigned word = (unsigned)(acc >> n);
+      if (first) {
+        atomicOr(out + w, word);  // shared with the block before
+        first = false;
+      } else {
+        out[w] = word;  // every bit of it is this lane's
+      }
+      ++w;
+      acc &= (1ull << n) - 1;
+    }
+  }
+  __device__ __forceinline__ void finish() {
+    if (n > 0) atomicOr(out + w, (unsigned)(acc << (32 - n)));  // shared with the block behind (or, `first`, with both)
+  }
+};
+
+// Block `c` (zig-zag, in LDS) with DC predictor `pred`: counts its bits and, EMIT, writes them.
+template <bool EMIT>
+__device__ __forceinline__ int encode_block(const short* c, int pred, const unsigned* lut, BitWriter* wr) {
+  int bits = 0;
+  {
+    const int diff = min(max((int)c[0] - pred, -2047), 2047);  // what the definition's clamps allow; a stray value cannot outgrow the block's words
+    const int cat = 32 - __clz(abs(diff));
+    const unsigned e = lut[256 + cat];
+    bits += (int)(e >> 16) + cat;
+    if (EMIT) wr->put((e & 0xffff) << cat | ((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << cat) - 1)), (int)(e >> 16) + cat);
+  }
+  int run = 0;
+  for (int k = 1; k < 64; ++k) {
+    const int v = min(max((int)c[k], -1023), 1023);
+    if (v == 0) {
+      ++run;
+      continue;
+    }
+    while (run > 15) {
+      const unsigned z = lut[0xf0];
+      bits += (int)(z >> 16);
+      if (EMIT) wr->put(z & 0xffff, (int)(z >> 16));
+      run -= 16;
+    }
+    const int cat = 32 - __clz(abs(v));
+    const unsigned e = lut[run << 4 | cat];
+    bits += (int)(e >> 16) + cat;
+    if (EMIT) wr->put((e & 0xffff) << cat | ((unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1)), (int)(e >> 16) + cat);
+    run = 0;
+  }
+  if (run > 0) {
+    const unsigned e = lut[0];
+    bits += (int)(e >> 16);
+    if (EMIT) wr->put(e & 0xffff, (int)(e >> 16));
+  }
+  return bits;
+}
+
+__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(64) void k_jpeg_entropy(const int* __restrict__ blob, JpegLimits lim, int n_pages,
+                                                     const short* __restrict__ coef, unsigned* __restrict__ stream,
+                                                     int* __restrict__ intervals) {
+  __shared__ unsigned s_lut[2][256 + 16];
+  __shared__ __align__(16) short s_coef[64 * EN_PITCH];  // written as 32-bit words: a block starts at a multiple of 132 bytes
+  const int lane = threadIdx.x;
+  for (int i = lane; i < 2 * (256 + 16); i += 64) (&s_lut[0][0])[i] = (&c_luts.e[0][0])[i];
+  JpegPage g;
+  const long long iv = blockIdx.x;
+  if (jpeg_find(blob, lim, n_pages, iv, true, g) < 0) return;  // the whole block
+  const int nb = g.mcu_w * g.per;                                // blocks of the interval: <= 1024 * 6
+  const long long blk0 = g.first_block + (iv - g.first_interval) * nb;
+  unsigned* out = stream + (size_t)blk0 * JP_BLOCK_WORDS;  // nb * JP_BLOCK_WORDS words are this interval's
+  int cum = 0, zeroed = 0;                                 // bits written so far (< 2^24); words zeroed so far
+  for (int base = 0; base < nb; base += 64) {
+    __syncthreads();  // the previous chunk's readers of s_coef (and, first time, the writers of s_lut)
+    for (int i = lane; i < 64 * 8; i += 64) {
+      const int blk = i >> 3, part = i & 7;
+      if (base + blk < nb) {
+        const uint4 v = *reinterpret_cast<const uint4*>(coef + (size_t)(blk0 + base + blk) * 64 + part * 8);
+        unsigned* d = reinterpret_cast<unsigned*>(&s_coef[blk * EN_PITCH + part * 8]);
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+      }
+    }
+    __syncthreads();
+    const int b = base + lane;
+    const bool active = b < nb;
+    const int comp = g.per == 6 ? max(b % 6 - 3, 0) : 0;  // 0 Y, 1 Cb, 2 Cr
+    int pred = 0;
+    if (active) {
+      // the previous block of the component: Y follows Y inside an MCU and Y3 of the MCU before; Cb / Cr the MCU before
+      const int prev = g.per == 1 ? b - 1 : (comp == 0 ? (b % 6 == 0 ? b - 3 : b - 1) : b - 6);
+      if (prev >= 0) pred = coef[(size_t)(blk0 + prev) * 64];
+    }
+    const unsigned* lut = s_lut[comp ? 1 : 0];
+    const short* mine = &s_coef[lane * EN_PITCH];
+    const int len = active ? encode_block<false>(mine, pred, lut, nullptr) : 0;
+    const int incl = wave_inclusive_scan(len, lane);
+    const int total = __shfl(incl, 63);
+    const int need = (cum + total + 31) >> 5;  // <= nb * JP_BLOCK_WORDS: a block is at most 1660 bits
+    for (int wd = zeroed + lane; wd < need; wd += 64) out[wd] = 0;
+    zeroed = max(zeroed, need);
+    __syncthreads();  // the zeros are in memory before any lane ORs into them
+    if (active && len > 0) {
+      const int start = cum + incl - len;
+      BitWriter wr{out, start >> 5, 0ull, start & 31, true};
+      encode_block<true>(mine, pred, lut, &wr);
+      wr.finish();
+    }
+    cum += total;
+  }
+  if (lane == 0 && (cum & 7)) {  // pad with 1-bits to a byte
+    const int pad = 8 - (cum & 7);
+    atomicOr(out + (cum >> 5), ((1u << pad) - 1) << (32 - (cum & 31) - pad));
+  }
+  __syncthreads();
+  const int nbytes = (cum + 7) >> 3;
+  int ff = 0;
+  for (int wd = lane; wd * 4 < nbytes; wd += 64) {
+    // read at the L2: a neighbouring interval's block on this CU may have pulled the line that holds this interval's first
+    // or last words into the L1 before they were complete
+    const unsigned v = __hip_atomic_load(out + wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ff += ((v >> (24 - 8 * k)) & 255) == 255;  // bytes behind the last are zero
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ff += __shfl_xor(ff, o);
+  if (lane == 0) {
+    intervals[2 * iv] = nbytes;
+    intervals[2 * iv + 1] = nbytes + ff;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ compaction
+__global__ __launch_bounds__(64) void k_jpeg_compact(const int* __restrict__ blob, JpegLimits lim, int n_pages,
+                                                     const unsigned* __restrict__ stream, const int* __restrict__ intervals,
+                                                     unsigned char* __restrict__ out, int* __restrict__ lengths) {
+  const int lane = threadIdx.x;
+  JpegPage g;
+  const long long iv = blockIdx.x;
+  const int p = jpeg_find(blob, lim, n_pages, iv, true, g);
+  if (p < 0) return;
+  const int row = (int)(iv - g.first_interval), n_iv = g.mcu_h;
+  long long before = 0, total = 0;
+  for (int i = lane; i < n_iv; i += 64) {
+    const long long s = max(intervals[2 * (g.first_interval + i) + 1], 0);
+    total += s;
+    if (i < row) before += s;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    total += __shfl_xor(total, o);
+    before += __shfl_xor(before, o);
+  }
+  const long long file_len = (long long)g.hdr_len + total + 2LL * (n_iv - 1) + 2;
+  if (file_len > g.capacity) return;  // lengths[p] stays -1 and not a byte of the page's output is written
+  unsigned char* page_out = out + g.out_off;
+  const long long cap = g.capacity;
+  if (row == 0) {
+    const unsigned char* hdr = reinterpret_cast<const unsigned char*>(blob) + g.hdr_off;
+    for (int i = lane; i < g.hdr_len; i += 64) page_out[i] = hdr[i];
+  }
+  const int nb = g.mcu_w * g.per;
+  const unsigned* src = stream + (size_t)(g.first_block + (long long)row * nb) * JP_BLOCK_WORDS;
+  const int nbytes = min(max(intervals[2 * iv], 0), nb * YMK_JPEG_BLOCK_STREAM_BYTES);
+  long long pos = (long long)g.hdr_len + before + 2LL * row;  // where this interval starts in the file
+  for (int wbase = 0; wbase * 4 < nbytes; wbase += 64) {
+    const int wd = wbase + lane;
+    const int valid = min(max(nbytes - wd * 4, 0), 4);
+    const unsigned v = valid > 0 ? src[wd] : 0u;
+    int mine = valid;
+    for (int k = 0; k < valid; ++k) mine += ((v >> (24 - 8 * k)) & 255) == 255;
+    const int incl = wave_inclusive_scan(mine, lane);
+    long long at = pos + incl - mine;
+    for (int k = 0; k < valid; ++k) {
+      const unsigned char byte = (unsigned char)(v >> (24 - 8 * k));
+      if (at < cap) page_out[at] = byte;  // always true when `intervals` is what k_jpeg_entropy wrote for this stream
+      ++at;
+      if (byte == 255) {
+        if (at < cap) page_out[at] = 0;
+        ++at;
+      }
+    }
+    pos += __shfl(incl, 63);
+  }
+  if (lane == 0 && pos + 2 <= cap) {
+    page_out[pos] = 0xff;
+    page_out[pos + 1] = row + 1 < n_iv ? (unsigned char)(0xd0 + (row & 7)) : (unsigned char)0xd9;  // RSTm | EOI
+    if (row + 1 == n_iv) lengths[p] = (int)file_len;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ Pillow resample -> uint8
+constexpr int RS_REC = YMK_PIL_RESIZE_U8_WORDS;
+__device__ __forceinline__ int clip8_22(int v) {
+  v >>= 22;
+  return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+template <int C>
+__device__ __forceinline__ void pil_resize_pixel(const unsigned char* __restrict__ src, int W, const int* xb, const int* xk, int ksx,
+                                                 const int* yb, const int* yk, int ksy, int x, int y, unsigned char* __restrict__ dst) {
+  const int xmin = xb[2 * x], xn = xb[2 * x + 1], ymin = yb[2 * y], yn = yb[2 * y + 1];
+  const int* kx = xk + (size_t)x * ksx;
+  const int* ky = yk + (size_t)y * ksy;
+  int acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 1 << 21;
+  for (int r = 0; r < yn; ++r) {
+    const unsigned char* row = src + ((size_t)(ymin + r) * W + xmin) * C;
+    int hsum[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) hsum[c] = 1 << 21;
+    for (int t = 0; t < xn; ++t) {
+      const int k = kx[t];
+#pragma unroll
+      for (int c = 0; c < C; ++c) hsum[c] += row[t * C + c] * k;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += clip8_22(hsum[c]) * ky[r];
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) dst[c] = (unsigned char)clip8_22(acc[c]);
+}
+__global__ void k_pil_resize_u8(const int* __restrict__ blob, long long blob_words) {
+  const int* rec = blob + (size_t)blockIdx.z * RS_REC;
+  const int H = rec[2], W = rec[3], C = rec[4], oh = rec[5], ow = rec[6], ksx = rec[7], ksy = rec[8];
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= ow || y >= oh || H < 1 || W < 1 || ksx < 1 || ksy < 1) return;
+  const long long off[4] = {rec[9], rec[10], rec[11], rec[12]}, len[4] = {2LL * ow, (long long)ow * ksx, 2LL * oh, (long long)oh * ksy};
+  for (int i = 0; i < 4; ++i)
+    if (off[i] < 0 || off[i] + len[i] > blob_words) return;  // a table outside the blob: nothing is read through it
+  const int *xb = blob + off[0], *xk = blob + off[1], *yb = blob + off[2], *yk = blob + off[3];
+  // a tap outside the page is not read: the bounds are the caller's, the page's size is the record's
+  if (xb[2 * x] < 0 || xb[2 * x + 1] < 0 || xb[2 * x + 1] > ksx || xb[2 * x] + xb[2 * x + 1] > W) return;
+  if (yb[2 * y] < 0 || yb[2 * y + 1] < 0 || yb[2 * y + 1] > ksy || yb[2 * y] + yb[2 * y + 1] > H) return;
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)rec[1] << 32) | (unsigned)rec[0]);
+  unsigned char* dst = reinterpret_cast<unsigned char*>(((unsigned long long)(unsigned)rec[14] << 32) | (unsigned)rec[13]);
+  if (C == 3)
+    pil_resize_pixel<3>(src, W, xb, xk, ksx, yb, yk, ksy, x, y, dst + ((size_t)y * ow + x) * 3);
+  else if (C == 1)
+    pil_resize_pixel<1>(src, W, xb, xk, ksx, yb, yk, ksy, x, y, dst + (size_t)y * ow + x);
+}
+
+static JpegLimits limits(int64_t blob_words, int64_t total_mcus, int64_t total_blocks, int64_t total_intervals, int64_t out_bytes) {
+  YMK_CHECK(blob_words >= 0 && total_mcus >= 0 && total_blocks >= 0 && total_intervals >= 0, "bad argument");
+  YMK_CHECK(total_mcus <= 0x7fffffffLL / JP_WAVES && total_blocks <= 0x7fffffffLL && total_intervals <= 0x7fffffffLL,
+            "a wave of at most 2^31 - 1 blocks");
+  return JpegLimits{blob_words, total_mcus, total_blocks, total_intervals, out_bytes};
+}
+static void check_table(const int* blob_dev, int64_t blob_words, int n_pages) {
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
+  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 15) == 0 && blob_words >= (int64_t)n_pages * JP_REC, "page table: 16-byte aligned, n records");
+}
+
+static void launch_coefficients(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, int16_t* coef) {
+  YMK_CHECK(coef && ((uintptr_t)coef & 15) == 0, "coefficients: 16-byte aligned");
+  const unsigned grid = (unsigned)((lim.total_mcus + JP_WAVES - 1) / JP_WAVES);
+  hipLaunchKernelGGL(k_jpeg_coefficients, dim3(grid), dim3(JP_WAVES * 64), 0, s, blob, lim, n_pages, (short*)coef);
+  YMK_HIP(hipGetLastError());
+}
+static void launch_entropy(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, const int16_t* coef, uint32_t* stream_dev,
+                           int64_t stream_bytes, int* intervals) {
+  YMK_CHECK(coef && ((uintptr_t)coef & 15) == 0 && stream_dev && ((uintptr_t)stream_dev & 3) == 0 && intervals, "null or misaligned scratch");
+  YMK_CHECK(stream_bytes >= lim.total_blocks * YMK_JPEG_BLOCK_STREAM_BYTES, "stream scratch smaller than ymk_jpeg_scratch_bytes says");
+  hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const short*)coef,
+                     (unsigned*)stream_dev, intervals);
+  YMK_HIP(hipGetLastError());
+}
+static void launch_compact(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, const uint32_t* stream_dev,
+                           int64_t stream_bytes, const int* intervals, unsigned char* out, int* lengths) {
+  YMK_CHECK(stream_dev && intervals && out && lengths && lim.out_bytes >= 0, "null scratch / output");
+  YMK_CHECK(stream_bytes >= lim.total_blocks * YMK_JPEG_BLOCK_STREAM_BYTES, "stream scratch smaller than ymk_jpeg_scratch_bytes says");
+  YMK_HIP(hipMemsetAsync(lengths, 0xff, (size_t)n_pages * sizeof(int), s));  // -1 until a page's last interval is in place
+  hipLaunchKernelGGL(k_jpeg_compact, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const unsigned*)stream_dev,
+                     intervals, out, lengths);
+  YMK_HIP(hipGetLastError());
+}
+
+}  // namespace ymk
+
+extern "C" {
+int ymk_jpeg_page_words(void) { return ymk::JP_REC; }
+
+int ymk_jpeg_quant_tables(int quality, int* zigzag128_out) {
+  try {
+    YMK_CHECK(zigzag128_out, "null output");
+    ymk::quant_tables(quality, zigzag128_out);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out, int capacity) {
+  try {
+    YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
+    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, channels == 1, quality);
+    YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
+    std::memcpy(out, hdr.data(), hdr.size());
+    return (int)hdr.size();
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return -1;
+  }
+}
+
+int ymk_jpeg_scratch_bytes(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes6_out) {
+  try {
+    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes6_out && (n_pages == 0 || (h && w && channels)), "bad argument");
+    int64_t mcus = 0, blocks = 0, intervals = 0;
+    for (int p = 0; p < n_pages; ++p) {
+      YMK_CHECK(h[p] >= 1 && w[p] >= 1 && h[p] <= 16383 && w[p] <= 16383 && (channels[p] == 1 || channels[p] == 3),
+                "page: 1..16383 pixels on a side, 1 or 3 channels");
+      const int m = channels[p] == 3 ? 16 : 8;
+      const int64_t mw = (w[p] + m - 1) / m, mh = (h[p] + m - 1) / m;
+      mcus += mw * mh;
+      blocks += mw * mh * (channels[p] == 3 ? 6 : 1);
+      intervals += mh;
+    }
+    sizes6_out[0] = mcus, sizes6_out[1] = blocks, sizes6_out[2] = intervals;
+    sizes6_out[3] = blocks * 64 * (int64_t)sizeof(int16_t);
+    sizes6_out[4] = blocks * YMK_JPEG_BLOCK_STREAM_BYTES;
+    sizes6_out[5] = intervals * 2 * (int64_t)sizeof(int);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_coefficients(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int16_t* coef_dev,
+                          int64_t total_blocks, void* stream) {
+  try {
+    const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, 0x7fffffffLL, -1);
+    if (n_pages == 0 || total_mcus == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    ymk::launch_coefficients((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_entropy(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
+                     uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, int64_t total_intervals, void* stream) {
+  try {
+    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
+    if (n_pages == 0 || total_intervals == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    ymk::launch_entropy((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_compact(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* stream_dev, int64_t stream_bytes,
+                     int64_t total_blocks, const int* intervals_dev, int64_t total_intervals, unsigned char* out_dev, int64_t out_bytes,
+                     int* lengths_dev, void* stream) {
+  try {
+    YMK_CHECK(out_bytes >= 0, "bad argument");
+    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, out_bytes);
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    if (total_intervals == 0) {
+      YMK_CHECK(lengths_dev, "null lengths");
+      YMK_HIP(hipMemsetAsync(lengths_dev, 0xff, (size_t)n_pages * sizeof(int), (hipStream_t)stream));
+      return 0;
+    }
+    ymk::launch_compact((hipStream_t)stream, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
+                          int64_t total_intervals, int16_t* coef_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
+                          unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream) {
+  try {
+    YMK_CHECK(out_bytes >= 0, "bad argument");
+    const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, total_intervals, out_bytes);
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    YMK_CHECK(total_mcus > 0 && total_intervals > 0, "pages without MCUs");
+    const hipStream_t s = (hipStream_t)stream;
+    ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
+    ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
+    ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_pil_resize_u8_record_words(void) { return ymk::RS_REC; }
+
+int ymk_pil_resize_u8(const int* blob_dev, int64_t blob_words, int n, int max_oh, int max_ow, void* stream) {
+  try {
+    YMK_CHECK(n >= 0 && n <= 65535 && max_oh >= 0 && max_oh <= 65535 && max_ow >= 0, "at most 65535 images and output rows per launch");
+    if (n == 0 || max_oh == 0 || max_ow == 0) return 0;
+    YMK_CHECK(blob_dev && blob_words >= (int64_t)n * ymk::RS_REC, "record table");
+    hipLaunchKernelGGL(ymk::k_pil_resize_u8, dim3((max_ow + 255) / 256, max_oh, n), dim3(256), 0, (hipStream_t)stream, blob_dev,
+                       (long long)blob_words);
+    YMK_HIP(hipGetLastError());
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+}

@@ -27,7 +27,7 @@ from .schemas import (
     OCRSchema,
     ParagraphSchema,
 )
-from .serving import StageAnalyzer
+from .serving import StageAnalyzer, check_jpeg_preset
 from .table_structure_recognizer import TableStructureRecognizer
 from .text_detector import TextDetector
 from .text_recognizer import TextRecognizer
@@ -511,7 +511,7 @@ class DocumentAnalyzer(StageAnalyzer):
         return reading_order_visualizer(page if layout is None else layout, results, to_host=False)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False):
+              overlays: bool = False, jpeg=None):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -526,12 +526,17 @@ class DocumentAnalyzer(StageAnalyzer):
         the two images `analyze_pages` returns for the page when everything was built with visualize=True (detection quads and
         recognised strings; layout boxes, table cells, reading order; no heat map), as uint8 H x W x 3 arrays the caller owns.
         They are drawn on the device by a render stage of the pipeline - text layout, per-tile culling and all canvases of a
-        wave in two launches ("Overlay rasteriser") - that only the waves of such a job visit."""
+        wave in two launches ("Overlay rasteriser") - that only the waves of such a job visit.
+        `jpeg`: a property of the job too - None, or a preset of the searchable PDF ("high", "middle", "low"; anything else is
+        a ValueError before a source is read): a page's entry ends with its EncodedJpeg (yomitoku_amd/jpeg.py), i.e. (schema,
+        EncodedJpeg) or (schema, ocr overlay, layout overlay, EncodedJpeg) - the file `searchable_pdf_bytes` embeds as it is,
+        encoded on the device in the same render stage from the clean page ("JPEG encoder")."""
+        check_jpeg_preset(jpeg)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: build the analyzer with "
                                       "visualize=False and ask per job, serve(..., overlays=True) (__call__ and analyze_pages "
                                       "draw with visualize=True)")
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg)
 
     def __call__(self, img):
         self.img = img

@@ -60,14 +60,26 @@ def detector_tensor(page_dev: torch.Tensor, shortest: int, limit: int, out: torc
 
 # ---------------------------------------------------------------------------------------------
 # Pillow bilinear resample coefficients (Resample.c: precompute_coeffs + normalize_coeffs_8bpc)
-def pil_bilinear_coeffs(in_size: int, out_size: int):
-    """(bounds int32 [out][2], coefs int32 [out][ksize], ksize).  All outputs at once in float64: the same operations in the
-    same order as the per-output loop of Resample.c (`_pil_bilinear_coeffs_scalar`, which tests hold this form to) - the
-    weights of an output are summed tap by tap, never pairwise.  A table crop has its own (width, height), so a wave of
-    table-heavy pages asks for ~340 new tables: as Python loops that was ~3 ms per crop and THE cost of the tables stage."""
+def _triangle(x):
+    a = np.abs(x)
+    return np.where(a < 1.0, 1.0 - a, 0.0)
+
+
+def _lanczos3(x):
+    """Resample.c lanczos_filter: sinc(x) sinc(x / 3) on [-3, 3), with libm's sin (what the C code calls), element by element."""
+    def sinc(v):
+        return 1.0 if v == 0.0 else math.sin(v * math.pi) / (v * math.pi)
+
+    flat = [sinc(v) * sinc(v / 3) if -3.0 <= v < 3.0 else 0.0 for v in x.reshape(-1).tolist()]
+    return np.asarray(flat, dtype=np.float64).reshape(x.shape)
+
+
+def _pil_coeffs(in_size: int, out_size: int, filter_support: float, kernel):
+    """precompute_coeffs + normalize_coeffs_8bpc for any filter: all outputs at once in float64, the same operations in the same
+    order as the per-output loop of Resample.c - the weights of an output are summed tap by tap, never pairwise."""
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
+    support = filter_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / filterscale
     center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
@@ -75,8 +87,7 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
     xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
     taps = np.arange(ksize, dtype=np.int64)[None, :]
     inside = taps < xmax[:, None]
-    a = np.abs((taps + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss
-    w = np.where(inside & (a < 1.0), 1.0 - a, 0.0)
+    w = np.where(inside, kernel(((taps + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss), 0.0)
     ww = np.zeros(out_size, dtype=np.float64)
     for x in range(ksize):  # sequential, like `ww += w` in the C loop (taps beyond xmax add an exact 0.0)
         ww = ww + w[:, x]
@@ -85,6 +96,19 @@ def pil_bilinear_coeffs(in_size: int, out_size: int):
     coefs[~inside] = 0
     bounds = np.stack([xmin, xmax], axis=1).astype(np.int32)
     return bounds, coefs, ksize
+
+
+def pil_bilinear_coeffs(in_size: int, out_size: int):
+    """(bounds int32 [out][2], coefs int32 [out][ksize], ksize) of Pillow's BILINEAR (`_pil_bilinear_coeffs_scalar`, which tests
+    hold this form to).  A table crop has its own (width, height), so a wave of table-heavy pages asks for ~340 new tables: as
+    Python loops that was ~3 ms per crop and THE cost of the tables stage."""
+    return _pil_coeffs(in_size, out_size, 1.0, _triangle)
+
+
+def pil_lanczos_coeffs(in_size: int, out_size: int):
+    """The same for Pillow's LANCZOS (support 3): the tables `Image.resize(..., Image.LANCZOS)` uses on 8-bit images, which
+    ymk_pil_resize_u8 applies on the device (yomitoku_amd/jpeg.py: the "middle" / "low" presets of the searchable PDF)."""
+    return _pil_coeffs(in_size, out_size, 3.0, _lanczos3)
 
 
 def _pil_bilinear_coeffs_scalar(in_size: int, out_size: int):

@@ -1,0 +1,261 @@
+"""Baseline JPEG files of pages that are already on the device: what a searchable PDF embeds (utils/searchable_pdf.py).
+
+    encoded = encode_jpeg_pages(pages, "high")          # device tensors or host arrays, uint8 H x W x 3 (B G R) or H x W
+    searchable_pdf_bytes(encoded, docs)                 # an EncodedJpeg is embedded as it is
+
+`DocumentAnalyzer.serve(sources, jpeg="high")` hands an EncodedJpeg back next to every page's schema; its render stage calls
+`encode_jpeg_pages` on the wave's clean pages with the wave slot's scratch.
+
+The whole file is made on the device (yomitoku_amd/csrc/ymk_jpeg.hip; DESIGN.md, "JPEG encoder"): colour conversion, 4:2:0
+chroma, DCT and quantiser in one launch, the Huffman coding of every restart interval (one MCU row) in a second, header +
+intervals + restart markers laid out per page in a third.  The presets are the searchable PDF's (`IMAGE_QUALITY_PRESETS`): a
+page whose long side exceeds the preset's is first shrunk with Pillow's Lanczos resample, restated on the device
+(ymk_pil_resize_u8), to int(w * scale) x int(h * scale) as the host path does.  The host sees one copy of the files' lengths and
+one of their bytes, both through pinned memory.  There is no host fallback: a page the device cannot encode is an exception.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import functools
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _lib, imaging
+from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
+
+PAGE_WORDS, RESIZE_WORDS = 16, 16  # YMK_JPEG_PAGE_WORDS, YMK_PIL_RESIZE_U8_WORDS
+MAX_SIDE = 16383
+
+
+@dataclass
+class EncodedJpeg:
+    """One page as a JFIF file.  `scale`: what the preset shrank the page by (1.0: not at all) - the factor a PDF writer applies
+    to the page's word coordinates."""
+
+    data: bytes
+    width: int
+    height: int
+    grey: bool
+    scale: float = 1.0
+
+
+def jpeg_preset(image_quality: str) -> dict:
+    """The preset of that name; an unknown name is a ValueError (the host path of searchable_pdf_bytes falls back to "high")."""
+    try:
+        return IMAGE_QUALITY_PRESETS[image_quality]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown jpeg preset {image_quality!r}: one of {sorted(IMAGE_QUALITY_PRESETS)}") from None
+
+
+@functools.lru_cache(maxsize=256)
+def _header(h: int, w: int, channels: int, quality: int) -> bytes:
+    buf = (ctypes.c_ubyte * 1024)()
+    n = _lib.load().ymk_jpeg_header(h, w, channels, quality, buf, len(buf))
+    if n < 0:
+        _lib.check(1, "ymk_jpeg_header")
+    return bytes(buf[:n])
+
+
+@functools.lru_cache(maxsize=16)
+def _quant_words(quality: int) -> np.ndarray:
+    out = (ctypes.c_int * 128)()
+    _lib.check(_lib.load().ymk_jpeg_quant_tables(quality, out), "ymk_jpeg_quant_tables")
+    return np.frombuffer(out, dtype=np.int32).copy()
+
+
+def scratch_sizes(shapes: Sequence) -> tuple:
+    """(MCUs, blocks, intervals, coefficient bytes, stream bytes, interval-record bytes) of pages of `shapes` = (h, w, channels)."""
+    n = len(shapes)
+    arr = ctypes.c_int * max(1, n)
+    sizes = (ctypes.c_int64 * 6)()
+    _lib.check(_lib.load().ymk_jpeg_scratch_bytes(arr(*[s[0] for s in shapes]), arr(*[s[1] for s in shapes]),
+                                                  arr(*[s[2] for s in shapes]), n, sizes), "ymk_jpeg_scratch_bytes")
+    return tuple(int(v) for v in sizes)
+
+
+@functools.lru_cache(maxsize=64)
+def _lanczos(in_size: int, out_size: int):
+    return imaging.pil_lanczos_coeffs(in_size, out_size)  # ~10 ms of host time per new (in, out) pair: the pages of a job share theirs
+
+
+def _addr_words(ptr: int):
+    return np.array([ptr & 0xFFFFFFFF, ptr >> 32], dtype=np.uint32).view(np.int32)
+
+
+def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]] = None):
+    """(int32 words of the page table of include/ymk.h, per page the byte offset of its file in the output, the output's bytes).
+    capacities: bytes per page's file; default the page's raw byte count."""
+    n = len(pages)
+    rec = np.zeros((n, PAGE_WORDS), np.int32)
+    headers = [_header(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3, quality) for p in pages]
+    at = n * PAGE_WORDS * 4  # byte offset of the first header
+    mcu = blk = iv = 0
+    out_at, offsets = 0, []
+    for k, p in enumerate(pages):
+        h, w = int(p.shape[0]), int(p.shape[1])
+        ch = 1 if p.dim() == 2 else 3
+        m = 8 if ch == 1 else 16
+        mw, mh = -(-w // m), -(-h // m)
+        cap = int(capacities[k]) if capacities is not None else h * w * ch
+        rec[k, 0:2] = _addr_words(p.data_ptr())
+        rec[k, 2:8] = (h, w, ch, mcu, blk, iv)
+        rec[k, 8:10] = _addr_words(out_at)
+        rec[k, 10:13] = (cap, at, len(headers[k]))
+        offsets.append(out_at)
+        mcu, blk, iv = mcu + mw * mh, blk + mw * mh * (6 if ch == 3 else 1), iv + mh
+        at += -(-len(headers[k]) // 4) * 4
+        out_at += -(-cap // 16) * 16
+    rec[:, 13] = at // 4  # one quality per call: one pair of tables behind the headers
+    blob = np.zeros(at // 4 + 128, np.int32)
+    blob[: n * PAGE_WORDS] = rec.reshape(-1)
+    raw = blob.view(np.uint8)
+    for k in range(n):
+        raw[rec[k, 11] : rec[k, 11] + len(headers[k])] = np.frombuffer(headers[k], np.uint8)
+    blob[at // 4 :] = _quant_words(quality)
+    return blob, offsets, out_at
+
+
+def _grown(scratch: dict, key: str, count: int, dtype, device=None, pinned=False) -> torch.Tensor:
+    """scratch[key] with room for `count` elements: kept between calls, replaced (never resized) when it is too small."""
+    t = scratch.get(key)
+    if t is None or t.numel() < count or (not pinned and t.device != device):
+        count = max(int(count * 1.25), 1024)
+        t = torch.empty(count, dtype=dtype, pin_memory=True) if pinned else torch.empty(count, dtype=dtype, device=device)
+        scratch[key] = t
+    return t
+
+
+def resize_pages(pages: Sequence[torch.Tensor], sizes: Sequence) -> List[torch.Tensor]:
+    """Pillow's `resize((ow, oh), LANCZOS)` of uint8 device pages (H x W x 3 or H x W), all in one launch on the current
+    stream; sizes: (oh, ow) per page."""
+    dev = pages[0].device
+    outs, tables, recs = [], [], np.zeros((len(pages), RESIZE_WORDS), np.int32)
+    at = len(pages) * RESIZE_WORDS
+    for k, (p, (oh, ow)) in enumerate(zip(pages, sizes)):
+        h, w = int(p.shape[0]), int(p.shape[1])
+        ch = 1 if p.dim() == 2 else 3
+        out = torch.empty((oh, ow) if ch == 1 else (oh, ow, 3), dtype=torch.uint8, device=dev)
+        xb, xk, ksx = _lanczos(w, ow)
+        yb, yk, ksy = _lanczos(h, oh)
+        recs[k, 0:2] = _addr_words(p.data_ptr())
+        recs[k, 2:9] = (h, w, ch, oh, ow, ksx, ksy)
+        for j, t in enumerate((xb, xk, yb, yk)):
+            recs[k, 9 + j] = at
+            tables.append(t.reshape(-1))
+            at += t.size
+        recs[k, 13:15] = _addr_words(out.data_ptr())
+        outs.append(out)
+    blob = np.concatenate([recs.reshape(-1)] + tables).astype(np.int32, copy=False)
+    blob_dev = imaging._stage_blob(blob, dev)
+    _lib.check(_lib.load().ymk_pil_resize_u8(blob_dev.data_ptr(), blob.size, len(pages), max(s[0] for s in sizes),
+                                             max(s[1] for s in sizes), _lib.current_stream_ptr()), "ymk_pil_resize_u8")
+    return outs
+
+
+def _as_device_page(page, device) -> torch.Tensor:
+    if isinstance(page, torch.Tensor):
+        t = page
+    else:
+        arr = np.ascontiguousarray(np.asarray(page))
+        if arr.dtype != np.uint8:
+            raise ValueError(f"a page is uint8, got {arr.dtype}")
+        t = torch.from_numpy(arr)
+    if t.dtype != torch.uint8 or not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)):
+        raise ValueError(f"a page is uint8 H x W x 3 (B G R) or H x W, got {t.dtype} {tuple(t.shape)}")
+    if min(t.shape[:2]) < 1 or max(t.shape[:2]) > MAX_SIDE:
+        raise ValueError(f"a page has 1..{MAX_SIDE} pixels on a side, got {tuple(t.shape[:2])}")
+    if t.device.type != "cuda":
+        t = t.to(device, non_blocking=False)
+    return t.contiguous()
+
+
+def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
+                      capacities: Optional[Sequence[int]] = None) -> List[Union[EncodedJpeg, Exception]]:
+    """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
+    file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
+    stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
+    the device and pinned buffers (serve: one per wave slot); capacities: bytes allowed per page's file - the default cannot
+    hold the ~620-byte header (~330 grey) plus the scan of a page below roughly 15 x 15 pixels, nor noise that does not compress."""
+    preset = jpeg_preset(image_quality)
+    quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
+    out: list = [None] * len(pages)
+    if not pages:
+        return out
+    if not torch.cuda.is_available():
+        raise _lib.YmkError("encode_jpeg_pages needs a HIP device (there is no host fallback)")
+    device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.device.type == "cuda"),
+                  torch.device("cuda", torch.cuda.current_device()))
+    scratch = {} if scratch is None else scratch
+    lib = _lib.load()
+    with torch.cuda.device(device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device)):
+        live, devs = [], []
+        for k, page in enumerate(pages):
+            try:
+                devs.append(_as_device_page(page, device))
+                live.append(k)
+            except Exception as exc:  # noqa: BLE001 - only this page fails
+                out[k] = exc
+        if not live:
+            return out
+        scales = [1.0] * len(live)
+        todo = []
+        for j, p in enumerate(devs):
+            h, w = int(p.shape[0]), int(p.shape[1])
+            if long_side is not None and max(h, w) > long_side:
+                scales[j] = long_side / max(w, h)
+                todo.append((j, (max(int(h * scales[j]), 1), max(int(w * scales[j]), 1))))
+        if todo:
+            for (j, _), small in zip(todo, resize_pages([devs[j] for j, _ in todo], [s for _, s in todo])):
+                devs[j] = small
+        caps = None if capacities is None else [int(capacities[k]) for k in live]
+        blob, offsets, out_bytes = page_table(devs, quality, caps)
+        mcus, blocks, intervals, coef_b, stream_b, iv_b = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3)
+                                                                        for p in devs])
+        coef = _grown(scratch, "coef", coef_b // 2, torch.int16, device)
+        bits = _grown(scratch, "stream", stream_b // 4, torch.int32, device)
+        ivals = _grown(scratch, "intervals", iv_b // 4, torch.int32, device)
+        files = _grown(scratch, "out", out_bytes, torch.uint8, device)
+        lengths = _grown(scratch, "lengths", len(devs), torch.int32, device)
+        blob_dev = imaging._stage_blob(blob, device)
+        _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, len(devs), mcus, blocks, intervals, coef.data_ptr(),
+                                             bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
+                                             lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
+        # the lengths first (one small copy), then the files' bytes, packed on the device, in one copy
+        pin_len = _grown(scratch, "pin_lengths", len(devs), torch.int32, pinned=True)
+        pin_len[: len(devs)].copy_(lengths[: len(devs)], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        sizes = pin_len[: len(devs)].tolist()
+        good = [j for j, n in enumerate(sizes) if n >= 0]
+        total = sum(sizes[j] for j in good)
+        host = None
+        if total:
+            packed = torch.cat([files[offsets[j] : offsets[j] + sizes[j]] for j in good])
+            pin = _grown(scratch, "pin_bytes", total, torch.uint8, pinned=True)
+            pin[:total].copy_(packed, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            host = pin[:total].numpy()
+        at = 0
+        for j, k in enumerate(live):
+            p = devs[j]
+            if sizes[j] < 0:
+                cap = caps[j] if caps is not None else p.numel()
+                out[k] = _lib.YmkError(f"page {k}: the JPEG file does not fit its capacity of {cap} bytes")
+                continue
+            out[k] = EncodedJpeg(host[at : at + sizes[j]].tobytes(), int(p.shape[1]), int(p.shape[0]), p.dim() == 2, float(scales[j]))
+            at += sizes[j]
+    return out
+
+
+def encode_jpeg(page, image_quality: str = "high", stream=None) -> EncodedJpeg:
+    """One page; raises what `encode_jpeg_pages` would have put in its place.  The file's capacity is the page's raw byte
+    count, and the header alone takes about 620 bytes (330 for a grey page): a colour page below roughly 15 x 15 pixels, or noise
+    that does not compress, raises YmkError here and in `serve(jpeg=...)` - `encode_jpeg_pages(..., capacities=[...])` gives
+    such a page the room it needs."""
+    res = encode_jpeg_pages([page], image_quality, stream)[0]
+    if isinstance(res, BaseException):
+        raise res
+    return res

@@ -14,7 +14,8 @@ leaves the device mostly idle, so `DocumentAnalyzer.serve` runs the page loop as
     tables          layout boxes (host), table-structure forward over all table crops            HIP stream
     cells           row / column / span filters, cell grids                                      host
     finish          word -> cell / paragraph aggregation and reading order, per page             host
-    render          serve(overlays=True) only: both overlay images of every page of the wave      HIP stream
+    render          serve(overlays=True) / serve(jpeg=...) only: both overlay images and / or the
+                    JPEG file of every page of the wave                                           HIP stream
 
 The host halves are their own stages on purpose: a thread that owns a network only ever launches - it never sits in box
 logic or string decoding while its stream runs dry (measured: with crop planning / decode inside the recognise stage
@@ -27,10 +28,10 @@ stream fit the eight hardware queues the package asks the HIP runtime for.  Wave
 waves are between upload and aggregation (a ring of pinned map buffers per wave slot), which bounds host and device
 memory.
 
-`render` is not one of the nine: its thread and stream are started by the first job that asks for overlays, and only the
-waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all canvases
-of a wave (two per page) with two launches (utils/visualizer.py: render_wave); a job without overlays runs exactly the stages
-above.
+`render` is not one of the nine: its thread and stream are started by the first job that asks for overlays or JPEG files, and
+only the waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all
+canvases of a wave (two per page) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
+as JPEG files with three (yomitoku_amd/jpeg.py: encode_jpeg_pages); a job with neither runs exactly the stages above.
 
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
 process while holding the GIL - measured 100-180 ms with the results of a few hundred pages alive, six times in a
@@ -103,10 +104,11 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False, options=None):
+    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None):
         self.results = {}
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, ocr overlay, layout overlay): the waves visit the render stage
+        self.jpeg = jpeg  # None or a preset name: the entries end with the page's EncodedJpeg, made in the render stage too
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -157,6 +159,15 @@ def _switch_interval(seconds):
             if _switch_users == 0 and _switch_saved is not None:
                 sys.setswitchinterval(_switch_saved)
                 _switch_saved = None
+
+
+def check_jpeg_preset(jpeg):
+    """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
+    public entry points before a source is read."""
+    from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
+
+    if jpeg is not None and (not isinstance(jpeg, str) or jpeg not in IMAGE_QUALITY_PRESETS):
+        raise ValueError(f"unknown jpeg preset {jpeg!r}: None or one of {sorted(IMAGE_QUALITY_PRESETS)}")
 
 
 def _run_stage(stream, wave, fn, *args):
@@ -280,8 +291,9 @@ class PagePipeline:
                 a._stage_split(wave)
 
     def _render_loop(self):
-        """The render stage: waves of overlays jobs, after aggregation.  Turns every page's schema into (schema, ocr overlay,
-        layout overlay); a page whose drawing fails - or every page of the wave, when the launches fail - gets the exception."""
+        """The render stage: waves of overlays and / or jpeg jobs, after aggregation.  Turns every page's schema into (schema,
+        ocr overlay, layout overlay), (schema, EncodedJpeg) or (schema, ocr overlay, layout overlay, EncodedJpeg); a page whose
+        drawing or encoding fails - or every page of the wave, when the launches fail - gets the exception."""
         stream = None
         if self._gpu:
             torch.cuda.set_device(self.device)
@@ -293,19 +305,24 @@ class PagePipeline:
             t_start = time.perf_counter()
             job, results = wave.job, wave.results
             try:
-                try:
-                    images = _run_stage(stream, wave, self.analyzer._stage_render, wave, results)
-                except BaseException as exc:  # noqa: BLE001 - delivered to the pages' result slots
-                    logger.error("wave %d failed in the render stage: %s: %s", wave.seq, type(exc).__name__, exc)
-                    images = [exc] * len(wave)
+                products = []  # per product of the job, per page: a tuple of entry members, or the exception
+                for wanted, fn in ((job.overlays, "_stage_render"), (job.jpeg, "_stage_jpeg")):
+                    if not wanted:
+                        continue
+                    try:
+                        products.append(_run_stage(stream, wave, getattr(self.analyzer, fn), wave, results))
+                    except BaseException as exc:  # noqa: BLE001 - delivered to the pages' result slots
+                        logger.error("wave %d failed in the render stage: %s: %s", wave.seq, type(exc).__name__, exc)
+                        products.append([exc] * len(wave))
                 for k, idx in enumerate(wave.ids):
+                    failed = next((made[k] for made in products if isinstance(made[k], BaseException)), None)
                     if isinstance(results[k], BaseException):
                         job.results[idx] = results[k]
-                    elif isinstance(images[k], BaseException):
-                        logger.error("page %d failed in the render stage: %s: %s", idx, type(images[k]).__name__, images[k])
-                        job.results[idx] = images[k]
+                    elif failed is not None:
+                        logger.error("page %d failed in the render stage: %s: %s", idx, type(failed).__name__, failed)
+                        job.results[idx] = failed
                     else:
-                        job.results[idx] = (results[k],) + tuple(images[k])
+                        job.results[idx] = (results[k],) + tuple(m for made in products for m in made[k])
                 if self.trace is not None:
                     self.trace.append(("render", wave.seq, len(wave), t_start, time.perf_counter()))
             finally:
@@ -345,7 +362,7 @@ class PagePipeline:
                 except Exception as exc:  # noqa: BLE001 - aggregation is per page: only this page fails
                     logger.error("page %d failed in aggregation: %s: %s", idx, type(exc).__name__, exc)
                     done.append(exc)
-            if job.overlays:  # the render stage writes the entries and hands the slot back
+            if job.overlays or job.jpeg:  # the render stage writes the entries and hands the slot back
                 wave.results = done
                 self._render_q.put(wave)
                 return
@@ -382,7 +399,7 @@ class PagePipeline:
         self._q["detect"].put(wave)
         self._q["layout"].put(wave)
 
-    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None) -> List:
+    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -391,13 +408,17 @@ class PagePipeline:
         `analyze_pages` returns for the page with visualize=True everywhere, as arrays the caller owns; a failed page's entry
         stays the bare exception.  The waves of such a job pass through the render stage, whose thread the first such job
         starts; a job without overlays runs what it always ran.
+        jpeg: None, or a preset name of the searchable PDF ("high", "middle", "low"; anything else is a ValueError before a
+        source is read): a page's entry ends with its EncodedJpeg (yomitoku_amd/jpeg.py) - (schema, EncodedJpeg), or (schema, ocr
+        overlay, layout overlay, EncodedJpeg) - encoded in the render stage from the clean page, never from a canvas.
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
 
+        check_jpeg_preset(jpeg)
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job(overlays=overlays, options=options)
-            if job.overlays:
+            job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg)
+            if job.overlays or job.jpeg:
                 self._start_render()
             n = 0
             origin = []  # page id -> (source index, frame index)
@@ -526,8 +547,9 @@ class StageAnalyzer:
 
     `_stage_finish(wave, k)` (host, subclass) returns page k's schema from dets / recs / lay_parsed / lays / imgs and the job
     (`wave.job.options`, `wave.job.overlays`); `_stage_render(wave, results)` (GPU, here; overlays jobs only) returns per page
-    the two pictures, from `_page_drawings(wave, k, results)` (subclass) and `wave.pages`.  `_nets()` (subclass): the modules
-    whose `model.close()` releases the analyzer's device memory.
+    the two pictures, from `_page_drawings(wave, k, results)` (subclass) and `wave.pages`; `_stage_jpeg(wave, results)` (GPU,
+    here; jpeg jobs only) returns per page a 1-tuple with its EncodedJpeg, from `wave.pages` and `wave.job.jpeg`.  `_nets()`
+    (subclass): the modules whose `model.close()` releases the analyzer's device memory.
 
     `handover`: None, or an object that sees - and may replace - what one stage hands to the next, AFTER the stage has
     produced it at full cost (`_handed`; yomitoku_amd.testing.Handover): measurements and tests with seeded weights, whose
@@ -547,6 +569,7 @@ class StageAnalyzer:
         self.chain_priority = _chain_priorities()
         self.handover = None
         self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
+        self._jpeg_scratch = {}  # wave slot -> the encoder's device and pinned buffers, made when the slot first needs them (serve(jpeg=...))
         self._pipeline = None
 
     # ---- the two concurrent chains, each on its own HIP stream
@@ -629,6 +652,23 @@ class StageAnalyzer:
                 out[k] = (images[2 * j], images[2 * j + 1])
         return out
 
+    def _stage_jpeg(self, wave, results, scratch=None):
+        """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`), an exception for a page
+        that could not be encoded, None for a page that had already failed.  All pages of the wave are encoded together on
+        the calling thread's stream (yomitoku_amd/jpeg.py: encode_jpeg_pages) from `wave.pages` - the clean pages: the
+        overlays are drawn on copies - with `scratch`, by default the wave slot's."""
+        from .jpeg import encode_jpeg_pages
+
+        out = [None] * len(wave)
+        live = [k for k in range(len(wave)) if not isinstance(results[k], BaseException)]
+        if live:
+            if scratch is None:
+                scratch = self._jpeg_scratch.setdefault(wave.ring, {})
+            files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch)
+            for k, made in zip(live, files):
+                out[k] = made if isinstance(made, BaseException) else (made,)
+        return out
+
     # ---- one wave at a time (`analyze_pages`, `parse_pages`): the same stage methods as two concurrent chains
     def _recognize_wave(self, wave):
         self._stage_crops(wave)
@@ -661,7 +701,7 @@ class StageAnalyzer:
         return wave
 
     # ---- the pipeline of this analyzer
-    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None):
+    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -669,7 +709,7 @@ class StageAnalyzer:
                 pipe.close()
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -
@@ -679,6 +719,7 @@ class StageAnalyzer:
             self._pipeline.close()
             self._pipeline = None
         self._render_pinned.clear()
+        self._jpeg_scratch.clear()
         self.text_recognizer.close_replicas()
         if release_models:
             for module in self._nets():

@@ -31,6 +31,7 @@ from __future__ import annotations
 import unicodedata
 import zlib
 from io import BytesIO
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -300,16 +301,26 @@ def _as_pil(image) -> Image.Image:
     return Image.fromarray(np.ascontiguousarray(arr))
 
 
+def _is_encoded(image) -> bool:
+    """An entry that already is a JPEG file: yomitoku_amd.jpeg.EncodedJpeg, recognised by its fields (`data` bytes, `width`,
+    `height`, `grey`, `scale`) so that this module needs neither torch nor the HIP library."""
+    return isinstance(getattr(image, "data", None), (bytes, bytearray)) and all(hasattr(image, a) for a in ("width", "height", "grey", "scale"))
+
+
 def _scaled_document(doc, scale: float):
+    """What `text_layer` reads of `doc`, every coordinate times `scale`: a plain view, not a copy of the schema - the schema's
+    boxes are integers and refuse the fractions a scale like 1500 / 1600 leaves."""
     if scale == 1.0:
         return doc
-    doc = doc.model_copy(deep=True)
-    boxes = [*doc.paragraphs, *(c for t in doc.tables for c in t.cells), *(p for f in doc.figures for p in f.paragraphs)]
-    for el in boxes:
-        el.box = [v * scale for v in el.box]
-    for w in doc.words:
-        w.points = [[x * scale, y * scale] for x, y in w.points]
-    return doc
+
+    def boxed(el, **more):
+        return SimpleNamespace(order=getattr(el, "order", None), box=[v * scale for v in el.box], direction=getattr(el, "direction", None), **more)
+
+    return SimpleNamespace(
+        paragraphs=[boxed(p) for p in doc.paragraphs],
+        tables=[SimpleNamespace(order=t.order, cells=[boxed(c, row=c.row, col=c.col) for c in t.cells]) for t in doc.tables],
+        figures=[SimpleNamespace(order=f.order, paragraphs=[boxed(p) for p in f.paragraphs]) for f in doc.figures],
+        words=[SimpleNamespace(points=[[x * scale, y * scale] for x, y in w.points], content=w.content, direction=w.direction) for w in doc.words])
 
 
 def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = "high") -> bytes:
@@ -319,20 +330,24 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
     kids = []
     preset = IMAGE_QUALITY_PRESETS.get(image_quality, IMAGE_QUALITY_PRESETS["high"])
     for image, doc in zip(images, docs):
-        image = _as_pil(image)
-        scale = 1.0
-        if preset["max_long_side"] is not None and max(image.size) > preset["max_long_side"]:
+        if _is_encoded(image):  # a finished JPEG (yomitoku_amd.jpeg.EncodedJpeg): embedded as it is, `image_quality` does not apply
+            data, w, h, grey, scale = bytes(image.data), int(image.width), int(image.height), bool(image.grey), float(image.scale)
+        else:
+            image = _as_pil(image)
+            scale = 1.0
+            if preset["max_long_side"] is not None and max(image.size) > preset["max_long_side"]:
+                w, h = image.size
+                scale = preset["max_long_side"] / max(w, h)
+                image = image.resize((int(w * scale), int(h * scale)), Image.LANCZOS)
+            grey = image.mode == "L"
+            if not grey and image.mode != "RGB":
+                image = image.convert("RGB")
+            jpeg = BytesIO()
+            image.save(jpeg, format="JPEG", quality=preset["jpeg_quality"])
+            data = jpeg.getvalue()
             w, h = image.size
-            scale = preset["max_long_side"] / max(w, h)
-            image = image.resize((int(w * scale), int(h * scale)), Image.LANCZOS)
-        grey = image.mode == "L"
-        if not grey and image.mode != "RGB":
-            image = image.convert("RGB")
-        jpeg = BytesIO()
-        image.save(jpeg, format="JPEG", quality=preset["jpeg_quality"])
-        w, h = image.size
         xobject = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ColorSpace /Device{'Gray' if grey else 'RGB'} "
-                                 "/BitsPerComponent 8 /Filter /DCTDecode", jpeg.getvalue(), compress=False)
+                                 "/BitsPerComponent 8 /Filter /DCTDecode", data, compress=False)
         contents = pdf.add_stream("", _content_stream(w, h, text_layer(_scaled_document(doc, scale), h), supplementary), compress=True)
         kids.append(pdf.add((f"<< /Type /Page /Parent {pages} 0 R /MediaBox [0 0 {w} {h}] /Contents {contents} 0 R "
                              f"/Resources << /XObject << /Im0 {xobject} 0 R >> /Font << /F1 {font} 0 R >> >> >>").encode("ascii")))
@@ -344,7 +359,9 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
 
 def create_searchable_pdf(images: List, docs: List, output_path: str, font_path: Optional[str] = None, image_quality: str = "high"):
     """Write `images` (PIL images; BGR arrays are taken too) with the words of `docs` (DocumentAnalyzerSchema, one per image)
-    as an invisible text layer to `output_path`.  utils/searchable_pdf.py:74."""
+    as an invisible text layer to `output_path`.  utils/searchable_pdf.py:74.  An entry of `images` that is an EncodedJpeg
+    (yomitoku_amd/jpeg.py; what `DocumentAnalyzer.serve(jpeg=...)` returns) is embedded as it is: size and colour space come
+    from the object, the words are scaled by its `scale`, and `image_quality` is ignored for that entry."""
     data = searchable_pdf_bytes(images, docs, image_quality)
     with open(output_path, "wb") as f:
         f.write(data)
