@@ -264,7 +264,7 @@ int ymk_overlay_cull_pass(void);
  *     words 5-7   first MCU, first block, first restart interval of the page (the pages' are numbered one after the other)
  *     words 8-9   byte offset of the page's file in out_dev, low / high           word 10  capacity of that file in bytes
  *     word 11-12  BYTE offset in the blob and length of the file's header (ymk_jpeg_header)
- *     word 13     WORD offset in the blob of the page's 128 quantisation values (ymk_jpeg_quant_tables)      words 14-15  0
+ *     word 13     WORD offset in the blob of the page's 128 quantisation values (ymk_jpeg_quant_tables)      words 14-15  0 (14: see *_opt)
  *   A record that does not fit (sizes, indices beyond the totals passed, offsets beyond the blob or out_bytes) is ignored, never
  *   trusted: its page gets length -1.
  * Scratch and output are the caller's; ymk_jpeg_scratch_bytes sizes them from HOST arrays h, w, channels: sizes6_out = total
@@ -294,6 +294,43 @@ int ymk_jpeg_compact(const int* blob_dev, int64_t blob_words, int n_pages, const
 int ymk_jpeg_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
                           int64_t total_intervals, int16_t* coef_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
                           unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream);
+/* Optimised Huffman tables, opt-in (encode_jpeg_pages(optimize=True), serve(jpeg_optimize=True); tests/jpeg_opt_ref.py is the
+ * definition; DESIGN.md, "JPEG encoder", has the rule): the same coefficients coded with tables made for each page, libjpeg's
+ * `optimize` rule, byte for byte.  The entries above do what they did; these stand next to them.
+ * Page table: as above, except that the header of words 11-12 comes from ymk_jpeg_header_opt - it has no DHT segments - and
+ *   word 14 holds the bytes of it that stand before their place (SOI .. SOF0; the rest is DRI, SOS).
+ * ymk_jpeg_header_opt: that header into the HOST buffer `out`, *split_out = word 14; returns its length, -1 on error.
+ * ymk_jpeg_scratch_bytes_opt: sizes9_out = the six of ymk_jpeg_scratch_bytes with stream_dev at
+ *   YMK_JPEG_BLOCK_STREAM_BYTES_OPT per block (a page's own DC code may have 16 bits, Annex K's at most 11: a block's worst case
+ *   is 16 + 11 + 63 * 26 = 1665 bits), then the bytes of hist_dev and of tables_dev (each int32 [n_pages][2][256 + 16] =
+ *   YMK_JPEG_TABLE_WORDS per page: luminance, chrominance; 256 AC entries, then 16 DC entries) and of dht_dev
+ *   (YMK_JPEG_DHT_BYTES per page: an int32 length, then the page's DHT segments, DC 0, AC 0, DC 1, AC 1).  All 4-byte aligned.
+ * ymk_jpeg_histogram: hist_dev zeroed on `stream`, then the symbols ymk_jpeg_entropy would emit for coef_dev counted into it;
+ *   one wave per interval, integer atomicAdd per page.
+ * ymk_jpeg_optimal_tables: hist_dev -> tables_dev (symbol -> code | length << 16, 0: no code) and dht_dev; one workgroup per
+ *   page, one wave per table.  Any counts are accepted; a table without a symbol has no code.
+ * ymk_jpeg_entropy_opt / ymk_jpeg_compact_opt: the two stages with the pages' tables / DHT records.  An entry of tables_dev with a
+ *   length above 16 is ignored, so that no block outgrows its reservation whatever tables_dev holds.
+ * ymk_jpeg_encode_pages_opt: the five stages in order on `stream`.  Nothing is allocated, nothing waited for. */
+#define YMK_JPEG_BLOCK_STREAM_BYTES_OPT 212
+#define YMK_JPEG_TABLE_WORDS 544
+#define YMK_JPEG_DHT_BYTES 656
+int ymk_jpeg_header_opt(int h, int w, int channels, int quality, unsigned char* out, int capacity, int* split_out);
+int ymk_jpeg_scratch_bytes_opt(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes9_out);
+int ymk_jpeg_histogram(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
+                       int64_t total_intervals, int* hist_dev, void* stream);
+int ymk_jpeg_optimal_tables(const int* blob_dev, int64_t blob_words, int n_pages, const int* hist_dev, uint32_t* tables_dev,
+                            unsigned char* dht_dev, void* stream);
+int ymk_jpeg_entropy_opt(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
+                         const uint32_t* tables_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
+                         int64_t total_intervals, void* stream);
+int ymk_jpeg_compact_opt(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* stream_dev, int64_t stream_bytes,
+                         int64_t total_blocks, const int* intervals_dev, int64_t total_intervals, const unsigned char* dht_dev,
+                         unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream);
+int ymk_jpeg_encode_pages_opt(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
+                              int64_t total_intervals, int16_t* coef_dev, int* hist_dev, uint32_t* tables_dev, unsigned char* dht_dev,
+                              uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, unsigned char* out_dev, int64_t out_bytes,
+                              int* lengths_dev, void* stream);
 /* ymk_pil_resize_u8: Pillow's two-pass 8-bit resample (as ymk_pil_resize_to_chw: 22-bit coefficients, 1 << 21 bias, clip to
  *   uint8 between the passes) for n images in one launch, written as uint8 [oh][ow][C] in the source's channel order.  blob_dev:
  *   n records of YMK_PIL_RESIZE_U8_WORDS int32 words {source address low, high; H; W; C (1 | 3); oh; ow; ksize_x; ksize_y; word

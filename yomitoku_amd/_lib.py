@@ -70,6 +70,16 @@ SIGNATURES = {
                                  c_void_p]),
     "ymk_jpeg_encode_pages": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                       c_void_p, c_int64, c_void_p, c_void_p]),
+    "ymk_jpeg_header_opt": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_int)]),
+    "ymk_jpeg_scratch_bytes_opt": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_jpeg_histogram": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "ymk_jpeg_optimal_tables": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ymk_jpeg_entropy_opt": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                     c_void_p]),
+    "ymk_jpeg_compact_opt": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                     c_int64, c_void_p, c_void_p]),
+    "ymk_jpeg_encode_pages_opt": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

@@ -19,7 +19,19 @@
 //                         does not fit the page's capacity is not written at all; its length stays -1.
 //   k_pil_resize_u8       k_pil_resize_batch (ymk_image.hip) with uint8 [oh][ow][C] outputs of differing sizes.
 //
-// Nothing is allocated and nothing waited for; no workgroup waits for another (the three stages are three launches).
+// Optimised Huffman tables (ymk_jpeg_encode_pages_opt; the definition is tests/jpeg_opt_ref.py) put two launches between the
+// coefficients and the entropy stage, and the entropy and compaction stages run in their OPT form:
+//   k_jpeg_histogram      k_jpeg_entropy's decomposition (one wave per interval, 64 blocks at a time in LDS, the same DC
+//                         predecessor): the symbols the coder will emit are counted in LDS, the non-zero bins added to the page's
+//                         histogram (integer atomicAdd: the sums do not depend on the order).
+//   k_jpeg_optimal_tables one workgroup per page, one wave per table.  libjpeg's rule: the two rarest symbols are merged until
+//                         one is left (two wave arg-min reductions per merge, the tie rule in the key; a subtree id per symbol
+//                         instead of libjpeg's chain), the lengths limited to 16 bits (Annex K.3), the codes assigned (Annex C).
+//                         Output: the page's symbol -> code table in c_luts' layout, and its DHT segments as bytes.
+//   k_jpeg_entropy<true>  s_lut filled from the page's table; YMK_JPEG_BLOCK_STREAM_BYTES_OPT per block (a DC code may have 16 bits).
+//   k_jpeg_compact<true>  the header is the blob's up to SOF0, the page's DHT bytes, the blob's from DRI.
+//
+// Nothing is allocated and nothing waited for; no workgroup waits for another (every stage is a launch of its own).
 #include "ymk_common.h"
 
 #include "../../include/ymk.h"
@@ -31,6 +43,14 @@ constexpr int JP_BLOCK_WORDS = YMK_JPEG_BLOCK_STREAM_BYTES / 4;  // 32-bit words
 constexpr int JP_WAVES = 4;                                      // MCUs per block of k_jpeg_coefficients
 static_assert(YMK_JPEG_BLOCK_STREAM_BYTES % 4 == 0 && YMK_JPEG_BLOCK_STREAM_BYTES * 8 >= 22 + 63 * 26,
               "a block's worst case: a 11 + 11 bit DC and 63 AC symbols of 16 + 10 bits");
+constexpr int JP_BLOCK_WORDS_OPT = YMK_JPEG_BLOCK_STREAM_BYTES_OPT / 4;
+static_assert(YMK_JPEG_BLOCK_STREAM_BYTES_OPT % 4 == 0 && YMK_JPEG_BLOCK_STREAM_BYTES_OPT * 8 >= 27 + 63 * 26,
+              "with a page's own tables any code may have 16 bits: a 16 + 11 bit DC and 63 AC symbols of 16 + 10 bits");
+constexpr int JP_LUT_WORDS = YMK_JPEG_TABLE_WORDS;  // one page's histogram or code table: [2][256 + 16]
+constexpr int JP_DHT_BYTES = YMK_JPEG_DHT_BYTES;    // one page's DHT record: an int32 length, then the segments
+constexpr int JP_SEG_BYTES = 2 + 2 + 1 + 16 + 256;  // the longest DHT segment
+static_assert(JP_LUT_WORDS == 2 * (256 + 16) && JP_DHT_BYTES % 4 == 0 && JP_DHT_BYTES >= 4 + 2 * (JP_SEG_BYTES - 240) + 2 * JP_SEG_BYTES,
+              "two DC segments of at most 16 symbols and two AC segments of at most 256 behind the length");
 
 // ------------------------------------------------------------------------------------------------ tables (Annex K)
 struct HuffSpec {
@@ -123,7 +143,8 @@ static void put_segment(std::vector<unsigned char>& out, int marker, const std::
 }
 
 // SOI, APP0, DQT, SOF0, DHT, DRI, SOS: everything before the scan's first byte
-static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quality) {
+// dht false: without the DHT segments, *split = the bytes before their place
+static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quality, bool dht = true, int* split = nullptr) {
   int q[128];
   quant_tables(quality, q);
   std::vector<unsigned char> out = {0xff, 0xd8};
@@ -142,7 +163,8 @@ static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quali
   put_segment(out, 0xc0, sof);
   const HuffSpec* specs[4] = {&DC_LUMA, &AC_LUMA, &DC_CHROMA, &AC_CHROMA};
   const unsigned char ids[4] = {0x00, 0x10, 0x01, 0x11};
-  for (int t = 0; t < (grey ? 2 : 4); ++t) {
+  if (split) *split = (int)out.size();
+  for (int t = 0; dht && t < (grey ? 2 : 4); ++t) {
     std::vector<unsigned char> p = {ids[t]};
     p.insert(p.end(), specs[t]->bits, specs[t]->bits + 16);
     p.insert(p.end(), specs[t]->vals, specs[t]->vals + specs[t]->n);
@@ -166,7 +188,7 @@ struct JpegPage {
   const unsigned char* src;
   int h, w, ch, mcu_w, mcu_h, per;  // per: blocks per MCU
   long long first_mcu, first_block, first_interval, out_off;
-  int capacity, hdr_off, hdr_len, q_off;
+  int capacity, hdr_off, hdr_len, q_off, hdr_split;  // hdr_split (word 14): the header's bytes before the DHT segments' place
 };
 // Record p, checked against the limits: a record that does not fit is no page (never trusted).
 __device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const JpegLimits& lim, int p, JpegPage& g) {
@@ -180,6 +202,7 @@ __device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const Jp
   g.first_mcu = r[5], g.first_block = r[6], g.first_interval = r[7];
   g.out_off = (long long)(((unsigned long long)(unsigned)r[9] << 32) | (unsigned long long)(unsigned)r[8]);
   g.capacity = r[10], g.hdr_off = r[11], g.hdr_len = r[12], g.q_off = r[13];
+  g.hdr_split = min(max(r[14], 0), max(g.hdr_len, 0));
   const long long mcus = (long long)g.mcu_w * g.mcu_h;
   if (g.first_mcu < 0 || g.first_block < 0 || g.first_interval < 0 || g.first_mcu + mcus > lim.total_mcus ||
       g.first_block + mcus * g.per > lim.total_blocks || g.first_interval + g.mcu_h > lim.total_intervals)
@@ -389,19 +412,29 @@ __device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
   return v;
 }
 
+// OPT: the codes are the page's own (`tables`, k_jpeg_optimal_tables) and a block has JP_BLOCK_WORDS_OPT words
+template <bool OPT>
 __global__ __launch_bounds__(64) void k_jpeg_entropy(const int* __restrict__ blob, JpegLimits lim, int n_pages,
                                                      const short* __restrict__ coef, unsigned* __restrict__ stream,
-                                                     int* __restrict__ intervals) {
+                                                     int* __restrict__ intervals, const unsigned* __restrict__ tables) {
+  constexpr int BLOCK_WORDS = OPT ? JP_BLOCK_WORDS_OPT : JP_BLOCK_WORDS;
   __shared__ unsigned s_lut[2][256 + 16];
   __shared__ __align__(16) short s_coef[64 * EN_PITCH];  // written as 32-bit words: a block starts at a multiple of 132 bytes
   const int lane = threadIdx.x;
-  for (int i = lane; i < 2 * (256 + 16); i += 64) (&s_lut[0][0])[i] = (&c_luts.e[0][0])[i];
+  if (!OPT)
+    for (int i = lane; i < 2 * (256 + 16); i += 64) (&s_lut[0][0])[i] = (&c_luts.e[0][0])[i];
   JpegPage g;
   const long long iv = blockIdx.x;
-  if (jpeg_find(blob, lim, n_pages, iv, true, g) < 0) return;  // the whole block
-  const int nb = g.mcu_w * g.per;                                // blocks of the interval: <= 1024 * 6
+  const int page = jpeg_find(blob, lim, n_pages, iv, true, g);
+  if (page < 0) return;  // the whole block
+  if (OPT)               // a length above 16 is not one k_jpeg_optimal_tables writes: such an entry codes nothing
+    for (int i = lane; i < JP_LUT_WORDS; i += 64) {
+      const unsigned e = tables[(size_t)page * JP_LUT_WORDS + i];
+      (&s_lut[0][0])[i] = (e >> 16) <= 16 ? e : 0u;
+    }
+  const int nb = g.mcu_w * g.per;  // blocks of the interval: <= 1024 * 6
   const long long blk0 = g.first_block + (iv - g.first_interval) * nb;
-  unsigned* out = stream + (size_t)blk0 * JP_BLOCK_WORDS;  // nb * JP_BLOCK_WORDS words are this interval's
+  unsigned* out = stream + (size_t)blk0 * BLOCK_WORDS;  // nb * BLOCK_WORDS words are this interval's
   int cum = 0, zeroed = 0;                                 // bits written so far (< 2^24); words zeroed so far
   for (int base = 0; base < nb; base += 64) {
     __syncthreads();  // the previous chunk's readers of s_coef (and, first time, the writers of s_lut)
@@ -428,7 +461,7 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(const int* __restrict__ blo
     const int len = active ? encode_block<false>(mine, pred, lut, nullptr) : 0;
     const int incl = wave_inclusive_scan(len, lane);
     const int total = __shfl(incl, 63);
-    const int need = (cum + total + 31) >> 5;  // <= nb * JP_BLOCK_WORDS: a block is at most 1660 bits
+    const int need = (cum + total + 31) >> 5;  // <= nb * BLOCK_WORDS: a block is at most 1660 (OPT: 1665) bits
     for (int wd = zeroed + lane; wd < need; wd += 64) out[wd] = 0;
     zeroed = max(zeroed, need);
     __syncthreads();  // the zeros are in memory before any lane ORs into them
@@ -462,15 +495,216 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(const int* __restrict__ blo
   }
 }
 
+// ------------------------------------------------------------------------------------------------ histograms
+// The symbols encode_block emits for block `c`, counted in `hist` (LDS, one class: 256 AC bins, then 16 DC bins).
+__device__ __forceinline__ void count_block(const short* c, int pred, int* hist) {
+  const int diff = min(max((int)c[0] - pred, -2047), 2047);
+  atomicAdd(hist + 256 + (32 - __clz(abs(diff))), 1);
+  int run = 0;
+  for (int k = 1; k < 64; ++k) {
+    const int v = min(max((int)c[k], -1023), 1023);
+    if (v == 0) {
+      ++run;
+      continue;
+    }
+    while (run > 15) {
+      atomicAdd(hist + 0xf0, 1);
+      run -= 16;
+    }
+    atomicAdd(hist + (run << 4 | (32 - __clz(abs(v)))), 1);
+    run = 0;
+  }
+  if (run > 0) atomicAdd(hist, 1);
+}
+
+// hist: int32 [n_pages][2][256 + 16], zero before the launch
+__global__ __launch_bounds__(64) void k_jpeg_histogram(const int* __restrict__ blob, JpegLimits lim, int n_pages,
+                                                       const short* __restrict__ coef, int* __restrict__ hist) {
+  __shared__ int s_hist[2][256 + 16];
+  __shared__ __align__(16) short s_coef[64 * EN_PITCH];
+  const int lane = threadIdx.x;
+  JpegPage g;
+  const long long iv = blockIdx.x;
+  const int page = jpeg_find(blob, lim, n_pages, iv, true, g);
+  if (page < 0) return;  // the whole block
+  for (int i = lane; i < JP_LUT_WORDS; i += 64) (&s_hist[0][0])[i] = 0;
+  const int nb = g.mcu_w * g.per;
+  const long long blk0 = g.first_block + (iv - g.first_interval) * nb;
+  for (int base = 0; base < nb; base += 64) {
+    __syncthreads();  // the previous chunk's readers of s_coef (and, first time, the zeros of s_hist)
+    for (int i = lane; i < 64 * 8; i += 64) {
+      const int blk = i >> 3, part = i & 7;
+      if (base + blk < nb) {
+        const uint4 v = *reinterpret_cast<const uint4*>(coef + (size_t)(blk0 + base + blk) * 64 + part * 8);
+        unsigned* d = reinterpret_cast<unsigned*>(&s_coef[blk * EN_PITCH + part * 8]);
+        d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+      }
+    }
+    __syncthreads();
+    const int b = base + lane;
+    if (b < nb) {
+      const int comp = g.per == 6 ? max(b % 6 - 3, 0) : 0;
+      const int prev = g.per == 1 ? b - 1 : (comp == 0 ? (b % 6 == 0 ? b - 3 : b - 1) : b - 6);  // as k_jpeg_entropy
+      const int pred = prev >= 0 ? coef[(size_t)(blk0 + prev) * 64] : 0;
+      count_block(&s_coef[lane * EN_PITCH], pred, s_hist[comp ? 1 : 0]);
+    }
+  }
+  __syncthreads();
+  int* mine = hist + (size_t)page * JP_LUT_WORDS;
+  for (int i = lane; i < JP_LUT_WORDS; i += 64) {
+    const int v = (&s_hist[0][0])[i];
+    if (v) atomicAdd(mine + i, v);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ optimal tables
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long t = __shfl_xor(v, o);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+
+// One workgroup per page, wave t makes table t of DC 0, AC 0, DC 1, AC 1 (a grey page: the first two; the other two come out
+// empty).  Symbol s = k * 64 + lane sits in register k of its lane; the reserved symbol 256 in lane 0.
+// Frequencies: a symbol's count is at most the symbols of a 16383 x 16383 page, 6 * 1024 * 1024 blocks of at most 64, and so is
+// the sum of all of them, 4.1e8: below libjpeg's 1e9 sentinel ("no symbol") and inside an int.  Counts from elsewhere are
+// clamped to that sum's range per symbol; whatever they are, the merges build a tree, so the lengths stay below 257.
+__global__ __launch_bounds__(256) void k_jpeg_optimal_tables(const int* __restrict__ blob, JpegLimits lim, int n_pages,
+                                                             const int* __restrict__ hist, unsigned* __restrict__ tables,
+                                                             unsigned char* __restrict__ dht) {
+  __shared__ int s_key[4][256];   // code length before limiting << 9 | symbol; INT_MAX: the symbol has no code
+  __shared__ int s_bits[4][260];  // codes of each length 0..256
+  __shared__ int s_first[4][17], s_cum[4][18];
+  __shared__ unsigned char s_seg[4][JP_SEG_BYTES + 3];
+  __shared__ int s_seglen[4];
+  const int t = threadIdx.x >> 6, lane = threadIdx.x & 63, page = blockIdx.x;
+  JpegPage g;
+  if (!jpeg_page(blob, lim, page, g)) return;  // the whole block
+  const int cls = t >> 1, ac = t & 1;
+  const int n = t < (g.ch == 3 ? 4 : 2) ? (ac ? 256 : 16) : 0;  // symbols this table may have
+  const int* src = hist + (size_t)page * JP_LUT_WORDS + cls * (256 + 16) + (ac ? 0 : 256);
+  unsigned freq[5];
+  int len[5], id[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const int s = k * 64 + lane;
+    freq[k] = k < 4 ? (s < n ? (unsigned)min(max(src[s], 0), 0x3fffffff) : 0u) : (lane == 0 ? 1u : 0u);
+    len[k] = 0, id[k] = s;
+  }
+  constexpr unsigned long long NONE = ~0ull;
+  for (int merge = 0; merge < 256; ++merge) {
+    // the smallest non-zero frequency, among equals the largest symbol: libjpeg scans upward with <=
+    unsigned long long k1 = NONE, k2 = NONE;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (freq[k]) k1 = min(k1, (unsigned long long)freq[k] << 32 | (unsigned)(0xffff - (k * 64 + lane)));
+    k1 = wave_min_u64(k1);
+    const int c1 = 0xffff - (int)(k1 & 0xffff);
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (freq[k] && k * 64 + lane != c1) k2 = min(k2, (unsigned long long)freq[k] << 32 | (unsigned)(0xffff - (k * 64 + lane)));
+    k2 = wave_min_u64(k2);
+    if (k2 == NONE) break;  // the same in every lane
+    const int c2 = 0xffff - (int)(k2 & 0xffff);
+    const unsigned long long sum64 = (k1 >> 32) + (k2 >> 32);
+    const unsigned sum = sum64 > 0xfffffffeull ? 0xfffffffeu : (unsigned)sum64;  // saturates on counts no page has: NONE stays free
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const int s = k * 64 + lane;
+      if (s == c1) freq[k] = sum;
+      if (s == c2) freq[k] = 0;
+      if (id[k] == c1 || id[k] == c2) ++len[k], id[k] = c1;  // both subtrees one bit longer, and one subtree from here on
+    }
+  }
+  for (int i = lane; i < 260; i += 64) s_bits[t][i] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const int s = k * 64 + lane;
+    if (s <= 256 && len[k] > 0) atomicAdd(&s_bits[t][min(len[k], 256)], 1);
+    if (k < 4) s_key[t][s] = len[k] > 0 ? (len[k] << 9 | s) : 0x7fffffff;
+  }
+  __syncthreads();
+  int longest = 0;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) longest = max(longest, min(len[k], 256));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
+  if (lane == 0) {  // tens of steps: Figure K.3, then the first code and the first place of every length
+    int* bits = s_bits[t];
+    for (int i = longest; i > 16; --i)
+      while (bits[i] > 0) {
+        int j = i - 2;
+        while (j > 0 && bits[j] == 0) --j;
+        if (j == 0) {  // not a tree's counts: not reached with lengths from the merges above
+          bits[i] = 0;
+          break;
+        }
+        bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
+      }
+    int top = 16;
+    while (top > 0 && bits[top] == 0) --top;
+    if (top > 0) --bits[top];  // the reserved symbol's code
+    int code = 0, at = 0;
+    for (int l = 1; l <= 16; ++l) {
+      s_first[t][l] = code, s_cum[t][l] = at;
+      code = (code + bits[l]) << 1, at += bits[l];
+    }
+    s_cum[t][17] = at;
+  }
+  __syncthreads();
+  const int total = min(max(s_cum[t][17], 0), n);
+  unsigned* lut = tables + (size_t)page * JP_LUT_WORDS + cls * (256 + 16) + (ac ? 0 : 256);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int s = k * 64 + lane, key = s_key[t][s];
+    unsigned entry = 0;
+    if (key != 0x7fffffff) {
+      int rank = 0;  // the symbol's place by (length before limiting, value)
+      for (int o = 0; o < 256; ++o) rank += s_key[t][o] < key;
+      if (rank < total) {
+        int l = 1;
+        while (l < 16 && rank >= s_cum[t][l + 1]) ++l;
+        entry = (unsigned)(s_first[t][l] + rank - s_cum[t][l]) | (unsigned)l << 16;
+        s_seg[t][5 + 16 + rank] = (unsigned char)s;
+      }
+    }
+    if (s < (ac ? 256 : 16)) lut[s] = entry;
+  }
+  if (lane < 16) s_seg[t][5 + lane] = (unsigned char)s_bits[t][lane + 1];
+  if (lane == 0) {
+    const int seg = n > 0 ? 5 + 16 + total : 0;
+    s_seg[t][0] = 0xff, s_seg[t][1] = 0xc4, s_seg[t][2] = (unsigned char)((seg - 2) >> 8), s_seg[t][3] = (unsigned char)((seg - 2) & 255);
+    s_seg[t][4] = (unsigned char)(ac << 4 | cls);
+    s_seglen[t] = seg;
+  }
+  __syncthreads();
+  unsigned char* rec = dht + (size_t)page * JP_DHT_BYTES;
+  int at = 4;
+  for (int u = 0; u < t; ++u) at += s_seglen[u];
+  for (int i = lane; i < s_seglen[t]; i += 64) rec[at + i] = s_seg[t][i];
+  if (threadIdx.x == 0) *reinterpret_cast<int*>(rec) = s_seglen[0] + s_seglen[1] + s_seglen[2] + s_seglen[3];
+}
+
 // ------------------------------------------------------------------------------------------------ compaction
+// OPT: the page's DHT record (k_jpeg_optimal_tables) stands between the header's two parts, and a block has JP_BLOCK_WORDS_OPT words
+template <bool OPT>
 __global__ __launch_bounds__(64) void k_jpeg_compact(const int* __restrict__ blob, JpegLimits lim, int n_pages,
                                                      const unsigned* __restrict__ stream, const int* __restrict__ intervals,
-                                                     unsigned char* __restrict__ out, int* __restrict__ lengths) {
+                                                     unsigned char* __restrict__ out, int* __restrict__ lengths,
+                                                     const unsigned char* __restrict__ dht) {
+  constexpr int BLOCK_WORDS = OPT ? JP_BLOCK_WORDS_OPT : JP_BLOCK_WORDS;
   const int lane = threadIdx.x;
   JpegPage g;
   const long long iv = blockIdx.x;
   const int p = jpeg_find(blob, lim, n_pages, iv, true, g);
   if (p < 0) return;
+  const unsigned char* dht_rec = OPT ? dht + (size_t)p * JP_DHT_BYTES : nullptr;
+  const int dht_len = OPT ? min(max(*reinterpret_cast<const int*>(dht_rec), 0), JP_DHT_BYTES - 4) : 0;
+  const int hdr_len = g.hdr_len + dht_len;  // SOI .. SOF0, the page's tables, DRI, SOS
   const int row = (int)(iv - g.first_interval), n_iv = g.mcu_h;
   long long before = 0, total = 0;
   for (int i = lane; i < n_iv; i += 64) {
@@ -483,18 +717,23 @@ __global__ __launch_bounds__(64) void k_jpeg_compact(const int* __restrict__ blo
     total += __shfl_xor(total, o);
     before += __shfl_xor(before, o);
   }
-  const long long file_len = (long long)g.hdr_len + total + 2LL * (n_iv - 1) + 2;
+  const long long file_len = (long long)hdr_len + total + 2LL * (n_iv - 1) + 2;
   if (file_len > g.capacity) return;  // lengths[p] stays -1 and not a byte of the page's output is written
   unsigned char* page_out = out + g.out_off;
   const long long cap = g.capacity;
   if (row == 0) {
     const unsigned char* hdr = reinterpret_cast<const unsigned char*>(blob) + g.hdr_off;
-    for (int i = lane; i < g.hdr_len; i += 64) page_out[i] = hdr[i];
+    if (OPT) {
+      for (int i = lane; i < hdr_len; i += 64)
+        page_out[i] = i < g.hdr_split ? hdr[i] : (i < g.hdr_split + dht_len ? dht_rec[4 + i - g.hdr_split] : hdr[i - dht_len]);
+    } else {
+      for (int i = lane; i < hdr_len; i += 64) page_out[i] = hdr[i];
+    }
   }
   const int nb = g.mcu_w * g.per;
-  const unsigned* src = stream + (size_t)(g.first_block + (long long)row * nb) * JP_BLOCK_WORDS;
-  const int nbytes = min(max(intervals[2 * iv], 0), nb * YMK_JPEG_BLOCK_STREAM_BYTES);
-  long long pos = (long long)g.hdr_len + before + 2LL * row;  // where this interval starts in the file
+  const unsigned* src = stream + (size_t)(g.first_block + (long long)row * nb) * BLOCK_WORDS;
+  const int nbytes = min(max(intervals[2 * iv], 0), nb * BLOCK_WORDS * 4);
+  long long pos = (long long)hdr_len + before + 2LL * row;  // where this interval starts in the file
   for (int wbase = 0; wbase * 4 < nbytes; wbase += 64) {
     const int wd = wbase + lane;
     const int valid = min(max(nbytes - wd * 4, 0), 4);
@@ -589,21 +828,49 @@ static void launch_coefficients(hipStream_t s, const int* blob, const JpegLimits
   hipLaunchKernelGGL(k_jpeg_coefficients, dim3(grid), dim3(JP_WAVES * 64), 0, s, blob, lim, n_pages, (short*)coef);
   YMK_HIP(hipGetLastError());
 }
+// tables: null = the Annex K codes; else the pages' own (k_jpeg_optimal_tables) and the larger reservation per block
 static void launch_entropy(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, const int16_t* coef, uint32_t* stream_dev,
-                           int64_t stream_bytes, int* intervals) {
+                           int64_t stream_bytes, int* intervals, const uint32_t* tables = nullptr) {
   YMK_CHECK(coef && ((uintptr_t)coef & 15) == 0 && stream_dev && ((uintptr_t)stream_dev & 3) == 0 && intervals, "null or misaligned scratch");
-  YMK_CHECK(stream_bytes >= lim.total_blocks * YMK_JPEG_BLOCK_STREAM_BYTES, "stream scratch smaller than ymk_jpeg_scratch_bytes says");
-  hipLaunchKernelGGL(k_jpeg_entropy, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const short*)coef,
-                     (unsigned*)stream_dev, intervals);
+  if (tables) {
+    YMK_CHECK(((uintptr_t)tables & 3) == 0, "misaligned tables");
+    YMK_CHECK(stream_bytes >= lim.total_blocks * YMK_JPEG_BLOCK_STREAM_BYTES_OPT, "stream scratch smaller than ymk_jpeg_scratch_bytes_opt says");
+    hipLaunchKernelGGL(k_jpeg_entropy<true>, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const short*)coef,
+                       (unsigned*)stream_dev, intervals, (const unsigned*)tables);
+  } else {
+    YMK_CHECK(stream_bytes >= lim.total_blocks * YMK_JPEG_BLOCK_STREAM_BYTES, "stream scratch smaller than ymk_jpeg_scratch_bytes says");
+    hipLaunchKernelGGL(k_jpeg_entropy<false>, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const short*)coef,
+                       (unsigned*)stream_dev, intervals, (const unsigned*)nullptr);
+  }
   YMK_HIP(hipGetLastError());
 }
+// dht: null = the header is the blob's; else the pages' DHT records go into it
 static void launch_compact(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, const uint32_t* stream_dev,
-                           int64_t stream_bytes, const int* intervals, unsigned char* out, int* lengths) {
+                           int64_t stream_bytes, const int* intervals, unsigned char* out, int* lengths, const unsigned char* dht = nullptr) {
   YMK_CHECK(stream_dev && intervals && out && lengths && lim.out_bytes >= 0, "null scratch / output");
-  YMK_CHECK(stream_bytes >= lim.total_blocks * YMK_JPEG_BLOCK_STREAM_BYTES, "stream scratch smaller than ymk_jpeg_scratch_bytes says");
+  YMK_CHECK(stream_bytes >= lim.total_blocks * (dht ? YMK_JPEG_BLOCK_STREAM_BYTES_OPT : YMK_JPEG_BLOCK_STREAM_BYTES),
+            "stream scratch smaller than ymk_jpeg_scratch_bytes says");
+  YMK_CHECK(((uintptr_t)dht & 3) == 0, "misaligned DHT records");
   YMK_HIP(hipMemsetAsync(lengths, 0xff, (size_t)n_pages * sizeof(int), s));  // -1 until a page's last interval is in place
-  hipLaunchKernelGGL(k_jpeg_compact, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const unsigned*)stream_dev,
-                     intervals, out, lengths);
+  if (dht)
+    hipLaunchKernelGGL(k_jpeg_compact<true>, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages,
+                       (const unsigned*)stream_dev, intervals, out, lengths, dht);
+  else
+    hipLaunchKernelGGL(k_jpeg_compact<false>, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages,
+                       (const unsigned*)stream_dev, intervals, out, lengths, (const unsigned char*)nullptr);
+  YMK_HIP(hipGetLastError());
+}
+static void launch_histogram(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, const int16_t* coef, int* hist) {
+  YMK_CHECK(coef && ((uintptr_t)coef & 15) == 0 && hist && ((uintptr_t)hist & 3) == 0, "null or misaligned scratch");
+  // on this stream, on every call: the caller's scratch holds the counts of its last wave
+  YMK_HIP(hipMemsetAsync(hist, 0, (size_t)n_pages * JP_LUT_WORDS * sizeof(int), s));
+  hipLaunchKernelGGL(k_jpeg_histogram, dim3((unsigned)lim.total_intervals), dim3(64), 0, s, blob, lim, n_pages, (const short*)coef, hist);
+  YMK_HIP(hipGetLastError());
+}
+static void launch_tables(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, const int* hist, uint32_t* tables,
+                          unsigned char* dht) {
+  YMK_CHECK(hist && tables && dht && (((uintptr_t)hist | (uintptr_t)tables | (uintptr_t)dht) & 3) == 0, "null or misaligned scratch");
+  hipLaunchKernelGGL(k_jpeg_optimal_tables, dim3((unsigned)n_pages), dim3(256), 0, s, blob, lim, n_pages, hist, (unsigned*)tables, dht);
   YMK_HIP(hipGetLastError());
 }
 
@@ -633,6 +900,34 @@ int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out,
   } catch (const std::exception& e) {
     ymk::set_error(e.what());
     return -1;
+  }
+}
+
+int ymk_jpeg_header_opt(int h, int w, int channels, int quality, unsigned char* out, int capacity, int* split_out) {
+  try {
+    YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
+    YMK_CHECK(split_out, "null output");
+    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, channels == 1, quality, false, split_out);
+    YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
+    std::memcpy(out, hdr.data(), hdr.size());
+    return (int)hdr.size();
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return -1;
+  }
+}
+
+int ymk_jpeg_scratch_bytes_opt(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes9_out) {
+  try {
+    YMK_CHECK(sizes9_out, "bad argument");
+    if (ymk_jpeg_scratch_bytes(h, w, channels, n_pages, sizes9_out)) return 1;
+    sizes9_out[4] = sizes9_out[1] * YMK_JPEG_BLOCK_STREAM_BYTES_OPT;
+    sizes9_out[6] = sizes9_out[7] = (int64_t)n_pages * YMK_JPEG_TABLE_WORDS * (int64_t)sizeof(int);
+    sizes9_out[8] = (int64_t)n_pages * YMK_JPEG_DHT_BYTES;
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
   }
 }
 
@@ -722,6 +1017,101 @@ int ymk_jpeg_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, 
     ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
     ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
     ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_histogram(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
+                       int64_t total_intervals, int* hist_dev, void* stream) {
+  try {
+    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    if (total_intervals == 0) {
+      YMK_CHECK(hist_dev, "null histograms");
+      YMK_HIP(hipMemsetAsync(hist_dev, 0, (size_t)n_pages * ymk::JP_LUT_WORDS * sizeof(int), (hipStream_t)stream));
+      return 0;
+    }
+    ymk::launch_histogram((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, hist_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_optimal_tables(const int* blob_dev, int64_t blob_words, int n_pages, const int* hist_dev, uint32_t* tables_dev,
+                            unsigned char* dht_dev, void* stream) {
+  try {
+    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, 0x7fffffffLL, 0x7fffffffLL, -1);
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    ymk::launch_tables((hipStream_t)stream, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_entropy_opt(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
+                         const uint32_t* tables_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
+                         int64_t total_intervals, void* stream) {
+  try {
+    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
+    if (n_pages == 0 || total_intervals == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    YMK_CHECK(tables_dev, "null tables");
+    ymk::launch_entropy((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_compact_opt(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* stream_dev, int64_t stream_bytes,
+                         int64_t total_blocks, const int* intervals_dev, int64_t total_intervals, const unsigned char* dht_dev,
+                         unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream) {
+  try {
+    YMK_CHECK(out_bytes >= 0, "bad argument");
+    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, out_bytes);
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    if (total_intervals == 0) {
+      YMK_CHECK(lengths_dev, "null lengths");
+      YMK_HIP(hipMemsetAsync(lengths_dev, 0xff, (size_t)n_pages * sizeof(int), (hipStream_t)stream));
+      return 0;
+    }
+    YMK_CHECK(dht_dev, "null DHT records");
+    ymk::launch_compact((hipStream_t)stream, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_encode_pages_opt(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
+                              int64_t total_intervals, int16_t* coef_dev, int* hist_dev, uint32_t* tables_dev, unsigned char* dht_dev,
+                              uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, unsigned char* out_dev, int64_t out_bytes,
+                              int* lengths_dev, void* stream) {
+  try {
+    YMK_CHECK(out_bytes >= 0, "bad argument");
+    const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, total_intervals, out_bytes);
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    YMK_CHECK(total_mcus > 0 && total_intervals > 0, "pages without MCUs");
+    YMK_CHECK(tables_dev && dht_dev, "null scratch");
+    const hipStream_t s = (hipStream_t)stream;
+    ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
+    ymk::launch_histogram(s, blob_dev, lim, n_pages, coef_dev, hist_dev);
+    ymk::launch_tables(s, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
+    ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
+    ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
     return 0;
   } catch (const std::exception& e) {
     ymk::set_error(e.what());

@@ -511,7 +511,7 @@ class DocumentAnalyzer(StageAnalyzer):
         return reading_order_visualizer(page if layout is None else layout, results, to_host=False)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False, jpeg=None):
+              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -530,13 +530,16 @@ class DocumentAnalyzer(StageAnalyzer):
         `jpeg`: a property of the job too - None, or a preset of the searchable PDF ("high", "middle", "low"; anything else is
         a ValueError before a source is read): a page's entry ends with its EncodedJpeg (yomitoku_amd/jpeg.py), i.e. (schema,
         EncodedJpeg) or (schema, ocr overlay, layout overlay, EncodedJpeg) - the file `searchable_pdf_bytes` embeds as it is,
-        encoded on the device in the same render stage from the clean page ("JPEG encoder")."""
-        check_jpeg_preset(jpeg)  # before the pipeline is built or a source read
+        encoded on the device in the same render stage from the clean page ("JPEG encoder").
+        `jpeg_optimize`: with `jpeg`, the files are coded with Huffman tables made for each page instead of Annex K's typical
+        ones (libjpeg's `optimize`): two more launches per wave, the same decoded pixels, about a third fewer bytes on scanned
+        pages; the EncodedJpeg says `optimized=True`.  Without `jpeg` it is a ValueError before a source is read."""
+        check_jpeg_preset(jpeg, jpeg_optimize)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: build the analyzer with "
                                       "visualize=False and ask per job, serve(..., overlays=True) (__call__ and analyze_pages "
                                       "draw with visualize=True)")
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
 
     def __call__(self, img):
         self.img = img

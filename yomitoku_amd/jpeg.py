@@ -12,6 +12,10 @@ intervals + restart markers laid out per page in a third.  The presets are the s
 page whose long side exceeds the preset's is first shrunk with Pillow's Lanczos resample, restated on the device
 (ymk_pil_resize_u8), to int(w * scale) x int(h * scale) as the host path does.  The host sees one copy of the files' lengths and
 one of their bytes, both through pinned memory.  There is no host fallback: a page the device cannot encode is an exception.
+
+`optimize=True` (serve: `jpeg_optimize=True`) codes the same coefficients with Huffman tables made for each page - libjpeg's
+`optimize` rule, byte for byte Pillow's `save(..., optimize=True, restart_marker_rows=1)` wherever the plain file is Pillow's:
+two more launches (the page's symbol histograms, then its tables), the same pixels when decoded, a smaller file.
 """
 
 from __future__ import annotations
@@ -41,6 +45,7 @@ class EncodedJpeg:
     height: int
     grey: bool
     scale: float = 1.0
+    optimized: bool = False  # coded with the page's own Huffman tables
 
 
 def jpeg_preset(image_quality: str) -> dict:
@@ -60,6 +65,16 @@ def _header(h: int, w: int, channels: int, quality: int) -> bytes:
     return bytes(buf[:n])
 
 
+@functools.lru_cache(maxsize=256)
+def _header_opt(h: int, w: int, channels: int, quality: int):
+    """(the header without its DHT segments, the bytes of it before their place)."""
+    buf, split = (ctypes.c_ubyte * 1024)(), ctypes.c_int(0)
+    n = _lib.load().ymk_jpeg_header_opt(h, w, channels, quality, buf, len(buf), ctypes.byref(split))
+    if n < 0:
+        _lib.check(1, "ymk_jpeg_header_opt")
+    return bytes(buf[:n]), int(split.value)
+
+
 @functools.lru_cache(maxsize=16)
 def _quant_words(quality: int) -> np.ndarray:
     out = (ctypes.c_int * 128)()
@@ -67,13 +82,15 @@ def _quant_words(quality: int) -> np.ndarray:
     return np.frombuffer(out, dtype=np.int32).copy()
 
 
-def scratch_sizes(shapes: Sequence) -> tuple:
-    """(MCUs, blocks, intervals, coefficient bytes, stream bytes, interval-record bytes) of pages of `shapes` = (h, w, channels)."""
+def scratch_sizes(shapes: Sequence, optimize: bool = False) -> tuple:
+    """(MCUs, blocks, intervals, coefficient bytes, stream bytes, interval-record bytes) of pages of `shapes` = (h, w, channels);
+    optimize: the stream bytes of that path, and behind the six the bytes of the histograms, the code tables and the DHT records."""
     n = len(shapes)
     arr = ctypes.c_int * max(1, n)
-    sizes = (ctypes.c_int64 * 6)()
-    _lib.check(_lib.load().ymk_jpeg_scratch_bytes(arr(*[s[0] for s in shapes]), arr(*[s[1] for s in shapes]),
-                                                  arr(*[s[2] for s in shapes]), n, sizes), "ymk_jpeg_scratch_bytes")
+    sizes = (ctypes.c_int64 * (9 if optimize else 6))()
+    name = "ymk_jpeg_scratch_bytes_opt" if optimize else "ymk_jpeg_scratch_bytes"
+    _lib.check(getattr(_lib.load(), name)(arr(*[s[0] for s in shapes]), arr(*[s[1] for s in shapes]),
+                                          arr(*[s[2] for s in shapes]), n, sizes), name)
     return tuple(int(v) for v in sizes)
 
 
@@ -86,12 +103,18 @@ def _addr_words(ptr: int):
     return np.array([ptr & 0xFFFFFFFF, ptr >> 32], dtype=np.uint32).view(np.int32)
 
 
-def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]] = None):
+def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]] = None, optimize: bool = False):
     """(int32 words of the page table of include/ymk.h, per page the byte offset of its file in the output, the output's bytes).
-    capacities: bytes per page's file; default the page's raw byte count."""
+    capacities: bytes per page's file; default the page's raw byte count.  optimize: the table of the *_opt entries - headers
+    without DHT segments, word 14 the place the device puts the page's own."""
     n = len(pages)
     rec = np.zeros((n, PAGE_WORDS), np.int32)
-    headers = [_header(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3, quality) for p in pages]
+    shapes = [(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in pages]
+    if optimize:
+        split = [_header_opt(h, w, ch, quality) for h, w, ch in shapes]
+        headers, rec[:, 14] = [s[0] for s in split], [s[1] for s in split]
+    else:
+        headers = [_header(h, w, ch, quality) for h, w, ch in shapes]
     at = n * PAGE_WORDS * 4  # byte offset of the first header
     mcu = blk = iv = 0
     out_at, offsets = 0, []
@@ -174,12 +197,14 @@ def _as_device_page(page, device) -> torch.Tensor:
 
 
 def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
-                      capacities: Optional[Sequence[int]] = None) -> List[Union[EncodedJpeg, Exception]]:
+                      capacities: Optional[Sequence[int]] = None, optimize: bool = False) -> List[Union[EncodedJpeg, Exception]]:
     """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
     file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
     stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
     the device and pinned buffers (serve: one per wave slot); capacities: bytes allowed per page's file - the default cannot
-    hold the ~620-byte header (~330 grey) plus the scan of a page below roughly 15 x 15 pixels, nor noise that does not compress."""
+    hold the ~620-byte header (~330 grey) plus the scan of a page below roughly 15 x 15 pixels, nor noise that does not compress.
+    optimize: Huffman tables made for each page (two more launches; the header shrinks with the tables, to ~270 bytes for a
+    flat colour page); the decoded pixels are those of the plain file."""
     preset = jpeg_preset(image_quality)
     quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
     out: list = [None] * len(pages)
@@ -212,18 +237,27 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
             for (j, _), small in zip(todo, resize_pages([devs[j] for j, _ in todo], [s for _, s in todo])):
                 devs[j] = small
         caps = None if capacities is None else [int(capacities[k]) for k in live]
-        blob, offsets, out_bytes = page_table(devs, quality, caps)
-        mcus, blocks, intervals, coef_b, stream_b, iv_b = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3)
-                                                                        for p in devs])
+        blob, offsets, out_bytes = page_table(devs, quality, caps, optimize)
+        sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in devs], optimize)
+        mcus, blocks, intervals, coef_b, stream_b, iv_b = sized[:6]
         coef = _grown(scratch, "coef", coef_b // 2, torch.int16, device)
         bits = _grown(scratch, "stream", stream_b // 4, torch.int32, device)
         ivals = _grown(scratch, "intervals", iv_b // 4, torch.int32, device)
         files = _grown(scratch, "out", out_bytes, torch.uint8, device)
         lengths = _grown(scratch, "lengths", len(devs), torch.int32, device)
         blob_dev = imaging._stage_blob(blob, device)
-        _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, len(devs), mcus, blocks, intervals, coef.data_ptr(),
-                                             bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
-                                             lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
+        if optimize:
+            hist = _grown(scratch, "hist", sized[6] // 4, torch.int32, device)
+            tables = _grown(scratch, "tables", sized[7] // 4, torch.int32, device)
+            dht = _grown(scratch, "dht", sized[8] // 4, torch.int32, device)
+            _lib.check(lib.ymk_jpeg_encode_pages_opt(blob_dev.data_ptr(), blob.size, len(devs), mcus, blocks, intervals, coef.data_ptr(),
+                                                     hist.data_ptr(), tables.data_ptr(), dht.data_ptr(), bits.data_ptr(), stream_b,
+                                                     ivals.data_ptr(), files.data_ptr(), out_bytes, lengths.data_ptr(),
+                                                     _lib.current_stream_ptr()), "ymk_jpeg_encode_pages_opt")
+        else:
+            _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, len(devs), mcus, blocks, intervals, coef.data_ptr(),
+                                                 bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
+                                                 lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
         # the lengths first (one small copy), then the files' bytes, packed on the device, in one copy
         pin_len = _grown(scratch, "pin_lengths", len(devs), torch.int32, pinned=True)
         pin_len[: len(devs)].copy_(lengths[: len(devs)], non_blocking=True)
@@ -245,17 +279,18 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
                 cap = caps[j] if caps is not None else p.numel()
                 out[k] = _lib.YmkError(f"page {k}: the JPEG file does not fit its capacity of {cap} bytes")
                 continue
-            out[k] = EncodedJpeg(host[at : at + sizes[j]].tobytes(), int(p.shape[1]), int(p.shape[0]), p.dim() == 2, float(scales[j]))
+            out[k] = EncodedJpeg(host[at : at + sizes[j]].tobytes(), int(p.shape[1]), int(p.shape[0]), p.dim() == 2, float(scales[j]),
+                                 bool(optimize))
             at += sizes[j]
     return out
 
 
-def encode_jpeg(page, image_quality: str = "high", stream=None) -> EncodedJpeg:
+def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False) -> EncodedJpeg:
     """One page; raises what `encode_jpeg_pages` would have put in its place.  The file's capacity is the page's raw byte
     count, and the header alone takes about 620 bytes (330 for a grey page): a colour page below roughly 15 x 15 pixels, or noise
     that does not compress, raises YmkError here and in `serve(jpeg=...)` - `encode_jpeg_pages(..., capacities=[...])` gives
     such a page the room it needs."""
-    res = encode_jpeg_pages([page], image_quality, stream)[0]
+    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize)[0]
     if isinstance(res, BaseException):
         raise res
     return res

@@ -31,7 +31,7 @@ memory.
 `render` is not one of the nine: its thread and stream are started by the first job that asks for overlays or JPEG files, and
 only the waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all
 canvases of a wave (two per page) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
-as JPEG files with three (yomitoku_amd/jpeg.py: encode_jpeg_pages); a job with neither runs exactly the stages above.
+as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages); a job with neither runs exactly the stages above.
 
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
 process while holding the GIL - measured 100-180 ms with the results of a few hundred pages alive, six times in a
@@ -104,11 +104,12 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None):
+    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False):
         self.results = {}
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, ocr overlay, layout overlay): the waves visit the render stage
         self.jpeg = jpeg  # None or a preset name: the entries end with the page's EncodedJpeg, made in the render stage too
+        self.jpeg_optimize = bool(jpeg_optimize)  # those files with Huffman tables of their own (encode_jpeg_pages(optimize=True))
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -161,13 +162,16 @@ def _switch_interval(seconds):
                 _switch_saved = None
 
 
-def check_jpeg_preset(jpeg):
+def check_jpeg_preset(jpeg, jpeg_optimize=False):
     """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
-    public entry points before a source is read."""
+    public entry points before a source is read.  `jpeg_optimize` asks for something of those files: without `jpeg` it is a
+    ValueError too."""
     from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
 
     if jpeg is not None and (not isinstance(jpeg, str) or jpeg not in IMAGE_QUALITY_PRESETS):
         raise ValueError(f"unknown jpeg preset {jpeg!r}: None or one of {sorted(IMAGE_QUALITY_PRESETS)}")
+    if jpeg_optimize and jpeg is None:
+        raise ValueError("jpeg_optimize=True needs jpeg=...: there is no JPEG file to optimise")
 
 
 def _run_stage(stream, wave, fn, *args):
@@ -399,7 +403,8 @@ class PagePipeline:
         self._q["detect"].put(wave)
         self._q["layout"].put(wave)
 
-    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None) -> List:
+    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
+              jpeg_optimize: bool = False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -411,13 +416,14 @@ class PagePipeline:
         jpeg: None, or a preset name of the searchable PDF ("high", "middle", "low"; anything else is a ValueError before a
         source is read): a page's entry ends with its EncodedJpeg (yomitoku_amd/jpeg.py) - (schema, EncodedJpeg), or (schema, ocr
         overlay, layout overlay, EncodedJpeg) - encoded in the render stage from the clean page, never from a canvas.
+        jpeg_optimize: those files with Huffman tables made for each page (smaller, the same pixels); a ValueError without `jpeg`.
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
 
-        check_jpeg_preset(jpeg)
+        check_jpeg_preset(jpeg, jpeg_optimize)
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg)
+            job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
             if job.overlays or job.jpeg:
                 self._start_render()
             n = 0
@@ -548,7 +554,7 @@ class StageAnalyzer:
     `_stage_finish(wave, k)` (host, subclass) returns page k's schema from dets / recs / lay_parsed / lays / imgs and the job
     (`wave.job.options`, `wave.job.overlays`); `_stage_render(wave, results)` (GPU, here; overlays jobs only) returns per page
     the two pictures, from `_page_drawings(wave, k, results)` (subclass) and `wave.pages`; `_stage_jpeg(wave, results)` (GPU,
-    here; jpeg jobs only) returns per page a 1-tuple with its EncodedJpeg, from `wave.pages` and `wave.job.jpeg`.  `_nets()`
+    here; jpeg jobs only) returns per page a 1-tuple with its EncodedJpeg, from `wave.pages`, `wave.job.jpeg` and `wave.job.jpeg_optimize`.  `_nets()`
     (subclass): the modules whose `model.close()` releases the analyzer's device memory.
 
     `handover`: None, or an object that sees - and may replace - what one stage hands to the next, AFTER the stage has
@@ -653,7 +659,7 @@ class StageAnalyzer:
         return out
 
     def _stage_jpeg(self, wave, results, scratch=None):
-        """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`), an exception for a page
+        """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`, tables `wave.job.jpeg_optimize`), an exception for a page
         that could not be encoded, None for a page that had already failed.  All pages of the wave are encoded together on
         the calling thread's stream (yomitoku_amd/jpeg.py: encode_jpeg_pages) from `wave.pages` - the clean pages: the
         overlays are drawn on copies - with `scratch`, by default the wave slot's."""
@@ -664,7 +670,8 @@ class StageAnalyzer:
         if live:
             if scratch is None:
                 scratch = self._jpeg_scratch.setdefault(wave.ring, {})
-            files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch)
+            files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch,
+                                      optimize=getattr(wave.job, "jpeg_optimize", False))
             for k, made in zip(live, files):
                 out[k] = made if isinstance(made, BaseException) else (made,)
         return out
@@ -701,7 +708,7 @@ class StageAnalyzer:
         return wave
 
     # ---- the pipeline of this analyzer
-    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None):
+    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -709,7 +716,7 @@ class StageAnalyzer:
                 pipe.close()
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -
