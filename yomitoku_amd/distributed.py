@@ -243,7 +243,7 @@ def claim_core_slice(local_rank: int, local_world: int):
 
 
 def thread_budget(cores: int) -> dict:
-    """Host threads of one rank for a share of `cores` cores.  The nine stage threads of DocumentAnalyzer.serve mostly sleep
+    """Host threads of one rank for a share of `cores` cores.  The stage threads of the analyzer's serve (nine stages for DocumentAnalyzer, six for OCR) mostly sleep
     in library calls (GIL released), so they stay; what scales with the share is the C++ box-extraction pool (4 at >= 16
     cores, never more than a quarter of the share) and the second recogniser lane (dropped below 8 cores, where its extra
     stream only adds runnable threads)."""
@@ -303,10 +303,11 @@ class ShardedServer:
     WORLD_SIZE), each a full replica.
 
         server = ShardedServer(make_analyzer, checkpoints)      # init -> core slice -> broadcast -> replica report -> analyzer
-        results = server.run(sources, wave=16, in_flight=4)      # deal (PageDealer) -> DocumentAnalyzer.serve -> ordered gather (rank 0)
+        results = server.run(sources, wave=16, in_flight=4)      # deal (PageDealer) -> the analyzer's serve -> ordered gather (rank 0)
         server.close()
 
-    make_analyzer(device, checkpoints, budget) builds this rank's DocumentAnalyzer from the broadcast checkpoints ({name:
+    make_analyzer(device, checkpoints, budget) builds this rank's analyzer (DocumentAnalyzer, TableSemanticParser, OCR: anything
+    with `serve` and `close`) from the broadcast checkpoints ({name:
     state dict}; `checkpoints` is that mapping - or a callable returning it - on rank 0 and ignored elsewhere).  Sources are
     dealt BY SOURCE (a multi-frame file stays on one rank), a wave's worth at a time, to whichever rank asks next; an entry that failed stays an exception object in
     its place, exactly as `serve` reports it, and cannot hold the other ranks (nothing on the per-page path communicates).
@@ -398,7 +399,7 @@ class ShardedServer:
         return shard_indices(n_sources, self.rank, self.world)
 
     def serve_local(self, sources: Sequence, assign: str = "dynamic", chunk: int | None = None, **serve_kwargs) -> list:
-        """This rank's share through DocumentAnalyzer.serve: [(global source index, frame index, entry)], in order.
+        """This rank's share through the analyzer's serve: [(global source index, frame index, entry)], in order.
         assign "dynamic" (default): the share is whatever this rank PULLS - `serve` reads its sources lazily (a new wave
         only when a wave slot is free), and every `chunk` sources (default: one wave) the generator claims the next chunk
         from the node's PageDealer; "static": source i belongs to rank i % world, known up front."""
@@ -476,7 +477,7 @@ class ShardedServer:
 
     def run(self, sources: Sequence, gather: str | None = "json", assign: str = "dynamic", chunk: int | None = None, **serve_kwargs) -> list | None:
         """deal -> serve -> gather.  assign / chunk: see `serve_local`.  gather: "json" (default: rank 0 gets every page as the
-        JSON text of its DocumentAnalyzerSchema - what a caller that writes the pages out wants, and nothing for rank 0 to
+        JSON text of its schema - what a caller that writes the pages out wants, and nothing for rank 0 to
         rebuild: see `gather`), "objects" (rank 0 gets the schema / exception objects themselves), or None - no result travels at
         all: EVERY rank returns its own [(global source index, frame index, entry)] and writes / forwards them itself, which is
         how a node of 8 GPUs keeps rank 0 out of the per-page path; a failed rank still fails the job on every rank."""

@@ -49,7 +49,14 @@ def ocr_aggregate(det_outputs, rec_outputs):
     ]
 
 
-class OCR:
+_NO_VIS_SERVE = ("visualize=True is not supported by serve / serve_sharded: build the analyzer with "
+                 "visualize=False and ask per job, serve(..., overlays=True) (__call__ and analyze_pages "
+                 "draw with visualize=True)")
+
+
+class OCR(StageAnalyzer):
+    chains = ("ocr",)  # the page pipeline runs detect ... decode and `finish` for it: there is no layout chain to wait for
+
     def __init__(self, configs={}, device="cuda", visualize=False, workspace_reuse=False):
         det_kwargs = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
         rec_kwargs = {"device": device, "visualize": visualize, "workspace_reuse": workspace_reuse}
@@ -59,12 +66,58 @@ class OCR:
         rec_kwargs.update(configs.get("text_recognizer", {}))
         self.detector = TextDetector(**det_kwargs)
         self.recognizer = TextRecognizer(**rec_kwargs)
+        self.visualize = visualize
+        self._init_chains()
+
+    # the reference's names are `detector` / `recognizer`; the shared stage bodies and close() say text_detector / text_recognizer
+    @property
+    def text_detector(self):
+        return self.detector
+
+    @property
+    def text_recognizer(self):
+        return self.recognizer
+
+    def _nets(self):
+        return self.detector, self.recognizer
 
     def __call__(self, img):
         page = imaging.page_to_device(img, self.detector.device) if not isinstance(img, torch.Tensor) else img
         det_outputs, vis = self.detector._call(page, to_host=False)  # the overlay stays on the device inside the chain
         rec_outputs, vis = self.recognizer._call(page, det_outputs.points, vis=vis, to_host=False)
         return OCRSchema(words=ocr_aggregate(det_outputs, rec_outputs)), _vis_to_host(vis)
+
+    def _stage_finish(self, wave, k):
+        """Page k of the wave -> OCRSchema: what `__call__` makes of the page's detections and strings."""
+        return OCRSchema(words=ocr_aggregate(wave.dets[k], wave.recs[k]))
+
+    def _page_drawings(self, wave, k, results):
+        """The one drawing of page k of a finished wave: the detection quads and the recognised strings, recorded as
+        DocumentAnalyzer records its OCR picture."""
+        return (self._ocr_drawing(wave, k),)
+
+    def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
+              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False):
+        """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
+        arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
+        yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
+        layout, tables or cells stage exists for this analyzer, neither thread nor stream.  Arguments and conventions are
+        `DocumentAnalyzer.serve`'s.  A page's entry is its OCRSchema - equal to `__call__(img)[0]` - or, when the page (or
+        its file) failed, the exception object; the other pages are not affected.
+        `wave`, `in_flight`, `defer_full_gc`, `with_source`, `rec_lanes`: see `DocumentAnalyzer.serve`.
+        `overlays`: a property of the job - True: a page's entry is (schema, ocr overlay), the picture with the detection quads
+        and the recognised strings (the first of DocumentAnalyzer's two, byte for byte) as a uint8 H x W x 3 array the caller
+        owns, drawn by the pipeline's render stage.
+        `jpeg`: None, or a preset of the searchable PDF ("high", "middle", "low"; anything else is a ValueError before a source
+        is read): a page's entry ends with its EncodedJpeg - (schema, EncodedJpeg), or (schema, ocr overlay, EncodedJpeg) -
+        encoded on the device from the clean page, so that
+            searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
+        is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
+        without `jpeg`."""
+        check_jpeg_preset(jpeg, jpeg_optimize)  # before the pipeline is built or a source read
+        if self.visualize:
+            raise NotImplementedError(_NO_VIS_SERVE)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -459,10 +512,7 @@ class DocumentAnalyzer(StageAnalyzer):
         reading order."""
         from .utils import visualizer as V
 
-        ocr, layout = V.RunOverlay(), V.RunOverlay()
-        V._det_commands(ocr, wave.dets[k].points)
-        cfg = self.text_recognizer._cfg.visualize
-        V._rec_commands(ocr, wave.recs[k], V.load_font(cfg.font, cfg.font_size), cfg.font_size, tuple(cfg.color[::-1]))
+        ocr, layout = self._ocr_drawing(wave, k), V.RunOverlay()
         V._layout_commands(layout, wave.lay_parsed[k])
         for table in wave.lays[k].tables:
             V._table_commands(layout, table)
@@ -536,9 +586,7 @@ class DocumentAnalyzer(StageAnalyzer):
         pages; the EncodedJpeg says `optimized=True`.  Without `jpeg` it is a ValueError before a source is read."""
         check_jpeg_preset(jpeg, jpeg_optimize)  # before the pipeline is built or a source read
         if self.visualize:
-            raise NotImplementedError("visualize=True is not supported by serve / serve_sharded: build the analyzer with "
-                                      "visualize=False and ask per job, serve(..., overlays=True) (__call__ and analyze_pages "
-                                      "draw with visualize=True)")
+            raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
 
     def __call__(self, img):

@@ -30,7 +30,7 @@ memory.
 
 `render` is not one of the nine: its thread and stream are started by the first job that asks for overlays or JPEG files, and
 only the waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all
-canvases of a wave (two per page) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
+canvases of a wave (as many per page as the analyzer draws: two, OCR one) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
 as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages); a job with neither runs exactly the stages above.
 
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
@@ -45,9 +45,11 @@ waves through the same pipeline, and a page that fails alone gets the exception 
 on (the reference's per-file `except: log, continue`).  Results equal `DocumentAnalyzer.__call__` page by page
 (tests/test_serving_gpu.py).
 
-What the pipeline asks of an analyzer is written down in `StageAnalyzer` (below), the base class of DocumentAnalyzer and
-TableSemanticParser: it holds the chain plumbing, the OCR chain and the render stage once, each analyzer adds its table chain,
-`finish` and the drawings of a page."""
+What the pipeline asks of an analyzer is written down in `StageAnalyzer` (below), the base class of DocumentAnalyzer,
+TableSemanticParser and OCR: it holds the chain plumbing, the OCR chain and the render stage once, each analyzer adds its table
+chain, `finish` and the drawings of a page.  The stage plan is data (`CHAINS`), and an analyzer says which chains it has:
+`OCR.serve` declares `chains = ("ocr",)` and runs detect ... decode, finish and render alone - no layout, tables or cells
+thread, no stream for them, `finish` after one arrival, one picture per page in the render stage."""
 
 from __future__ import annotations
 
@@ -107,7 +109,7 @@ class _Job:
     def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False):
         self.results = {}
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
-        self.overlays = bool(overlays)  # entries are (schema, ocr overlay, layout overlay): the waves visit the render stage
+        self.overlays = bool(overlays)  # entries are (schema, the analyzer's pictures...): the waves visit the render stage
         self.jpeg = jpeg  # None or a preset name: the entries end with the page's EncodedJpeg, made in the render stage too
         self.jpeg_optimize = bool(jpeg_optimize)  # those files with Huffman tables of their own (encode_jpeg_pages(optimize=True))
         self.cond = threading.Condition()
@@ -195,6 +197,28 @@ def _run_stage(stream, wave, fn, *args):
         raise
 
 
+# The stage plan, once: per chain its stages in order as (stage, the analyzer's method, launches on the GPU?).  A wave enters
+# every chain its analyzer declares at the chain's first stage; the chains join in `finish`.
+CHAINS = {
+    "ocr": (("detect", "_stage_detect", True), ("boxes", "_stage_boxes", False), ("crops", "_stage_crops", True),
+            ("recognize", "_stage_recognize", True), ("decode", "_stage_decode", False)),
+    "layout": (("layout", "_stage_layout", True), ("tables", "_stage_tables", True), ("cells", "_stage_cells", False)),
+}
+
+
+def _declared_chains(analyzer):
+    """The analyzer's `chains` - a tuple out of CHAINS' names; an analyzer that says nothing runs both - checked: a ValueError
+    for none, an unknown or a repeated name, and for `split_text_across_cells` (the words are cut at the cells of the
+    layout chain) without "layout"."""
+    chains = tuple(getattr(analyzer, "chains", tuple(CHAINS)))
+    unknown = [c for c in chains if c not in CHAINS]
+    if not chains or unknown or len(set(chains)) != len(chains):
+        raise ValueError(f"chains must be a non-empty tuple out of {tuple(CHAINS)} without repeats, got {chains!r}")
+    if getattr(analyzer, "split_text_across_cells", False) and "layout" not in chains:
+        raise ValueError(f"split_text_across_cells needs the layout chain, the analyzer declares chains={chains!r}")
+    return chains
+
+
 class PagePipeline:
     def __init__(self, analyzer, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, stage_priority=None,
                  rec_lanes: int = 2):
@@ -226,21 +250,25 @@ class PagePipeline:
         self._rings: "queue.Queue" = queue.Queue()
         for r in range(self.in_flight):
             self._rings.put(r)
-        names = ("detect", "boxes", "crops", "recognize", "decode", "layout", "tables", "cells", "finish")
-        self._q = {name: queue.Queue() for name in names}
+        self.chains = _declared_chains(analyzer)
         self._job: Optional[_Job] = None
         self._seq = 0
         self.trace = None  # a list: every stage appends (stage, wave seq, pages, t_start, t_end) - tools/serve_trace.py
         self._serve_lock = threading.Lock()
         self._render_q: "queue.Queue" = queue.Queue()
         self._render_thread = None  # started by the first job that asks for overlays
-        a = analyzer
-        # (stage, function, launches on the GPU?, next stages); the recognise chain and the layout chain join in `finish`
-        plan = (("detect", a._stage_detect, True, ("boxes",)), ("boxes", self._boxes, False, ("crops",)),
-                ("crops", a._stage_crops, True, ("recognize",)), ("recognize", a._stage_recognize, True, ("decode",)),
-                ("decode", a._stage_decode, False, ("finish",)),
-                ("layout", a._stage_layout, True, ("tables",)), ("tables", a._stage_tables, True, ("cells",)),
-                ("cells", a._stage_cells, False, ("finish",)), ("finish", self._finish, False, ()))
+        # (stage, function, launches on the GPU?, next stages), built from CHAINS for the chains the analyzer declares: every
+        # chain is entered at its first stage (_launch) and all of them join in `finish`.  A stage of a chain that is not
+        # declared has no thread, no stream and no queue, and its method is never looked up
+        plan = []
+        for chain in self.chains:
+            stages = CHAINS[chain]
+            for (name, method, on_gpu), after in zip(stages, stages[1:] + (("finish",),)):
+                fn = self._boxes if name == "boxes" else getattr(analyzer, method)  # `boxes` may wait for the layout chain
+                plan.append((name, fn, on_gpu, (after[0],)))
+        plan.append(("finish", self._finish, False, ()))
+        self._entries = tuple(CHAINS[chain][0][0] for chain in self.chains)  # where _launch puts a wave
+        self._q = {spec[0]: queue.Queue() for spec in plan}
         self._workers = {spec[0]: (self.rec_lanes if spec[0] == "recognize" else 1) for spec in plan}
         self._threads = [threading.Thread(target=self._loop, args=spec + (lane,), name=f"ymk-{spec[0]}-{lane}" if self._workers[spec[0]] > 1 else f"ymk-{spec[0]}",
                                           daemon=True) for spec in plan for lane in range(self._workers[spec[0]])]
@@ -266,7 +294,7 @@ class PagePipeline:
                 return
             if name == "finish":
                 wave.joined += 1
-                if wave.joined < 2:  # arrives once from the recognise chain and once from the layout chain
+                if wave.joined < len(self.chains):  # arrives once from every chain the analyzer declares
                     continue
             if wave.error is None or name == "finish":
                 t_start = time.perf_counter()
@@ -289,14 +317,15 @@ class PagePipeline:
     def _boxes(self, wave):
         a = self.analyzer
         a._stage_boxes(wave)
-        if a.split_text_across_cells:
+        if getattr(a, "split_text_across_cells", False):
             wave.layout_done.wait()
             if wave.error is None:
                 a._stage_split(wave)
 
     def _render_loop(self):
         """The render stage: waves of overlays and / or jpeg jobs, after aggregation.  Turns every page's schema into (schema,
-        ocr overlay, layout overlay), (schema, EncodedJpeg) or (schema, ocr overlay, layout overlay, EncodedJpeg); a page whose
+        the analyzer's pictures...) - ocr and layout overlay; OCR: the ocr overlay alone -, (schema, EncodedJpeg) or (schema,
+        pictures..., EncodedJpeg); a page whose
         drawing or encoding fails - or every page of the wave, when the launches fail - gets the exception."""
         stream = None
         if self._gpu:
@@ -400,8 +429,8 @@ class PagePipeline:
         with job.cond:
             job.outstanding += 1
             job.waves += 1
-        self._q["detect"].put(wave)
-        self._q["layout"].put(wave)
+        for name in self._entries:
+            self._q[name].put(wave)
 
     def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
               jpeg_optimize: bool = False) -> List:
@@ -532,28 +561,38 @@ def _chain_priorities():
 
 
 class StageAnalyzer:
-    """What `PagePipeline` asks of its analyzer, and the part of it that DocumentAnalyzer and TableSemanticParser share.  The
-    pipeline is duck-typed (the tests drive it with stubs); a real analyzer derives from this class and adds its table chain.
+    """What `PagePipeline` asks of its analyzer, and the part of it that DocumentAnalyzer, TableSemanticParser and OCR share.
+    The pipeline is duck-typed (the tests drive it with stubs); a real analyzer derives from this class and adds its table
+    chain - or, like OCR, declares that it has none.
 
     Attributes the pipeline reads: `text_detector.device`, `text_recognizer` (its `rec_orientation_fallback` forces one
-    recogniser lane) and `split_text_across_cells` (True: `boxes` waits for the wave's `cells`, then calls `_stage_split(wave)`).
+    recogniser lane), `split_text_across_cells` (True: `boxes` waits for the wave's `cells`, then calls `_stage_split(wave)`;
+    needs the layout chain) and `chains`:
+
+        chains              stage threads and streams                     who
+        ("ocr", "layout")   all nine; `finish` after both chains          the default: DocumentAnalyzer, TableSemanticParser
+        ("ocr",)            detect ... decode, finish; no layout chain    OCR
+
+    An analyzer without the attribute runs both chains.  The stages of a chain that is not declared have no thread, no HIP
+    stream and no queue, and their methods are never looked up: an analyzer need not have them.
 
     Stage methods, each called with the `Wave` by the stage's one thread (GPU: on that thread's HIP stream, after the wave's
     upload; the stream is waited for before the wave moves on):
 
-        stage      launches  reads                                  writes              defined
-        detect     GPU       pages, ring                            maps                here
-        boxes      host      maps, sizes                            dets                here
-        crops      GPU       pages, dets                            rec_plan            here
-        recognize  GPU       rec_plan; called (wave, lane)          rec_plan            here
-        decode     host      rec_plan                               recs, rec_plan=None here
-        layout     GPU       pages                                  lay_raw             subclass
-        tables     GPU       pages, lay_raw, ids (hand-over)        lay_parsed, tab_raw subclass
-        cells      host      tab_raw, lay_parsed                    lays                subclass
+        stage      chain   launches  reads                                  writes              defined
+        detect     ocr     GPU       pages, ring                            maps                here
+        boxes      ocr     host      maps, sizes                            dets                here
+        crops      ocr     GPU       pages, dets                            rec_plan            here
+        recognize  ocr     GPU       rec_plan; called (wave, lane)          rec_plan            here
+        decode     ocr     host      rec_plan                               recs, rec_plan=None here
+        layout     layout  GPU       pages                                  lay_raw             subclass
+        tables     layout  GPU       pages, lay_raw, ids (hand-over)        lay_parsed, tab_raw subclass
+        cells      layout  host      tab_raw, lay_parsed                    lays                subclass
 
     `_stage_finish(wave, k)` (host, subclass) returns page k's schema from dets / recs / lay_parsed / lays / imgs and the job
     (`wave.job.options`, `wave.job.overlays`); `_stage_render(wave, results)` (GPU, here; overlays jobs only) returns per page
-    the two pictures, from `_page_drawings(wave, k, results)` (subclass) and `wave.pages`; `_stage_jpeg(wave, results)` (GPU,
+    its pictures - pictures per page: as many as `_page_drawings(wave, k, results)` (subclass) records, the same for every page
+    of an analyzer (DocumentAnalyzer and TableSemanticParser two, OCR one) -, from those drawings and `wave.pages`; `_stage_jpeg(wave, results)` (GPU,
     here; jpeg jobs only) returns per page a 1-tuple with its EncodedJpeg, from `wave.pages`, `wave.job.jpeg` and `wave.job.jpeg_optimize`.  `_nets()`
     (subclass): the modules whose `model.close()` releases the analyzer's device memory.
 
@@ -562,6 +601,7 @@ class StageAnalyzer:
     detections are noise.  A hook the object lacks - or a data attribute of that name - passes the value through."""
 
     split_text_across_cells = False
+    chains = tuple(CHAINS)  # both: an analyzer without a layout chain says ("ocr",)
 
     def _init_chains(self):
         """The constructors' shared part: the two chains of a page or wave (OCR; layout / tables) run on one thread and HIP
@@ -632,8 +672,20 @@ class StageAnalyzer:
             wave.recs = self.text_recognizer.finish_plan(wave.rec_plan)
             wave.rec_plan = None
 
+    def _ocr_drawing(self, wave, k):
+        """The OCR picture of page k of a finished wave, recorded for the wave renderer: the detection quads, then the
+        recognised strings in the recogniser's configured font, size and colour."""
+        from .utils import visualizer as V
+
+        ocr = V.RunOverlay()
+        V._det_commands(ocr, wave.dets[k].points)
+        cfg = self.text_recognizer._cfg.visualize
+        V._rec_commands(ocr, wave.recs[k], V.load_font(cfg.font, cfg.font_size), cfg.font_size, tuple(cfg.color[::-1]))
+        return ocr
+
     def _stage_render(self, wave, results, pinned=None):
-        """Overlays: per page of the wave its two pictures as owned host arrays, in the order `_page_drawings` records them;
+        """Overlays: per page of the wave its pictures as owned host arrays - as many as `_page_drawings` records for a page, in
+        that order (the same number for every page of an analyzer: DocumentAnalyzer and TableSemanticParser two, OCR one);
         an exception for a page whose drawing raised, None for a page that had already failed.  All canvases of the wave are
         drawn by the wave renderer (utils/visualizer.py: render_wave) on the calling thread's stream and come back through
         `pinned` - by default the wave slot's pinned buffer."""
@@ -645,17 +697,21 @@ class StageAnalyzer:
             if isinstance(results[k], BaseException):
                 continue
             try:
-                drawings.extend(self._page_drawings(wave, k, results[k]))
-                live.append(k)
+                made = tuple(self._page_drawings(wave, k, results[k]))
             except Exception as exc:  # noqa: BLE001 - only this page fails
                 out[k] = exc
+                continue
+            drawings.append(made)
+            live.append(k)
         wave.dags = None
         if live:
+            n = len(drawings[0])  # pictures per page: what the analyzer draws (OCR one, the others two)
+            assert all(len(made) == n for made in drawings), "an analyzer draws the same number of pictures for every page"
             if pinned is None:
                 pinned = self._render_pinned.setdefault(wave.ring, [None])
-            images = render_wave([wave.pages[k] for k in live for _ in range(2)], drawings, pinned)
+            images = render_wave([wave.pages[k] for k in live for _ in range(n)], [d for made in drawings for d in made], pinned)
             for j, k in enumerate(live):
-                out[k] = (images[2 * j], images[2 * j + 1])
+                out[k] = tuple(images[n * j : n * (j + 1)])
         return out
 
     def _stage_jpeg(self, wave, results, scratch=None):

@@ -127,7 +127,17 @@ def poly2rect(points):
 def words_in_reading_order(doc) -> list:
     """utils/searchable_pdf.py:122-187: paragraphs, table cells (by row, column) and figure paragraphs as containers sorted by
     (order, sub-order); a container takes the words of which more than 0.7 lies inside it, sorted right-to-left then
-    top-to-bottom when it is vertical, top-to-bottom then left-to-right otherwise."""
+    top-to-bottom when it is vertical, top-to-bottom then left-to-right otherwise.
+    A document of words alone (OCRSchema: it has no paragraphs, tables or figures to be empty - what OCR.serve returns) is one
+    container, the page: every word, sorted by the same rule, vertical when more of its words are vertical than horizontal."""
+    if not any(hasattr(doc, name) for name in ("paragraphs", "tables", "figures")):
+        rects = [poly2rect(w.points) for w in doc.words]
+        dirs = [w.direction for w in doc.words]
+        if dirs.count("vertical") > dirs.count("horizontal"):
+            order = sorted(range(len(rects)), key=lambda k: (-rects[k][0], rects[k][1]))
+        else:
+            order = sorted(range(len(rects)), key=lambda k: (rects[k][1], rects[k][0]))
+        return [doc.words[k] for k in order]
     containers = []
     for p in doc.paragraphs:
         containers.append((p.order, 0, p.box, p.direction))
@@ -316,11 +326,14 @@ def _scaled_document(doc, scale: float):
     def boxed(el, **more):
         return SimpleNamespace(order=getattr(el, "order", None), box=[v * scale for v in el.box], direction=getattr(el, "direction", None), **more)
 
+    words = [SimpleNamespace(points=[[x * scale, y * scale] for x, y in w.points], content=w.content, direction=w.direction) for w in doc.words]
+    if not any(hasattr(doc, name) for name in ("paragraphs", "tables", "figures")):  # an OCRSchema: words alone
+        return SimpleNamespace(words=words)
     return SimpleNamespace(
         paragraphs=[boxed(p) for p in doc.paragraphs],
         tables=[SimpleNamespace(order=t.order, cells=[boxed(c, row=c.row, col=c.col) for c in t.cells]) for t in doc.tables],
         figures=[SimpleNamespace(order=f.order, paragraphs=[boxed(p) for p in f.paragraphs]) for f in doc.figures],
-        words=[SimpleNamespace(points=[[x * scale, y * scale] for x, y in w.points], content=w.content, direction=w.direction) for w in doc.words])
+        words=words)
 
 
 def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = "high") -> bytes:
