@@ -447,6 +447,35 @@ int ymk_op_conv2d(const float* x_dev, int n, int h, int w, int c, /* c % 4 == 0,
                   const float* w_host_oihw, int cout, int cin, int kh, int kw, const float* scale_host,
                   const float* bias_host, const float* res_dev, int stride, int pad, int dil, int act, int tap4,
                   float* y_dev, void* stream);
+/* ymk_op_conv2d with nothing fixed (tests/test_conv_views_gpu.py): everything conv2d_impl's launch record carries that the
+ * entry above pins.  x / res / y address the FIRST channel of a view into a wider NHWC buffer - in_ld / res_ld / out_ld floats
+ * between pixels (the caller does the channel offset; Tensor::slice_c in the models); res_ld == 0 broadcasts one residual row
+ * to every output pixel; res_post: y = res + act(conv) instead of act(conv + res).  w_host_oihw: [cout][c][kh][kw] (tap4: c == 4,
+ * in_ld == 4).  stride_h x stride_w, one pad and one dilation for both axes.  row_group_dev [n*h*w] / group_open_dev (both or
+ * neither; plain linear layers only - the launch then goes through the row-major GEMM view and its "gemm_row_limit" chunks):
+ * M tiles all of whose rows sit in groups with group_open[g] == 0 keep their old contents.  amax_in_dev (optional): the max|x|
+ * record of the input view, AMAX_REC_WORDS = 1024 words (32 lines of 32 words, the value in word 0 of each line);
+ * amax_out_dev (optional, zeroed by the caller): receives max|y| of what the launch stored.  Kernels are selected as for
+ * ymk_op_conv2d ("conv_split", "conv_split_tile", "splitk_force", "no_splitk", "conv_variant", "conv_fast").  No checks beyond null
+ * and sign: the preconditions conv2d_impl enforces are part of what the tests exercise. */
+int ymk_op_conv2d_view(const float* x_dev, int n, int h, int w, int c, int in_ld, const float* w_host_oihw, int cout, int kh, int kw,
+                       int tap4, const float* scale_host, const float* bias_host, const float* res_dev, int res_ld, int res_post,
+                       int stride_h, int stride_w, int pad, int dil, int act, const int* row_group_dev, const int* group_open_dev,
+                       const unsigned* amax_in_dev, unsigned* amax_out_dev, float* y_dev, int out_ld, void* stream);
+/* A producer convolution (c -> cout1) and the k x k convolution (cout1 -> cout2) that is its only reader, run the way
+ * DBNetModel::bottleneck runs them under the fp16-split form (tests/test_conv_planes_gpu.py): where conv_planes_pair_ok accepts
+ * the pair ("act_planes" on, both launches fill the chip, no residual on the producer, cout1 % 32 == 0, ...) the intermediate
+ * mid_dev [n][h1][w1][cout1] holds fp16 PLANES (per pixel and 32-channel slice 32 high halves, then 32 low halves, scaled by
+ * 2^(141 - e), e = the biased exponent of the record clamped to 27 .. 227) and mid_amax_dev (1024 words, zeroed here) the BOUND
+ * pl_a max|x| + pl_b; otherwise mid_dev holds fp32 values and the record their measured maximum.  Square strides, contiguous
+ * tensors; res1_dev / res2_dev: optional residuals (added before the activation); amax_in_dev: optional record of x (else the
+ * producer measures it).  *planes_taken = 0 / 1, *pl_a / *pl_b = the producer's bound constants. */
+int ymk_op_conv_planes_pair(const float* x_dev, int n, int h, int w, int c, const unsigned* amax_in_dev, const float* w1_host_oihw,
+                            int cout1, int kh1, int kw1, int stride1, int pad1, int dil1, int act1, const float* scale1_host,
+                            const float* bias1_host, const float* res1_dev, const float* w2_host_oihw, int cout2, int kh2, int kw2,
+                            int stride2, int pad2, int dil2, int act2, const float* scale2_host, const float* bias2_host,
+                            const float* res2_dev, float* mid_dev, unsigned* mid_amax_dev, float* y_dev, int* planes_taken,
+                            float* pl_a, float* pl_b, void* stream);
 /* rows x d LayerNorm (eps as given); attention over contiguous [b][l][heads*hd] q/k/v with optional
  * boolean masks (non-zero = blocked): mask_qk [lq][lk], kpm [b][lk]; use_small selects the masked
  * small-query kernel even without masks (otherwise the fp32-MFMA flash kernel runs). */

@@ -54,6 +54,127 @@ def conv2d(x, weight, scale=None, bias=None, residual=None, stride=1, padding=0,
     return _nchw(y)
 
 
+SENTINEL = 0x7FA5A5A5  # what conv2d_view pre-fills its output buffer with: a NaN bit pattern no kernel produces
+AMAX_REC_WORDS = 1024  # a max|x| record: 32 lines of 32 words, the value in word 0 of each line (csrc/ymk_common.h)
+
+
+def amax_record(value, device):
+    """A caller-filled max|x| record holding `value` (as absmax_record leaves it: word 0, the rest zero)."""
+    rec = torch.zeros(AMAX_REC_WORDS, dtype=torch.int32)
+    rec[0] = torch.tensor(abs(float(value)), dtype=torch.float32).view(torch.int32)
+    return rec.to(device)
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def _into_view(t_nhwc, view):
+    """t [..., c] -> (whole NaN-filled buffer [..., ld] with t at channels c0 .., the view's first-channel address)."""
+    c0, ld = view
+    c = t_nhwc.shape[-1]
+    assert 0 <= c0 and c0 + c <= ld
+    buf = torch.full(t_nhwc.shape[:-1] + (ld,), float("nan"), dtype=torch.float32, device=t_nhwc.device)
+    buf[..., c0:c0 + c] = t_nhwc
+    return buf, buf.data_ptr() + 4 * c0
+
+
+def conv2d_view(x, weight, scale=None, bias=None, residual=None, stride=1, padding=0, dilation=1, act="none", res_post=False,
+                in_view=None, out_view=None, res_view=None, row_group=None, group_open=None, amax_in=None, record=False):
+    """ymk_op_conv2d_view: conv2d with leading dimensions, a rectangular stride, the residual on either side of the activation,
+    a row predicate and records.  x NCHW on the device, weight OIHW; stride an int or (vertical, horizontal).
+    *_view = (first channel, leading dimension) of the tensor inside a wider NHWC buffer allocated here (default: contiguous):
+    inputs and residuals get NaN outside the view, the output SENTINEL everywhere.  residual: NCHW like the output, or a [cout]
+    vector = one row broadcast to every pixel (res_ld 0).  row_group [M] / group_open [groups]: int32 on the device.
+    -> (y NCHW: the output view, the whole output buffer [n, oh, ow, out_ld], the output's record as int32 [1024] or None)."""
+    lib = _lib.load()
+    assert x.is_cuda
+    n, c, h, w = x.shape
+    cout, cin, kh, kw = weight.shape
+    assert cin == c
+    tap4 = c <= 4
+    xh = _nhwc(x.float())
+    wh = weight.detach().float().cpu().contiguous()
+    if tap4 and c < 4:  # the 4-channel stem form: the image and the weights zero padded to four channels
+        xh = torch.cat([xh, xh.new_zeros(n, h, w, 4 - c)], dim=-1).contiguous()
+        wh = torch.cat([wh, wh.new_zeros(cout, 4 - c, kh, kw)], dim=1).contiguous()
+    cpad = xh.shape[-1]
+    sh_, sw_ = _pair(stride)
+    oh = (h + 2 * padding - dilation * (kh - 1) - 1) // sh_ + 1
+    ow = (w + 2 * padding - dilation * (kw - 1) - 1) // sw_ + 1
+    xbuf, xptr = _into_view(xh, in_view or (0, cpad))
+    oc0, out_ld = out_view or (0, cout)
+    assert 0 <= oc0 and oc0 + cout <= out_ld
+    ybuf = torch.empty((n, oh, ow, out_ld), dtype=torch.float32, device=x.device)
+    ybuf.view(torch.int32).fill_(SENTINEL)
+    sh = scale.detach().float().cpu().contiguous() if scale is not None else None
+    bh = bias.detach().float().cpu().contiguous() if bias is not None else None
+    rbuf, rptr, res_ld = None, None, 0
+    if residual is not None and residual.dim() == 1:
+        assert residual.numel() == cout
+        rbuf, rptr = _into_view(residual.float().to(x.device).reshape(1, cout), res_view or (0, cout))
+    elif residual is not None:
+        assert tuple(residual.shape) == (n, cout, oh, ow)
+        rbuf, rptr = _into_view(_nhwc(residual.float().to(x.device)), res_view or (0, cout))
+        res_ld = rbuf.shape[-1]
+    rg, go = _i32(row_group, x.device), _i32(group_open, x.device)
+    if rg is not None:
+        assert rg.numel() == n * oh * ow and 0 <= int(rg.min()) and int(rg.max()) < go.numel()  # the kernel trusts its indices
+    rec = torch.zeros(AMAX_REC_WORDS, dtype=torch.int32, device=x.device) if record else None
+    if amax_in is not None:
+        assert amax_in.is_cuda and amax_in.dtype == torch.int32 and amax_in.numel() == AMAX_REC_WORDS
+    with torch.cuda.device(x.device):
+        _lib.check(
+            lib.ymk_op_conv2d_view(xptr, n, h, w, cpad, xbuf.shape[-1], wh.data_ptr(), cout, kh, kw, 1 if tap4 else 0, _lib.ptr(sh),
+                                   _lib.ptr(bh), rptr, res_ld, 1 if res_post else 0, sh_, sw_, padding, dilation, ACT[act],
+                                   _lib.ptr(rg), _lib.ptr(go), _lib.ptr(amax_in), _lib.ptr(rec), ybuf.data_ptr() + 4 * oc0, out_ld,
+                                   _lib.current_stream_ptr()),
+            "ymk_op_conv2d_view",
+        )
+    return _nchw(ybuf[..., oc0:oc0 + cout]), ybuf, rec
+
+
+def conv_planes_pair(x, w1, w2, p1=None, p2=None, amax_in=None):
+    """ymk_op_conv_planes_pair: y = conv2(conv1(x)) under the fp16-split form, the intermediate as fp16 planes where the pair
+    qualifies.  x NCHW on the device; w1 / w2 OIHW; p1 / p2: dicts of stride, padding, dilation (ints), act, scale, bias,
+    residual (NCHW).  -> (y NCHW, the raw intermediate [n, h1, w1, cout1] fp32 words on the device - planes or values -, its
+    record int32 [1024], planes_taken, pl_a, pl_b)."""
+    import ctypes
+
+    lib = _lib.load()
+    assert x.is_cuda
+    n, c, h, w = x.shape
+    xh = _nhwc(x.float())
+    keep, args, dims = [], [], []
+    hh, ww = h, w
+    for wt, p in ((w1, p1 or {}), (w2, p2 or {})):
+        cout, _, kh, kw = wt.shape
+        st, pad, dil = int(p.get("stride", 1)), int(p.get("padding", 0)), int(p.get("dilation", 1))
+        hh = (hh + 2 * pad - dil * (kh - 1) - 1) // st + 1
+        ww = (ww + 2 * pad - dil * (kw - 1) - 1) // st + 1
+        host = [wt.detach().float().cpu().contiguous()]
+        host += [p[k].detach().float().cpu().contiguous() if p.get(k) is not None else None for k in ("scale", "bias")]
+        res = _nhwc(p["residual"].float().to(x.device)) if p.get("residual") is not None else None
+        if res is not None:
+            assert tuple(res.shape) == (n, hh, ww, cout)
+        keep += host + [res]
+        args += [host[0].data_ptr(), cout, kh, kw, st, pad, dil, ACT[p.get("act", "none")], _lib.ptr(host[1]), _lib.ptr(host[2]), _lib.ptr(res)]
+        dims.append((n, hh, ww, cout))
+    assert w1.shape[1] == c and w2.shape[1] == w1.shape[0]
+    mid = torch.empty(dims[0], dtype=torch.float32, device=x.device)
+    mid.view(torch.int32).fill_(SENTINEL)
+    y = torch.empty(dims[1], dtype=torch.float32, device=x.device)
+    rec = torch.zeros(AMAX_REC_WORDS, dtype=torch.int32, device=x.device)
+    if amax_in is not None:
+        assert amax_in.is_cuda and amax_in.dtype == torch.int32 and amax_in.numel() == AMAX_REC_WORDS
+    taken, pl_a, pl_b = ctypes.c_int(-1), ctypes.c_float(), ctypes.c_float()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_conv_planes_pair(xh.data_ptr(), n, h, w, c, _lib.ptr(amax_in), *args, mid.data_ptr(), rec.data_ptr(),
+                                               y.data_ptr(), ctypes.byref(taken), ctypes.byref(pl_a), ctypes.byref(pl_b),
+                                               _lib.current_stream_ptr()), "ymk_op_conv_planes_pair")
+    return _nchw(y), mid, rec, int(taken.value), float(pl_a.value), float(pl_b.value)
+
+
 def conv1x1_astat(x, weight, scale=None, bias=None, residual=None, act="none", reps=1, ln=None):
     """The A-stationary kernel at any row count (ymk_op_conv1x1_astat): x [M, C] on the device, weight [Cout, C] -> (y [M, Cout],
     ms of the last of `reps` launches).  ln = (gamma [C], beta [C], eps): LayerNorm folded into the operand load."""

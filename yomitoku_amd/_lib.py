@@ -104,6 +104,17 @@ SIGNATURES = {
         [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
          c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
     ),
+    "ymk_op_conv2d_view": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+         c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+    ),
+    "ymk_op_conv_planes_pair": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_void_p]
+        + [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p] * 2
+        + [c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_float), POINTER(c_float), c_void_p],
+    ),
     "ymk_op_conv1x1_astat": (
         c_int,
         [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,

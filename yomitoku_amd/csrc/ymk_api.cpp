@@ -314,6 +314,119 @@ int ymk_op_conv2d(const float* x_dev, int n, int h, int w, int c, const float* w
   YMK_API_END
 }
 
+// a layer of one single-operator call: the packed panel, scale / bias and the plane bound, as make_conv builds them
+static ymk::ConvW op_conv_weight(ymk::DevicePool& pool, const float* w_host_oihw, int cout, int cin, int kh, int kw, bool tap4,
+                                 const float* scale_host, const float* bias_host) {
+  using namespace ymk;
+  ConvW cw;
+  cw.cout = cout;
+  cw.cin = tap4 ? 4 : cin;
+  cw.kh = kh;
+  cw.kw = kw;
+  cw.mode = tap4 ? 1 : 0;
+  std::vector<float> panel;
+  pack_conv_weight(w_host_oihw, cout, cin, kh, kw, tap4, panel, cw.kpad, cw.ctiles);
+  cw.w = pool.upload(panel);
+  std::vector<float> scale, bias;
+  if (scale_host) scale.assign(scale_host, scale_host + cout);
+  if (bias_host) bias.assign(bias_host, bias_host + cout);
+  if (scale_host) cw.scale = pool.upload(scale);
+  if (bias_host) cw.bias = pool.upload(bias);
+  plane_bound(cw, w_host_oihw, (size_t)cin * kh * kw, scale, bias);
+  return cw;
+}
+
+int ymk_op_conv2d_view(const float* x_dev, int n, int h, int w, int c, int in_ld, const float* w_host_oihw, int cout, int kh, int kw,
+                       int tap4, const float* scale_host, const float* bias_host, const float* res_dev, int res_ld, int res_post,
+                       int stride_h, int stride_w, int pad, int dil, int act, const int* row_group_dev, const int* group_open_dev,
+                       const unsigned* amax_in_dev, unsigned* amax_out_dev, float* y_dev, int out_ld, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && w_host_oihw && y_dev, "null argument");
+  YMK_CHECK(n > 0 && h > 0 && w > 0 && c > 0 && in_ld > 0 && cout > 0 && kh > 0 && kw > 0 && res_ld >= 0 && out_ld > 0 &&
+                stride_h > 0 && stride_w > 0 && pad >= 0 && dil > 0,
+            "conv2d_view: sizes, strides and leading dimensions are positive (res_ld may be 0)");
+  hipStream_t s = (hipStream_t)stream;
+  DevicePool pool;
+  const ConvW cw = op_conv_weight(pool, w_host_oihw, cout, c, kh, kw, tap4 != 0, scale_host, bias_host);
+  SplitCtxOwner split_ctx;
+  ConvSplitScope scope(-1, split_ctx.get(), 0);  // as ymk_op_conv2d: exact fp32 unless the process-wide option says otherwise
+  if (row_group_dev || group_open_dev) {
+    // skipped rows exist for linear layers only, and those reach the kernels through gemm() (its row chunks included)
+    YMK_CHECK(kh == 1 && kw == 1 && stride_h == 1 && stride_w == 1 && pad == 0 && !res_post && !tap4,
+              "conv2d_view: a row predicate comes with a plain linear layer");
+    gemm(s, x_dev, n * h * w, c, in_ld, cw, act, res_dev, res_ld, y_dev, out_ld, row_group_dev, group_open_dev, EPI_STORE, amax_in_dev,
+         amax_out_dev);
+  } else {
+    Tensor in{const_cast<float*>(x_dev), n, h, w, c, in_ld};
+    const int oh = conv_out_dim(h, kh, stride_h, pad, dil), ow = conv_out_dim(w, kw, stride_w, pad, dil);
+    Tensor out{y_dev, n, oh, ow, cout, out_ld};
+    Tensor res{const_cast<float*>(res_dev), n, oh, ow, cout, res_ld};
+    ConvArgs a;
+    a.stride = stride_h;
+    a.stride_w = stride_w;
+    a.pad = pad;
+    a.dil = dil;
+    a.act = act;
+    a.res = res_dev ? &res : nullptr;
+    a.res_post = res_post != 0;
+    a.amax_in = amax_in_dev;
+    a.amax_out = amax_out_dev;
+    conv2d(s, in, cw, a, out);
+  }
+  YMK_HIP(hipStreamSynchronize(s));  // pool frees the panel on return
+  YMK_API_END
+}
+
+int ymk_op_conv_planes_pair(const float* x_dev, int n, int h, int w, int c, const unsigned* amax_in_dev, const float* w1_host_oihw,
+                            int cout1, int kh1, int kw1, int stride1, int pad1, int dil1, int act1, const float* scale1_host,
+                            const float* bias1_host, const float* res1_dev, const float* w2_host_oihw, int cout2, int kh2, int kw2,
+                            int stride2, int pad2, int dil2, int act2, const float* scale2_host, const float* bias2_host,
+                            const float* res2_dev, float* mid_dev, unsigned* mid_amax_dev, float* y_dev, int* planes_taken,
+                            float* pl_a, float* pl_b, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && w1_host_oihw && w2_host_oihw && mid_dev && mid_amax_dev && y_dev && planes_taken && pl_a && pl_b, "null argument");
+  YMK_CHECK(n > 0 && h > 0 && w > 0 && c > 0 && cout1 > 0 && kh1 > 0 && kw1 > 0 && stride1 > 0 && pad1 >= 0 && dil1 > 0 && cout2 > 0 &&
+                kh2 > 0 && kw2 > 0 && stride2 > 0 && pad2 >= 0 && dil2 > 0,
+            "conv_planes_pair: sizes and strides are positive");
+  hipStream_t s = (hipStream_t)stream;
+  DevicePool pool;
+  const ConvW c1 = op_conv_weight(pool, w1_host_oihw, cout1, c, kh1, kw1, false, scale1_host, bias1_host);
+  const ConvW c2 = op_conv_weight(pool, w2_host_oihw, cout2, cout1, kh2, kw2, false, scale2_host, bias2_host);
+  Tensor in{const_cast<float*>(x_dev), n, h, w, c, c};
+  in.amax = const_cast<unsigned*>(amax_in_dev);
+  Tensor mid{mid_dev, n, conv_out_dim(h, kh1, stride1, pad1, dil1), conv_out_dim(w, kw1, stride1, pad1, dil1), cout1, cout1};
+  mid.amax = mid_amax_dev;
+  Tensor out{y_dev, n, conv_out_dim(mid.h, kh2, stride2, pad2, dil2), conv_out_dim(mid.w, kw2, stride2, pad2, dil2), cout2, cout2};
+  Tensor r1{const_cast<float*>(res1_dev), mid.n, mid.h, mid.w, cout1, cout1};
+  Tensor r2{const_cast<float*>(res2_dev), out.n, out.h, out.w, cout2, cout2};
+  ConvArgs a1, a2;
+  a1.stride = stride1;
+  a1.pad = pad1;
+  a1.dil = dil1;
+  a1.act = act1;
+  a1.res = res1_dev ? &r1 : nullptr;
+  a2.stride = stride2;
+  a2.pad = pad2;
+  a2.dil = dil2;
+  a2.act = act2;
+  a2.res = res2_dev ? &r2 : nullptr;
+  SplitCtxOwner split_ctx;  // the fp16 planes of this call's panels live and die with it
+  ConvSplitScope scope(SPLIT_F16X2, split_ctx.get(), 0);
+  // as DBNetModel::bottleneck: the intermediate always has a record, and is planes where the pair qualifies
+  mid.planes = conv_planes_pair_ok(in, c1, a1, c2, a2);
+  a1.out_planes = mid.planes;
+  YMK_HIP(hipMemsetAsync(mid_amax_dev, 0, AMAX_REC_WORDS * sizeof(unsigned), s));
+  conv2d(s, in, c1, a1, mid);
+  conv2d(s, mid, c2, a2, out);
+  YMK_HIP(hipStreamSynchronize(s));
+  *planes_taken = mid.planes ? 1 : 0;
+  *pl_a = c1.pl_a;
+  *pl_b = c1.pl_b;
+  YMK_API_END
+}
+
 int ymk_op_conv1x1_astat(const float* x_dev, int m, int c, const float* w_host_oc, int cout, const float* scale_host,
                          const float* bias_host, const float* res_dev, int act, const float* ln_g_host, const float* ln_b_host, float ln_eps,
                          float* y_dev, int reps, float* kernel_ms, void* stream) {

@@ -424,6 +424,9 @@ class DevicePool {
   std::vector<ConvW> convs_, perm_;
 };
 
+// ConvW::pl_a / pl_b of a layer from its OIHW weights (per_out = cin * kh * kw values per output channel) and its folded
+// scale / bias (empty = 1 / 0): what every make_* below calls, and the single-operator entry that writes planes (ymk_api.cpp)
+void plane_bound(ConvW& c, const float* oihw, size_t per_out, const std::vector<float>& scale, const std::vector<float>& bias);
 // conv (+ optional BatchNorm folded to scale/bias) from a state-dict
 ConvW make_conv(DevicePool& pool, const WeightStore& ws, const std::string& conv_prefix,
                 const std::string& bn_prefix /* "" = none */, bool tap4 = false, float bn_eps = 1e-5f);

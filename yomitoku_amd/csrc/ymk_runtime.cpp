@@ -388,7 +388,7 @@ const HostTensor& WeightStore::get(const std::string& name) const {
 // ---------------------------------------------------------------- packing helpers
 // ConvW::pl_a / pl_b from the OIHW weights and the folded scale / bias (1 / 0 where absent); a little head room for the
 // rounding of the fp32 sums and of the bound's own arithmetic
-static void plane_bound(ConvW& c, const float* oihw, size_t per_out, const std::vector<float>& scale, const std::vector<float>& bias) {
+void plane_bound(ConvW& c, const float* oihw, size_t per_out, const std::vector<float>& scale, const std::vector<float>& bias) {
   double a = 0.0, b = 0.0;
   for (int o = 0; o < c.cout; ++o) {
     double l1 = 0.0;
