@@ -264,7 +264,8 @@ int ymk_overlay_cull_pass(void);
  *     words 5-7   first MCU, first block, first restart interval of the page (the pages' are numbered one after the other)
  *     words 8-9   byte offset of the page's file in out_dev, low / high           word 10  capacity of that file in bytes
  *     word 11-12  BYTE offset in the blob and length of the file's header (ymk_jpeg_header)
- *     word 13     WORD offset in the blob of the page's 128 quantisation values (ymk_jpeg_quant_tables)      words 14-15  0 (14: see *_opt)
+ *     word 13     WORD offset in the blob of the page's 128 quantisation values (ymk_jpeg_quant_tables)      word 14  0 (see *_opt)
+ *     word 15     the page's mode, 0 = what is said above (see YMK_JPEG_MODE_*)
  *   A record that does not fit (sizes, indices beyond the totals passed, offsets beyond the blob or out_bytes) is ignored, never
  *   trusted: its page gets length -1.
  * Scratch and output are the caller's; ymk_jpeg_scratch_bytes sizes them from HOST arrays h, w, channels: sizes6_out = total
@@ -331,6 +332,36 @@ int ymk_jpeg_encode_pages_opt(const int* blob_dev, int64_t blob_words, int n_pag
                               int64_t total_intervals, int16_t* coef_dev, int* hist_dev, uint32_t* tables_dev, unsigned char* dht_dev,
                               uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, unsigned char* out_dev, int64_t out_bytes,
                               int* lengths_dev, void* stream);
+/* Per-page modes, opt-in (encode_jpeg_pages(subsampling=..., grey="auto"), serve(jpeg_subsampling=..., jpeg_grey=...);
+ * tests/jpeg_modes_ref.py is the definition).  Word 15 of a page's record:
+ *     YMK_JPEG_MODE_420 (0)  a [h][w][3] page as 4:2:0 - today's file - or a [h][w] page as one component; the only mode of a [h][w] page
+ *     YMK_JPEG_MODE_422      [h][w][3]: luminance sampling 2 x 1, MCU 16 x 8 pixels, four blocks Y0 Y1 Cb Cr; chroma = the mean of each
+ *                            horizontal pair, (a + b + bias) >> 1, bias 0 in even output columns and 1 in odd ones
+ *     YMK_JPEG_MODE_444      [h][w][3]: luminance sampling 1 x 1, MCU 8 x 8 pixels, three blocks Y Cb Cr; chroma at full resolution
+ *     YMK_JPEG_MODE_GREY     [h][w][3], three interleaved source channels: channel 0 is encoded as the one-component file of the
+ *                            [h][w] page it is (MCU 8 x 8, one block), read in place with a pixel stride of 3
+ *   Any other value makes the record one that does not fit.  With luminance sampling hs x vs an MCU is 8 hs x 8 vs pixels of
+ *   hs vs + 2 blocks, a restart interval one MCU row (at most 2048 MCUs of 3 blocks, 1024 of 4 or of 6), the SOF0 luminance byte
+ *   hs << 4 | vs and DRI ceil(w / (8 hs)).  Word 5 and total_mcus count what a wave of ymk_jpeg_coefficients takes: the 16 x 16 pixel
+ *   tiles of a [h][w][3] page in every mode (one, two or four MCUs; at 4:2:0 the MCU itself), the 8 x 8 MCUs of a [h][w] page.
+ * ymk_jpeg_header_mode / ymk_jpeg_header_opt_mode / ymk_jpeg_scratch_bytes_mode / ymk_jpeg_scratch_bytes_opt_mode: the entries
+ *   without _mode for pages of these modes (modes: HOST int [n_pages], null = all 0; sizes[0] = the tiles); mode 0 gives what
+ *   those give.
+ * ymk_jpeg_pages_grey: diff_dev int32 [n_pages], zeroed on `stream`, then per page the OR over its pixels of (B ^ G) | (B ^ R)
+ *   reduced to 0 / 1: 0 = every pixel of the page has B == G == R (the page may be written with YMK_JPEG_MODE_GREY).  blob_dev:
+ *   n_pages records of YMK_JPEG_PAGE_WORDS words of which only words 0-4 are read; a record that is not a [h][w][3] page gets -1.
+ *   max_pixels: h * w of the largest page (sizes the launch).  16-byte loads where the page's address allows, pixel by pixel
+ *   where it does not and behind the last whole 16 pixels.  Nothing is allocated, nothing waited for. */
+#define YMK_JPEG_MODE_420 0
+#define YMK_JPEG_MODE_422 1
+#define YMK_JPEG_MODE_444 2
+#define YMK_JPEG_MODE_GREY 4
+int ymk_jpeg_header_mode(int h, int w, int channels, int mode, int quality, unsigned char* out, int capacity);
+int ymk_jpeg_header_opt_mode(int h, int w, int channels, int mode, int quality, unsigned char* out, int capacity, int* split_out);
+int ymk_jpeg_scratch_bytes_mode(const int* h, const int* w, const int* channels, const int* modes, int n_pages, int64_t* sizes6_out);
+int ymk_jpeg_scratch_bytes_opt_mode(const int* h, const int* w, const int* channels, const int* modes, int n_pages,
+                                    int64_t* sizes9_out);
+int ymk_jpeg_pages_grey(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* diff_dev, void* stream);
 /* ymk_pil_resize_u8: Pillow's two-pass 8-bit resample (as ymk_pil_resize_to_chw: 22-bit coefficients, 1 << 21 bias, clip to
  *   uint8 between the passes) for n images in one launch, written as uint8 [oh][ow][C] in the source's channel order.  blob_dev:
  *   n records of YMK_PIL_RESIZE_U8_WORDS int32 words {source address low, high; H; W; C (1 | 3); oh; ow; ksize_x; ksize_y; word

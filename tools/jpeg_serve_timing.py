@@ -8,6 +8,11 @@ hand on the GPU, not by the suite).
     python tools/jpeg_serve_timing.py --optimize --legs b --presets high --out profiles/jpeg_serve_optimized.json
                                                                  # (b) next to (o); without --optimize this form also runs on
                                                                  # a checkout of the commit before the optimised tables
+    python tools/jpeg_serve_timing.py --legs b --presets high --subsampling 4:4:4 [--grey auto] [--grey-pages] --out FILE
+                                                                 # (b) in another mode of the encoder; tools/jobs/jpeg_serve_modes.sh
+                                                                 # runs the modes one after the other -> profiles/jpeg_serve_modes.json.
+                                                                 # Without the three options this form also runs on a checkout
+                                                                 # of the commit before the modes
 
 Legs, each one job over all pages, pages/s = pages / wall time, median over the repetitions, for the presets "high" and "low":
   (c) plain   serve(pages): the headline path, 2 x reps jobs as a block of their own before the other legs.
@@ -19,7 +24,10 @@ Legs, each one job over all pages, pages/s = pages / wall time, median over the 
 (a), (b) and (o) alternate within a repetition; --legs picks among c, a, b.
 Also: the device time of the encoder's stages for one wave (HIP events around each C-ABI call, median of 10 after a warm-up; for
 "low" the wall time of the Lanczos call), and bytes per page next to Pillow's own file for the same page; with --optimize the five
-stages of the optimised path and the bytes of its files next to Pillow's `optimize=True` as well."""
+stages of the optimised path and the bytes of its files next to Pillow's `optimize=True` as well.
+--subsampling / --grey: legs (b) and (o) and the stage times in that mode of the encoder (serve(jpeg_subsampling=, jpeg_grey=)); with
+--grey auto the grey test's launch is timed as a stage of its own.  --grey-pages: the job's pages are made grey-valued (B = G = R =
+the page's green plane) before anything runs - what a black-and-white scan is when load_image hands it over."""
 import argparse
 import io
 import json
@@ -37,7 +45,49 @@ from PIL import Image  # noqa: E402
 import bench  # noqa: E402
 
 
-def stage_times(pages_dev, preset, reps=10):
+def mode_kwargs(args, serve=True):
+    """The keywords of --subsampling / --grey for serve() or encode_jpeg_pages(); none at the defaults (so that the tool also runs
+    on a tree before the modes)."""
+    out = {}
+    if args.subsampling != "4:2:0":
+        out["jpeg_subsampling" if serve else "subsampling"] = args.subsampling
+    if args.grey != "off":
+        out["jpeg_grey" if serve else "grey"] = args.grey
+    return out
+
+
+def page_modes(pages_dev, subsampling, grey, times=None, reps=10):
+    """Word 15 of every page's record, as encode_jpeg_pages chooses it (None at the defaults); with grey "auto" the grey test's
+    launch goes into times["grey_test"] (device milliseconds, HIP events around the C-ABI call)."""
+    if subsampling == "4:2:0" and grey == "off":
+        return None
+    from yomitoku_amd import _lib, imaging
+    from yomitoku_amd.jpeg import MODE_GREY, PAGE_WORDS, SUBSAMPLINGS, _addr_words, grey_pages
+
+    as_grey = [False] * len(pages_dev)
+    if grey == "auto":
+        as_grey = grey_pages(pages_dev)
+        rec = np.zeros((len(pages_dev), PAGE_WORDS), np.int32)
+        for k, t in enumerate(pages_dev):
+            rec[k, 0:2] = _addr_words(t.data_ptr())
+            rec[k, 2:5] = (int(t.shape[0]), int(t.shape[1]), 3)
+        blob_dev = imaging._stage_blob(rec.reshape(-1), pages_dev[0].device)
+        diff = torch.empty(len(pages_dev), dtype=torch.int32, device=pages_dev[0].device)
+        most = max(int(t.shape[0]) * int(t.shape[1]) for t in pages_dev)
+        for rep in range(reps + 1):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            a.record()
+            _lib.check(_lib.load().ymk_jpeg_pages_grey(blob_dev.data_ptr(), rec.size, len(pages_dev), most, diff.data_ptr(),
+                                                       torch.cuda.current_stream().cuda_stream))
+            b.record()
+            torch.cuda.synchronize()
+            if rep and times is not None:
+                times.setdefault("grey_test", []).append(a.elapsed_time(b))
+    return [MODE_GREY if g else SUBSAMPLINGS[subsampling] for g in as_grey]
+
+
+def stage_times(pages_dev, preset, reps=10, subsampling="4:2:0", grey="off"):
     """One wave of device pages: median device milliseconds of the three encoder stages (HIP events around each C-ABI call),
     and - for a preset that shrinks - the wall time of the whole Lanczos call, host part (blob, upload) and wait included."""
     from yomitoku_amd import _lib
@@ -60,8 +110,10 @@ def stage_times(pages_dev, preset, reps=10):
             torch.cuda.synchronize()
             if rep:  # the first pass builds the coefficient tables
                 times["resize_call_wall"].append((time.perf_counter() - t0) * 1e3)
-    blob, _, out_bytes = page_table(small, p["jpeg_quality"])
-    mcus, blocks, intervals, coef_b, stream_b, iv_b = scratch_sizes([(int(t.shape[0]), int(t.shape[1]), 3) for t in small])
+    modes = page_modes(small, subsampling, grey, times, reps)
+    mode_kw = {} if modes is None else {"modes": modes}
+    blob, _, out_bytes = page_table(small, p["jpeg_quality"], **mode_kw)
+    mcus, blocks, intervals, coef_b, stream_b, iv_b = scratch_sizes([(int(t.shape[0]), int(t.shape[1]), 3) for t in small], **mode_kw)
     dev = small[0].device
     coef, bits, ivals, out, lengths = (torch.empty(n, dtype=torch.uint8, device=dev) for n in (coef_b, stream_b, iv_b, out_bytes, 4 * len(small)))
     blob_dev = torch.from_numpy(blob).to(dev)
@@ -84,7 +136,7 @@ def stage_times(pages_dev, preset, reps=10):
     return {k: round(statistics.median(v), 3) for k, v in times.items() if v}
 
 
-def stage_times_optimized(pages_dev, preset, reps=10):
+def stage_times_optimized(pages_dev, preset, reps=10, subsampling="4:2:0", grey="off"):
     """stage_times for the five stages of the optimised path (the preset's shrink is not repeated here)."""
     from yomitoku_amd import _lib
     from yomitoku_amd.jpeg import jpeg_preset, page_table, resize_pages, scratch_sizes
@@ -100,8 +152,10 @@ def stage_times_optimized(pages_dev, preset, reps=10):
             sizes.append((int(h * s), int(w * s)))
         small = resize_pages(pages_dev, sizes)
     n = len(small)
-    blob, _, out_bytes = page_table(small, p["jpeg_quality"], optimize=True)
-    sized = scratch_sizes([(int(t.shape[0]), int(t.shape[1]), 3) for t in small], optimize=True)
+    modes = page_modes(small, subsampling, grey)
+    mode_kw = {} if modes is None else {"modes": modes}
+    blob, _, out_bytes = page_table(small, p["jpeg_quality"], optimize=True, **mode_kw)
+    sized = scratch_sizes([(int(t.shape[0]), int(t.shape[1]), 3) for t in small], optimize=True, **mode_kw)
     mcus, blocks, intervals, coef_b, stream_b, iv_b, hist_b, tables_b, dht_b = sized
     dev = small[0].device
     coef, bits, ivals, hist, tables, dht, out, lengths = (torch.empty(b, dtype=torch.uint8, device=dev)
@@ -145,6 +199,9 @@ def main():
                     "file also runs on a checkout of the commit before the encoder")
     ap.add_argument("--optimize", action="store_true", help="leg (o) next to (b), the optimised path's stage times and file sizes")
     ap.add_argument("--legs", default="c,a,b", help="which of the legs c, a, b to run (default: all three)")
+    ap.add_argument("--subsampling", default="4:2:0", choices=["4:2:0", "4:2:2", "4:4:4"], help="the chroma of the device's colour files")
+    ap.add_argument("--grey", default="off", choices=["off", "auto"], help="auto: grey-valued pages become grey files (one more launch and wait)")
+    ap.add_argument("--grey-pages", action="store_true", help="make every page grey-valued (B = G = R) first")
     ap.add_argument("--out")
     args = ap.parse_args()
     device = bench.rank_device(0)
@@ -154,6 +211,8 @@ def main():
     an = bench.build_analyzer(device, sds, "lite")
     an.truth = pages
     host = [p.img for p in pages]
+    if args.grey_pages:
+        host = [np.ascontiguousarray(np.stack([img[..., 1]] * 3, -1)) for img in host]
     presets = [q for q in args.presets.split(",") if q]
     legs = {"c", "a"} if args.host_only else {leg for leg in args.legs.split(",") if leg}
     if args.optimize and "b" not in legs:
@@ -163,12 +222,14 @@ def main():
         from yomitoku_amd.jpeg import encode_jpeg_pages
 
         for q in presets:  # the render thread, the wave slots' scratch, the Lanczos tables
-            an.serve(host, wave=args.wave, jpeg=q)
+            an.serve(host, wave=args.wave, jpeg=q, **mode_kwargs(args))
             if args.optimize:
-                an.serve(host, wave=args.wave, jpeg=q, jpeg_optimize=True)
+                an.serve(host, wave=args.wave, jpeg=q, jpeg_optimize=True, **mode_kwargs(args))
     torch.cuda.synchronize()
     result = {"pages": args.pages, "wave": args.wave, "reps": args.reps, "device": torch.cuda.get_device_name(0),
               "legs": ", ".join(sorted(legs, key="cab".index)) + (", o" if args.optimize else ""), "presets": {}}
+    if mode_kwargs(args) or args.grey_pages:
+        result.update({"subsampling": args.subsampling, "grey": args.grey, "grey_pages": args.grey_pages})
     # (c) first, as a block of its own: nothing else between its jobs
     plain = []
     for _ in range(2 * args.reps if "c" in legs else 0):
@@ -196,7 +257,7 @@ def main():
                 if "b" not in legs or (name == "optimized" and not args.optimize):
                     continue
                 t0 = time.perf_counter()
-                out = an.serve(host, wave=args.wave, jpeg=q, **kwargs)
+                out = an.serve(host, wave=args.wave, jpeg=q, **kwargs, **mode_kwargs(args))
                 good = [e for e in out if isinstance(e, tuple)]
                 pdf_bytes[name] = len(searchable_pdf_bytes([e[1] for e in good], [e[0] for e in good]))
                 rates[name].append(len(out) / (time.perf_counter() - t0))
@@ -206,32 +267,35 @@ def main():
         if "b" in legs:
             preset = IMAGE_QUALITY_PRESETS[q]
             wave_dev = [torch.from_numpy(img).to(device) for img in host[: args.wave]]
-            files = encode_jpeg_pages(wave_dev, q)
+            files = encode_jpeg_pages(wave_dev, q, **mode_kwargs(args, serve=False))
             pil_sizes, pil_opt_sizes = [], []
+            pil_kw = {} if args.subsampling == "4:2:0" else {"subsampling": args.subsampling}  # Pillow's file in the same mode
             for img in host[: args.wave]:
                 image = Image.fromarray(np.ascontiguousarray(img[:, :, ::-1]))
+                if args.grey == "auto" and args.grey_pages:
+                    image, pil_kw = image.convert("L"), {}
                 if preset["max_long_side"] is not None and max(image.size) > preset["max_long_side"]:
                     s = preset["max_long_side"] / max(image.size)
                     image = image.resize((int(image.size[0] * s), int(image.size[1] * s)), Image.LANCZOS)
                 data = io.BytesIO()
-                image.save(data, "JPEG", quality=preset["jpeg_quality"])
+                image.save(data, "JPEG", quality=preset["jpeg_quality"], **pil_kw)
                 pil_sizes.append(len(data.getvalue()))
                 if args.optimize:
                     data = io.BytesIO()
-                    image.save(data, "JPEG", quality=preset["jpeg_quality"], optimize=True)
+                    image.save(data, "JPEG", quality=preset["jpeg_quality"], optimize=True, **pil_kw)
                     pil_opt_sizes.append(len(data.getvalue()))
             entry.update({
                 "pages_per_s_device_jpeg": [round(v, 2) for v in rates["device"]],
                 "pages_per_s_device_jpeg_median": round(statistics.median(rates["device"]), 2),
-                "device_ms_per_wave": stage_times(wave_dev, q),
+                "device_ms_per_wave": stage_times(wave_dev, q, **({"subsampling": args.subsampling, "grey": args.grey} if mode_kwargs(args) else {})),
                 "bytes_per_page_device": round(statistics.mean(len(f.data) for f in files)), "bytes_per_page_pillow": round(statistics.mean(pil_sizes)),
             })
             if args.optimize:
-                files = encode_jpeg_pages(wave_dev, q, optimize=True)
+                files = encode_jpeg_pages(wave_dev, q, optimize=True, **mode_kwargs(args, serve=False))
                 entry.update({
                     "pages_per_s_optimized_jpeg": [round(v, 2) for v in rates["optimized"]],
                     "pages_per_s_optimized_jpeg_median": round(statistics.median(rates["optimized"]), 2),
-                    "optimized_ms_per_wave": stage_times_optimized(wave_dev, q),
+                    "optimized_ms_per_wave": stage_times_optimized(wave_dev, q, **({"subsampling": args.subsampling, "grey": args.grey} if mode_kwargs(args) else {})),
                     "bytes_per_page_optimized": round(statistics.mean(len(f.data) for f in files)),
                     "bytes_per_page_pillow_optimize": round(statistics.mean(pil_opt_sizes)),
                 })

@@ -80,6 +80,12 @@ SIGNATURES = {
                                      c_int64, c_void_p, c_void_p]),
     "ymk_jpeg_encode_pages_opt": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ymk_jpeg_header_mode": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int]),
+    "ymk_jpeg_header_opt_mode": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, POINTER(c_int)]),
+    "ymk_jpeg_scratch_bytes_mode": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_jpeg_scratch_bytes_opt_mode": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int,
+                                                POINTER(c_int64)]),
+    "ymk_jpeg_pages_grey": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

@@ -2,11 +2,17 @@
 // uint8 form of the Pillow resample that shrinks a page first.  DESIGN.md, "JPEG encoder", has the pixel rules and the format;
 // tests/jpeg_ref.py is the definition every stage equals byte for byte.  All arithmetic is integer.
 //
-//   k_jpeg_coefficients   one wave per MCU (16 x 16 pixels of a colour page, 8 x 8 of a grey one), four MCUs per block.  The MCU's
-//                         rows come in as 16-byte loads into LDS (an edge MCU, or a page whose rows are not 16-byte aligned: byte
-//                         loads with the coordinates clamped = edge replication), are converted to Y Cb Cr, the chroma averaged
-//                         2 x 2, and the six 8 x 8 blocks go through libjpeg's `islow` DCT - 8 lanes per block, one row, then one
-//                         column each - and the quantiser.  Output: zig-zag int16 [block][64] in scan order.
+//   k_jpeg_coefficients   one wave per tile (16 x 16 pixels of a colour page - the MCU at 4:2:0, two MCUs at 4:2:2, four at 4:4:4 -,
+//                         8 x 8 of a one-component one), four tiles per block.  The tile's rows come in as 16-byte loads into LDS
+//                         (an edge tile, or a page whose rows are not 16-byte aligned: byte loads with the coordinates clamped =
+//                         edge replication), are converted to Y Cb Cr, the chroma averaged 2 x 2 / in pairs / not at all, and the
+//                         six / eight / twelve 8 x 8 blocks go through libjpeg's `islow` DCT - 8 lanes per block, one row, then
+//                         one column each; twelve blocks in two turns - and the quantiser.  Output: zig-zag int16 [block][64] in
+//                         scan order; an MCU of an edge tile that is not the page's is not written.  A page's mode (word 15 of
+//                         its record; tests/jpeg_modes_ref.py is the definition) also makes channel 0 of a three-channel page a
+//                         one-component file: the same tile and loads, four MCUs of one block, no copy of the plane.
+//   k_jpeg_pages_grey     whether a three-channel page has B == G == R everywhere (what decides that mode): an OR-reduction of
+//                         the pixels' XORs, 16-byte loads, one int per page.
 //   k_jpeg_entropy        one wave per restart interval (= one MCU row).  64 blocks at a time: their coefficients staged in LDS,
 //                         each lane sizes ITS block (DC predictor = the previous block of the component, 0 at the start of the
 //                         interval), a wave prefix sum turns the sizes into bit positions, the words the chunk will touch are
@@ -40,7 +46,8 @@ namespace ymk {
 
 constexpr int JP_REC = YMK_JPEG_PAGE_WORDS;
 constexpr int JP_BLOCK_WORDS = YMK_JPEG_BLOCK_STREAM_BYTES / 4;  // 32-bit words of the unstuffed stream reserved per block
-constexpr int JP_WAVES = 4;                                      // MCUs per block of k_jpeg_coefficients
+constexpr int JP_WAVES = 4;                                      // tiles per block of k_jpeg_coefficients
+constexpr int JP_TILE_BLOCKS = 12;                               // blocks of a 16 x 16 tile at 4:4:4 (4:2:2: 8, 4:2:0: 6)
 static_assert(YMK_JPEG_BLOCK_STREAM_BYTES % 4 == 0 && YMK_JPEG_BLOCK_STREAM_BYTES * 8 >= 22 + 63 * 26,
               "a block's worst case: a 11 + 11 bit DC and 63 AC symbols of 16 + 10 bits");
 constexpr int JP_BLOCK_WORDS_OPT = YMK_JPEG_BLOCK_STREAM_BYTES_OPT / 4;
@@ -134,6 +141,26 @@ static void quant_tables(int quality, int* out128) {
     }
 }
 
+// A page's mode (word 15 of its record), host and device.  The luminance sampling factors are 1 << lh and 1 << lv (a
+// one-component file: 1 x 1, an MCU of one block).  A tile - the pixels a wave of k_jpeg_coefficients takes - has 1 << lt pixels on
+// a side: 16 of a three-channel page in every mode (one, two or four MCUs), the MCU's 8 of a one-channel page.  Logarithms, so
+// that the device derives a page's geometry with shifts.
+struct JpegMode {
+  int comps, lh, lv, lt;
+};
+__host__ __device__ inline bool jpeg_mode(int channels, int mode, JpegMode& m) {
+  if (channels == 1 && mode == 0) {
+    m = {1, 0, 0, 3};
+  } else if (channels == 3 && mode == YMK_JPEG_MODE_GREY) {
+    m = {1, 0, 0, 4};
+  } else if (channels == 3 && (mode == YMK_JPEG_MODE_420 || mode == YMK_JPEG_MODE_422 || mode == YMK_JPEG_MODE_444)) {
+    m = {3, mode == YMK_JPEG_MODE_444 ? 0 : 1, mode == YMK_JPEG_MODE_420 ? 1 : 0, 4};
+  } else {
+    return false;
+  }
+  return true;
+}
+
 static void put_segment(std::vector<unsigned char>& out, int marker, const std::vector<unsigned char>& payload) {
   out.push_back(0xff);
   out.push_back((unsigned char)marker);
@@ -144,7 +171,8 @@ static void put_segment(std::vector<unsigned char>& out, int marker, const std::
 
 // SOI, APP0, DQT, SOF0, DHT, DRI, SOS: everything before the scan's first byte
 // dht false: without the DHT segments, *split = the bytes before their place
-static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quality, bool dht = true, int* split = nullptr) {
+static std::vector<unsigned char> jpeg_header(int h, int w, const JpegMode& mode, int quality, bool dht = true, int* split = nullptr) {
+  const bool grey = mode.comps == 1;
   int q[128];
   quant_tables(quality, q);
   std::vector<unsigned char> out = {0xff, 0xd8};
@@ -158,7 +186,7 @@ static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quali
   if (grey) {
     sof.insert(sof.end(), {1, 1, 0x11, 0});
   } else {
-    sof.insert(sof.end(), {3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1});
+    sof.insert(sof.end(), {3, 1, (unsigned char)(1 << (mode.lh + 4) | 1 << mode.lv), 0, 2, 0x11, 1, 3, 0x11, 1});
   }
   put_segment(out, 0xc0, sof);
   const HuffSpec* specs[4] = {&DC_LUMA, &AC_LUMA, &DC_CHROMA, &AC_CHROMA};
@@ -170,7 +198,7 @@ static std::vector<unsigned char> jpeg_header(int h, int w, bool grey, int quali
     p.insert(p.end(), specs[t]->vals, specs[t]->vals + specs[t]->n);
     put_segment(out, 0xc4, p);
   }
-  const int mcus = grey ? (w + 7) / 8 : (w + 15) / 16;
+  const int mcus = (w + (8 << mode.lh) - 1) >> (3 + mode.lh);  // one MCU row per restart interval
   put_segment(out, 0xdd, {(unsigned char)(mcus >> 8), (unsigned char)(mcus & 255)});
   if (grey) {
     put_segment(out, 0xda, {1, 1, 0x00, 0, 63, 0});
@@ -187,7 +215,9 @@ struct JpegLimits {
 struct JpegPage {
   const unsigned char* src;
   int h, w, ch, mcu_w, mcu_h, per;  // per: blocks per MCU
-  long long first_mcu, first_block, first_interval, out_off;
+  int comps, lh, lv, lt;            // JpegMode's
+  int tile_w, tile_h;               // the page in k_jpeg_coefficients' tiles
+  long long first_mcu, first_block, first_interval, out_off;  // first_mcu (word 5) counts tiles
   int capacity, hdr_off, hdr_len, q_off, hdr_split;  // hdr_split (word 14): the header's bytes before the DHT segments' place
 };
 // Record p, checked against the limits: a record that does not fit is no page (never trusted).
@@ -195,16 +225,18 @@ __device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const Jp
   const int* r = blob + (size_t)p * JP_REC;
   g.src = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)r[1] << 32) | (unsigned long long)(unsigned)r[0]);
   g.h = r[2], g.w = r[3], g.ch = r[4];
-  if (g.src == nullptr || g.h < 1 || g.w < 1 || g.h > 16383 || g.w > 16383 || (g.ch != 1 && g.ch != 3)) return false;
-  const int m = g.ch == 3 ? 16 : 8;
-  g.per = g.ch == 3 ? 6 : 1;
-  g.mcu_w = (g.w + m - 1) / m, g.mcu_h = (g.h + m - 1) / m;
+  JpegMode m;
+  if (g.src == nullptr || g.h < 1 || g.w < 1 || g.h > 16383 || g.w > 16383 || !jpeg_mode(g.ch, r[15], m)) return false;
+  g.comps = m.comps, g.lh = m.lh, g.lv = m.lv, g.lt = m.lt;
+  g.per = m.comps == 3 ? (1 << (m.lh + m.lv)) + 2 : 1;
+  g.mcu_w = (g.w + (8 << m.lh) - 1) >> (3 + m.lh), g.mcu_h = (g.h + (8 << m.lv) - 1) >> (3 + m.lv);
+  g.tile_w = (g.w + (1 << m.lt) - 1) >> m.lt, g.tile_h = (g.h + (1 << m.lt) - 1) >> m.lt;
   g.first_mcu = r[5], g.first_block = r[6], g.first_interval = r[7];
   g.out_off = (long long)(((unsigned long long)(unsigned)r[9] << 32) | (unsigned long long)(unsigned)r[8]);
   g.capacity = r[10], g.hdr_off = r[11], g.hdr_len = r[12], g.q_off = r[13];
   g.hdr_split = min(max(r[14], 0), max(g.hdr_len, 0));
   const long long mcus = (long long)g.mcu_w * g.mcu_h;
-  if (g.first_mcu < 0 || g.first_block < 0 || g.first_interval < 0 || g.first_mcu + mcus > lim.total_mcus ||
+  if (g.first_mcu < 0 || g.first_block < 0 || g.first_interval < 0 || g.first_mcu + (long long)g.tile_w * g.tile_h > lim.total_mcus ||
       g.first_block + mcus * g.per > lim.total_blocks || g.first_interval + g.mcu_h > lim.total_intervals)
     return false;
   if (g.q_off < 0 || (long long)g.q_off + 128 > lim.blob_words) return false;
@@ -212,14 +244,23 @@ __device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const Jp
   if (lim.out_bytes >= 0 && (g.capacity < 0 || g.out_off < 0 || g.out_off + g.capacity > lim.out_bytes)) return false;
   return true;
 }
-// the page whose MCUs (by_interval false) / restart intervals (true) contain global index `idx`, or -1
+// The page whose tiles (by_interval false) / restart intervals (true) contain global index `idx`, or -1: the first record that is
+// a page (jpeg_page) and has the index.  Every wave of every stage searches, through half the table on average, and a whole
+// jpeg_page per record passed was most of what a wave of k_jpeg_coefficients executed.  So a record is first asked whether the
+// index could be its own, from the five words that say so - its first and its count as jpeg_page derives them, from words not
+// yet checked (a record that is no page may answer anything: jpeg_page is asked next, and answers as it always did).
 __device__ __forceinline__ int jpeg_find(const int* __restrict__ blob, const JpegLimits& lim, int n_pages, long long idx, bool by_interval,
                                          JpegPage& g) {
   for (int p = 0; p < n_pages; ++p) {
-    if (!jpeg_page(blob, lim, p, g)) continue;
-    const long long first = by_interval ? g.first_interval : g.first_mcu;
-    const long long count = by_interval ? g.mcu_h : (long long)g.mcu_w * g.mcu_h;
-    if (idx >= first && idx < first + count) return p;
+    const int* r = blob + (size_t)p * JP_REC;
+    JpegMode m;
+    if (!jpeg_mode(r[4], r[15], m)) continue;
+    const unsigned h = (unsigned)r[2], w = (unsigned)r[3];
+    const long long first = by_interval ? r[7] : r[5];
+    const long long count = by_interval ? (long long)((h + (8u << m.lv) - 1) >> (3 + m.lv))
+                                        : (long long)((w + (1u << m.lt) - 1) >> m.lt) * (long long)((h + (1u << m.lt) - 1) >> m.lt);
+    if (idx < first || idx >= first + count) continue;
+    if (jpeg_page(blob, lim, p, g)) return p;
   }
   return -1;
 }
@@ -259,21 +300,36 @@ __device__ __forceinline__ void fdct_pass(int* d, int stride) {
 
 __global__ __launch_bounds__(JP_WAVES * 64) void k_jpeg_coefficients(const int* __restrict__ blob, JpegLimits lim, int n_pages,
                                                                      short* __restrict__ coef) {
-  __shared__ __align__(16) unsigned char s_raw[JP_WAVES][16 * 48];  // the MCU's pixels, B G R
-  __shared__ short s_chroma[JP_WAVES][2][256];                      // Cb, Cr at full resolution
-  __shared__ int s_blk[JP_WAVES][6][64];                            // Y0 Y1 Y2 Y3 Cb Cr, samples - 128, then the DCT in place
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long mcu = (long long)blockIdx.x * JP_WAVES + wave;
+  __shared__ __align__(16) unsigned char s_raw[JP_WAVES][16 * 48];  // the tile's pixels, B G R
+  // The tile's MCUs one after the other, each Y.. Cb Cr: samples - 128, then the DCT in place.  Only 4:4:4 has more than eight
+  // blocks, and it needs no chroma at full resolution next to them: in the other modes blocks 8 - 11 hold that, Cb and Cr as
+  // short [2][256].  15 KB of LDS per workgroup, where blocks and planes side by side would take 19 (4:2:0 alone took 13).
+  __shared__ int s_blk[JP_WAVES][JP_TILE_BLOCKS][64];
+  static_assert(JP_TILE_BLOCKS == 12 && 4 * 64 * sizeof(int) == 2 * 256 * sizeof(short), "the planes fill blocks 8 - 11");
+  // the wave's index is the same in all its lanes; said so, the search for the tile's page and the page's geometry are scalar work
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const long long tile = (long long)blockIdx.x * JP_WAVES + wave;
   JpegPage g;
-  const bool ok = mcu < lim.total_mcus && jpeg_find(blob, lim, n_pages, mcu, false, g) >= 0;  // the same in all lanes of a wave
-  const bool colour = ok && g.ch == 3, grey = ok && g.ch == 1;
-  int mx = 0, my = 0;
+  const bool ok = tile < lim.total_mcus && jpeg_find(blob, lim, n_pages, tile, false, g) >= 0;  // the same in all lanes of a wave
+  const bool colour = ok && g.comps == 3, grey = ok && g.comps == 1;
+  const bool wide = ok && g.lt == 4;  // a 16 x 16 tile of a three-channel page: colour, or channel 0 alone
+  int tx = 0, ty = 0;
+  int d_luma = 8, d_chroma = 8;  // this lane's two divisors, asked for now: every block of the tile uses one of them at the end
   if (ok) {
-    const long long local = mcu - g.first_mcu;
-    my = (int)(local / g.mcu_w), mx = (int)(local % g.mcu_w);
+    const long long local = tile - g.first_mcu;
+    ty = (int)(local / g.tile_w), tx = (int)(local % g.tile_w);
+    const int* qt = blob + g.q_off;
+    d_luma = min(max(qt[lane], 1), 255) * 8, d_chroma = min(max(qt[64 + lane], 1), 255) * 8;
   }
-  if (colour) {
-    const int x0 = mx * 16, y0 = my * 16;
+  // The sampling factors are 1 or 2: sh, sv are their logarithms and the masks hs - 1, vs - 1 at once.  The tile has
+  // mcus_x x mcus_y MCUs of `per` blocks, the first ny of them luminance.
+  const int sh = ok ? g.lh : 0, sv = ok ? g.lv : 0;
+  const int lx = wide ? 1 - sh : 0, mcus_x = 1 << lx, mcus_y = wide ? 2 >> sv : 1;
+  const int per = ok ? g.per : 0, ny = 1 << (sh + sv);
+  const bool full = colour && sh + sv == 0;  // 4:4:4: Cb and Cr go into their blocks as they are
+  short* s_chroma = reinterpret_cast<short*>(&s_blk[wave][8][0]);
+  if (wide) {
+    const int x0 = tx * 16, y0 = ty * 16;
     const size_t pitch = (size_t)g.w * 3;
     const bool whole = x0 + 16 <= g.w && y0 + 16 <= g.h && (pitch & 15) == 0 && ((uintptr_t)g.src & 15) == 0;
     if (whole) {
@@ -297,40 +353,60 @@ __global__ __launch_bounds__(JP_WAVES * 64) void k_jpeg_coefficients(const int* 
       const int y = (19595 * r + 38470 * gr + 7471 * b + 32768) >> 16;
       const int cb = (-11059 * r - 21709 * gr + 32768 * b + (128 << 16) + 32767) >> 16;
       const int cr = (32768 * r - 27439 * gr - 5329 * b + (128 << 16) + 32767) >> 16;
+      const int py = i >> 4, px = i & 15, by = py >> 3, bx = px >> 3;
+      // block (by, bx) of the tile: its MCU, and its place among the MCU's luminance blocks (row-major)
+      const int slot = (((by >> sv) << lx) + (bx >> sh)) * per + ((by & sv) << sh) + (bx & sh);
+      s_blk[wave][slot][(py & 7) * 8 + (px & 7)] = y - 128;
+      if (full) {
+        s_blk[wave][slot + 1][(py & 7) * 8 + (px & 7)] = cb - 128;
+        s_blk[wave][slot + 2][(py & 7) * 8 + (px & 7)] = cr - 128;
+      } else {
+        s_chroma[i] = (short)cb;
+        s_chroma[256 + i] = (short)cr;
+      }
+    }
+  } else if (wide) {  // the grey file of a three-channel page: channel 0, four MCUs of one block
+    for (int i = lane; i < 256; i += 64) {
       const int py = i >> 4, px = i & 15;
-      s_blk[wave][(py >> 3) * 2 + (px >> 3)][(py & 7) * 8 + (px & 7)] = y - 128;
-      s_chroma[wave][0][i] = (short)cb;
-      s_chroma[wave][1][i] = (short)cr;
+      s_blk[wave][(py >> 3) * 2 + (px >> 3)][(py & 7) * 8 + (px & 7)] = (int)s_raw[wave][i * 3] - 128;
     }
   } else if (grey) {
-    const int sy = min(my * 8 + (lane >> 3), g.h - 1), sx = min(mx * 8 + (lane & 7), g.w - 1);
+    const int sy = min(ty * 8 + (lane >> 3), g.h - 1), sx = min(tx * 8 + (lane & 7), g.w - 1);
     s_blk[wave][0][lane] = (int)g.src[(size_t)sy * g.w + sx] - 128;
   }
   __syncthreads();
-  if (colour) {
-    const int cy = lane >> 3, cx = lane & 7, at = cy * 32 + cx * 2;
+  if (colour && !full) {  // one MCU at 4:2:0, two (one below the other) at 4:2:2: blocks 0 - 7 at the most
+    const int cy = lane >> 3, cx = lane & 7;
+    for (int m = 0; m < mcus_y; ++m) {
+      // the MCU's first row in the tile, then this lane's sample: 8 chroma columns per MCU, so cx's parity is the column's
+      const int at = ((m * 8 + cy) << sv) * 16 + cx * 2;
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const short* s = s_chroma[wave][c];
-      s_blk[wave][4 + c][lane] = ((s[at] + s[at + 1] + s[at + 16] + s[at + 17] + 1 + (cx & 1)) >> 2) - 128;  // MCUs are 8 chroma columns wide
+      for (int c = 0; c < 2; ++c) {
+        const short* s = s_chroma + c * 256;
+        const int v = sv ? (s[at] + s[at + 1] + s[at + 16] + s[at + 17] + 1 + (cx & 1)) >> 2 : (s[at] + s[at + 1] + (cx & 1)) >> 1;
+        s_blk[wave][m * per + ny + c][lane] = v - 128;
+      }
     }
   }
   __syncthreads();
-  const int nb = ok ? g.per : 0;
-  if (lane < nb * 8) fdct_pass<true>(&s_blk[wave][lane >> 3][(lane & 7) * 8], 1);
+  const int nb = mcus_x * mcus_y * per;  // 6, 8 or 12 of a colour page, 4 or 1 of a grey one
+  for (int i = lane; i < nb * 8; i += 64) fdct_pass<true>(&s_blk[wave][i >> 3][(i & 7) * 8], 1);
   __syncthreads();
-  if (lane < nb * 8) fdct_pass<false>(&s_blk[wave][lane >> 3][lane & 7], 8);
+  for (int i = lane; i < nb * 8; i += 64) fdct_pass<false>(&s_blk[wave][i >> 3][i & 7], 8);
   __syncthreads();
   if (ok) {
-    const int* qt = blob + g.q_off;
-    const long long first = g.first_block + (mcu - g.first_mcu) * g.per;
-    for (int b = 0; b < nb; ++b) {
-      const int v = s_blk[wave][b][c_zigzag[lane]];
-      const int d = min(max(qt[(b >= 4 ? 64 : 0) + lane], 1), 255) * 8;
-      int c = (abs(v) + d / 2) / d;
-      c = v < 0 ? -c : c;
-      c = min(max(c, lane == 0 ? -1024 : -1023), 1023);
-      coef[(size_t)(first + b) * 64 + lane] = (short)c;
+    for (int m = 0; m < mcus_x * mcus_y; ++m) {
+      const int mx = tx * mcus_x + (m & (mcus_x - 1)), my = ty * mcus_y + (m >> lx);
+      if (mx >= g.mcu_w || my >= g.mcu_h) continue;  // a tile at the page's edge: the MCU is not the page's
+      const long long first = g.first_block + ((long long)my * g.mcu_w + mx) * per;  // < first_block + MCUs * per: jpeg_page
+      for (int b = 0; b < per; ++b) {
+        const int v = s_blk[wave][m * per + b][c_zigzag[lane]];
+        const int d = b >= ny ? d_chroma : d_luma;
+        int c = (abs(v) + d / 2) / d;
+        c = v < 0 ? -c : c;
+        c = min(max(c, lane == 0 ? -1024 : -1023), 1023);
+        coef[(size_t)(first + b) * 64 + lane] = (short)c;
+      }
     }
   }
 }
@@ -412,6 +488,16 @@ __device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
   return v;
 }
 
+// Block `b` of a restart interval: its component (0 Y, 1 Cb, 2 Cr) - an MCU is per - 2 luminance blocks, then Cb, then Cr; a
+// one-component page's is its block -
+__device__ __forceinline__ int jpeg_component(const JpegPage& g, int b) { return g.comps == 3 ? max(b % g.per - (g.per - 3), 0) : 0; }
+// - and the block before it of the same component, whose DC is its predictor (negative: none, the interval starts here).  Y
+// follows Y inside an MCU and the last Y of the MCU before; Cb / Cr the MCU before.
+__device__ __forceinline__ int jpeg_predecessor(const JpegPage& g, int b, int comp) {
+  if (g.comps != 3) return b - 1;
+  return comp == 0 ? (b % g.per == 0 ? b - 3 : b - 1) : b - g.per;
+}
+
 // OPT: the codes are the page's own (`tables`, k_jpeg_optimal_tables) and a block has JP_BLOCK_WORDS_OPT words
 template <bool OPT>
 __global__ __launch_bounds__(64) void k_jpeg_entropy(const int* __restrict__ blob, JpegLimits lim, int n_pages,
@@ -449,11 +535,10 @@ __global__ __launch_bounds__(64) void k_jpeg_entropy(const int* __restrict__ blo
     __syncthreads();
     const int b = base + lane;
     const bool active = b < nb;
-    const int comp = g.per == 6 ? max(b % 6 - 3, 0) : 0;  // 0 Y, 1 Cb, 2 Cr
+    const int comp = jpeg_component(g, b);  // 0 Y, 1 Cb, 2 Cr
     int pred = 0;
     if (active) {
-      // the previous block of the component: Y follows Y inside an MCU and Y3 of the MCU before; Cb / Cr the MCU before
-      const int prev = g.per == 1 ? b - 1 : (comp == 0 ? (b % 6 == 0 ? b - 3 : b - 1) : b - 6);
+      const int prev = jpeg_predecessor(g, b, comp);
       if (prev >= 0) pred = coef[(size_t)(blk0 + prev) * 64];
     }
     const unsigned* lut = s_lut[comp ? 1 : 0];
@@ -543,8 +628,8 @@ __global__ __launch_bounds__(64) void k_jpeg_histogram(const int* __restrict__ b
     __syncthreads();
     const int b = base + lane;
     if (b < nb) {
-      const int comp = g.per == 6 ? max(b % 6 - 3, 0) : 0;
-      const int prev = g.per == 1 ? b - 1 : (comp == 0 ? (b % 6 == 0 ? b - 3 : b - 1) : b - 6);  // as k_jpeg_entropy
+      const int comp = jpeg_component(g, b);
+      const int prev = jpeg_predecessor(g, b, comp);  // as k_jpeg_entropy
       const int pred = prev >= 0 ? coef[(size_t)(blk0 + prev) * 64] : 0;
       count_block(&s_coef[lane * EN_PITCH], pred, s_hist[comp ? 1 : 0]);
     }
@@ -569,8 +654,9 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
 
 // One workgroup per page, wave t makes table t of DC 0, AC 0, DC 1, AC 1 (a grey page: the first two; the other two come out
 // empty).  Symbol s = k * 64 + lane sits in register k of its lane; the reserved symbol 256 in lane 0.
-// Frequencies: a symbol's count is at most the symbols of a 16383 x 16383 page, 6 * 1024 * 1024 blocks of at most 64, and so is
-// the sum of all of them, 4.1e8: below libjpeg's 1e9 sentinel ("no symbol") and inside an int.  Counts from elsewhere are
+// Frequencies: a symbol's count is at most the symbols of one class of a 16383 x 16383 page - the most are the chrominance's at
+// 4:4:4, 2 * 2048 * 2048 blocks of at most 64 -, and so is the sum of a table's, 5.4e8: below libjpeg's 1e9 sentinel ("no
+// symbol") and inside an int.  Counts from elsewhere are
 // clamped to that sum's range per symbol; whatever they are, the merges build a tree, so the lengths stay below 257.
 __global__ __launch_bounds__(256) void k_jpeg_optimal_tables(const int* __restrict__ blob, JpegLimits lim, int n_pages,
                                                              const int* __restrict__ hist, unsigned* __restrict__ tables,
@@ -584,7 +670,7 @@ __global__ __launch_bounds__(256) void k_jpeg_optimal_tables(const int* __restri
   JpegPage g;
   if (!jpeg_page(blob, lim, page, g)) return;  // the whole block
   const int cls = t >> 1, ac = t & 1;
-  const int n = t < (g.ch == 3 ? 4 : 2) ? (ac ? 256 : 16) : 0;  // symbols this table may have
+  const int n = t < (g.comps == 3 ? 4 : 2) ? (ac ? 256 : 16) : 0;  // symbols this table may have
   const int* src = hist + (size_t)page * JP_LUT_WORDS + cls * (256 + 16) + (ac ? 0 : 256);
   unsigned freq[5];
   int len[5], id[5];
@@ -760,6 +846,48 @@ __global__ __launch_bounds__(64) void k_jpeg_compact(const int* __restrict__ blo
   }
 }
 
+// ------------------------------------------------------------------------------------------------ grey test
+constexpr int GT_THREADS = 256, GT_GROUP = 48;  // a group: 16 pixels = three 16-byte loads
+// diff[p] |= the OR over page p of (B ^ G) | (G ^ R) - zero exactly where (B ^ G) | (B ^ R) is: a page all of whose pixels have
+// B == G == R.  diff is zero before the launch.  Of a record only words 0 - 4 are read (the pixels, h, w, channels); one that is
+// not a three-channel page of 1..16383 pixels on a side gets -1.  The page is h * w * 3 contiguous bytes: where its address is
+// 16-byte aligned a thread takes whole groups - XOR of every byte with the byte behind it, kept where the byte is a B or a G -
+// and the pixels behind the last whole group (all of them where it is not aligned) go one at a time.  Every page is read to its
+// end: stopping once another wave has found a difference was tried - a look at the page's word (at the L2) before each step - and
+// made the launch slower on colour pages, 0.23 against 0.10 ms per wave of 16 pages.
+__global__ __launch_bounds__(GT_THREADS) void k_jpeg_pages_grey(const int* __restrict__ blob, int* __restrict__ diff) {
+  const int p = blockIdx.y;
+  const int* r = blob + (size_t)p * JP_REC;
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)r[1] << 32) | (unsigned long long)(unsigned)r[0]);
+  const int h = r[2], w = r[3];
+  if (src == nullptr || h < 1 || w < 1 || h > 16383 || w > 16383 || r[4] != 3) {  // the whole block
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(diff + p, -1);
+    return;
+  }
+  const long long pixels = (long long)h * w;
+  const long long groups = ((uintptr_t)src & 15) == 0 ? pixels / 16 : 0;
+  const long long tid = (long long)blockIdx.x * GT_THREADS + threadIdx.x, step = (long long)gridDim.x * GT_THREADS;
+  unsigned acc = 0;
+  for (long long i = tid; i < groups; i += step) {
+    const uint4* q = reinterpret_cast<const uint4*>(src + i * GT_GROUP);
+    const uint4 a = q[0], b = q[1], c = q[2];
+    const unsigned v[13] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, 0u};  // byte 47 is an R: nothing behind it is looked at
+#pragma unroll
+    for (int k = 0; k < 12; k += 3) {  // bytes 12 k / 4 ...: B G R B | G R B G | R B G R
+      acc |= (v[k] ^ (v[k] >> 8 | v[k + 1] << 24)) & 0xff00ffffu;
+      acc |= (v[k + 1] ^ (v[k + 1] >> 8 | v[k + 2] << 24)) & 0xffff00ffu;
+      acc |= (v[k + 2] ^ (v[k + 2] >> 8 | v[k + 3] << 24)) & 0x00ffff00u;
+    }
+  }
+  for (long long i = groups * 16 + tid; i < pixels; i += step) {
+    const unsigned char* px = src + i * 3;
+    acc |= (unsigned)((px[0] ^ px[1]) | (px[1] ^ px[2]));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc |= __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0 && acc) atomicOr(diff + p, 1);
+}
+
 // ------------------------------------------------------------------------------------------------ Pillow resample -> uint8
 constexpr int RS_REC = YMK_PIL_RESIZE_U8_WORDS;
 __device__ __forceinline__ int clip8_22(int v) {
@@ -816,6 +944,11 @@ static JpegLimits limits(int64_t blob_words, int64_t total_mcus, int64_t total_b
   YMK_CHECK(total_mcus <= 0x7fffffffLL / JP_WAVES && total_blocks <= 0x7fffffffLL && total_intervals <= 0x7fffffffLL,
             "a wave of at most 2^31 - 1 blocks");
   return JpegLimits{blob_words, total_mcus, total_blocks, total_intervals, out_bytes};
+}
+static JpegMode checked_mode(int channels, int mode) {
+  JpegMode m;
+  YMK_CHECK(jpeg_mode(channels, mode, m), "mode: 0 for a one-channel page; YMK_JPEG_MODE_420 / _422 / _444 / _GREY for a three-channel one");
+  return m;
 }
 static void check_table(const int* blob_dev, int64_t blob_words, int n_pages) {
   YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
@@ -891,9 +1024,13 @@ int ymk_jpeg_quant_tables(int quality, int* zigzag128_out) {
 }
 
 int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out, int capacity) {
+  return ymk_jpeg_header_mode(h, w, channels, 0, quality, out, capacity);
+}
+
+int ymk_jpeg_header_mode(int h, int w, int channels, int mode, int quality, unsigned char* out, int capacity) {
   try {
     YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
-    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, channels == 1, quality);
+    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, ymk::checked_mode(channels, mode), quality);
     YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
     std::memcpy(out, hdr.data(), hdr.size());
     return (int)hdr.size();
@@ -904,10 +1041,14 @@ int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out,
 }
 
 int ymk_jpeg_header_opt(int h, int w, int channels, int quality, unsigned char* out, int capacity, int* split_out) {
+  return ymk_jpeg_header_opt_mode(h, w, channels, 0, quality, out, capacity, split_out);
+}
+
+int ymk_jpeg_header_opt_mode(int h, int w, int channels, int mode, int quality, unsigned char* out, int capacity, int* split_out) {
   try {
     YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
     YMK_CHECK(split_out, "null output");
-    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, channels == 1, quality, false, split_out);
+    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, ymk::checked_mode(channels, mode), quality, false, split_out);
     YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
     std::memcpy(out, hdr.data(), hdr.size());
     return (int)hdr.size();
@@ -918,9 +1059,13 @@ int ymk_jpeg_header_opt(int h, int w, int channels, int quality, unsigned char* 
 }
 
 int ymk_jpeg_scratch_bytes_opt(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes9_out) {
+  return ymk_jpeg_scratch_bytes_opt_mode(h, w, channels, nullptr, n_pages, sizes9_out);
+}
+
+int ymk_jpeg_scratch_bytes_opt_mode(const int* h, const int* w, const int* channels, const int* modes, int n_pages, int64_t* sizes9_out) {
   try {
     YMK_CHECK(sizes9_out, "bad argument");
-    if (ymk_jpeg_scratch_bytes(h, w, channels, n_pages, sizes9_out)) return 1;
+    if (ymk_jpeg_scratch_bytes_mode(h, w, channels, modes, n_pages, sizes9_out)) return 1;
     sizes9_out[4] = sizes9_out[1] * YMK_JPEG_BLOCK_STREAM_BYTES_OPT;
     sizes9_out[6] = sizes9_out[7] = (int64_t)n_pages * YMK_JPEG_TABLE_WORDS * (int64_t)sizeof(int);
     sizes9_out[8] = (int64_t)n_pages * YMK_JPEG_DHT_BYTES;
@@ -932,19 +1077,23 @@ int ymk_jpeg_scratch_bytes_opt(const int* h, const int* w, const int* channels, 
 }
 
 int ymk_jpeg_scratch_bytes(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes6_out) {
+  return ymk_jpeg_scratch_bytes_mode(h, w, channels, nullptr, n_pages, sizes6_out);
+}
+
+int ymk_jpeg_scratch_bytes_mode(const int* h, const int* w, const int* channels, const int* modes, int n_pages, int64_t* sizes6_out) {
   try {
     YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes6_out && (n_pages == 0 || (h && w && channels)), "bad argument");
-    int64_t mcus = 0, blocks = 0, intervals = 0;
+    int64_t tiles = 0, blocks = 0, intervals = 0;
     for (int p = 0; p < n_pages; ++p) {
       YMK_CHECK(h[p] >= 1 && w[p] >= 1 && h[p] <= 16383 && w[p] <= 16383 && (channels[p] == 1 || channels[p] == 3),
                 "page: 1..16383 pixels on a side, 1 or 3 channels");
-      const int m = channels[p] == 3 ? 16 : 8;
-      const int64_t mw = (w[p] + m - 1) / m, mh = (h[p] + m - 1) / m;
-      mcus += mw * mh;
-      blocks += mw * mh * (channels[p] == 3 ? 6 : 1);
+      const ymk::JpegMode m = ymk::checked_mode(channels[p], modes ? modes[p] : 0);
+      const int64_t mw = (w[p] + (8 << m.lh) - 1) >> (3 + m.lh), mh = (h[p] + (8 << m.lv) - 1) >> (3 + m.lv);
+      tiles += (int64_t)((w[p] + (1 << m.lt) - 1) >> m.lt) * ((h[p] + (1 << m.lt) - 1) >> m.lt);
+      blocks += mw * mh * (m.comps == 3 ? (1 << (m.lh + m.lv)) + 2 : 1);
       intervals += mh;
     }
-    sizes6_out[0] = mcus, sizes6_out[1] = blocks, sizes6_out[2] = intervals;
+    sizes6_out[0] = tiles, sizes6_out[1] = blocks, sizes6_out[2] = intervals;
     sizes6_out[3] = blocks * 64 * (int64_t)sizeof(int16_t);
     sizes6_out[4] = blocks * YMK_JPEG_BLOCK_STREAM_BYTES;
     sizes6_out[5] = intervals * 2 * (int64_t)sizeof(int);
@@ -1112,6 +1261,26 @@ int ymk_jpeg_encode_pages_opt(const int* blob_dev, int64_t blob_words, int n_pag
     ymk::launch_tables(s, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
     ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
     ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_jpeg_pages_grey(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* diff_dev, void* stream) {
+  try {
+    YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
+    if (n_pages == 0) return 0;
+    ymk::check_table(blob_dev, blob_words, n_pages);
+    YMK_CHECK(diff_dev && ((uintptr_t)diff_dev & 3) == 0, "null or misaligned output");
+    const hipStream_t s = (hipStream_t)stream;
+    YMK_HIP(hipMemsetAsync(diff_dev, 0, (size_t)n_pages * sizeof(int), s));
+    // four groups per thread where the largest page has that many; 256 blocks per page at the most (the loops stride the rest)
+    const int64_t per_block = (int64_t)ymk::GT_THREADS * 16 * 4;
+    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_pixels + per_block - 1) / per_block, 1), 256);
+    hipLaunchKernelGGL(ymk::k_jpeg_pages_grey, dim3(gx, (unsigned)n_pages), dim3(ymk::GT_THREADS), 0, s, blob_dev, diff_dev);
+    YMK_HIP(hipGetLastError());
     return 0;
   } catch (const std::exception& e) {
     ymk::set_error(e.what());

@@ -97,7 +97,7 @@ class OCR(StageAnalyzer):
         return (self._ocr_drawing(wave, k),)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False):
+              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False):
         """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
         arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
         yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
@@ -113,11 +113,12 @@ class OCR(StageAnalyzer):
         encoded on the device from the clean page, so that
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
-        without `jpeg`."""
-        check_jpeg_preset(jpeg, jpeg_optimize)  # before the pipeline is built or a source read
+        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`: as DocumentAnalyzer.serve."""
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -561,7 +562,7 @@ class DocumentAnalyzer(StageAnalyzer):
         return reading_order_visualizer(page if layout is None else layout, results, to_host=False)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False):
+              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -583,11 +584,18 @@ class DocumentAnalyzer(StageAnalyzer):
         encoded on the device in the same render stage from the clean page ("JPEG encoder").
         `jpeg_optimize`: with `jpeg`, the files are coded with Huffman tables made for each page instead of Annex K's typical
         ones (libjpeg's `optimize`): two more launches per wave, the same decoded pixels, about a third fewer bytes on scanned
-        pages; the EncodedJpeg says `optimized=True`.  Without `jpeg` it is a ValueError before a source is read."""
-        check_jpeg_preset(jpeg, jpeg_optimize)  # before the pipeline is built or a source read
+        pages; the EncodedJpeg says `optimized=True`.  Without `jpeg` it is a ValueError before a source is read.
+        `jpeg_subsampling`: None (4:2:0), "4:2:0", "4:2:2" or "4:4:4" - how much of the chroma the colour files keep: "4:4:4"
+        keeps all of it (red seals, coloured ruling and small coloured print stay sharp; about a third more bytes on a scanned
+        page), "4:2:2" its full height.  `jpeg_grey`: False, or "auto" - every page is tested on the device after the preset's
+        resize, and one whose pixels all have B == G == R (a black-and-white scan loaded as B G R) is written as a grey file, a
+        third of the blocks; its EncodedJpeg says `grey=True`, `subsampling=None`.  Any other value, and either option without
+        `jpeg`, is a ValueError before a source is read."""
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
 
     def __call__(self, img):
         self.img = img

@@ -16,6 +16,13 @@ one of their bytes, both through pinned memory.  There is no host fallback: a pa
 `optimize=True` (serve: `jpeg_optimize=True`) codes the same coefficients with Huffman tables made for each page - libjpeg's
 `optimize` rule, byte for byte Pillow's `save(..., optimize=True, restart_marker_rows=1)` wherever the plain file is Pillow's:
 two more launches (the page's symbol histograms, then its tables), the same pixels when decoded, a smaller file.
+
+`subsampling="4:2:2"` / `"4:4:4"` (serve: `jpeg_subsampling=`) keeps the chroma of colour pages at full height / at full size -
+libjpeg's sampling 2x1 / 1x1, what Pillow calls `subsampling=1` / `0`: red seals, coloured ruling and small coloured print stay
+sharp, the file grows.  `grey="auto"` (serve: `jpeg_grey="auto"`) tests every three-channel page on the device after the
+preset's resize - one more launch and one wait for its answer - and writes a page all of whose pixels have B == G == R as the
+one-component file of that plane, a third of the blocks: `EncodedJpeg.grey` is True and `subsampling` None.  The definition of
+the modes is tests/jpeg_modes_ref.py; the defaults write the bytes they always wrote.
 """
 
 from __future__ import annotations
@@ -33,6 +40,9 @@ from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
 
 PAGE_WORDS, RESIZE_WORDS = 16, 16  # YMK_JPEG_PAGE_WORDS, YMK_PIL_RESIZE_U8_WORDS
 MAX_SIDE = 16383
+SUBSAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}  # word 15 of a page's record: YMK_JPEG_MODE_420 / _422 / _444
+MODE_GREY = 4  # YMK_JPEG_MODE_GREY: channel 0 of a three-channel page as a one-component file
+_SAMPLING = {0: (2, 2), 1: (2, 1), 2: (1, 1)}  # mode -> the luminance sampling factors (hs, vs)
 
 
 @dataclass
@@ -46,6 +56,7 @@ class EncodedJpeg:
     grey: bool
     scale: float = 1.0
     optimized: bool = False  # coded with the page's own Huffman tables
+    subsampling: Optional[str] = "4:2:0"  # of a colour file; None: a grey file has no chroma
 
 
 def jpeg_preset(image_quality: str) -> dict:
@@ -56,22 +67,43 @@ def jpeg_preset(image_quality: str) -> dict:
         raise ValueError(f"unknown jpeg preset {image_quality!r}: one of {sorted(IMAGE_QUALITY_PRESETS)}") from None
 
 
+def check_modes(subsampling="4:2:0", grey=False) -> int:
+    """The mode of a call's colour pages; a `subsampling` that is not one of SUBSAMPLINGS, or a `grey` that is neither False
+    nor "auto", is a ValueError."""
+    if not isinstance(subsampling, str) or subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"unknown jpeg subsampling {subsampling!r}: one of {sorted(SUBSAMPLINGS)}")
+    if grey is not False and grey != "auto":
+        raise ValueError(f"unknown jpeg grey {grey!r}: False or 'auto'")
+    return SUBSAMPLINGS[subsampling]
+
+
+def _geometry(h: int, w: int, channels: int, mode: int):
+    """(tiles of the coefficient stage, blocks, restart intervals) of a page in `mode`."""
+    if channels == 1 or mode == MODE_GREY:
+        hs, vs, per, tile = 1, 1, 1, 8 if channels == 1 else 16
+    else:
+        (hs, vs), tile = _SAMPLING[mode], 16
+        per = hs * vs + 2
+    mw, mh = -(-w // (8 * hs)), -(-h // (8 * vs))
+    return (-(-w // tile)) * (-(-h // tile)), mw * mh * per, mh
+
+
 @functools.lru_cache(maxsize=256)
-def _header(h: int, w: int, channels: int, quality: int) -> bytes:
+def _header(h: int, w: int, channels: int, quality: int, mode: int = 0) -> bytes:
     buf = (ctypes.c_ubyte * 1024)()
-    n = _lib.load().ymk_jpeg_header(h, w, channels, quality, buf, len(buf))
+    n = _lib.load().ymk_jpeg_header_mode(h, w, channels, mode, quality, buf, len(buf))
     if n < 0:
-        _lib.check(1, "ymk_jpeg_header")
+        _lib.check(1, "ymk_jpeg_header_mode")
     return bytes(buf[:n])
 
 
 @functools.lru_cache(maxsize=256)
-def _header_opt(h: int, w: int, channels: int, quality: int):
+def _header_opt(h: int, w: int, channels: int, quality: int, mode: int = 0):
     """(the header without its DHT segments, the bytes of it before their place)."""
     buf, split = (ctypes.c_ubyte * 1024)(), ctypes.c_int(0)
-    n = _lib.load().ymk_jpeg_header_opt(h, w, channels, quality, buf, len(buf), ctypes.byref(split))
+    n = _lib.load().ymk_jpeg_header_opt_mode(h, w, channels, mode, quality, buf, len(buf), ctypes.byref(split))
     if n < 0:
-        _lib.check(1, "ymk_jpeg_header_opt")
+        _lib.check(1, "ymk_jpeg_header_opt_mode")
     return bytes(buf[:n]), int(split.value)
 
 
@@ -82,15 +114,16 @@ def _quant_words(quality: int) -> np.ndarray:
     return np.frombuffer(out, dtype=np.int32).copy()
 
 
-def scratch_sizes(shapes: Sequence, optimize: bool = False) -> tuple:
-    """(MCUs, blocks, intervals, coefficient bytes, stream bytes, interval-record bytes) of pages of `shapes` = (h, w, channels);
-    optimize: the stream bytes of that path, and behind the six the bytes of the histograms, the code tables and the DHT records."""
+def scratch_sizes(shapes: Sequence, optimize: bool = False, modes: Optional[Sequence[int]] = None) -> tuple:
+    """(tiles - the MCUs of 4:2:0 and grey pages -, blocks, intervals, coefficient bytes, stream bytes, interval-record bytes) of
+    pages of `shapes` = (h, w, channels) and `modes` (word 15 of their records; default 0 each); optimize: the stream bytes of
+    that path, and behind the six the bytes of the histograms, the code tables and the DHT records."""
     n = len(shapes)
     arr = ctypes.c_int * max(1, n)
     sizes = (ctypes.c_int64 * (9 if optimize else 6))()
-    name = "ymk_jpeg_scratch_bytes_opt" if optimize else "ymk_jpeg_scratch_bytes"
-    _lib.check(getattr(_lib.load(), name)(arr(*[s[0] for s in shapes]), arr(*[s[1] for s in shapes]),
-                                          arr(*[s[2] for s in shapes]), n, sizes), name)
+    name = "ymk_jpeg_scratch_bytes_opt_mode" if optimize else "ymk_jpeg_scratch_bytes_mode"
+    _lib.check(getattr(_lib.load(), name)(arr(*[s[0] for s in shapes]), arr(*[s[1] for s in shapes]), arr(*[s[2] for s in shapes]),
+                                          None if modes is None else arr(*[int(m) for m in modes]), n, sizes), name)
     return tuple(int(v) for v in sizes)
 
 
@@ -103,33 +136,36 @@ def _addr_words(ptr: int):
     return np.array([ptr & 0xFFFFFFFF, ptr >> 32], dtype=np.uint32).view(np.int32)
 
 
-def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]] = None, optimize: bool = False):
+def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]] = None, optimize: bool = False,
+               modes: Optional[Sequence[int]] = None):
     """(int32 words of the page table of include/ymk.h, per page the byte offset of its file in the output, the output's bytes).
     capacities: bytes per page's file; default the page's raw byte count.  optimize: the table of the *_opt entries - headers
-    without DHT segments, word 14 the place the device puts the page's own."""
+    without DHT segments, word 14 the place the device puts the page's own.  modes: word 15 per page - 0 (default), a value of
+    SUBSAMPLINGS or MODE_GREY for a three-channel page, 0 for a grey one."""
     n = len(pages)
     rec = np.zeros((n, PAGE_WORDS), np.int32)
     shapes = [(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in pages]
+    modes = [0] * n if modes is None else [int(m) for m in modes]
+    rec[:, 15] = modes
     if optimize:
-        split = [_header_opt(h, w, ch, quality) for h, w, ch in shapes]
+        split = [_header_opt(h, w, ch, quality, m) for (h, w, ch), m in zip(shapes, modes)]
         headers, rec[:, 14] = [s[0] for s in split], [s[1] for s in split]
     else:
-        headers = [_header(h, w, ch, quality) for h, w, ch in shapes]
+        headers = [_header(h, w, ch, quality, m) for (h, w, ch), m in zip(shapes, modes)]
     at = n * PAGE_WORDS * 4  # byte offset of the first header
     mcu = blk = iv = 0
     out_at, offsets = 0, []
     for k, p in enumerate(pages):
         h, w = int(p.shape[0]), int(p.shape[1])
         ch = 1 if p.dim() == 2 else 3
-        m = 8 if ch == 1 else 16
-        mw, mh = -(-w // m), -(-h // m)
+        tiles, blocks, rows = _geometry(h, w, ch, modes[k])
         cap = int(capacities[k]) if capacities is not None else h * w * ch
         rec[k, 0:2] = _addr_words(p.data_ptr())
         rec[k, 2:8] = (h, w, ch, mcu, blk, iv)
         rec[k, 8:10] = _addr_words(out_at)
         rec[k, 10:13] = (cap, at, len(headers[k]))
         offsets.append(out_at)
-        mcu, blk, iv = mcu + mw * mh, blk + mw * mh * (6 if ch == 3 else 1), iv + mh
+        mcu, blk, iv = mcu + tiles, blk + blocks, iv + rows
         at += -(-len(headers[k]) // 4) * 4
         out_at += -(-cap // 16) * 16
     rec[:, 13] = at // 4  # one quality per call: one pair of tables behind the headers
@@ -196,16 +232,47 @@ def _as_device_page(page, device) -> torch.Tensor:
     return t.contiguous()
 
 
+def grey_pages(pages: Sequence[torch.Tensor], scratch: Optional[dict] = None) -> List[bool]:
+    """Per device page (uint8 H x W x 3 or H x W, contiguous): whether it is a three-channel page all of whose pixels have
+    B == G == R.  One launch over all three-channel pages on the current stream (ymk_jpeg_pages_grey), then one wait for its
+    answer, read through pinned memory."""
+    out = [False] * len(pages)
+    cand = [k for k, p in enumerate(pages) if p.dim() == 3]
+    if not cand:
+        return out
+    scratch = {} if scratch is None else scratch
+    device = pages[cand[0]].device
+    rec = np.zeros((len(cand), PAGE_WORDS), np.int32)
+    for j, k in enumerate(cand):
+        rec[j, 0:2] = _addr_words(pages[k].data_ptr())
+        rec[j, 2:5] = (int(pages[k].shape[0]), int(pages[k].shape[1]), 3)
+    blob_dev = imaging._stage_blob(rec.reshape(-1), device)
+    diff = _grown(scratch, "grey", len(cand), torch.int32, device)
+    _lib.check(_lib.load().ymk_jpeg_pages_grey(blob_dev.data_ptr(), rec.size, len(cand), max(int(pages[k].shape[0]) * int(pages[k].shape[1]) for k in cand),
+                                               diff.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_pages_grey")
+    pin = _grown(scratch, "pin_grey", len(cand), torch.int32, pinned=True)
+    pin[: len(cand)].copy_(diff[: len(cand)], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    for k, v in zip(cand, pin[: len(cand)].tolist()):
+        out[k] = v == 0
+    return out
+
+
 def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
-                      capacities: Optional[Sequence[int]] = None, optimize: bool = False) -> List[Union[EncodedJpeg, Exception]]:
+                      capacities: Optional[Sequence[int]] = None, optimize: bool = False, subsampling: str = "4:2:0",
+                      grey=False) -> List[Union[EncodedJpeg, Exception]]:
     """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
     file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
     stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
     the device and pinned buffers (serve: one per wave slot); capacities: bytes allowed per page's file - the default cannot
     hold the ~620-byte header (~330 grey) plus the scan of a page below roughly 15 x 15 pixels, nor noise that does not compress.
     optimize: Huffman tables made for each page (two more launches; the header shrinks with the tables, to ~270 bytes for a
-    flat colour page); the decoded pixels are those of the plain file."""
+    flat colour page); the decoded pixels are those of the plain file.
+    subsampling: "4:2:0", "4:2:2" or "4:4:4", the chroma of the colour files; grey: False, or "auto" - a three-channel page
+    whose pixels all have B == G == R (tested on the device, after the preset's resize) becomes a grey file.  Anything else is
+    a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
     preset = jpeg_preset(image_quality)
+    colour_mode = check_modes(subsampling, grey)
     quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
     out: list = [None] * len(pages)
     if not pages:
@@ -237,8 +304,12 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
             for (j, _), small in zip(todo, resize_pages([devs[j] for j, _ in todo], [s for _, s in todo])):
                 devs[j] = small
         caps = None if capacities is None else [int(capacities[k]) for k in live]
-        blob, offsets, out_bytes = page_table(devs, quality, caps, optimize)
-        sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in devs], optimize)
+        as_grey = grey_pages(devs, scratch) if grey == "auto" else [False] * len(devs)
+        modes = [0 if p.dim() == 2 else (MODE_GREY if g else colour_mode) for p, g in zip(devs, as_grey)]
+        if not any(modes):
+            modes = None  # the defaults: the table and the sizes of every call before there were modes
+        blob, offsets, out_bytes = page_table(devs, quality, caps, optimize, modes)
+        sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in devs], optimize, modes)
         mcus, blocks, intervals, coef_b, stream_b, iv_b = sized[:6]
         coef = _grown(scratch, "coef", coef_b // 2, torch.int16, device)
         bits = _grown(scratch, "stream", stream_b // 4, torch.int32, device)
@@ -279,18 +350,20 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
                 cap = caps[j] if caps is not None else p.numel()
                 out[k] = _lib.YmkError(f"page {k}: the JPEG file does not fit its capacity of {cap} bytes")
                 continue
-            out[k] = EncodedJpeg(host[at : at + sizes[j]].tobytes(), int(p.shape[1]), int(p.shape[0]), p.dim() == 2, float(scales[j]),
-                                 bool(optimize))
+            one = p.dim() == 2 or as_grey[j]
+            out[k] = EncodedJpeg(host[at : at + sizes[j]].tobytes(), int(p.shape[1]), int(p.shape[0]), one, float(scales[j]),
+                                 bool(optimize), None if one else subsampling)
             at += sizes[j]
     return out
 
 
-def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False) -> EncodedJpeg:
+def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False, subsampling: str = "4:2:0",
+                grey=False) -> EncodedJpeg:
     """One page; raises what `encode_jpeg_pages` would have put in its place.  The file's capacity is the page's raw byte
     count, and the header alone takes about 620 bytes (330 for a grey page): a colour page below roughly 15 x 15 pixels, or noise
     that does not compress, raises YmkError here and in `serve(jpeg=...)` - `encode_jpeg_pages(..., capacities=[...])` gives
     such a page the room it needs."""
-    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize)[0]
+    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize, subsampling=subsampling, grey=grey)[0]
     if isinstance(res, BaseException):
         raise res
     return res

@@ -106,12 +106,14 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False):
+    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False):
         self.results = {}
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, the analyzer's pictures...): the waves visit the render stage
         self.jpeg = jpeg  # None or a preset name: the entries end with the page's EncodedJpeg, made in the render stage too
         self.jpeg_optimize = bool(jpeg_optimize)  # those files with Huffman tables of their own (encode_jpeg_pages(optimize=True))
+        self.jpeg_subsampling = jpeg_subsampling  # None (4:2:0) or the chroma of those files (encode_jpeg_pages(subsampling=...))
+        self.jpeg_grey = jpeg_grey  # False, or "auto": grey-valued colour pages become grey files (encode_jpeg_pages(grey="auto"))
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -164,16 +166,23 @@ def _switch_interval(seconds):
                 _switch_saved = None
 
 
-def check_jpeg_preset(jpeg, jpeg_optimize=False):
+def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False):
     """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
-    public entry points before a source is read.  `jpeg_optimize` asks for something of those files: without `jpeg` it is a
-    ValueError too."""
+    public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0", "4:2:2", "4:4:4") and
+    `jpeg_grey` (False, "auto") ask for something of those files: a value that is none of these is a ValueError, and so is any
+    of the three without `jpeg`."""
+    from .jpeg import check_modes
     from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
 
     if jpeg is not None and (not isinstance(jpeg, str) or jpeg not in IMAGE_QUALITY_PRESETS):
         raise ValueError(f"unknown jpeg preset {jpeg!r}: None or one of {sorted(IMAGE_QUALITY_PRESETS)}")
     if jpeg_optimize and jpeg is None:
         raise ValueError("jpeg_optimize=True needs jpeg=...: there is no JPEG file to optimise")
+    check_modes("4:2:0" if jpeg_subsampling is None else jpeg_subsampling, jpeg_grey)
+    if jpeg is None and jpeg_subsampling is not None:
+        raise ValueError(f"jpeg_subsampling={jpeg_subsampling!r} needs jpeg=...: there is no JPEG file to write that way")
+    if jpeg is None and jpeg_grey is not False:
+        raise ValueError(f"jpeg_grey={jpeg_grey!r} needs jpeg=...: there is no JPEG file to write that way")
 
 
 def _run_stage(stream, wave, fn, *args):
@@ -433,7 +442,7 @@ class PagePipeline:
             self._q[name].put(wave)
 
     def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
-              jpeg_optimize: bool = False) -> List:
+              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -446,13 +455,16 @@ class PagePipeline:
         source is read): a page's entry ends with its EncodedJpeg (yomitoku_amd/jpeg.py) - (schema, EncodedJpeg), or (schema, ocr
         overlay, layout overlay, EncodedJpeg) - encoded in the render stage from the clean page, never from a canvas.
         jpeg_optimize: those files with Huffman tables made for each page (smaller, the same pixels); a ValueError without `jpeg`.
+        jpeg_subsampling: None (4:2:0), "4:2:0", "4:2:2" or "4:4:4" - the chroma of those files; jpeg_grey: False, or "auto" - a page
+        whose pixels all have B == G == R becomes a grey file.  Other values, and either without `jpeg`, are a ValueError.
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
 
-        check_jpeg_preset(jpeg, jpeg_optimize)
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey)
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
+            job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
+                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
             if job.overlays or job.jpeg:
                 self._start_render()
             n = 0
@@ -715,7 +727,8 @@ class StageAnalyzer:
         return out
 
     def _stage_jpeg(self, wave, results, scratch=None):
-        """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`, tables `wave.job.jpeg_optimize`), an exception for a page
+        """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`, tables `wave.job.jpeg_optimize`,
+        chroma `wave.job.jpeg_subsampling`, grey files `wave.job.jpeg_grey`), an exception for a page
         that could not be encoded, None for a page that had already failed.  All pages of the wave are encoded together on
         the calling thread's stream (yomitoku_amd/jpeg.py: encode_jpeg_pages) from `wave.pages` - the clean pages: the
         overlays are drawn on copies - with `scratch`, by default the wave slot's."""
@@ -727,7 +740,9 @@ class StageAnalyzer:
             if scratch is None:
                 scratch = self._jpeg_scratch.setdefault(wave.ring, {})
             files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch,
-                                      optimize=getattr(wave.job, "jpeg_optimize", False))
+                                      optimize=getattr(wave.job, "jpeg_optimize", False),
+                                      subsampling=getattr(wave.job, "jpeg_subsampling", None) or "4:2:0",
+                                      grey=getattr(wave.job, "jpeg_grey", False))
             for k, made in zip(live, files):
                 out[k] = made if isinstance(made, BaseException) else (made,)
         return out
@@ -764,7 +779,8 @@ class StageAnalyzer:
         return wave
 
     # ---- the pipeline of this analyzer
-    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False):
+    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False,
+               jpeg_subsampling=None, jpeg_grey=False):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -772,7 +788,8 @@ class StageAnalyzer:
                 pipe.close()
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
+                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -
