@@ -372,6 +372,52 @@ int ymk_jpeg_pages_grey(const int* blob_dev, int64_t blob_words, int n_pages, in
 int ymk_pil_resize_u8_record_words(void);
 int ymk_pil_resize_u8(const int* blob_dev, int64_t blob_words, int n, int max_oh, int max_ow, void* stream);
 
+/* ---- Group 4 encoder: CCITT T.6 files of the two-valued pages of a wave, opt-in (yomitoku_amd/csrc/ymk_ccitt.hip;
+ * yomitoku_amd/ccitt.py; encode_jpeg_pages(bilevel="auto"), serve(jpeg=..., jpeg_bilevel="auto")).  DESIGN.md, "Two-valued
+ * pages"; tests/ccitt_ref.py is the definition, and every stage equals it bit for bit.  A page - uint8 [h][w] or [h][w][3],
+ * 1..16383 pixels on a side - is two-valued when every sample is 0 or 255 and, of three channels, B == G == R; 0 is black.
+ * Page table (DEVICE, int32 words): n_pages records of YMK_G4_PAGE_WORDS words.
+ *     word 0-1   address of the page's pixels (low, high); read by ymk_g4_test_pack only     word 2-4  h, w, channels (1 | 3)
+ *     word 5     index of the page's row 0 among the rows of the call: the pages' rows follow one another, sum = total_rows
+ *     word 6-7   WORD offset (low, high) in packed_dev of the page's packed rows: h rows of ceil(w / 32) words, 1 = black, the
+ *                leftmost pixel of a word in its bit 31, zero bits behind column w
+ *     word 8-9   BYTE offset (low, high) of the page's file in out_dev, a multiple of 4     word 10  the file's capacity in bytes
+ *     word 11-12 WORD offset (low, high) in slots_dev of row 0's slot; a row's slot has ymk_g4_slot_words(w) words    13-15  0
+ * A record that does not fit the sizes the caller states is taken as absent (flag -1, length -1): nothing outside the stated
+ * buffers is touched.  All buffers 8-byte aligned (out_dev 16).
+ * ymk_g4_slot_words: ceil((7 w + 32) / 32): no row of w pixels takes more than 7 w + 21 bits (the proof is in ymk_ccitt.hip).
+ * ymk_g4_file_capacity: the bytes no file of an h x w page exceeds - h such rows, EOFB, the pad.  HOST, -1 on a bad size.
+ * ymk_g4_scratch_bytes: HOST arrays h, w -> sizes5_out = total_rows, then the bytes of packed_dev, slots_dev, rowbits_dev
+ *   (uint32 [total_rows]) and rowoff_dev (uint64 [total_rows + n_pages]: page p's h + 1 bit offsets at word-5 + p).
+ * ymk_g4_test_pack: flags_dev int32 [n_pages] zeroed on `stream`, then one launch over the pages: flags 0 = two-valued, 1 = not,
+ *   -1 = no page; packed_dev = every page's packed rows (whatever its flag).  max_pixels: h w of the largest page.
+ * ymk_g4_code_rows: one thread per row codes it against the packed row above (row 0: an all-white row) into its slot - the
+ *   codes MSB first in 32-bit words - and its bit count into rowbits_dev.  Reads no flags: the table holds the pages to code.
+ *   max_rows: h of the tallest page.
+ * ymk_g4_scan: one block per page: rowoff_dev from rowbits_dev; lengths_dev[p] = the file's bytes (rows + EOFB, zero-padded to a
+ *   byte), -1 where that exceeds the capacity.
+ * ymk_g4_concat: one thread per 32-bit word of every file gathers its bits from the slots; EOFB and the pad behind the rows.
+ *   Bytes of out_dev outside the files (and the up to 3 behind a file's end that complete its last word) are not written.
+ *   max_capacity: the largest capacity of the table.
+ * ymk_g4_encode_pages: rows, scan, concatenate in order on `stream`.  Nothing is allocated, nothing waited for. */
+#define YMK_G4_PAGE_WORDS 16
+int ymk_g4_page_words(void);
+int ymk_g4_slot_words(int w);
+int64_t ymk_g4_file_capacity(int h, int w);
+int ymk_g4_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes5_out);
+int ymk_g4_test_pack(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* flags_dev, uint32_t* packed_dev,
+                     int64_t packed_bytes, void* stream);
+int ymk_g4_code_rows(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int max_rows, const uint32_t* packed_dev,
+                     int64_t packed_bytes, uint32_t* slots_dev, int64_t slot_bytes, int64_t out_bytes, uint32_t* rowbits_dev, void* stream);
+int ymk_g4_scan(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int64_t packed_bytes, int64_t slot_bytes,
+                int64_t out_bytes, const uint32_t* rowbits_dev, uint64_t* rowoff_dev, int* lengths_dev, void* stream);
+int ymk_g4_concat(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int64_t packed_bytes, const uint32_t* slots_dev,
+                  int64_t slot_bytes, const uint64_t* rowoff_dev, const int* lengths_dev, unsigned char* out_dev, int64_t out_bytes,
+                  int64_t max_capacity, void* stream);
+int ymk_g4_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int max_rows, const uint32_t* packed_dev,
+                        int64_t packed_bytes, uint32_t* slots_dev, int64_t slot_bytes, uint32_t* rowbits_dev, uint64_t* rowoff_dev,
+                        unsigned char* out_dev, int64_t out_bytes, int64_t max_capacity, int* lengths_dev, void* stream);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

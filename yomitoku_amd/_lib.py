@@ -86,6 +86,17 @@ SIGNATURES = {
     "ymk_jpeg_scratch_bytes_opt_mode": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int,
                                                 POINTER(c_int64)]),
     "ymk_jpeg_pages_grey": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "ymk_g4_page_words": (c_int, []),
+    "ymk_g4_slot_words": (c_int, [c_int]),
+    "ymk_g4_file_capacity": (c_int64, [c_int, c_int]),
+    "ymk_g4_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_g4_test_pack": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ymk_g4_code_rows": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "ymk_g4_scan": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ymk_g4_concat": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                              c_void_p]),
+    "ymk_g4_encode_pages": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_int64, c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

@@ -97,7 +97,8 @@ class OCR(StageAnalyzer):
         return (self._ocr_drawing(wave, k),)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False):
+              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
+              jpeg_bilevel=False):
         """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
         arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
         yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
@@ -113,12 +114,12 @@ class OCR(StageAnalyzer):
         encoded on the device from the clean page, so that
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
-        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`: as DocumentAnalyzer.serve."""
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey)  # before the pipeline is built or a source read
+        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel`: as DocumentAnalyzer.serve."""
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -562,7 +563,8 @@ class DocumentAnalyzer(StageAnalyzer):
         return reading_order_visualizer(page if layout is None else layout, results, to_host=False)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False):
+              overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
+              jpeg_bilevel=False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -590,12 +592,17 @@ class DocumentAnalyzer(StageAnalyzer):
         page), "4:2:2" its full height.  `jpeg_grey`: False, or "auto" - every page is tested on the device after the preset's
         resize, and one whose pixels all have B == G == R (a black-and-white scan loaded as B G R) is written as a grey file, a
         third of the blocks; its EncodedJpeg says `grey=True`, `subsampling=None`.  Any other value, and either option without
-        `jpeg`, is a ValueError before a source is read."""
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey)  # before the pipeline is built or a source read
+        `jpeg`, is a ValueError before a source is read.
+        `jpeg_bilevel`: False, or "auto" - every page is tested on the device as it arrived, before the preset's resize, and a
+        two-valued one (every sample 0 or 255 and B == G == R: what a 1-bit scan loads as) is written as a CCITT Group 4 file
+        instead: its entry ends with an EncodedBilevel (yomitoku_amd/ccitt.py; `scale` 1.0, the full-size page, lossless) that
+        `searchable_pdf_bytes` embeds as a /CCITTFaxDecode image.  Such a page ignores the preset's resize and the three options
+        above; every other page goes the way it goes without the switch.  The same refusals."""
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
 
     def __call__(self, img):
         self.img = img

@@ -23,6 +23,9 @@ sharp, the file grows.  `grey="auto"` (serve: `jpeg_grey="auto"`) tests every th
 preset's resize - one more launch and one wait for its answer - and writes a page all of whose pixels have B == G == R as the
 one-component file of that plane, a third of the blocks: `EncodedJpeg.grey` is True and `subsampling` None.  The definition of
 the modes is tests/jpeg_modes_ref.py; the defaults write the bytes they always wrote.
+
+`bilevel="auto"` (serve: `jpeg_bilevel="auto"`) tests every page on the device as it arrived and gives a two-valued one - every
+sample 0 or 255, B == G == R - a CCITT Group 4 file, an `EncodedBilevel` of yomitoku_amd/ccitt.py, in place of the EncodedJpeg.
 """
 
 from __future__ import annotations
@@ -232,15 +235,12 @@ def _as_device_page(page, device) -> torch.Tensor:
     return t.contiguous()
 
 
-def grey_pages(pages: Sequence[torch.Tensor], scratch: Optional[dict] = None) -> List[bool]:
-    """Per device page (uint8 H x W x 3 or H x W, contiguous): whether it is a three-channel page all of whose pixels have
-    B == G == R.  One launch over all three-channel pages on the current stream (ymk_jpeg_pages_grey), then one wait for its
-    answer, read through pinned memory."""
-    out = [False] * len(pages)
+def _grey_launch(pages: Sequence[torch.Tensor], scratch: dict):
+    """Launch the grey test of the three-channel pages among `pages` on the current stream and the copy of its answer to
+    pinned memory; waits for nothing.  -> (their indices, the pinned answer), or None where there is no such page."""
     cand = [k for k, p in enumerate(pages) if p.dim() == 3]
     if not cand:
-        return out
-    scratch = {} if scratch is None else scratch
+        return None
     device = pages[cand[0]].device
     rec = np.zeros((len(cand), PAGE_WORDS), np.int32)
     for j, k in enumerate(cand):
@@ -252,15 +252,52 @@ def grey_pages(pages: Sequence[torch.Tensor], scratch: Optional[dict] = None) ->
                                                diff.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_pages_grey")
     pin = _grown(scratch, "pin_grey", len(cand), torch.int32, pinned=True)
     pin[: len(cand)].copy_(diff[: len(cand)], non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    for k, v in zip(cand, pin[: len(cand)].tolist()):
-        out[k] = v == 0
+    return cand, pin
+
+
+def _grey_answers(n: int, launched) -> List[bool]:
+    """Per page of the `n` a `_grey_launch` was given whether it is a grey-valued three-channel page - once the stream has been
+    waited for."""
+    out = [False] * n
+    if launched is not None:
+        cand, pin = launched
+        for k, v in zip(cand, pin[: len(cand)].tolist()):
+            out[k] = v == 0
+    return out
+
+
+def grey_pages(pages: Sequence[torch.Tensor], scratch: Optional[dict] = None) -> List[bool]:
+    """Per device page (uint8 H x W x 3 or H x W, contiguous): whether it is a three-channel page all of whose pixels have
+    B == G == R.  One launch over all three-channel pages on the current stream (ymk_jpeg_pages_grey), then one wait for its
+    answer, read through pinned memory."""
+    launched = _grey_launch(pages, {} if scratch is None else scratch)
+    if launched is not None:
+        torch.cuda.current_stream().synchronize()
+    return _grey_answers(len(pages), launched)
+
+
+def _gather_files(parts: Sequence, scratch: dict, key: str = "pin_bytes") -> list:
+    """parts: (device buffer, byte offset, length or -1) per file -> their bytes (None for -1): packed on the device, then one
+    copy through pinned memory and one wait."""
+    good = [(buf, at, n) for buf, at, n in parts if n >= 0]
+    total = sum(n for _, _, n in good)
+    host = None
+    if total:
+        packed = torch.cat([buf[at : at + n] for buf, at, n in good])
+        pin = _grown(scratch, key, total, torch.uint8, pinned=True)
+        pin[:total].copy_(packed, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        host = pin[:total].numpy()
+    out, at = [], 0
+    for _, _, n in parts:
+        out.append(None if n < 0 else host[at : at + n].tobytes())
+        at += max(n, 0)
     return out
 
 
 def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
                       capacities: Optional[Sequence[int]] = None, optimize: bool = False, subsampling: str = "4:2:0",
-                      grey=False) -> List[Union[EncodedJpeg, Exception]]:
+                      grey=False, bilevel=False) -> list:
     """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
     file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
     stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
@@ -269,10 +306,19 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     optimize: Huffman tables made for each page (two more launches; the header shrinks with the tables, to ~270 bytes for a
     flat colour page); the decoded pixels are those of the plain file.
     subsampling: "4:2:0", "4:2:2" or "4:4:4", the chroma of the colour files; grey: False, or "auto" - a three-channel page
-    whose pixels all have B == G == R (tested on the device, after the preset's resize) becomes a grey file.  Anything else is
-    a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
+    whose pixels all have B == G == R (tested on the device, after the preset's resize) becomes a grey file.
+    bilevel: False, or "auto" - a two-valued page (every sample 0 or 255, B == G == R; tested on the device on the page as it
+    arrived) gets an EncodedBilevel, a Group 4 file (yomitoku_amd/ccitt.py), in place of the EncodedJpeg: full size whatever
+    the preset (scale 1.0), lossless, untouched by optimize / subsampling / grey / capacities; every other page goes the way it
+    goes without the switch, in the same call.  The test is one more launch and one more wait for its answer - with
+    grey="auto" and no page to resize the two tests share that wait.
+    Anything else is a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
     preset = jpeg_preset(image_quality)
     colour_mode = check_modes(subsampling, grey)
+    if bilevel is not False:
+        from . import ccitt  # imports this module
+
+        ccitt.check_bilevel(bilevel)
     quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
     out: list = [None] * len(pages)
     if not pages:
@@ -293,77 +339,96 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
                 out[k] = exc
         if not live:
             return out
+        large = [long_side is not None and max(int(p.shape[0]), int(p.shape[1])) > long_side for p in devs]
+        two, test, early_grey = [False] * len(devs), None, None
+        if bilevel is not False:
+            # on the pages as they arrived: the preset's resample would leave a two-valued page grey-valued.  Where no page can be
+            # resized the grey test sees the same pixels before and after that step: it is launched here and shares the wait
+            test = ccitt.start_test(devs, scratch)
+            if grey == "auto" and not any(large):
+                early_grey = _grey_launch(devs, scratch)
+            torch.cuda.current_stream().synchronize()
+            two = test.answers()
         scales = [1.0] * len(live)
         todo = []
         for j, p in enumerate(devs):
             h, w = int(p.shape[0]), int(p.shape[1])
-            if long_side is not None and max(h, w) > long_side:
+            if large[j] and not two[j]:
                 scales[j] = long_side / max(w, h)
                 todo.append((j, (max(int(h * scales[j]), 1), max(int(w * scales[j]), 1))))
         if todo:
             for (j, _), small in zip(todo, resize_pages([devs[j] for j, _ in todo], [s for _, s in todo])):
                 devs[j] = small
-        caps = None if capacities is None else [int(capacities[k]) for k in live]
-        as_grey = grey_pages(devs, scratch) if grey == "auto" else [False] * len(devs)
-        modes = [0 if p.dim() == 2 else (MODE_GREY if g else colour_mode) for p, g in zip(devs, as_grey)]
-        if not any(modes):
-            modes = None  # the defaults: the table and the sizes of every call before there were modes
-        blob, offsets, out_bytes = page_table(devs, quality, caps, optimize, modes)
-        sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in devs], optimize, modes)
-        mcus, blocks, intervals, coef_b, stream_b, iv_b = sized[:6]
-        coef = _grown(scratch, "coef", coef_b // 2, torch.int16, device)
-        bits = _grown(scratch, "stream", stream_b // 4, torch.int32, device)
-        ivals = _grown(scratch, "intervals", iv_b // 4, torch.int32, device)
-        files = _grown(scratch, "out", out_bytes, torch.uint8, device)
-        lengths = _grown(scratch, "lengths", len(devs), torch.int32, device)
-        blob_dev = imaging._stage_blob(blob, device)
-        if optimize:
-            hist = _grown(scratch, "hist", sized[6] // 4, torch.int32, device)
-            tables = _grown(scratch, "tables", sized[7] // 4, torch.int32, device)
-            dht = _grown(scratch, "dht", sized[8] // 4, torch.int32, device)
-            _lib.check(lib.ymk_jpeg_encode_pages_opt(blob_dev.data_ptr(), blob.size, len(devs), mcus, blocks, intervals, coef.data_ptr(),
-                                                     hist.data_ptr(), tables.data_ptr(), dht.data_ptr(), bits.data_ptr(), stream_b,
-                                                     ivals.data_ptr(), files.data_ptr(), out_bytes, lengths.data_ptr(),
-                                                     _lib.current_stream_ptr()), "ymk_jpeg_encode_pages_opt")
+        rest = [j for j in range(len(devs)) if not two[j]]  # the pages that get a JPEG file: all of them without `bilevel`
+        jdevs = [devs[j] for j in rest]
+        caps = None if capacities is None else [int(capacities[live[j]]) for j in rest]
+        if early_grey is not None:
+            all_grey = _grey_answers(len(devs), early_grey)
+            as_grey = [all_grey[j] for j in rest]
         else:
-            _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, len(devs), mcus, blocks, intervals, coef.data_ptr(),
-                                                 bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
-                                                 lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
-        # the lengths first (one small copy), then the files' bytes, packed on the device, in one copy
-        pin_len = _grown(scratch, "pin_lengths", len(devs), torch.int32, pinned=True)
-        pin_len[: len(devs)].copy_(lengths[: len(devs)], non_blocking=True)
+            as_grey = grey_pages(jdevs, scratch) if grey == "auto" and jdevs else [False] * len(jdevs)
+        sizes = []
+        if jdevs:
+            modes = [0 if p.dim() == 2 else (MODE_GREY if g else colour_mode) for p, g in zip(jdevs, as_grey)]
+            if not any(modes):
+                modes = None  # the defaults: the table and the sizes of every call before there were modes
+            blob, offsets, out_bytes = page_table(jdevs, quality, caps, optimize, modes)
+            sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in jdevs], optimize, modes)
+            mcus, blocks, intervals, coef_b, stream_b, iv_b = sized[:6]
+            coef = _grown(scratch, "coef", coef_b // 2, torch.int16, device)
+            bits = _grown(scratch, "stream", stream_b // 4, torch.int32, device)
+            ivals = _grown(scratch, "intervals", iv_b // 4, torch.int32, device)
+            files = _grown(scratch, "out", out_bytes, torch.uint8, device)
+            lengths = _grown(scratch, "lengths", len(jdevs), torch.int32, device)
+            blob_dev = imaging._stage_blob(blob, device)
+            if optimize:
+                hist = _grown(scratch, "hist", sized[6] // 4, torch.int32, device)
+                tables = _grown(scratch, "tables", sized[7] // 4, torch.int32, device)
+                dht = _grown(scratch, "dht", sized[8] // 4, torch.int32, device)
+                _lib.check(lib.ymk_jpeg_encode_pages_opt(blob_dev.data_ptr(), blob.size, len(jdevs), mcus, blocks, intervals, coef.data_ptr(),
+                                                         hist.data_ptr(), tables.data_ptr(), dht.data_ptr(), bits.data_ptr(), stream_b,
+                                                         ivals.data_ptr(), files.data_ptr(), out_bytes, lengths.data_ptr(),
+                                                         _lib.current_stream_ptr()), "ymk_jpeg_encode_pages_opt")
+            else:
+                _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, len(jdevs), mcus, blocks, intervals, coef.data_ptr(),
+                                                     bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
+                                                     lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
+            # the lengths first (one small copy), then the files' bytes, packed on the device, in one copy
+            pin_len = _grown(scratch, "pin_lengths", len(jdevs), torch.int32, pinned=True)
+            pin_len[: len(jdevs)].copy_(lengths[: len(jdevs)], non_blocking=True)
+        which = [j for j in range(len(devs)) if two[j]]
+        if which:  # the Group 4 files: launched behind the JPEG stages, their lengths and bytes in the same two copies' waits
+            g4_files, g4_offsets, g4_lengths = ccitt.launch_encode(test, which, scratch)
+            g4_pin = _grown(scratch, "g4_pin_lengths", len(which), torch.int32, pinned=True)
+            g4_pin[: len(which)].copy_(g4_lengths[: len(which)], non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        sizes = pin_len[: len(devs)].tolist()
-        good = [j for j, n in enumerate(sizes) if n >= 0]
-        total = sum(sizes[j] for j in good)
-        host = None
-        if total:
-            packed = torch.cat([files[offsets[j] : offsets[j] + sizes[j]] for j in good])
-            pin = _grown(scratch, "pin_bytes", total, torch.uint8, pinned=True)
-            pin[:total].copy_(packed, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            host = pin[:total].numpy()
-        at = 0
-        for j, k in enumerate(live):
-            p = devs[j]
-            if sizes[j] < 0:
-                cap = caps[j] if caps is not None else p.numel()
+        parts = []
+        if jdevs:
+            sizes = pin_len[: len(jdevs)].tolist()
+            parts += [(files, offsets[i], sizes[i]) for i in range(len(jdevs))]
+        if which:
+            parts += [(g4_files, g4_offsets[i], n) for i, n in enumerate(g4_pin[: len(which)].tolist())]
+        datas = _gather_files(parts, scratch)
+        for i, j in enumerate(rest):
+            p, k = devs[j], live[j]
+            if sizes[i] < 0:
+                cap = caps[i] if caps is not None else p.numel()
                 out[k] = _lib.YmkError(f"page {k}: the JPEG file does not fit its capacity of {cap} bytes")
                 continue
-            one = p.dim() == 2 or as_grey[j]
-            out[k] = EncodedJpeg(host[at : at + sizes[j]].tobytes(), int(p.shape[1]), int(p.shape[0]), one, float(scales[j]),
-                                 bool(optimize), None if one else subsampling)
-            at += sizes[j]
+            one = p.dim() == 2 or as_grey[i]
+            out[k] = EncodedJpeg(datas[i], int(p.shape[1]), int(p.shape[0]), one, float(scales[j]), bool(optimize), None if one else subsampling)
+        for i, j in enumerate(which):
+            out[live[j]] = ccitt.bilevel_entry(devs[j], datas[len(rest) + i], live[j])
     return out
 
 
 def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False, subsampling: str = "4:2:0",
-                grey=False) -> EncodedJpeg:
+                grey=False, bilevel=False):
     """One page; raises what `encode_jpeg_pages` would have put in its place.  The file's capacity is the page's raw byte
     count, and the header alone takes about 620 bytes (330 for a grey page): a colour page below roughly 15 x 15 pixels, or noise
     that does not compress, raises YmkError here and in `serve(jpeg=...)` - `encode_jpeg_pages(..., capacities=[...])` gives
-    such a page the room it needs."""
-    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize, subsampling=subsampling, grey=grey)[0]
+    such a page the room it needs.  bilevel="auto": an EncodedBilevel where the page is two-valued."""
+    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize, subsampling=subsampling, grey=grey, bilevel=bilevel)[0]
     if isinstance(res, BaseException):
         raise res
     return res

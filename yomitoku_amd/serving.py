@@ -31,7 +31,8 @@ memory.
 `render` is not one of the nine: its thread and stream are started by the first job that asks for overlays or JPEG files, and
 only the waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all
 canvases of a wave (as many per page as the analyzer draws: two, OCR one) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
-as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages); a job with neither runs exactly the stages above.
+as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages), its two-valued pages as Group 4 files with four
+more where the job says `jpeg_bilevel="auto"` (yomitoku_amd/ccitt.py); a job with neither runs exactly the stages above.
 
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
 process while holding the GIL - measured 100-180 ms with the results of a few hundred pages alive, six times in a
@@ -106,7 +107,8 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False):
+    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False,
+                 jpeg_bilevel=False):
         self.results = {}
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, the analyzer's pictures...): the waves visit the render stage
@@ -114,6 +116,7 @@ class _Job:
         self.jpeg_optimize = bool(jpeg_optimize)  # those files with Huffman tables of their own (encode_jpeg_pages(optimize=True))
         self.jpeg_subsampling = jpeg_subsampling  # None (4:2:0) or the chroma of those files (encode_jpeg_pages(subsampling=...))
         self.jpeg_grey = jpeg_grey  # False, or "auto": grey-valued colour pages become grey files (encode_jpeg_pages(grey="auto"))
+        self.jpeg_bilevel = jpeg_bilevel  # False, or "auto": two-valued pages get Group 4 files (encode_jpeg_pages(bilevel="auto"))
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -166,11 +169,12 @@ def _switch_interval(seconds):
                 _switch_saved = None
 
 
-def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False):
+def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False):
     """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
-    public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0", "4:2:2", "4:4:4") and
-    `jpeg_grey` (False, "auto") ask for something of those files: a value that is none of these is a ValueError, and so is any
-    of the three without `jpeg`."""
+    public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0", "4:2:2", "4:4:4"),
+    `jpeg_grey` (False, "auto") and `jpeg_bilevel` (False, "auto") ask for something of those files: a value that is none of
+    these is a ValueError, and so is any of the four without `jpeg`."""
+    from .ccitt import check_bilevel
     from .jpeg import check_modes
     from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
 
@@ -183,6 +187,8 @@ def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_gre
         raise ValueError(f"jpeg_subsampling={jpeg_subsampling!r} needs jpeg=...: there is no JPEG file to write that way")
     if jpeg is None and jpeg_grey is not False:
         raise ValueError(f"jpeg_grey={jpeg_grey!r} needs jpeg=...: there is no JPEG file to write that way")
+    if check_bilevel(jpeg_bilevel) and jpeg is None:
+        raise ValueError(f"jpeg_bilevel={jpeg_bilevel!r} needs jpeg=...: there are no page files to write that way")
 
 
 def _run_stage(stream, wave, fn, *args):
@@ -442,7 +448,7 @@ class PagePipeline:
             self._q[name].put(wave)
 
     def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
-              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False) -> List:
+              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -457,14 +463,16 @@ class PagePipeline:
         jpeg_optimize: those files with Huffman tables made for each page (smaller, the same pixels); a ValueError without `jpeg`.
         jpeg_subsampling: None (4:2:0), "4:2:0", "4:2:2" or "4:4:4" - the chroma of those files; jpeg_grey: False, or "auto" - a page
         whose pixels all have B == G == R becomes a grey file.  Other values, and either without `jpeg`, are a ValueError.
+        jpeg_bilevel: False, or "auto" - a two-valued page (every sample 0 or 255) gets an EncodedBilevel (yomitoku_amd/ccitt.py), a
+        lossless Group 4 file of the full-size page, in place of the EncodedJpeg; the same refusals.
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
 
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey)
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
             job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
+                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
             if job.overlays or job.jpeg:
                 self._start_render()
             n = 0
@@ -742,7 +750,7 @@ class StageAnalyzer:
             files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch,
                                       optimize=getattr(wave.job, "jpeg_optimize", False),
                                       subsampling=getattr(wave.job, "jpeg_subsampling", None) or "4:2:0",
-                                      grey=getattr(wave.job, "jpeg_grey", False))
+                                      grey=getattr(wave.job, "jpeg_grey", False), bilevel=getattr(wave.job, "jpeg_bilevel", False))
             for k, made in zip(live, files):
                 out[k] = made if isinstance(made, BaseException) else (made,)
         return out
@@ -780,7 +788,7 @@ class StageAnalyzer:
 
     # ---- the pipeline of this analyzer
     def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False,
-               jpeg_subsampling=None, jpeg_grey=False):
+               jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -789,7 +797,7 @@ class StageAnalyzer:
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
         return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey)
+                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -

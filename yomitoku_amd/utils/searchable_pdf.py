@@ -317,6 +317,13 @@ def _is_encoded(image) -> bool:
     return isinstance(getattr(image, "data", None), (bytes, bytearray)) and all(hasattr(image, a) for a in ("width", "height", "grey", "scale"))
 
 
+def _is_bilevel(image) -> bool:
+    """An entry that is a finished CCITT Group 4 stream: yomitoku_amd.ccitt.EncodedBilevel, recognised by `bilevel` and its
+    fields (`data` bytes, `width`, `height`, `scale`), again without torch or the HIP library."""
+    return getattr(image, "bilevel", False) is True and isinstance(getattr(image, "data", None), (bytes, bytearray)) and all(
+        hasattr(image, a) for a in ("width", "height", "scale"))
+
+
 def _scaled_document(doc, scale: float):
     """What `text_layer` reads of `doc`, every coordinate times `scale`: a plain view, not a copy of the schema - the schema's
     boxes are integers and refuse the fractions a scale like 1500 / 1600 leaves."""
@@ -343,7 +350,10 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
     kids = []
     preset = IMAGE_QUALITY_PRESETS.get(image_quality, IMAGE_QUALITY_PRESETS["high"])
     for image, doc in zip(images, docs):
-        if _is_encoded(image):  # a finished JPEG (yomitoku_amd.jpeg.EncodedJpeg): embedded as it is, `image_quality` does not apply
+        bilevel = _is_bilevel(image)
+        if bilevel:  # a finished T.6 stream (yomitoku_amd.ccitt.EncodedBilevel): 1 bit a pixel, 0 = white (BlackIs1 false, the default)
+            data, w, h, scale = bytes(image.data), int(image.width), int(image.height), float(image.scale)
+        elif _is_encoded(image):  # a finished JPEG (yomitoku_amd.jpeg.EncodedJpeg): embedded as it is, `image_quality` does not apply
             data, w, h, grey, scale = bytes(image.data), int(image.width), int(image.height), bool(image.grey), float(image.scale)
         else:
             image = _as_pil(image)
@@ -359,8 +369,12 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
             image.save(jpeg, format="JPEG", quality=preset["jpeg_quality"])
             data = jpeg.getvalue()
             w, h = image.size
-        xobject = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ColorSpace /Device{'Gray' if grey else 'RGB'} "
-                                 "/BitsPerComponent 8 /Filter /DCTDecode", data, compress=False)
+        if bilevel:
+            xobject = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ColorSpace /DeviceGray /BitsPerComponent 1 "
+                                     f"/Filter /CCITTFaxDecode /DecodeParms << /K -1 /Columns {w} /Rows {h} >>", data, compress=False)
+        else:
+            xobject = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ColorSpace /Device{'Gray' if grey else 'RGB'} "
+                                     "/BitsPerComponent 8 /Filter /DCTDecode", data, compress=False)
         contents = pdf.add_stream("", _content_stream(w, h, text_layer(_scaled_document(doc, scale), h), supplementary), compress=True)
         kids.append(pdf.add((f"<< /Type /Page /Parent {pages} 0 R /MediaBox [0 0 {w} {h}] /Contents {contents} 0 R "
                              f"/Resources << /XObject << /Im0 {xobject} 0 R >> /Font << /F1 {font} 0 R >> >> >>").encode("ascii")))
@@ -374,7 +388,9 @@ def create_searchable_pdf(images: List, docs: List, output_path: str, font_path:
     """Write `images` (PIL images; BGR arrays are taken too) with the words of `docs` (DocumentAnalyzerSchema, one per image)
     as an invisible text layer to `output_path`.  utils/searchable_pdf.py:74.  An entry of `images` that is an EncodedJpeg
     (yomitoku_amd/jpeg.py; what `DocumentAnalyzer.serve(jpeg=...)` returns) is embedded as it is: size and colour space come
-    from the object, the words are scaled by its `scale`, and `image_quality` is ignored for that entry."""
+    from the object, the words are scaled by its `scale`, and `image_quality` is ignored for that entry.  An EncodedBilevel
+    (yomitoku_amd/ccitt.py; `serve(jpeg=..., jpeg_bilevel="auto")` returns one for a two-valued page) is embedded as a 1-bit
+    /CCITTFaxDecode image, K -1 (Group 4), likewise as it is."""
     data = searchable_pdf_bytes(images, docs, image_quality)
     with open(output_path, "wb") as f:
         f.write(data)
