@@ -587,6 +587,26 @@ int ymk_op_attention(const float* q_dev, const float* k_dev, const float* v_dev,
  * o [b][lq][heads * hd] = softmax(scale * q k^T) v per head, fp32 softmax, no masks.  heads <= 8, hd <= 96. */
 int ymk_op_nar_cross_attention(const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int b, int heads, int lq,
                                int lk, int hd, float scale, const int* koff_dev, const int* klen_dev, void* stream);
+/* Two test-only entries that carry what the models' launch sites carry and ymk_op_layernorm / ymk_op_attention /
+ * ymk_op_nar_cross_attention pin (tests/test_attention_views_gpu.py).  Neither allocates, synchronises or measures anything: each
+ * is one call of the launcher the models call (csrc/ymk_seq.h).
+ * layernorm_view: input rows of ldx floats, output rows of ldy floats (both >= d); in_rows_mod > 0 reads input row
+ *   m % in_rows_mod - a [in_rows_mod][ldx] table broadcast over the rows.
+ * attention_view: kernel 0 = flash_attention, 1 = small_attention, 2 = nar_cross_attention.  q / k / v / o point at the first
+ *   column of head 0 inside rows of ldq / ldk / ldv / ldo floats; bs*: batch strides in floats (bsq may be 0 for the small kernel:
+ *   one query table for the batch; the nar kernel always has one and takes bsq = 0).  mask_qk [lq][ld_mask] / kpm [b][ld_kpm]
+ *   (non-zero = blocked): the small kernel only, and not together with tables.  (qoff, qlen) / (koff, klen): int32 [b] each,
+ *   both of a pair or neither - the rows of sample i start at row off[i] of the buffer and number len[i] (>= 1), replacing the
+ *   batch strides and lq / lk, which then are the maxima over the batch; the nar kernel takes the key pair only.  amax_*: the
+ *   caller's max|x| records of 1024 words bounding q, k and v (any may be null, any two may be the same record): with all
+ *   three, scale <= 1 and "conv_split" 16 in force the flash kernel multiplies fp16 planes, otherwise exact fp32. */
+int ymk_op_layernorm_view(const float* x_dev, int ldx, int in_rows_mod, int rows, int d, const float* g_dev, const float* b_dev,
+                          float eps, float* y_dev, int ldy, void* stream);
+int ymk_op_attention_view(int kernel, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int b, int heads, int lq,
+                          int lk, int hd, float scale, int ldq, int ldk, int ldv, int ldo, int64_t bsq, int64_t bsk, int64_t bsv,
+                          int64_t bso, const unsigned char* mask_qk_dev, int ld_mask, const unsigned char* kpm_dev, int ld_kpm,
+                          const int* qoff_dev, const int* qlen_dev, const int* koff_dev, const int* klen_dev,
+                          const unsigned* amax_q_dev, const unsigned* amax_k_dev, const unsigned* amax_v_dev, void* stream);
 int ymk_op_maxpool3x3s2(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream);
 int ymk_op_upsample_bilinear(const float* x_dev, int n, int h, int w, int c, int oh, int ow, const float* add_dev,
                              float* y_dev, void* stream);

@@ -285,6 +285,176 @@ def attention(q, k, v, heads, scale=None, mask_qk=None, key_padding_mask=None, u
     return o
 
 
+def layernorm_view(x, weight, bias, eps, m, x_view=None, y_view=None, in_rows_mod=0):
+    """ymk_op_layernorm_view: x [in_rows_mod or m, D] on the device -> (y [m, D]: the output view, the whole output buffer
+    [m, ldy]).  *_view = (first column, leading dimension) inside a wider buffer allocated here: NaN beside the input view,
+    SENTINEL in every word of the output buffer.  in_rows_mod > 0: output row r reads input row r % in_rows_mod."""
+    lib = _lib.load()
+    assert x.is_cuda and x.dim() == 2
+    rows_in, d = x.shape
+    assert rows_in == (in_rows_mod or m)
+    xbuf, xptr = _into_view(x.float(), x_view or (0, d))
+    yc0, ldy = y_view or (0, d)
+    assert 0 <= yc0 and yc0 + d <= ldy
+    for c0, ld in ((x_view or (0, d)), (yc0, ldy)):  # the kernel moves 16-byte words
+        assert c0 % 4 == 0 and ld % 4 == 0 and d % 4 == 0 and d <= 1024
+    ybuf = torch.empty((m, ldy), dtype=torch.float32, device=x.device)
+    ybuf.view(torch.int32).fill_(SENTINEL)
+    g = weight.float().to(x.device).contiguous()
+    b = bias.float().to(x.device).contiguous()
+    with torch.cuda.device(x.device):
+        _lib.check(lib.ymk_op_layernorm_view(xptr, xbuf.shape[-1], in_rows_mod, m, d, g.data_ptr(), b.data_ptr(), float(eps),
+                                             ybuf.data_ptr() + 4 * yc0, ldy, _lib.current_stream_ptr()), "ymk_op_layernorm_view")
+    return ybuf[:, yc0:yc0 + d].clone(), ybuf
+
+
+def nar_cross_attention(q, ks, vs, heads, device, scale=None):
+    """ymk_op_nar_cross_attention on contiguous operands: q [lq, D] shared by the batch, ks / vs lists of per-sample [lk_i, D]
+    laid end to end and found through the (koff, klen) tables -> list of [lq, D] device tensors."""
+    lib = _lib.load()
+    b, (lq, d) = len(ks), q.shape
+    hd = d // heads
+    lens = [int(k.shape[0]) for k in ks]
+    assert heads <= 8 and hd <= 96 and min(lens) >= 1
+    qd = q.float().to(device).contiguous()
+    kd, vd = (torch.cat([t.float() for t in ts]).to(device).contiguous() for ts in (ks, vs))
+    off = [sum(lens[:i]) for i in range(b)]
+    koff, klen = (torch.tensor(t, dtype=torch.int32, device=device) for t in (off, lens))
+    o = torch.empty((b, lq, d), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.ymk_op_nar_cross_attention(qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), o.data_ptr(), b, heads, lq, max(lens), hd,
+                                                  float(hd**-0.5 if scale is None else scale), koff.data_ptr(), klen.data_ptr(),
+                                                  _lib.current_stream_ptr()), "ymk_op_nar_cross_attention")
+    return list(o)
+
+
+ATTN_KERNELS = {"flash": 0, "small": 1, "nar": 2}
+# which operands share one buffer: the PARSeq encoder's [.., 3D] rows, RT-DETR's [.., 2D] q|k with its own v, the decoders'
+# q with the [.., 2D] k|v of memkv / skv, and three buffers
+ATTN_PACKS = {"qkv": ("A", "A", "A"), "qk": ("A", "A", "V"), "kv": ("Q", "A", "A"), "sep": ("Q", "K", "V")}
+
+
+def _row_layout(caps, rowgap, table, order=None):
+    """Row offsets of the samples of a buffer holding caps[i] rows of sample i, `rowgap` spare rows after each (and before the
+    first, with tables): the uniform form - equal caps, one batch stride - or, with tables, the samples in `order`.
+    -> (offsets, rows of the buffer)"""
+    b = len(caps)
+    if not table:
+        assert len(set(caps)) == 1, "the uniform form has one length"
+        return [i * (caps[0] + rowgap) for i in range(b)], b * (caps[0] + rowgap)
+    off, r = [0] * b, rowgap
+    for i in (order if order is not None else range(b)):
+        off[i] = r
+        r += caps[i] + rowgap
+    return off, r
+
+
+def attention_view(kernel, qs, ks, vs, heads, device, scale=None, pack="sep", colgap=0, rowgap=1, q_tab=False, k_tab=False, order=None,
+                   o_view=None, mask_qk=None, kpm=None, amax=(None, None, None)):
+    """ymk_op_attention_view: one launch of flash_attention / small_attention / nar_cross_attention ("flash" / "small" / "nar")
+    with the strides, tables, masks and records a model passes.  qs: a list of per-sample [lq_i, D] tensors, or ONE [lq, D]
+    table for the whole batch (bsq = 0; always so for "nar"); ks / vs: lists of [lk_i, D] (CPU or device, fp32).
+    pack (ATTN_PACKS) puts operands side by side in one buffer, `colgap` spare columns after each; samples follow each other
+    with `rowgap` spare rows - at one batch stride, or with q_tab / k_tab at the rows of int32 offset / length tables (samples
+    placed in `order`; lengths may then differ).  Operands that share a buffer share its rows: a sample gets max(lq_i, lk_i) of
+    them.  o_view = (first column, leading dimension) of the output, whose rows follow the queries'.  mask_qk [lq, ld_mask] /
+    kpm [b, ld_kpm]: bool, True = blocked.  amax: the max|x| records of q, k, v (amax_record; None = absent).
+    Every spare word of an operand buffer is NaN, every word of the output buffer SENTINEL before the launch.
+    -> (outs: per-sample [lq_i, D] device tensors, the whole output buffer [rows, ldo], written: bool [rows, ldo] on the CPU,
+    True where the launch has to store)."""
+    lib = _lib.load()
+    kid = ATTN_KERNELS[kernel]
+    b = len(ks)
+    shared_q = torch.is_tensor(qs)
+    assert shared_q or kernel != "nar"
+    d = ks[0].shape[1]
+    hd = d // heads
+    assert hd * heads == d and len(vs) == b and (shared_q or len(qs) == b)
+    lks = [int(k.shape[0]) for k in ks]
+    lqs = [int(qs.shape[0])] * b if shared_q else [int(q.shape[0]) for q in qs]
+    assert all(v.shape == k.shape for k, v in zip(ks, vs)) and min(lks) >= 1 and min(lqs) >= 1
+    scale = hd**-0.5 if scale is None else float(scale)
+    names = ATTN_PACKS[pack]
+    share = names[0] == names[1]
+    assert not (share and shared_q) and (not share or q_tab == k_tab) and not (shared_q and q_tab)
+    assert (q_tab or len(set(lqs)) == 1) and (k_tab or len(set(lks)) == 1), "lengths differ only under tables"
+    # what the kernels trust
+    if kernel == "nar":
+        assert heads <= 8 and hd <= 96
+    if kernel == "small" or (kernel == "flash" and hd not in (32, 48, 64, 96)):
+        assert max(lks) <= 1024 and hd <= 128
+    if kernel != "small":
+        assert mask_qk is None and kpm is None
+    assert not ((q_tab or k_tab) and (mask_qk is not None or kpm is not None)), "ragged batches come without masks"
+
+    # columns: operand j of a buffer at j * (D + colgap)
+    col, ld = {}, {}
+    for op, name in zip("qkv", names):
+        col[op] = ld.get(name, 0)
+        ld[name] = col[op] + d + colgap
+    # rows: the key side (k, v) and the query side (q, o) - one and the same where q and k share a buffer
+    kcaps = [max(a, c) for a, c in zip(lqs, lks)] if share else lks
+    koff, krows = _row_layout(kcaps, rowgap, k_tab, order)
+    if share:
+        qoff, qrows = koff, krows
+    elif shared_q:
+        qoff, qrows = [0] * b, lqs[0]
+    else:
+        qoff, qrows = _row_layout(lqs, rowgap, q_tab, order)
+    ooff, orows = _row_layout(lqs, rowgap, False) if shared_q else (qoff, qrows)
+    bufs = {name: torch.full((qrows if name == "Q" else krows, ld[name]), float("nan"), dtype=torch.float32) for name in set(names)}
+    for i in range(b):
+        if not shared_q:
+            bufs[names[0]][qoff[i]:qoff[i] + lqs[i], col["q"]:col["q"] + d] = qs[i].float().cpu()
+        bufs[names[1]][koff[i]:koff[i] + lks[i], col["k"]:col["k"] + d] = ks[i].float().cpu()
+        bufs[names[2]][koff[i]:koff[i] + lks[i], col["v"]:col["v"] + d] = vs[i].float().cpu()
+    if shared_q:
+        bufs["Q"][:, col["q"]:col["q"] + d] = qs.float().cpu()
+    bufs = {name: t.to(device) for name, t in bufs.items()}
+    oc0, ldo = o_view or (0, d)
+    assert 0 <= oc0 and oc0 + d <= ldo
+    obuf = torch.empty((orows, ldo), dtype=torch.float32, device=device)
+    obuf.view(torch.int32).fill_(SENTINEL)
+    written = torch.zeros(orows, ldo, dtype=torch.bool)
+    for i in range(b):
+        written[ooff[i]:ooff[i] + lqs[i], oc0:oc0 + d] = True
+    lds = [ld[names[0]], ld[names[1]], ld[names[2]], ldo]
+    if kernel == "flash":
+        assert all(v % 4 == 0 for v in lds + [col["q"], col["k"], col["v"], oc0]), "flash attention moves 16-byte words"
+    # the tables, in range
+    tabs = [None] * 4
+    if q_tab:
+        tabs[0], tabs[1] = (torch.tensor(t, dtype=torch.int32, device=device) for t in (qoff, lqs))
+        assert all(0 <= o and o + n <= qrows and n >= 1 for o, n in zip(qoff, lqs))
+    if k_tab:
+        tabs[2], tabs[3] = (torch.tensor(t, dtype=torch.int32, device=device) for t in (koff, lks))
+        assert all(0 <= o and o + n <= krows and n >= 1 for o, n in zip(koff, lks))
+    stride = lambda off: (off[1] - off[0]) if b > 1 else 0  # noqa: E731 - rows between samples (uniform form)
+    bsq = 0 if (shared_q or q_tab) else stride(qoff) * lds[0]
+    bsk, bsv = (0, 0) if k_tab else (stride(koff) * lds[1], stride(koff) * lds[2])
+    bso = 0 if q_tab else stride(ooff) * ldo
+    m = mask_qk.to(device=device, dtype=torch.uint8).contiguous() if mask_qk is not None else None
+    kp = kpm.to(device=device, dtype=torch.uint8).contiguous() if kpm is not None else None
+    if m is not None:
+        assert m.dim() == 2 and m.shape[0] >= lqs[0] and m.shape[1] >= lks[0]
+    if kp is not None:
+        assert kp.dim() == 2 and kp.shape[0] >= b and kp.shape[1] >= lks[0]
+    for rec in amax:
+        assert rec is None or (rec.is_cuda and rec.dtype == torch.int32 and rec.numel() == AMAX_REC_WORDS)
+    ptr = lambda op, name: bufs[name].data_ptr() + 4 * col[op]  # noqa: E731
+    with torch.cuda.device(device):
+        _lib.check(
+            lib.ymk_op_attention_view(kid, ptr("q", names[0]), ptr("k", names[1]), ptr("v", names[2]), obuf.data_ptr() + 4 * oc0, b, heads,
+                                      max(lqs), max(lks), hd, scale, lds[0], lds[1], lds[2], ldo, bsq, bsk, bsv, bso,
+                                      _lib.ptr(m), m.shape[1] if m is not None else 0, _lib.ptr(kp), kp.shape[1] if kp is not None else 0,
+                                      _lib.ptr(tabs[0]), _lib.ptr(tabs[1]), _lib.ptr(tabs[2]), _lib.ptr(tabs[3]),
+                                      _lib.ptr(amax[0]), _lib.ptr(amax[1]), _lib.ptr(amax[2]), _lib.current_stream_ptr()),
+            "ymk_op_attention_view",
+        )
+    outs = [obuf[ooff[i]:ooff[i] + lqs[i], oc0:oc0 + d].clone() for i in range(b)]
+    return outs, obuf, written
+
+
 # ---- the RT-DETRv2 decoder's token kernels: rows are level-major across the images (include/ymk.h, ymk_op_topk_tokens)
 def _level_hw(levels):
     """levels ((h0, w0), (h1, w1), (h2, w2)) -> the HOST int array {h0, w0, h1, w1, h2, w2} of the ABI."""

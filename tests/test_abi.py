@@ -26,6 +26,21 @@ def test_ctypes_table_matches_header():
     assert sorted(_lib.SIGNATURES) == _header_symbols()
 
 
+def test_view_entries_of_the_sequence_kernels_have_as_many_ctypes_arguments_as_the_header():
+    """ymk_op_attention_view / ymk_op_layernorm_view: one ctypes argument per declared parameter, the batch strides as int64"""
+    import ctypes
+
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ymk.h")).read(), flags=re.S)
+    for name, count in (("ymk_op_attention_view", 31), ("ymk_op_layernorm_view", 11)):
+        params = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)", src, flags=re.S).group(1).split(",")
+        res, args = _lib.SIGNATURES[name]
+        assert res is ctypes.c_int and len(args) == len(params) == count, name
+        for p, a in zip(params, args):
+            assert ("int64_t" in p) == (a is ctypes.c_int64), (name, p)
+            assert ("*" in p) == (a is ctypes.c_void_p), (name, p)
+            assert ("float " in p and "*" not in p) == (a is ctypes.c_float), (name, p)
+
+
 def test_version_and_error_slot():
     lib = _lib.load()
     assert lib.ymk_version() >= 100

@@ -571,6 +571,46 @@ int ymk_op_nar_cross_attention(const float* q_dev, const float* k_dev, const flo
   YMK_API_END
 }
 
+int ymk_op_layernorm_view(const float* x_dev, int ldx, int in_rows_mod, int rows, int d, const float* g_dev, const float* b_dev,
+                          float eps, float* y_dev, int ldy, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(x_dev && g_dev && b_dev && y_dev, "null argument");
+  YMK_CHECK(rows >= 0 && d > 0 && ldx >= d && ldy >= d && in_rows_mod >= 0, "layernorm_view: rows of at least d floats, in_rows_mod >= 0");
+  ymk::layernorm((hipStream_t)stream, x_dev, ldx, in_rows_mod, g_dev, b_dev, eps, y_dev, ldy, rows, d);
+  YMK_API_END
+}
+
+int ymk_op_attention_view(int kernel, const float* q_dev, const float* k_dev, const float* v_dev, float* o_dev, int b, int heads, int lq,
+                          int lk, int hd, float scale, int ldq, int ldk, int ldv, int ldo, int64_t bsq, int64_t bsk, int64_t bsv,
+                          int64_t bso, const unsigned char* mask_qk_dev, int ld_mask, const unsigned char* kpm_dev, int ld_kpm,
+                          const int* qoff_dev, const int* qlen_dev, const int* koff_dev, const int* klen_dev,
+                          const unsigned* amax_q_dev, const unsigned* amax_k_dev, const unsigned* amax_v_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(q_dev && k_dev && v_dev && o_dev, "null argument");
+  YMK_CHECK(kernel >= 0 && kernel <= 2, "attention_view: kernel is 0 (flash), 1 (small) or 2 (nar cross)");
+  YMK_CHECK((qoff_dev == nullptr) == (qlen_dev == nullptr) && (koff_dev == nullptr) == (klen_dev == nullptr),
+            "offset and length tables come in pairs");
+  YMK_CHECK(kernel == 1 || (!mask_qk_dev && !kpm_dev), "attention_view: masks come with the small kernel");
+  YMK_CHECK(kernel != 2 || (!qoff_dev && bsq == 0), "attention_view: the nar kernel has one query table and no query batch stride");
+  hipStream_t s = (hipStream_t)stream;
+  SeqTab tab;
+  tab.qoff = qoff_dev;
+  tab.qlen = qlen_dev;
+  tab.koff = koff_dev;
+  tab.klen = klen_dev;
+  const SeqTab* tp = (qoff_dev || koff_dev) ? &tab : nullptr;
+  if (kernel == 0)
+    flash_attention(s, q_dev, k_dev, v_dev, o_dev, b, heads, lq, lk, hd, ldq, ldk, ldv, ldo, (long)bsq, (long)bsk, (long)bsv, (long)bso, scale,
+                    tp, amax_q_dev, amax_k_dev, amax_v_dev);
+  else if (kernel == 1)
+    small_attention(s, q_dev, k_dev, v_dev, o_dev, b, heads, lq, lk, hd, ldq, ldk, ldv, ldo, (long)bsq, (long)bsk, (long)bsv, (long)bso, scale,
+                    mask_qk_dev, ld_mask, kpm_dev, ld_kpm, tp);
+  else
+    nar_cross_attention(s, q_dev, k_dev, v_dev, o_dev, b, heads, lq, lk, hd, ldq, ldk, ldv, ldo, (long)bsk, (long)bsv, (long)bso, scale, tp);
+  YMK_API_END
+}
+
 int ymk_op_maxpool3x3s2(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream) {
   YMK_API_BEGIN
   using namespace ymk;
