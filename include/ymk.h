@@ -382,7 +382,8 @@ int ymk_pil_resize_u8(const int* blob_dev, int64_t blob_words, int n, int max_oh
  *     word 6-7   WORD offset (low, high) in packed_dev of the page's packed rows: h rows of ceil(w / 32) words, 1 = black, the
  *                leftmost pixel of a word in its bit 31, zero bits behind column w
  *     word 8-9   BYTE offset (low, high) of the page's file in out_dev, a multiple of 4     word 10  the file's capacity in bytes
- *     word 11-12 WORD offset (low, high) in slots_dev of row 0's slot; a row's slot has ymk_g4_slot_words(w) words    13-15  0
+ *     word 11-12 WORD offset (low, high) in slots_dev of row 0's slot; a row's slot has ymk_g4_slot_words(w) words    13  0
+ *     word 14-15 not read by these calls (the binariser's: see below); 0 otherwise
  * A record that does not fit the sizes the caller states is taken as absent (flag -1, length -1): nothing outside the stated
  * buffers is touched.  All buffers 8-byte aligned (out_dev 16).
  * ymk_g4_slot_words: ceil((7 w + 32) / 32): no row of w pixels takes more than 7 w + 21 bits (the proof is in ymk_ccitt.hip).
@@ -417,6 +418,35 @@ int ymk_g4_concat(const int* blob_dev, int64_t blob_words, int n_pages, int64_t 
 int ymk_g4_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int max_rows, const uint32_t* packed_dev,
                         int64_t packed_bytes, uint32_t* slots_dev, int64_t slot_bytes, uint32_t* rowbits_dev, uint64_t* rowoff_dev,
                         unsigned char* out_dev, int64_t out_bytes, int64_t max_capacity, int* lengths_dev, void* stream);
+
+/* ---- Binariser: grey-valued pages of a wave thresholded into the packed rows of the Group 4 encoder, opt-in
+ * (yomitoku_amd/csrc/ymk_binarize.hip; yomitoku_amd/ccitt.py; encode_jpeg_pages(bilevel="otsu" | "adaptive"), serve(jpeg=...,
+ * jpeg_bilevel=...)).  DESIGN.md, "Thresholded pages"; tests/binarize_ref.py is the definition, and every stage equals it bit
+ * for bit.  A page is grey-valued when it has one channel, or three with B == G == R everywhere; p is that value, 1 = black.
+ * The page table is the Group 4 encoder's; of it these calls read words 0-4 (pixels, h, w, channels), 6-7 (the packed rows) and
+ *     word 14-15 WORD offset (low, high) in sat_dev of the page's summed-area table, h w words (ymk_bin_adaptive_pack only)
+ * which the Group 4 calls ignore.  A record that does not fit the sizes the caller states is taken as absent (flag -1, nothing
+ * written).  packed_dev, sat_dev 8-byte aligned.  Nothing is allocated, nothing waited for.  ymk_g4_encode_pages codes the rows.
+ * ymk_bin_scratch_bytes: HOST arrays h, w -> sizes2_out = the bytes of hist_dev (uint32 [n_pages][256]) and of sat_dev (uint32,
+ *   the pages' h w words one behind the other).
+ * ymk_bin_test_hist: flags_dev int32 [n_pages] (and hist_dev, where not null) zeroed on `stream`, then one launch over the pages:
+ *   flags 0 = grey-valued, 1 = not, -1 = no page; hist_dev[p] = the histogram of the page's first channel.
+ * ymk_bin_otsu: one block per page: thresholds_dev[p] = the smallest t in 0..254 with both classes non-empty that maximises
+ *   sigma(t) = double(d) * double(d) / double(w0 w1), d = m1 w0 - m0 w1 in int64 (w, m: counts and first moments of the classes
+ *   <= t and > t); 0 where no t has both classes.
+ * ymk_bin_otsu_pack: packed rows with black iff p <= thresholds_dev[page].
+ * ymk_bin_adaptive_pack: three launches: row sums, column sums (a uint32 summed-area table that wraps; window sums are below 2^31
+ *   and so exact), then packed rows with black iff p n 20 <= S 17 in 64 bits, n and S the pixel count and the sum of the window
+ *   rows [y - r, y + r] x columns [x - r, x + r] clipped to the page, r = max(1, max(h, w) / 16).  max_h, max_w: the largest of
+ *   the table. */
+int ymk_bin_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes2_out);
+int ymk_bin_test_hist(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* flags_dev, uint32_t* hist_dev,
+                      void* stream);
+int ymk_bin_otsu(int n_pages, const uint32_t* hist_dev, int* thresholds_dev, void* stream);
+int ymk_bin_otsu_pack(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, const int* thresholds_dev,
+                      uint32_t* packed_dev, int64_t packed_bytes, void* stream);
+int ymk_bin_adaptive_pack(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* sat_dev, int64_t sat_bytes,
+                          uint32_t* packed_dev, int64_t packed_bytes, void* stream);
 
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,

@@ -97,6 +97,11 @@ SIGNATURES = {
                               c_void_p]),
     "ymk_g4_encode_pages": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                     c_int64, c_int64, c_void_p, c_void_p]),
+    "ymk_bin_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_bin_test_hist": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ymk_bin_otsu": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
+    "ymk_bin_otsu_pack": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ymk_bin_adaptive_pack": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

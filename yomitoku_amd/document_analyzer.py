@@ -114,7 +114,8 @@ class OCR(StageAnalyzer):
         encoded on the device from the clean page, so that
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
-        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel`: as DocumentAnalyzer.serve."""
+        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"): as
+        DocumentAnalyzer.serve."""
         check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
@@ -597,7 +598,15 @@ class DocumentAnalyzer(StageAnalyzer):
         two-valued one (every sample 0 or 255 and B == G == R: what a 1-bit scan loads as) is written as a CCITT Group 4 file
         instead: its entry ends with an EncodedBilevel (yomitoku_amd/ccitt.py; `scale` 1.0, the full-size page, lossless) that
         `searchable_pdf_bytes` embeds as a /CCITTFaxDecode image.  Such a page ignores the preset's resize and the three options
-        above; every other page goes the way it goes without the switch.  The same refusals."""
+        above; every other page goes the way it goes without the switch.  The same refusals.
+        `jpeg_bilevel`: "otsu" or "adaptive" - every GREY-VALUED page (one channel, or B == G == R everywhere: a flatbed or phone
+        scan of a black-and-white document, with paper noise, soft edges, a gradient of light - and a grey photograph too: the
+        switch is a decision about the job, not a guess about a page) is thresholded on the device and written as a Group 4 file
+        the same way; its EncodedBilevel says `method` and, for "otsu", `threshold`.  "otsu" takes one threshold per page from its
+        histogram; "adaptive" calls a pixel black where it is 15 % below the mean of its window of max(h, w) // 16 pixels each
+        way, which follows uneven light (tests/binarize_ref.py is the definition of both).  OCR and layout see the page as it
+        arrived; only the file changes.  A colour page goes the way it goes without the switch; a two-valued page gives the file
+        of "auto"."""
         check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)

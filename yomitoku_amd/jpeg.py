@@ -26,6 +26,8 @@ the modes is tests/jpeg_modes_ref.py; the defaults write the bytes they always w
 
 `bilevel="auto"` (serve: `jpeg_bilevel="auto"`) tests every page on the device as it arrived and gives a two-valued one - every
 sample 0 or 255, B == G == R - a CCITT Group 4 file, an `EncodedBilevel` of yomitoku_amd/ccitt.py, in place of the EncodedJpeg.
+`bilevel="otsu"` / `"adaptive"` thresholds every grey-valued page on the device instead - a scan with paper noise, soft edges
+or a gradient of light, but a grey photograph too - and codes the result the same way.
 """
 
 from __future__ import annotations
@@ -312,6 +314,11 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     the preset (scale 1.0), lossless, untouched by optimize / subsampling / grey / capacities; every other page goes the way it
     goes without the switch, in the same call.  The test is one more launch and one more wait for its answer - with
     grey="auto" and no page to resize the two tests share that wait.
+    bilevel: "otsu" or "adaptive" - every GREY-VALUED page (one channel, or B == G == R everywhere; a grey photograph too: it is
+    the caller's decision about the job) is thresholded on the device, by Otsu's threshold of the page or by a locally adaptive
+    one (yomitoku_amd/ccitt.py; tests/binarize_ref.py is the definition), and gets an EncodedBilevel with `method` and
+    `threshold` set, exactly as above: full size, scale 1.0.  A colour page goes the way it goes without the switch.  The
+    launches that threshold stand where the test stands, in front of the same single wait for the pages' flags.
     Anything else is a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
     preset = jpeg_preset(image_quality)
     colour_mode = check_modes(subsampling, grey)
@@ -340,15 +347,17 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
         if not live:
             return out
         large = [long_side is not None and max(int(p.shape[0]), int(p.shape[1])) > long_side for p in devs]
-        two, test, early_grey = [False] * len(devs), None, None
+        two, test, early_grey, thresholds = [False] * len(devs), None, None, [None] * len(devs)
         if bilevel is not False:
             # on the pages as they arrived: the preset's resample would leave a two-valued page grey-valued.  Where no page can be
             # resized the grey test sees the same pixels before and after that step: it is launched here and shares the wait
-            test = ccitt.start_test(devs, scratch)
+            # "otsu" / "adaptive": the launches that threshold every page in place of the test; `two` is then "grey-valued"
+            test = ccitt.start_test(devs, scratch) if bilevel == "auto" else ccitt.start_binarize(devs, scratch, bilevel)
             if grey == "auto" and not any(large):
                 early_grey = _grey_launch(devs, scratch)
             torch.cuda.current_stream().synchronize()
             two = test.answers()
+            thresholds = test.thresholds() if bilevel != "auto" else [None] * len(devs)
         scales = [1.0] * len(live)
         todo = []
         for j, p in enumerate(devs):
@@ -418,7 +427,7 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
             one = p.dim() == 2 or as_grey[i]
             out[k] = EncodedJpeg(datas[i], int(p.shape[1]), int(p.shape[0]), one, float(scales[j]), bool(optimize), None if one else subsampling)
         for i, j in enumerate(which):
-            out[live[j]] = ccitt.bilevel_entry(devs[j], datas[len(rest) + i], live[j])
+            out[live[j]] = ccitt.bilevel_entry(devs[j], datas[len(rest) + i], live[j], bilevel, thresholds[j])
     return out
 
 
@@ -427,7 +436,8 @@ def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool =
     """One page; raises what `encode_jpeg_pages` would have put in its place.  The file's capacity is the page's raw byte
     count, and the header alone takes about 620 bytes (330 for a grey page): a colour page below roughly 15 x 15 pixels, or noise
     that does not compress, raises YmkError here and in `serve(jpeg=...)` - `encode_jpeg_pages(..., capacities=[...])` gives
-    such a page the room it needs.  bilevel="auto": an EncodedBilevel where the page is two-valued."""
+    such a page the room it needs.  bilevel="auto": an EncodedBilevel where the page is two-valued; "otsu" / "adaptive": where
+    it is grey-valued, thresholded."""
     res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize, subsampling=subsampling, grey=grey, bilevel=bilevel)[0]
     if isinstance(res, BaseException):
         raise res

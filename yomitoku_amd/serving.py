@@ -32,7 +32,8 @@ memory.
 only the waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all
 canvases of a wave (as many per page as the analyzer draws: two, OCR one) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
 as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages), its two-valued pages as Group 4 files with four
-more where the job says `jpeg_bilevel="auto"` (yomitoku_amd/ccitt.py); a job with neither runs exactly the stages above.
+more where the job says `jpeg_bilevel="auto"` (yomitoku_amd/ccitt.py) - or its grey-valued pages, thresholded, with `"otsu"` (six
+more) or `"adaptive"` (seven more); a job with neither runs exactly the stages above.
 
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
 process while holding the GIL - measured 100-180 ms with the results of a few hundred pages alive, six times in a
@@ -116,7 +117,7 @@ class _Job:
         self.jpeg_optimize = bool(jpeg_optimize)  # those files with Huffman tables of their own (encode_jpeg_pages(optimize=True))
         self.jpeg_subsampling = jpeg_subsampling  # None (4:2:0) or the chroma of those files (encode_jpeg_pages(subsampling=...))
         self.jpeg_grey = jpeg_grey  # False, or "auto": grey-valued colour pages become grey files (encode_jpeg_pages(grey="auto"))
-        self.jpeg_bilevel = jpeg_bilevel  # False, or "auto": two-valued pages get Group 4 files (encode_jpeg_pages(bilevel="auto"))
+        self.jpeg_bilevel = jpeg_bilevel  # False, "auto": two-valued pages get Group 4 files; "otsu" / "adaptive": grey-valued ones, thresholded
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -172,7 +173,7 @@ def _switch_interval(seconds):
 def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False):
     """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
     public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0", "4:2:2", "4:4:4"),
-    `jpeg_grey` (False, "auto") and `jpeg_bilevel` (False, "auto") ask for something of those files: a value that is none of
+    `jpeg_grey` (False, "auto") and `jpeg_bilevel` (False, "auto", "otsu", "adaptive") ask for something of those files: a value that is none of
     these is a ValueError, and so is any of the four without `jpeg`."""
     from .ccitt import check_bilevel
     from .jpeg import check_modes
@@ -464,7 +465,9 @@ class PagePipeline:
         jpeg_subsampling: None (4:2:0), "4:2:0", "4:2:2" or "4:4:4" - the chroma of those files; jpeg_grey: False, or "auto" - a page
         whose pixels all have B == G == R becomes a grey file.  Other values, and either without `jpeg`, are a ValueError.
         jpeg_bilevel: False, or "auto" - a two-valued page (every sample 0 or 255) gets an EncodedBilevel (yomitoku_amd/ccitt.py), a
-        lossless Group 4 file of the full-size page, in place of the EncodedJpeg; the same refusals.
+        lossless Group 4 file of the full-size page, in place of the EncodedJpeg; "otsu" or "adaptive" - every grey-valued page
+        (one channel, or B == G == R everywhere) is thresholded on the device, by one threshold per page or by a locally adaptive
+        one, and gets such a file; the same refusals.
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
