@@ -448,6 +448,59 @@ int ymk_bin_otsu_pack(const int* blob_dev, int64_t blob_words, int n_pages, int6
 int ymk_bin_adaptive_pack(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* sat_dev, int64_t sat_bytes,
                           uint32_t* packed_dev, int64_t packed_bytes, void* stream);
 
+/* ---- Page skew: the pages of a wave estimated and turned upright, opt-in (yomitoku_amd/csrc/ymk_deskew.hip;
+ * yomitoku_amd/deskew.py; deskew_pages, serve(deskew=True)).  DESIGN.md, "Page skew"; tests/deskew_ref.py is the definition, and
+ * every stage equals it bit for bit.  A page is uint8 [h][w] or [h][w][3] (B G R), 1..16383 pixels on a side.
+ * Page table (DEVICE, int32 words): n_pages records of YMK_DSK_PAGE_WORDS words, laid out as the Group 4 encoder's.
+ *     word 0-1   address of the page's pixels (low, high)     word 2-4  h, w, channels (1 | 3)     word 5, 10, 13  0
+ *     word 6-7   WORD offset (low, high) in packed_dev of the page's ink: h rows of ceil(w / 32) words, 1 = ink, the leftmost
+ *                pixel of a word in its bit 31, zero bits behind column w
+ *     word 8-9   BYTE offset (low, high) in luma_dev of a three-channel page's Y plane, h w bytes, a multiple of 4
+ *     word 11-12 address (low, high) of the destination page of ymk_dsk_rotate: same shape, 4-byte aligned, not the page itself
+ *     word 14-15 WORD offset (low, high) in sat_dev of the page's summed-area table, h w words (the binariser's)
+ * A record that does not fit the sizes the caller states is taken as absent (flag -1, k 0, scores 0, nothing written): nothing
+ * outside the stated buffers is touched.  luma_dev, sat_dev, packed_dev, scores_dev, choice_dev 8-byte aligned.  Nothing is
+ * allocated, nothing waited for.
+ * Angle table (DEVICE for the launches, HOST for ymk_dsk_check_angles): int32 [n_angles][2] = (s_k, c_k) = round(2^14 sin, cos
+ *   (k step)), k = -K .. K, n_angles = 2 K + 1 <= 401; s_max the largest |s_k|; dead: k is 0 where |k| < dead.
+ * A profile in LDS has 16128 bins.  A page is ESTIMATED when h + 2 m(w) and w + 2 m(h) are at most that, m(n) = ceil((n - 1)
+ *   s_max / 2^14): at the default table (5 degrees) every page up to 13700 x 13700.  A larger page gets scores 0, k 0 and flag
+ *   0: it is copied, not failed.
+ * ymk_dsk_check_angles: HOST: the table is odd, symmetric, 0 < c <= 2^14, s^2 + c^2 = 2^28 to rounding, its middle (0, 2^14);
+ *   *s_max_out.
+ * ymk_dsk_scratch_bytes: HOST arrays h, w, ch -> sizes5_out = the bytes of luma_dev (three-channel pages' planes, each rounded
+ *   up to 16), sat_dev, packed_dev, scores_dev (uint64 [n_pages][n_angles]) and choice_dev; fits_out[p] (may be null) = 1 where
+ *   the page is estimated.
+ * ymk_dsk_luma: Y = (29 B + 150 G + 77 R + 128) >> 8 of every three-channel page into its plane; a one-channel page is its own.
+ *   planes_dev: int32 [n_pages][16], written: the binariser's table of the planes, which ymk_bin_adaptive_pack (unchanged)
+ *   takes to write the pages' ink into packed_dev.  max_pixels: h w of the largest page.
+ * ymk_dsk_scores: scores_dev zeroed on `stream`, then one block per (page, angle, axis): the profile of the ink along the axis
+ *   in LDS - row bin (y c + x s + off) >> 14, column bin (x c - y s + off) >> 14 -, S[page][angle] += sum_b (P[b + 1] - P[b])^2.
+ * ymk_dsk_choose: one wave per page.  choice_dev: int32 [n_pages][YMK_DSK_CHOICE_WORDS]: word 0 k - the angle of the largest S,
+ *   of equal ones the smallest |k|, then the negative; 0 where |k| < dead or 8 S_k < 9 S_0 -, word 1 the flag (1 estimated, 0
+ *   too large, -1 no page), words 2-3 the largest S (uint64), 4-5 S_0, 6-7 zero.
+ * ymk_dsk_rotate: reads k from choice_dev; the destination = the page turned by angle k (k = 0: a copy): u = 2 X - (w - 1), v =
+ *   2 Y - (h - 1), SX = c u + s v + ((w - 1) << 14), SY = -s u + c v + ((h - 1) << 14), x0 = SX >> 15, fx = (SX >> 7) & 255,
+ *   bilinear with weights in 1/256, + 32768 >> 16, a tap outside the page 255.  max_bytes: h w channels of the largest page.
+ * ymk_dsk_pages: luma, ymk_bin_adaptive_pack, scores, choose and - `rotate` non-zero - rotate, in order on `stream`. */
+#define YMK_DSK_PAGE_WORDS 16
+#define YMK_DSK_CHOICE_WORDS 8
+int ymk_dsk_page_words(void);
+int ymk_dsk_check_angles(const int* table_host, int n_angles, int* s_max_out);
+int ymk_dsk_scratch_bytes(const int* h, const int* w, const int* ch, int n_pages, int n_angles, int s_max, int64_t* sizes5_out,
+                          int* fits_out);
+int ymk_dsk_luma(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, unsigned char* luma_dev, int64_t luma_bytes,
+                 int64_t packed_bytes, int64_t sat_bytes, int* planes_dev, void* stream);
+int ymk_dsk_scores(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* packed_dev, int64_t packed_bytes, int64_t sat_bytes,
+                   int64_t luma_bytes, const int* table_dev, int n_angles, int s_max, uint64_t* scores_dev, void* stream);
+int ymk_dsk_choose(const int* blob_dev, int64_t blob_words, int n_pages, int64_t packed_bytes, int64_t sat_bytes, int64_t luma_bytes,
+                   const uint64_t* scores_dev, int n_angles, int s_max, int dead, int* choice_dev, void* stream);
+int ymk_dsk_rotate(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_bytes, const int* table_dev, int n_angles,
+                   const int* choice_dev, void* stream);
+int ymk_dsk_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, unsigned char* luma_dev, int64_t luma_bytes,
+                  uint32_t* sat_dev, int64_t sat_bytes, uint32_t* packed_dev, int64_t packed_bytes, int* planes_dev, const int* table_dev,
+                  int n_angles, int s_max, int dead, uint64_t* scores_dev, int* choice_dev, int rotate, void* stream);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

@@ -102,6 +102,15 @@ SIGNATURES = {
     "ymk_bin_otsu": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
     "ymk_bin_otsu_pack": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "ymk_bin_adaptive_pack": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "ymk_dsk_page_words": (c_int, []),
+    "ymk_dsk_check_angles": (c_int, [POINTER(c_int), c_int, POINTER(c_int)]),
+    "ymk_dsk_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int)]),
+    "ymk_dsk_luma": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "ymk_dsk_scores": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_dsk_choose": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_dsk_rotate": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "ymk_dsk_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                              c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

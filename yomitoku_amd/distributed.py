@@ -411,6 +411,9 @@ class ShardedServer:
         if serve_kwargs.get("jpeg") is not None:
             raise NotImplementedError("jpeg=... is not supported by serve_sharded: the ranks' encoded pages are not gathered "
                                       "(DocumentAnalyzer.serve(..., jpeg=...) encodes on one GPU)")
+        if serve_kwargs.get("deskew", False) is not False:
+            raise NotImplementedError("deskew=... is not supported by serve_sharded: the ranks' PageSkew entries are not gathered "
+                                      "(DocumentAnalyzer.serve(..., deskew=True) corrects on one GPU)")
         serve_kwargs.setdefault("rec_lanes", self.budget["rec_lanes"])
         self._jobs += 1  # run() is called by every rank for every job: the job number is the same everywhere
         if assign == "static":

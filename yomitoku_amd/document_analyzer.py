@@ -27,6 +27,7 @@ from .schemas import (
     OCRSchema,
     ParagraphSchema,
 )
+from .deskew import check_deskew
 from .serving import StageAnalyzer, check_jpeg_preset
 from .table_structure_recognizer import TableStructureRecognizer
 from .text_detector import TextDetector
@@ -98,7 +99,7 @@ class OCR(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False):
+              jpeg_bilevel=False, deskew=False):
         """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
         arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
         yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
@@ -114,13 +115,14 @@ class OCR(StageAnalyzer):
         encoded on the device from the clean page, so that
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
-        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"): as
+        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"), `deskew`: as
         DocumentAnalyzer.serve."""
         check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
+        check_deskew(deskew)
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -565,7 +567,7 @@ class DocumentAnalyzer(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False):
+              jpeg_bilevel=False, deskew=False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -606,12 +608,18 @@ class DocumentAnalyzer(StageAnalyzer):
         histogram; "adaptive" calls a pixel black where it is 15 % below the mean of its window of max(h, w) // 16 pixels each
         way, which follows uneven light (tests/binarize_ref.py is the definition of both).  OCR and layout see the page as it
         arrived; only the file changes.  A colour page goes the way it goes without the switch; a two-valued page gives the file
-        of "auto"."""
+        of "auto".
+        `deskew`: False, True, or a dict with any of `max_angle` (5.0), `step` (0.1), `min_angle` (0.3), in degrees; anything
+        else is a ValueError before a source is read.  Every page's skew is estimated and undone on the device behind its upload
+        (yomitoku_amd/deskew.py; DESIGN.md, "Page skew"), so every network, the overlays and the page files see the corrected
+        page, and a page's entry ends with its PageSkew: (schema, PageSkew), (schema, EncodedJpeg, PageSkew) and so on.  All
+        coordinates of the schema are the corrected page's; `PageSkew.to_original` maps them back."""
         check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
+        check_deskew(deskew)
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
 
     def __call__(self, img):
         self.img = img

@@ -35,6 +35,11 @@ as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/j
 more where the job says `jpeg_bilevel="auto"` (yomitoku_amd/ccitt.py) - or its grey-valued pages, thresholded, with `"otsu"` (six
 more) or `"adaptive"` (seven more); a job with neither runs exactly the stages above.
 
+`serve(deskew=...)` adds no stage either: the skew of every page of a wave is estimated and undone on the copy stream, behind the
+wave's uploads and before the event every stage waits for (yomitoku_amd/deskew.py: launch; five launches and the binariser's three),
+so the stages above see the corrected pages; the decision reaches the host through pinned words that are read when the wave's
+entries are written.
+
 Garbage collection: a full (generation-2) pass of CPython's cyclic collector walks every live container object of the
 process while holding the GIL - measured 100-180 ms with the results of a few hundred pages alive, six times in a
 4 s job - and every stage thread that needs the interpreter to issue its next launch stalls behind it (the GPU idles;
@@ -82,13 +87,14 @@ class Wave:
     """The pages that share device batches, and what the stages have produced for them so far."""
 
     __slots__ = ("seq", "ids", "imgs", "pages", "ring", "uploaded", "maps", "sizes", "dets", "rec_plan", "recs", "lay_raw",
-                 "lay_parsed", "tab_raw", "lays", "error", "failed_stage", "layout_done", "joined", "retry", "job", "results", "dags")
+                 "lay_parsed", "tab_raw", "lays", "error", "failed_stage", "layout_done", "joined", "retry", "job", "results", "dags", "skew")
 
     def __init__(self, seq=0, ids=(), imgs=(), pages=(), ring=0, uploaded=None, retry=False, job=None):
         self.seq, self.ids, self.imgs, self.pages, self.ring, self.uploaded = seq, list(ids), list(imgs), list(pages), ring, uploaded
         self.job = job  # the serve() call this wave belongs to: a late wave of an aborted job must not write into the next one
         self.results = None  # per page, what `finish` made of it (schema or exception): only kept for the render stage
         self.dags = None  # TableSemanticParser, overlays jobs: per page the grid graphs `finish` parsed, for the render stage
+        self.skew = None  # serve(deskew=...): the wave's launched skew step (yomitoku_amd/deskew.py); `pages` are the corrected ones
         self.sizes = [tuple(int(v) for v in p.shape[:2]) for p in self.pages]
         self.maps = self.dets = self.rec_plan = self.recs = self.lay_raw = self.lay_parsed = self.tab_raw = self.lays = None
         self.error: Optional[BaseException] = None
@@ -109,8 +115,9 @@ class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
     def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False,
-                 jpeg_bilevel=False):
+                 jpeg_bilevel=False, deskew=None):
         self.results = {}
+        self.deskew = deskew  # None, or the parameters of check_deskew: the pages are turned upright behind their upload
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, the analyzer's pictures...): the waves visit the render stage
         self.jpeg = jpeg  # None or a preset name: the entries end with the page's EncodedJpeg, made in the render stage too
@@ -273,6 +280,8 @@ class PagePipeline:
         self._serve_lock = threading.Lock()
         self._render_q: "queue.Queue" = queue.Queue()
         self._render_thread = None  # started by the first job that asks for overlays
+        self._deskew_scratch = {}  # serve(deskew=...): the step's device buffers, made by the first such job
+        self._deskew_pinned = {}  # wave slot -> the pinned buffer its choice words come back through
         # (stage, function, launches on the GPU?, next stages), built from CHAINS for the chains the analyzer declares: every
         # chain is entered at its first stage (_launch) and all of them join in `finish`.  A stage of a chain that is not
         # declared has no thread, no stream and no queue, and its method is never looked up
@@ -354,6 +363,7 @@ class PagePipeline:
             t_start = time.perf_counter()
             job, results = wave.job, wave.results
             try:
+                skews = self._skews(wave)
                 products = []  # per product of the job, per page: a tuple of entry members, or the exception
                 for wanted, fn in ((job.overlays, "_stage_render"), (job.jpeg, "_stage_jpeg")):
                     if not wanted:
@@ -371,7 +381,7 @@ class PagePipeline:
                         logger.error("page %d failed in the render stage: %s: %s", idx, type(failed).__name__, failed)
                         job.results[idx] = failed
                     else:
-                        job.results[idx] = (results[k],) + tuple(m for made in products for m in made[k])
+                        job.results[idx] = (results[k],) + tuple(m for made in products for m in made[k]) + (() if skews is None else (skews[k],))
                 if self.trace is not None:
                     self.trace.append(("render", wave.seq, len(wave), t_start, time.perf_counter()))
             finally:
@@ -385,7 +395,7 @@ class PagePipeline:
 
     def _release(self, wave):
         job = wave.job
-        wave.pages = wave.maps = wave.rec_plan = None  # the device pages, the pinned map views and the crop tensors go back
+        wave.pages = wave.maps = wave.rec_plan = wave.skew = None  # the device pages, the pinned map views and the crop tensors go back
         self._rings.put(wave.ring)
         with job.cond:
             job.outstanding -= 1
@@ -415,9 +425,16 @@ class PagePipeline:
                 wave.results = done
                 self._render_q.put(wave)
                 return
-            for idx, entry in zip(wave.ids, done):
-                job.results[idx] = entry
+            skews = self._skews(wave)
+            for k, (idx, entry) in enumerate(zip(wave.ids, done)):
+                job.results[idx] = entry if skews is None or isinstance(entry, BaseException) else (entry, skews[k])
         self._release(wave)
+
+    @staticmethod
+    def _skews(wave):
+        """Per page of a deskew job's wave its PageSkew, else None.  The choice words were copied to pinned memory on the copy
+        stream before the wave's `uploaded` event, which every stage stream has waited for and been waited for since: no wait."""
+        return None if wave.skew is None else wave.skew.skews()
 
     # ------------------------------------------------------------------ caller side
     def _launch(self, job, ids, imgs, retry=False, ring=None, waited=0.0):
@@ -430,10 +447,20 @@ class PagePipeline:
         try:
             if self._gpu:
                 pages = [self.stager.upload(img, wait=False) for img in imgs]
+                skew = None
+                if job.deskew is not None:
+                    # behind the uploads on the copy stream, before the event every stage waits for: the chains see the corrected
+                    # pages and nothing downstream changes.  Device scratch: one set (the step is serialised on this stream); the
+                    # pinned choice words: one per wave slot, read when the wave's entries are written
+                    from .deskew import launch as launch_deskew
+
+                    with torch.cuda.device(self.device), torch.cuda.stream(self.stager.stream):
+                        skew = launch_deskew(pages, job.deskew, self._deskew_scratch, pin_scratch=self._deskew_pinned.setdefault(ring, {}))
+                    pages, skew.corrected = skew.corrected, None  # the wave holds them; the uploaded originals go back now
                 uploaded = torch.cuda.Event()
                 uploaded.record(self.stager.stream)
             else:
-                pages, uploaded = list(imgs), None
+                pages, uploaded, skew = list(imgs), None, None
         except BaseException:
             self._rings.put(ring)
             raise
@@ -442,6 +469,7 @@ class PagePipeline:
             self.trace.append(("wait_slot", self._seq, len(ids), t_start, t_ring))
             self.trace.append(("stage_h2d", self._seq, len(ids), t_ring, time.perf_counter()))
         wave = Wave(self._seq, ids, imgs, pages, ring, uploaded, retry, job)
+        wave.skew = skew
         with job.cond:
             job.outstanding += 1
             job.waves += 1
@@ -449,7 +477,7 @@ class PagePipeline:
             self._q[name].put(wave)
 
     def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
-              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False) -> List:
+              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -468,14 +496,23 @@ class PagePipeline:
         lossless Group 4 file of the full-size page, in place of the EncodedJpeg; "otsu" or "adaptive" - every grey-valued page
         (one channel, or B == G == R everywhere) is thresholded on the device, by one threshold per page or by a locally adaptive
         one, and gets such a file; the same refusals.
+        deskew: False, True, or a dict with any of max_angle, step, min_angle in degrees (yomitoku_amd/deskew.py: check_deskew;
+        anything else is a ValueError before a source is read): every page's skew is estimated and undone on the device behind
+        its upload, so words, boxes, overlays and page files are those of the corrected page, and a page's entry ends with its
+        PageSkew - (schema, PageSkew), (schema, ..., EncodedJpeg, PageSkew); a failed page's entry stays the bare exception.  A
+        page that is re-run alone is estimated again from its host original.  Needs a HIP device.
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
+        from .deskew import check_deskew
 
         check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)
+        deskew = check_deskew(deskew)
+        if deskew is not None and not self._gpu:
+            raise ValueError("deskew needs a HIP device: this pipeline has none (there is no host fallback)")
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
             job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
+                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
             if job.overlays or job.jpeg:
                 self._start_render()
             n = 0
@@ -791,7 +828,7 @@ class StageAnalyzer:
 
     # ---- the pipeline of this analyzer
     def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False,
-               jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False):
+               jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -800,7 +837,7 @@ class StageAnalyzer:
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
         return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel)
+                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -

@@ -478,7 +478,7 @@ class TableSemanticParser(StageAnalyzer):
         return self._drawings(results, wave.dags[k], RunOverlay)
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
-              overlays: bool = False, template=None, grid_only=False, kv_only=False):
+              overlays: bool = False, template=None, grid_only=False, kv_only=False, deskew=False):
         """The multi-page entry point, as `DocumentAnalyzer.serve`: host pages (uint8 H x W x 3 BGR arrays) and / or image file
         paths in, one entry per page out, in page order, through the stage pipeline of yomitoku_amd/serving.py - `wave` pages
         per device batch, up to `in_flight` waves between upload and the semantic stage, every host stage (table boxes, the
@@ -489,8 +489,12 @@ class TableSemanticParser(StageAnalyzer):
         a page's entry is (schema, layout picture, OCR picture), the two pictures of `__call__(img, overlays=True)` as uint8
         H x W x 3 arrays the caller owns, drawn by the pipeline's render stage; a failed page's entry stays the exception.
         `template`, `grid_only`, `kv_only`, `overlays` are properties of the JOB: they travel with it and the next job starts
-        without them.  `defer_full_gc`, `rec_lanes`: see `DocumentAnalyzer.serve`."""
+        without them.  `defer_full_gc`, `rec_lanes`, `deskew` (the entry ends with the page's PageSkew): see
+        `DocumentAnalyzer.serve`."""
+        from .deskew import check_deskew
+
+        check_deskew(deskew)  # before the pipeline is built or a source read
         if self.visualize:
             raise NotImplementedError(_NO_VIS)
         options = {"template": template, "grid_only": bool(grid_only), "kv_only": bool(kv_only)}
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options, deskew=deskew)
