@@ -501,6 +501,54 @@ int ymk_dsk_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_
                   uint32_t* sat_dev, int64_t sat_bytes, uint32_t* packed_dev, int64_t packed_bytes, int* planes_dev, const int* table_dev,
                   int n_angles, int s_max, int dead, uint64_t* scores_dev, int* choice_dev, int rotate, void* stream);
 
+/* ---- Layered pages: the pages of a wave separated into an ink mask and two low-resolution pictures, opt-in
+ * (yomitoku_amd/csrc/ymk_mrc.hip; yomitoku_amd/mrc.py; separate_pages, encode_jpeg_pages(mrc=...), serve(jpeg=..., jpeg_mrc=...)).
+ * DESIGN.md, "Layered pages"; tests/mrc_ref.py is the definition, and every stage equals it bit for bit.  A page is uint8 [h][w]
+ * or [h][w][3] (B G R), 1..16383 pixels on a side.  bg_cell, fg_cell: the cells of the two layers, each 1, 2, 4, 8 or 16, one pair
+ * per call.  A layer with cell d has a level 0 of H0 x W0 = ceil(h / d) x ceil(w / d) cells; its PYRAMID is the levels 0 .. L one
+ * behind the other, level l + 1 of ceil(H_l / 2) x ceil(W_l / 2) cells, the last 1 x 1; a cell is one uint32: byte k the value of
+ * channel k (a one-channel page: byte 0), byte 3 whether the cell is known.  Its IMAGE is uint8 [H0][W0][channels].
+ * Page table (DEVICE, int32 words): n_pages records of YMK_MRC_PAGE_WORDS words, laid out as the page-skew table, so that
+ * ymk_dsk_luma and ymk_bin_adaptive_pack take it unchanged.
+ *     word 0-1   address of the page's pixels (low, high)     word 2-4  h, w, channels (1 | 3)     word 10, 13  0
+ *     word 5     WORD offset in pyr_dev of the page's pyramids: the foreground's, then the background's
+ *     word 6-7   WORD offset (low, high) in packed_dev of the page's ink: h rows of ceil(w / 32) words, 1 = ink, the leftmost
+ *                pixel of a word in its bit 31, zero bits behind column w
+ *     word 8-9   BYTE offset (low, high) in luma_dev of a three-channel page's Y plane, h w bytes, a multiple of 4
+ *     word 11-12 BYTE offset (low, high) in layers_dev of the foreground's image, a multiple of 16; the background's follows at
+ *                the next multiple of 16 behind it
+ *     word 14-15 WORD offset (low, high) in sat_dev of the page's summed-area table, h w words (the binariser's)
+ * A record that does not fit the sizes the caller states is taken as absent (flag -1, nothing written): nothing outside the stated
+ * buffers is touched.  luma_dev, sat_dev, packed_dev, pyr_dev 8-byte aligned, layers_dev 16.  Nothing is allocated, nothing
+ * waited for.  max_h, max_w: the largest of the table.
+ * ymk_mrc_scratch_bytes: HOST arrays h, w, ch -> sizes6_out = the bytes of luma_dev, sat_dev, packed_dev, pyr_dev (fewer than 2^31
+ *   words), layers_dev and flags_dev; places_out (may be null): int64 [n_pages][3] = word 5, words 11-12 and the byte offset of
+ *   the background's image for pages laid out one behind the other.
+ * ymk_mrc_cells: level 0 of both pyramids of every page in one pass over its pixels and its packed ink: the foreground selects
+ *   the ink M, the background the pixels outside D = M dilated by the 3 x 3 square, clipped at the page's edge; a cell with N > 0
+ *   selected pixels of sum S is known, value (2 S + N) / (2 N) per channel.
+ * ymk_mrc_pull: one launch per level: a cell is known iff one of its up to four children is, value (2 sum + k) / (2 k) over its k
+ *   known children.
+ * ymk_mrc_push: flags_dev int32 [n_pages]: 1 = the top cell of both pyramids is known, 0 = not (no ink, or no paper: the images
+ *   are not written), -1 = no page; then the images of the pages with flag 1: a level-0 cell's value, or where it is not known
+ *   that of its nearest known ancestor.
+ * ymk_mrc_pages: - planes_dev (int32 [n_pages][16], written) not null: ymk_dsk_luma and ymk_bin_adaptive_pack, the ink of the
+ *   pages themselves; null: packed_dev holds the caller's ink - then cells, pull and push, in order on `stream`. */
+#define YMK_MRC_PAGE_WORDS 16
+int ymk_mrc_page_words(void);
+int ymk_mrc_scratch_bytes(const int* h, const int* w, const int* ch, int n_pages, int bg_cell, int fg_cell, int64_t* sizes6_out,
+                          int64_t* places_out);
+int ymk_mrc_cells(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell,
+                  const uint32_t* packed_dev, int64_t packed_bytes, uint32_t* pyr_dev, int64_t pyr_bytes, int64_t layers_bytes, void* stream);
+int ymk_mrc_pull(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, int64_t packed_bytes,
+                 uint32_t* pyr_dev, int64_t pyr_bytes, int64_t layers_bytes, void* stream);
+int ymk_mrc_push(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, int64_t packed_bytes,
+                 const uint32_t* pyr_dev, int64_t pyr_bytes, unsigned char* layers_dev, int64_t layers_bytes, int* flags_dev, void* stream);
+int ymk_mrc_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell,
+                  unsigned char* luma_dev, int64_t luma_bytes, uint32_t* sat_dev, int64_t sat_bytes, uint32_t* packed_dev, int64_t packed_bytes,
+                  int* planes_dev, uint32_t* pyr_dev, int64_t pyr_bytes, unsigned char* layers_dev, int64_t layers_bytes, int* flags_dev,
+                  void* stream);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

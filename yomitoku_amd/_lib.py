@@ -111,6 +111,14 @@ SIGNATURES = {
     "ymk_dsk_rotate": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "ymk_dsk_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                               c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "ymk_mrc_page_words": (c_int, []),
+    "ymk_mrc_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "ymk_mrc_cells": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "ymk_mrc_pull": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "ymk_mrc_push": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                             c_void_p]),
+    "ymk_mrc_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                              c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

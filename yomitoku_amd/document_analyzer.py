@@ -99,7 +99,7 @@ class OCR(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False):
         """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
         arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
         yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
@@ -115,14 +115,14 @@ class OCR(StageAnalyzer):
         encoded on the device from the clean page, so that
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
-        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"), `deskew`: as
-        DocumentAnalyzer.serve."""
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
+        without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"), `jpeg_mrc`
+        (False, True or the cells), `deskew`: as DocumentAnalyzer.serve."""
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
         check_deskew(deskew)
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew, jpeg_mrc=jpeg_mrc)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -567,7 +567,7 @@ class DocumentAnalyzer(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -613,13 +613,21 @@ class DocumentAnalyzer(StageAnalyzer):
         else is a ValueError before a source is read.  Every page's skew is estimated and undone on the device behind its upload
         (yomitoku_amd/deskew.py; DESIGN.md, "Page skew"), so every network, the overlays and the page files see the corrected
         page, and a page's entry ends with its PageSkew: (schema, PageSkew), (schema, EncodedJpeg, PageSkew) and so on.  All
-        coordinates of the schema are the corrected page's; `PageSkew.to_original` maps them back."""
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)  # before the pipeline is built or a source read
+        coordinates of the schema are the corrected page's; `PageSkew.to_original` maps them back.
+        `jpeg_mrc`: False, True, or a dict with any of `bg_cell` (2) and `fg_cell` (8), each one of 1, 2, 4, 8, 16; anything else, and
+        the switch without `jpeg`, is a ValueError before a source is read.  Of the pages `jpeg_bilevel` leaves - colour or grey, a
+        form with a stamp, tinted paper - every page with ink and with paper is written as a layered page (yomitoku_amd/mrc.py;
+        DESIGN.md, "Layered pages"): its entry ends with an EncodedMrc - the ink mask as a lossless Group 4 file of the full-size
+        page, the paper as a JPEG of one pixel per `bg_cell` x `bg_cell` pixels, the ink's colour as one per `fg_cell` x `fg_cell` -
+        which `searchable_pdf_bytes` embeds as three images, the foreground painted through the mask.  Such a page is never
+        resized (`scale` 1.0); `jpeg_optimize` and `jpeg_subsampling` apply to its two layer files, `jpeg_grey` does not.  A blank
+        page, or one that is all ink, keeps its plain file.  OCR and layout see the page as it arrived; only the file changes."""
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
         check_deskew(deskew)
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
         return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
+                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew, jpeg_mrc=jpeg_mrc)
 
     def __call__(self, img):
         self.img = img

@@ -28,6 +28,10 @@ the modes is tests/jpeg_modes_ref.py; the defaults write the bytes they always w
 sample 0 or 255, B == G == R - a CCITT Group 4 file, an `EncodedBilevel` of yomitoku_amd/ccitt.py, in place of the EncodedJpeg.
 `bilevel="otsu"` / `"adaptive"` thresholds every grey-valued page on the device instead - a scan with paper noise, soft edges
 or a gradient of light, but a grey photograph too - and codes the result the same way.
+
+`mrc=True` (serve: `jpeg_mrc=True`) writes every remaining page that has ink and paper as a layered page, an `EncodedMrc` of
+yomitoku_amd/mrc.py: its ink mask as a Group 4 file and two low-resolution pictures - the paper, the ink's colour - as JPEG files
+from this encoder, which takes the layers as pages like any other.
 """
 
 from __future__ import annotations
@@ -299,7 +303,7 @@ def _gather_files(parts: Sequence, scratch: dict, key: str = "pin_bytes") -> lis
 
 def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
                       capacities: Optional[Sequence[int]] = None, optimize: bool = False, subsampling: str = "4:2:0",
-                      grey=False, bilevel=False) -> list:
+                      grey=False, bilevel=False, mrc=False) -> list:
     """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
     file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
     stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
@@ -319,9 +323,23 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     one (yomitoku_amd/ccitt.py; tests/binarize_ref.py is the definition), and gets an EncodedBilevel with `method` and
     `threshold` set, exactly as above: full size, scale 1.0.  A colour page goes the way it goes without the switch.  The
     launches that threshold stand where the test stands, in front of the same single wait for the pages' flags.
+    mrc: False, True or {"bg_cell": 2, "fg_cell": 8} (yomitoku_amd/mrc.py: check_mrc) - of the pages `bilevel` leaves, one channel or
+    three, every page with ink and with paper outside it gets an EncodedMrc in place of the EncodedJpeg: its ink mask as a Group 4
+    file and two low-resolution layers as JPEG files at the preset's quality - full size whatever the preset (scale 1.0);
+    `optimize` and `subsampling` apply to the two layer files as they would to a page, `grey` and `capacities` do not (a layer's
+    capacity is its raw bytes plus 2048).  A page without ink or without paper goes the way it goes without the switch.  The
+    separation is launched behind `bilevel`'s wait and has one wait of its own, for its flags: with both switches on that is one
+    further wait; the layers then join the JPEG launches and the masks the Group 4 launches, and the files come back in the same
+    two copies.
     Anything else is a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
     preset = jpeg_preset(image_quality)
     colour_mode = check_modes(subsampling, grey)
+    mrc_params = None
+    if mrc is not False:
+        from . import ccitt
+        from . import mrc as layered  # imports this module
+
+        mrc_params = layered.check_mrc(mrc)
     if bilevel is not False:
         from . import ccitt  # imports this module
 
@@ -358,24 +376,42 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
             torch.cuda.current_stream().synchronize()
             two = test.answers()
             thresholds = test.thresholds() if bilevel != "auto" else [None] * len(devs)
+        sep, sep_of = None, {}  # the separation of the pages `bilevel` left, and page -> its index there where its flag is 1
+        if mrc_params is not None:
+            cand = [j for j in range(len(devs)) if not two[j]]
+            if cand:
+                # with `bilevel` the ink goes where the test packed these pages' rows, which nothing reads any more: one buffer
+                # of packed rows for the one set of Group 4 launches
+                shared = None if test is None else (test.packed, [test.packed_at[j] for j in cand], test.packed_bytes)
+                sep = layered.launch([devs[j] for j in cand], mrc_params, scratch, packed=shared)
+                torch.cuda.current_stream().synchronize()
+                sep_of = {j: i for i, (j, flag) in enumerate(zip(cand, sep.flags())) if flag == 1}
         scales = [1.0] * len(live)
         todo = []
         for j, p in enumerate(devs):
             h, w = int(p.shape[0]), int(p.shape[1])
-            if large[j] and not two[j]:
+            if large[j] and not two[j] and j not in sep_of:
                 scales[j] = long_side / max(w, h)
                 todo.append((j, (max(int(h * scales[j]), 1), max(int(w * scales[j]), 1))))
         if todo:
             for (j, _), small in zip(todo, resize_pages([devs[j] for j, _ in todo], [s for _, s in todo])):
                 devs[j] = small
-        rest = [j for j in range(len(devs)) if not two[j]]  # the pages that get a JPEG file: all of them without `bilevel`
+        rest = [j for j in range(len(devs)) if not two[j] and j not in sep_of]  # the pages that get a JPEG file: all of them without `bilevel`
         jdevs = [devs[j] for j in rest]
         caps = None if capacities is None else [int(capacities[live[j]]) for j in rest]
+        n_plain = len(jdevs)
         if early_grey is not None:
             all_grey = _grey_answers(len(devs), early_grey)
             as_grey = [all_grey[j] for j in rest]
         else:
             as_grey = grey_pages(jdevs, scratch) if grey == "auto" and jdevs else [False] * len(jdevs)
+        if sep_of:  # behind the plain pages the two layers of every layered page, foreground first: pages like any other
+            if caps is None:
+                caps = [p.numel() for p in jdevs]
+            for j, i in sep_of.items():
+                jdevs += [sep.foreground(i), sep.background(i)]
+            caps += [p.numel() + layered.LAYER_ROOM for p in jdevs[n_plain:]]
+            as_grey = list(as_grey) + [False] * (len(jdevs) - n_plain)
         sizes = []
         if jdevs:
             modes = [0 if p.dim() == 2 else (MODE_GREY if g else colour_mode) for p, g in zip(jdevs, as_grey)]
@@ -406,8 +442,15 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
             pin_len = _grown(scratch, "pin_lengths", len(jdevs), torch.int32, pinned=True)
             pin_len[: len(jdevs)].copy_(lengths[: len(jdevs)], non_blocking=True)
         which = [j for j in range(len(devs)) if two[j]]
+        if sep_of:  # the masks behind the two-valued pages; `coded` is what holds the packed rows of both
+            if test is None:
+                coded, which = sep, list(sep_of.values())
+            else:
+                coded, which = test, which + list(sep_of)
+        else:
+            coded = test
         if which:  # the Group 4 files: launched behind the JPEG stages, their lengths and bytes in the same two copies' waits
-            g4_files, g4_offsets, g4_lengths = ccitt.launch_encode(test, which, scratch)
+            g4_files, g4_offsets, g4_lengths = ccitt.launch_encode(coded, which, scratch)
             g4_pin = _grown(scratch, "g4_pin_lengths", len(which), torch.int32, pinned=True)
             g4_pin[: len(which)].copy_(g4_lengths[: len(which)], non_blocking=True)
         torch.cuda.current_stream().synchronize()
@@ -418,27 +461,36 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
         if which:
             parts += [(g4_files, g4_offsets[i], n) for i, n in enumerate(g4_pin[: len(which)].tolist())]
         datas = _gather_files(parts, scratch)
-        for i, j in enumerate(rest):
-            p, k = devs[j], live[j]
+        def jpeg_entry(i, p, k, scale, what="the JPEG file"):
             if sizes[i] < 0:
                 cap = caps[i] if caps is not None else p.numel()
-                out[k] = _lib.YmkError(f"page {k}: the JPEG file does not fit its capacity of {cap} bytes")
-                continue
+                return _lib.YmkError(f"page {k}: {what} does not fit its capacity of {cap} bytes")
             one = p.dim() == 2 or as_grey[i]
-            out[k] = EncodedJpeg(datas[i], int(p.shape[1]), int(p.shape[0]), one, float(scales[j]), bool(optimize), None if one else subsampling)
-        for i, j in enumerate(which):
-            out[live[j]] = ccitt.bilevel_entry(devs[j], datas[len(rest) + i], live[j], bilevel, thresholds[j])
+            return EncodedJpeg(datas[i], int(p.shape[1]), int(p.shape[0]), one, float(scale), bool(optimize), None if one else subsampling)
+
+        for i, j in enumerate(rest):
+            out[live[j]] = jpeg_entry(i, devs[j], live[j], scales[j])
+        n_two = len(which) - len(sep_of)
+        for i, j in enumerate(which[:n_two]):
+            out[live[j]] = ccitt.bilevel_entry(devs[j], datas[len(jdevs) + i], live[j], bilevel, thresholds[j])
+        for i, j in enumerate(sep_of):
+            k, at = live[j], n_plain + 2 * i
+            parts3 = [ccitt.bilevel_entry(devs[j], datas[len(jdevs) + n_two + i], k, "adaptive"),
+                      jpeg_entry(at, jdevs[at], k, 1.0, "the foreground's file"), jpeg_entry(at + 1, jdevs[at + 1], k, 1.0, "the background's file")]
+            failed = [e for e in parts3 if isinstance(e, BaseException)]
+            out[k] = failed[0] if failed else layered.EncodedMrc(parts3[0], parts3[2], parts3[1], int(devs[j].shape[1]), int(devs[j].shape[0]), 1.0,
+                                                                mrc_params["bg_cell"], mrc_params["fg_cell"])
     return out
 
 
 def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False, subsampling: str = "4:2:0",
-                grey=False, bilevel=False):
+                grey=False, bilevel=False, mrc=False):
     """One page; raises what `encode_jpeg_pages` would have put in its place.  The file's capacity is the page's raw byte
     count, and the header alone takes about 620 bytes (330 for a grey page): a colour page below roughly 15 x 15 pixels, or noise
     that does not compress, raises YmkError here and in `serve(jpeg=...)` - `encode_jpeg_pages(..., capacities=[...])` gives
     such a page the room it needs.  bilevel="auto": an EncodedBilevel where the page is two-valued; "otsu" / "adaptive": where
-    it is grey-valued, thresholded."""
-    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize, subsampling=subsampling, grey=grey, bilevel=bilevel)[0]
+    it is grey-valued, thresholded.  mrc: an EncodedMrc where the page has ink and paper (yomitoku_amd/mrc.py)."""
+    res = encode_jpeg_pages([page], image_quality, stream, optimize=optimize, subsampling=subsampling, grey=grey, bilevel=bilevel, mrc=mrc)[0]
     if isinstance(res, BaseException):
         raise res
     return res

@@ -33,7 +33,9 @@ only the waves of such a job visit it - after `finish` has aggregated them, befo
 canvases of a wave (as many per page as the analyzer draws: two, OCR one) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
 as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages), its two-valued pages as Group 4 files with four
 more where the job says `jpeg_bilevel="auto"` (yomitoku_amd/ccitt.py) - or its grey-valued pages, thresholded, with `"otsu"` (six
-more) or `"adaptive"` (seven more); a job with neither runs exactly the stages above.
+more) or `"adaptive"` (seven more); `jpeg_mrc` separates the pages that leaves into an ink mask and two layers in front of those
+launches (yomitoku_amd/mrc.py: the page-skew step's luminance and ink, cells, a pull per level, flags, push) and hands the layers
+to the JPEG launches and the masks to the Group 4 launches; a job with neither runs exactly the stages above.
 
 `serve(deskew=...)` adds no stage either: the skew of every page of a wave is estimated and undone on the copy stream, behind the
 wave's uploads and before the event every stage waits for (yomitoku_amd/deskew.py: launch; five launches and the binariser's three),
@@ -115,7 +117,7 @@ class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
     def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False,
-                 jpeg_bilevel=False, deskew=None):
+                 jpeg_bilevel=False, deskew=None, jpeg_mrc=False):
         self.results = {}
         self.deskew = deskew  # None, or the parameters of check_deskew: the pages are turned upright behind their upload
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
@@ -125,6 +127,7 @@ class _Job:
         self.jpeg_subsampling = jpeg_subsampling  # None (4:2:0) or the chroma of those files (encode_jpeg_pages(subsampling=...))
         self.jpeg_grey = jpeg_grey  # False, or "auto": grey-valued colour pages become grey files (encode_jpeg_pages(grey="auto"))
         self.jpeg_bilevel = jpeg_bilevel  # False, "auto": two-valued pages get Group 4 files; "otsu" / "adaptive": grey-valued ones, thresholded
+        self.jpeg_mrc = jpeg_mrc  # False, True or the cells: pages with ink and paper get an EncodedMrc (encode_jpeg_pages(mrc=...))
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -177,13 +180,15 @@ def _switch_interval(seconds):
                 _switch_saved = None
 
 
-def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False):
+def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, jpeg_mrc=False):
     """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
     public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0", "4:2:2", "4:4:4"),
     `jpeg_grey` (False, "auto") and `jpeg_bilevel` (False, "auto", "otsu", "adaptive") ask for something of those files: a value that is none of
-    these is a ValueError, and so is any of the four without `jpeg`."""
+    these is a ValueError, and so is any of the four without `jpeg`.  `jpeg_mrc` (False, True or a dict of cells: yomitoku_amd/mrc.py,
+    check_mrc) likewise."""
     from .ccitt import check_bilevel
     from .jpeg import check_modes
+    from .mrc import check_mrc
     from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
 
     if jpeg is not None and (not isinstance(jpeg, str) or jpeg not in IMAGE_QUALITY_PRESETS):
@@ -197,6 +202,8 @@ def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_gre
         raise ValueError(f"jpeg_grey={jpeg_grey!r} needs jpeg=...: there is no JPEG file to write that way")
     if check_bilevel(jpeg_bilevel) and jpeg is None:
         raise ValueError(f"jpeg_bilevel={jpeg_bilevel!r} needs jpeg=...: there are no page files to write that way")
+    if check_mrc(jpeg_mrc) is not None and jpeg is None:
+        raise ValueError(f"jpeg_mrc={jpeg_mrc!r} needs jpeg=...: there are no page files to write that way")
 
 
 def _run_stage(stream, wave, fn, *args):
@@ -477,7 +484,8 @@ class PagePipeline:
             self._q[name].put(wave)
 
     def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
-              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False) -> List:
+              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False,
+              jpeg_mrc=False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -496,6 +504,9 @@ class PagePipeline:
         lossless Group 4 file of the full-size page, in place of the EncodedJpeg; "otsu" or "adaptive" - every grey-valued page
         (one channel, or B == G == R everywhere) is thresholded on the device, by one threshold per page or by a locally adaptive
         one, and gets such a file; the same refusals.
+        jpeg_mrc: False, True, or a dict with any of bg_cell, fg_cell (each 1, 2, 4, 8 or 16; yomitoku_amd/mrc.py: check_mrc) - of the
+        pages `jpeg_bilevel` leaves, every page with ink and with paper gets an EncodedMrc - its ink mask as a Group 4 file and two
+        low-resolution JPEG layers - in place of the EncodedJpeg; the same refusals.
         deskew: False, True, or a dict with any of max_angle, step, min_angle in degrees (yomitoku_amd/deskew.py: check_deskew;
         anything else is a ValueError before a source is read): every page's skew is estimated and undone on the device behind
         its upload, so words, boxes, overlays and page files are those of the corrected page, and a page's entry ends with its
@@ -506,13 +517,14 @@ class PagePipeline:
         from .data.functions import load_image
         from .deskew import check_deskew
 
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel)
+        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)
         deskew = check_deskew(deskew)
         if deskew is not None and not self._gpu:
             raise ValueError("deskew needs a HIP device: this pipeline has none (there is no host fallback)")
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
             job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
+                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew,
+                                   jpeg_mrc=jpeg_mrc)
             if job.overlays or job.jpeg:
                 self._start_render()
             n = 0
@@ -776,7 +788,8 @@ class StageAnalyzer:
 
     def _stage_jpeg(self, wave, results, scratch=None):
         """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`, tables `wave.job.jpeg_optimize`,
-        chroma `wave.job.jpeg_subsampling`, grey files `wave.job.jpeg_grey`), an exception for a page
+        chroma `wave.job.jpeg_subsampling`, grey files `wave.job.jpeg_grey`; an EncodedBilevel or an EncodedMrc where
+        `wave.job.jpeg_bilevel` / `wave.job.jpeg_mrc` give the page one), an exception for a page
         that could not be encoded, None for a page that had already failed.  All pages of the wave are encoded together on
         the calling thread's stream (yomitoku_amd/jpeg.py: encode_jpeg_pages) from `wave.pages` - the clean pages: the
         overlays are drawn on copies - with `scratch`, by default the wave slot's."""
@@ -790,7 +803,8 @@ class StageAnalyzer:
             files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch,
                                       optimize=getattr(wave.job, "jpeg_optimize", False),
                                       subsampling=getattr(wave.job, "jpeg_subsampling", None) or "4:2:0",
-                                      grey=getattr(wave.job, "jpeg_grey", False), bilevel=getattr(wave.job, "jpeg_bilevel", False))
+                                      grey=getattr(wave.job, "jpeg_grey", False), bilevel=getattr(wave.job, "jpeg_bilevel", False),
+                                      mrc=getattr(wave.job, "jpeg_mrc", False))
             for k, made in zip(live, files):
                 out[k] = made if isinstance(made, BaseException) else (made,)
         return out
@@ -828,7 +842,7 @@ class StageAnalyzer:
 
     # ---- the pipeline of this analyzer
     def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False,
-               jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False):
+               jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False, jpeg_mrc=False):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -837,7 +851,7 @@ class StageAnalyzer:
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
         return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew)
+                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew, jpeg_mrc=jpeg_mrc)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -

@@ -290,8 +290,12 @@ def _font_objects(pdf: _PdfFile, font: int, supplementary: dict):
                    f"/DescendantFonts [{cid} 0 R] /ToUnicode {to_unicode} 0 R >>").encode("ascii"))
 
 
-def _content_stream(width: int, height: int, ops: Sequence, supplementary: dict) -> bytes:
+def _content_stream(width: int, height: int, ops: Sequence, supplementary: dict, background=None) -> bytes:
+    """background: None, or (W0 d, H0 d) of a layered page - the box of its background, anchored at the page's top-left (the MediaBox
+    clips what hangs over at the right and the bottom); /Im0 is then the foreground, painted through its mask over the page."""
     lines = [f"q {width} 0 0 {height} 0 0 cm /Im0 Do Q", "BT", "3 Tr"]
+    if background is not None:
+        lines.insert(0, f"q {background[0]} 0 0 {background[1]} 0 {height - background[1]} cm /Im1 Do Q")
     for op in ops:
         if op[0] == "font":
             lines.append(f"/F1 {_num(op[1])} Tf")
@@ -324,6 +328,20 @@ def _is_bilevel(image) -> bool:
         hasattr(image, a) for a in ("width", "height", "scale"))
 
 
+def _is_mrc(image) -> bool:
+    """An entry that is a layered page: yomitoku_amd.mrc.EncodedMrc, recognised by `mrc` and its fields - `mask` an
+    EncodedBilevel, `background` and `foreground` EncodedJpegs, `width`, `height`, `scale`, `bg_cell`, `fg_cell` -, again without
+    torch or the HIP library."""
+    return (getattr(image, "mrc", False) is True and _is_bilevel(getattr(image, "mask", None)) and _is_encoded(getattr(image, "background", None))
+            and _is_encoded(getattr(image, "foreground", None)) and all(hasattr(image, a) for a in ("width", "height", "scale", "bg_cell", "fg_cell")))
+
+
+def _jpeg_xobject(pdf, image, more: str = "") -> int:
+    return pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {int(image.width)} /Height {int(image.height)} "
+                          f"/ColorSpace /Device{'Gray' if image.grey else 'RGB'} /BitsPerComponent 8{more} /Filter /DCTDecode", bytes(image.data),
+                          compress=False)
+
+
 def _scaled_document(doc, scale: float):
     """What `text_layer` reads of `doc`, every coordinate times `scale`: a plain view, not a copy of the schema - the schema's
     boxes are integers and refuse the fractions a scale like 1500 / 1600 leaves."""
@@ -350,6 +368,21 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
     kids = []
     preset = IMAGE_QUALITY_PRESETS.get(image_quality, IMAGE_QUALITY_PRESETS["high"])
     for image, doc in zip(images, docs):
+        if _is_mrc(image):
+            # a layered page (yomitoku_amd.mrc.EncodedMrc): the background in its exact box of whole cells, then the foreground
+            # over the page through the mask - an explicit mask paints where its samples decode to 0, which is the stream's ink.
+            # The mask is exact; the colour layer is stretched by less than one cell
+            w, h, mask = int(image.width), int(image.height), image.mask
+            stencil = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ImageMask true /BitsPerComponent 1 "
+                                     f"/Filter /CCITTFaxDecode /DecodeParms << /K -1 /Columns {w} /Rows {h} >>", bytes(mask.data), compress=False)
+            back = _jpeg_xobject(pdf, image.background)
+            fore = _jpeg_xobject(pdf, image.foreground, f" /Mask {stencil} 0 R")
+            box = (int(image.background.width) * int(image.bg_cell), int(image.background.height) * int(image.bg_cell))
+            contents = pdf.add_stream("", _content_stream(w, h, text_layer(_scaled_document(doc, float(image.scale)), h), supplementary, box),
+                                      compress=True)
+            kids.append(pdf.add((f"<< /Type /Page /Parent {pages} 0 R /MediaBox [0 0 {w} {h}] /Contents {contents} 0 R "
+                                 f"/Resources << /XObject << /Im0 {fore} 0 R /Im1 {back} 0 R >> /Font << /F1 {font} 0 R >> >> >>").encode("ascii")))
+            continue
         bilevel = _is_bilevel(image)
         if bilevel:  # a finished T.6 stream (yomitoku_amd.ccitt.EncodedBilevel): 1 bit a pixel, 0 = white (BlackIs1 false, the default)
             data, w, h, scale = bytes(image.data), int(image.width), int(image.height), float(image.scale)
@@ -390,7 +423,8 @@ def create_searchable_pdf(images: List, docs: List, output_path: str, font_path:
     (yomitoku_amd/jpeg.py; what `DocumentAnalyzer.serve(jpeg=...)` returns) is embedded as it is: size and colour space come
     from the object, the words are scaled by its `scale`, and `image_quality` is ignored for that entry.  An EncodedBilevel
     (yomitoku_amd/ccitt.py; `serve(jpeg=..., jpeg_bilevel="auto")` returns one for a two-valued page) is embedded as a 1-bit
-    /CCITTFaxDecode image, K -1 (Group 4), likewise as it is."""
+    /CCITTFaxDecode image, K -1 (Group 4), likewise as it is.  An EncodedMrc (yomitoku_amd/mrc.py; `serve(jpeg=..., jpeg_mrc=True)`)
+    becomes three images: the background, and the foreground painted through the Group 4 mask."""
     data = searchable_pdf_bytes(images, docs, image_quality)
     with open(output_path, "wb") as f:
         f.write(data)
