@@ -162,7 +162,7 @@ def test_serve_refuses_the_new_values_without_jpeg_before_a_source_is_read():
 
     from tests.test_serving import StubAnalyzer
     from yomitoku_amd.document_analyzer import OCR, DocumentAnalyzer
-    from yomitoku_amd.serving import PagePipeline
+    from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
     def sources():
         raise AssertionError("a source was read")
@@ -172,7 +172,7 @@ def test_serve_refuses_the_new_values_without_jpeg_before_a_source_is_read():
     try:
         for mode in ("otsu", "adaptive"):
             for serve in (lambda **kw: DocumentAnalyzer.serve(SimpleNamespace(visualize=False), sources(), **kw),
-                          lambda **kw: OCR.serve(SimpleNamespace(visualize=False), sources(), **kw), lambda **kw: pipe.serve(sources(), **kw)):
+                          lambda **kw: OCR.serve(SimpleNamespace(visualize=False), sources(), **kw), lambda **kw: pipe.serve(sources(), files=check_jpeg_preset(**{"jpeg": None, **kw}))):
                 with pytest.raises(ValueError, match="jpeg_bilevel"):
                     serve(jpeg_bilevel=mode)
                 with pytest.raises(ValueError, match="bilevel"):

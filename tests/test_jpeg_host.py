@@ -220,7 +220,7 @@ def test_the_real_encoded_jpeg_class_is_recognised_by_the_writer():
 def test_an_unknown_preset_is_refused_before_a_page_is_read():
     from yomitoku_amd.document_analyzer import DocumentAnalyzer
     from yomitoku_amd.jpeg import encode_jpeg_pages
-    from yomitoku_amd.serving import PagePipeline
+    from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
     def sources():
         raise AssertionError("a source was read")
@@ -233,7 +233,7 @@ def test_an_unknown_preset_is_refused_before_a_page_is_read():
     pipe = PagePipeline(StubAnalyzer(), wave=2, in_flight=1)
     try:
         with pytest.raises(ValueError, match="nope"):
-            pipe.serve(sources(), jpeg="nope")
+            pipe.serve(sources(), files=check_jpeg_preset("nope"))
     finally:
         pipe.close()
     with pytest.raises(ValueError, match="nope"):
@@ -258,22 +258,22 @@ def test_jpeg_jobs_visit_the_render_stage_and_plain_jobs_do_not():
             return [None if isinstance(r, BaseException) else (np.zeros((1, 1, 3), np.uint8), np.ones((1, 1, 3), np.uint8)) for r in results]
 
         def _stage_jpeg(self, wave, results):
-            assert wave.job.jpeg == "low"
+            assert wave.job.files.preset == "low"
             return [None if isinstance(r, BaseException) else (ValueError("no room") if img[0, 1, 0] == 77 else (("file", wave.ids[k]),))
                     for k, (r, img) in enumerate(zip(results, wave.imgs))]
 
-    from yomitoku_amd.serving import PagePipeline
+    from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
     pipe = PagePipeline(Stub(), wave=4, in_flight=2)
     try:
         pages = [page(i) for i in range(6)]
         pages[3][0, 1, 0] = 77
         pipe.trace = []
-        out = pipe.serve(pages, jpeg="low")
+        out = pipe.serve(pages, files=check_jpeg_preset("low"))
         assert isinstance(out[3], ValueError)
         assert [(o[0][0], o[1]) for i, o in enumerate(out) if i != 3] == [(i, ("file", i)) for i in range(6) if i != 3]
         assert all(len(o) == 2 for i, o in enumerate(out) if i != 3) and "render" in {t[0] for t in pipe.trace}
-        both = pipe.serve([page(i) for i in range(3)], overlays=True, jpeg="low")
+        both = pipe.serve([page(i) for i in range(3)], overlays=True, files=check_jpeg_preset("low"))
         assert all(len(o) == 4 and o[3] == ("file", i) and isinstance(o[1], np.ndarray) for i, o in enumerate(both))
         pipe.trace = []
         plain = pipe.serve([page(i) for i in range(3)])

@@ -152,7 +152,7 @@ BAD = [dict(jpeg="high", jpeg_subsampling="4:1:1"), dict(jpeg="high", jpeg_subsa
 def test_bad_values_are_refused_before_a_source_is_read(kwargs):
     from tests.test_serving import StubAnalyzer
     from yomitoku_amd.document_analyzer import OCR, DocumentAnalyzer
-    from yomitoku_amd.serving import PagePipeline
+    from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
     for cls in (DocumentAnalyzer, OCR):
         with pytest.raises(ValueError, match="jpeg"):
@@ -160,7 +160,7 @@ def test_bad_values_are_refused_before_a_source_is_read(kwargs):
     pipe = PagePipeline(StubAnalyzer(), wave=2, in_flight=1)
     try:
         with pytest.raises(ValueError, match="jpeg"):
-            pipe.serve(_no_sources(), **kwargs)
+            pipe.serve(_no_sources(), files=check_jpeg_preset(**{"jpeg": None, **kwargs}))
     finally:
         pipe.close()
 
@@ -185,23 +185,23 @@ def test_encode_jpeg_pages_refuses_bad_values_before_any_device_work(monkeypatch
 
 def test_the_options_travel_on_the_job_to_the_jpeg_stage():
     from tests.test_serving import StubAnalyzer, page
-    from yomitoku_amd.serving import PagePipeline
+    from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
     seen = []
 
     class Stub(StubAnalyzer):
         def _stage_jpeg(self, wave, results):
-            seen.append((wave.job.jpeg, wave.job.jpeg_optimize, wave.job.jpeg_subsampling, wave.job.jpeg_grey))
+            seen.append((wave.job.files.preset, wave.job.files.optimize, wave.job.files.subsampling, wave.job.files.grey))
             return [(("file", wave.ids[k]),) for k in range(len(results))]
 
     pipe = PagePipeline(Stub(), wave=4, in_flight=2)
     try:
-        out = pipe.serve([page(i) for i in range(3)], jpeg="low", jpeg_subsampling="4:4:4", jpeg_grey="auto")
+        out = pipe.serve([page(i) for i in range(3)], files=check_jpeg_preset("low", jpeg_subsampling="4:4:4", jpeg_grey="auto"))
         assert [o[1] for o in out] == [("file", i) for i in range(3)]
-        pipe.serve([page(0)], jpeg="low")
+        pipe.serve([page(0)], files=check_jpeg_preset("low"))
     finally:
         pipe.close()
-    assert seen == [("low", False, "4:4:4", "auto"), ("low", False, None, False)]
+    assert seen == [("low", False, "4:4:4", "auto"), ("low", False, "4:2:0", False)]
 
 
 def test_encoded_jpeg_says_its_subsampling():

@@ -152,7 +152,7 @@ def test_the_host_entries_of_the_optimised_path():
 def test_jpeg_optimize_without_jpeg_is_refused_before_a_page_is_read():
     from tests.test_serving import StubAnalyzer
     from yomitoku_amd.document_analyzer import DocumentAnalyzer
-    from yomitoku_amd.serving import PagePipeline
+    from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
     def sources():
         raise AssertionError("a source was read")
@@ -163,6 +163,6 @@ def test_jpeg_optimize_without_jpeg_is_refused_before_a_page_is_read():
     pipe = PagePipeline(StubAnalyzer(), wave=2, in_flight=1)
     try:
         with pytest.raises(ValueError, match="jpeg_optimize"):
-            pipe.serve(sources(), jpeg_optimize=True)
+            pipe.serve(sources(), files=check_jpeg_preset(None, jpeg_optimize=True))
     finally:
         pipe.close()

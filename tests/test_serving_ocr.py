@@ -9,7 +9,7 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from yomitoku_amd.serving import PagePipeline
+from yomitoku_amd.serving import PagePipeline, check_jpeg_preset
 
 
 class OcrStub:
@@ -138,13 +138,13 @@ def test_entry_shapes_of_overlays_and_jpeg_jobs_and_every_slot_comes_back():
         schema, picture = out[i]
         assert schema[0] == i and isinstance(picture, np.ndarray) and int(picture[0, 0, 0]) == i
 
-    out = pipe.serve(pages, jpeg="high")
+    out = pipe.serve(pages, files=check_jpeg_preset("high"))
     assert isinstance(out[6], ValueError)
     for i in good + [4]:  # nothing is drawn in a jpeg job: page 4 is fine
         schema, made = out[i]
         assert schema[0] == i and made == f"file:{i}"
 
-    out = pipe.serve(pages, overlays=True, jpeg="high")
+    out = pipe.serve(pages, overlays=True, files=check_jpeg_preset("high"))
     assert isinstance(out[4], ValueError) and isinstance(out[6], ValueError)
     for i in good:
         schema, picture, made = out[i]

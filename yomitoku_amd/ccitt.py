@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib, imaging
-from .jpeg import _addr_words, _as_device_page, _gather_files, _grown
+from .devpages import PACKED_ROWS, SUMMED_AREA, addr_words, entered, gather_files, grown, shape_args, to_pinned
 
 PAGE_WORDS = 16  # YMK_G4_PAGE_WORDS
 
@@ -89,11 +89,8 @@ def file_capacity(h: int, w: int) -> int:
 def scratch_sizes(shapes: Sequence) -> tuple:
     """(rows, bytes of the packed rows, of the rows' slots, of their bit counts, of their bit offsets) of pages of `shapes` =
     (h, w, ...)."""
-    n = len(shapes)
-    arr = ctypes.c_int * max(1, n)
     sizes = (ctypes.c_int64 * 5)()
-    _lib.check(_lib.load().ymk_g4_scratch_bytes(arr(*[int(s[0]) for s in shapes]), arr(*[int(s[1]) for s in shapes]), n, sizes),
-               "ymk_g4_scratch_bytes")
+    _lib.check(_lib.load().ymk_g4_scratch_bytes(*shape_args(shapes), len(shapes), sizes), "ymk_g4_scratch_bytes")
     return tuple(int(v) for v in sizes)
 
 
@@ -111,14 +108,14 @@ def page_table(pages: Sequence[torch.Tensor], packed_at: Optional[Sequence[int]]
         h, w = int(p.shape[0]), int(p.shape[1])
         at = pack if packed_at is None else int(packed_at[k])
         cap = file_capacity(h, w) if capacities is None else int(capacities[k])
-        rec[k, 0:2] = _addr_words(p.data_ptr())
+        rec[k, 0:2] = addr_words(p.data_ptr())
         rec[k, 2:6] = (h, w, 1 if p.dim() == 2 else 3, row)
-        rec[k, 6:8] = _addr_words(at)
-        rec[k, 8:10] = _addr_words(out_at)
+        rec[k, 6:8] = addr_words(at)
+        rec[k, 8:10] = addr_words(out_at)
         rec[k, 10] = cap
-        rec[k, 11:13] = _addr_words(slot)
+        rec[k, 11:13] = addr_words(slot)
         if tables:
-            rec[k, 14:16] = _addr_words(sat)
+            rec[k, 14:16] = addr_words(sat)
             sat += h * w
         packs.append(at)
         offsets.append(out_at)
@@ -144,14 +141,12 @@ def start_test(pages: Sequence[torch.Tensor], scratch: dict) -> _Test:
     device = pages[0].device
     blob, packed_at, _, _ = page_table(pages, capacities=[0] * len(pages))
     packed_bytes = scratch_sizes([p.shape for p in pages])[1]
-    packed = _grown(scratch, "g4_packed", packed_bytes // 4, torch.int32, device)
-    flags = _grown(scratch, "g4_flags", len(pages), torch.int32, device)
+    packed = grown(scratch, PACKED_ROWS, packed_bytes // 4, torch.int32, device)
+    flags = grown(scratch, "g4_flags", len(pages), torch.int32, device)
     blob_dev = imaging._stage_blob(blob, device)
     _lib.check(_lib.load().ymk_g4_test_pack(blob_dev.data_ptr(), blob.size, len(pages), max(int(p.shape[0]) * int(p.shape[1]) for p in pages),
                                             flags.data_ptr(), packed.data_ptr(), packed_bytes, _lib.current_stream_ptr()), "ymk_g4_test_pack")
-    pin = _grown(scratch, "g4_pin_flags", len(pages), torch.int32, pinned=True)
-    pin[: len(pages)].copy_(flags[: len(pages)], non_blocking=True)
-    return _Test(list(pages), packed, packed_at, packed_bytes, pin)
+    return _Test(list(pages), packed, packed_at, packed_bytes, to_pinned(scratch, "g4_pin_flags", flags, len(pages)))
 
 
 class _Binarized(_Test):
@@ -171,11 +166,8 @@ class _Binarized(_Test):
 
 def binarize_scratch_sizes(shapes: Sequence) -> tuple:
     """(bytes of the histograms, bytes of the summed-area tables) of pages of `shapes` = (h, w, ...)."""
-    n = len(shapes)
-    arr = ctypes.c_int * max(1, n)
     sizes = (ctypes.c_int64 * 2)()
-    _lib.check(_lib.load().ymk_bin_scratch_bytes(arr(*[int(s[0]) for s in shapes]), arr(*[int(s[1]) for s in shapes]), n, sizes),
-               "ymk_bin_scratch_bytes")
+    _lib.check(_lib.load().ymk_bin_scratch_bytes(*shape_args(shapes), len(shapes), sizes), "ymk_bin_scratch_bytes")
     return tuple(int(v) for v in sizes)
 
 
@@ -192,27 +184,25 @@ def start_binarize(pages: Sequence[torch.Tensor], scratch: dict, method: str) ->
     shapes = [p.shape for p in pages]
     packed_bytes = scratch_sizes(shapes)[1]
     hist_bytes, sat_bytes = binarize_scratch_sizes(shapes)
-    packed = _grown(scratch, "g4_packed", packed_bytes // 4, torch.int32, device)
-    answer = _grown(scratch, "bin_answer", 2 * n, torch.int32, device)  # the flags, then the thresholds: one copy
+    packed = grown(scratch, PACKED_ROWS, packed_bytes // 4, torch.int32, device)
+    answer = grown(scratch, "bin_answer", 2 * n, torch.int32, device)  # the flags, then the thresholds: one copy
     blob_dev = imaging._stage_blob(blob, device)
     stream = _lib.current_stream_ptr()
     most = max(int(p.shape[0]) * int(p.shape[1]) for p in pages)
     if method == "otsu":
-        hist = _grown(scratch, "bin_hist", hist_bytes // 4, torch.int32, device)
+        hist = grown(scratch, "bin_hist", hist_bytes // 4, torch.int32, device)
         _lib.check(lib.ymk_bin_test_hist(blob_dev.data_ptr(), blob.size, n, most, answer.data_ptr(), hist.data_ptr(), stream), "ymk_bin_test_hist")
         thresholds = answer.data_ptr() + 4 * n
         _lib.check(lib.ymk_bin_otsu(n, hist.data_ptr(), thresholds, stream), "ymk_bin_otsu")
         _lib.check(lib.ymk_bin_otsu_pack(blob_dev.data_ptr(), blob.size, n, most, thresholds, packed.data_ptr(), packed_bytes, stream),
                    "ymk_bin_otsu_pack")
     else:
-        sat = _grown(scratch, "bin_sat", sat_bytes // 4, torch.int32, device)
+        sat = grown(scratch, SUMMED_AREA, sat_bytes // 4, torch.int32, device)
         _lib.check(lib.ymk_bin_test_hist(blob_dev.data_ptr(), blob.size, n, most, answer.data_ptr(), None, stream), "ymk_bin_test_hist")
         _lib.check(lib.ymk_bin_adaptive_pack(blob_dev.data_ptr(), blob.size, n, max(int(p.shape[0]) for p in pages),
                                              max(int(p.shape[1]) for p in pages), sat.data_ptr(), sat_bytes, packed.data_ptr(), packed_bytes,
                                              stream), "ymk_bin_adaptive_pack")
-    count = 2 * n if method == "otsu" else n
-    pin = _grown(scratch, "bin_pin_answer", 2 * n, torch.int32, pinned=True)
-    pin[:count].copy_(answer[:count], non_blocking=True)
+    pin = to_pinned(scratch, "bin_pin_answer", answer, 2 * n if method == "otsu" else n, room=2 * n)
     res = _Binarized(list(pages), packed, packed_at, packed_bytes, pin)
     res.method = method
     return res
@@ -225,11 +215,11 @@ def launch_encode(test: _Test, which: Sequence[int], scratch: dict, capacities: 
     device = pages[0].device
     blob, _, offsets, out_bytes = page_table(pages, [test.packed_at[j] for j in which], capacities)
     rows, _, slot_b, bits_b, off_b = scratch_sizes([p.shape for p in pages])
-    slots = _grown(scratch, "g4_slots", slot_b // 4, torch.int32, device)
-    rowbits = _grown(scratch, "g4_rowbits", bits_b // 4, torch.int32, device)
-    rowoff = _grown(scratch, "g4_rowoff", off_b // 8, torch.int64, device)
-    files = _grown(scratch, "g4_out", out_bytes, torch.uint8, device)
-    lengths = _grown(scratch, "g4_lengths", len(pages), torch.int32, device)
+    slots = grown(scratch, "g4_slots", slot_b // 4, torch.int32, device)
+    rowbits = grown(scratch, "g4_rowbits", bits_b // 4, torch.int32, device)
+    rowoff = grown(scratch, "g4_rowoff", off_b // 8, torch.int64, device)
+    files = grown(scratch, "g4_out", out_bytes, torch.uint8, device)
+    lengths = grown(scratch, "g4_lengths", len(pages), torch.int32, device)
     blob_dev = imaging._stage_blob(blob, device)
     tallest, largest = max(int(p.shape[0]) for p in pages), int(blob.reshape(-1, PAGE_WORDS)[:, 10].max())
     _lib.check(_lib.load().ymk_g4_encode_pages(blob_dev.data_ptr(), blob.size, len(pages), rows, tallest, test.packed.data_ptr(), test.packed_bytes,
@@ -248,24 +238,11 @@ def encode_g4_pages(pages: Sequence, stream=None, scratch: Optional[dict] = None
     the device and coded; a page that is not grey-valued gets a ValueError entry."""
     if binarize is not None and not (isinstance(binarize, str) and binarize in BINARIZE_MODES):
         raise ValueError(f"unknown bilevel method {binarize!r}: None, 'otsu' or 'adaptive'")
-    out: list = [None] * len(pages)
-    if not pages:
-        return out
-    if not torch.cuda.is_available():
-        raise _lib.YmkError("encode_g4_pages needs a HIP device (there is no host fallback)")
-    device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.device.type == "cuda"),
-                  torch.device("cuda", torch.cuda.current_device()))
     scratch = {} if scratch is None else scratch
-    with torch.cuda.device(device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device)):
-        live, devs = [], []
-        for k, page in enumerate(pages):
-            try:
-                devs.append(_as_device_page(page, device))
-                live.append(k)
-            except Exception as exc:  # noqa: BLE001 - only this page fails
-                out[k] = exc
+    with entered(pages, stream, "encode_g4_pages needs") as (_, live, devs, out):
         if not live:
             return out
+        # sort: the test, or the launches that threshold, and one wait for the pages' flags
         test = start_test(devs, scratch) if binarize is None else start_binarize(devs, scratch, binarize)
         torch.cuda.current_stream().synchronize()
         two = test.answers()
@@ -278,12 +255,12 @@ def encode_g4_pages(pages: Sequence, stream=None, scratch: Optional[dict] = None
         which = [j for j in range(len(devs)) if two[j]]
         if not which:
             return out
+        # launch Group 4, then one wait, one gather, the entries
         files, offsets, lengths = launch_encode(test, which, scratch)
-        pin_len = _grown(scratch, "g4_pin_lengths", len(which), torch.int32, pinned=True)
-        pin_len[: len(which)].copy_(lengths[: len(which)], non_blocking=True)
+        pin_len = to_pinned(scratch, "g4_pin_lengths", lengths, len(which))
         torch.cuda.current_stream().synchronize()
         sizes = pin_len[: len(which)].tolist()
-        for (j, data) in zip(which, _gather_files([(files, offsets[i], sizes[i]) for i in range(len(which))], scratch, "g4_pin_bytes")):
+        for (j, data) in zip(which, gather_files([(files, offsets[i], sizes[i]) for i in range(len(which))], scratch, "g4_pin_bytes")):
             out[live[j]] = bilevel_entry(devs[j], data, live[j], binarize or "auto", thresholds[j])
     return out
 

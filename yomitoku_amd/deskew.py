@@ -130,34 +130,32 @@ def scratch_sizes(shapes: Sequence, n_angles: int, s_max: int):
     """((bytes of the planes, the summed-area tables, the packed rows, the scores, the choice words), per page whether it is
     estimated) of pages of `shapes` = (h, w) or (h, w, 3)."""
     from . import _lib
+    from .devpages import shape_args
 
     n = len(shapes)
-    arr = ctypes.c_int * max(1, n)
-    sizes, fits = (ctypes.c_int64 * 5)(), arr()
-    _lib.check(_lib.load().ymk_dsk_scratch_bytes(arr(*[int(s[0]) for s in shapes]), arr(*[int(s[1]) for s in shapes]),
-                                                 arr(*[1 if len(s) == 2 else 3 for s in shapes]), n, n_angles, s_max, sizes, fits),
-               "ymk_dsk_scratch_bytes")
+    sizes, fits = (ctypes.c_int64 * 5)(), (ctypes.c_int * max(1, n))()
+    _lib.check(_lib.load().ymk_dsk_scratch_bytes(*shape_args(shapes, channels=True), n, n_angles, s_max, sizes, fits), "ymk_dsk_scratch_bytes")
     return tuple(int(v) for v in sizes), [bool(fits[k]) for k in range(n)]
 
 
 def page_table(pages: Sequence, dsts: Sequence) -> np.ndarray:
     """int32 [n][16]: the page table of include/ymk.h ("Page skew") - the planes, packed rows and summed-area tables one page
     behind the other; dsts[k]: the destination tensor of page k, or None (estimate only)."""
-    from .jpeg import _addr_words
+    from .devpages import addr_words
 
     rec = np.zeros((len(pages), PAGE_WORDS), np.int32)
     pack = luma = sat = 0
     for k, p in enumerate(pages):
         h, w, ch = int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3
-        rec[k, 0:2] = _addr_words(p.data_ptr())
+        rec[k, 0:2] = addr_words(p.data_ptr())
         rec[k, 2:5] = (h, w, ch)
-        rec[k, 6:8] = _addr_words(pack)
+        rec[k, 6:8] = addr_words(pack)
         if ch == 3:
-            rec[k, 8:10] = _addr_words(luma)
+            rec[k, 8:10] = addr_words(luma)
             luma += -(-(h * w) // 16) * 16
         if dsts[k] is not None:
-            rec[k, 11:13] = _addr_words(dsts[k].data_ptr())
-        rec[k, 14:16] = _addr_words(sat)
+            rec[k, 11:13] = addr_words(dsts[k].data_ptr())
+        rec[k, 14:16] = addr_words(sat)
         pack, sat = pack + h * (-(-w // 32)), sat + h * w
     return rec
 
@@ -191,7 +189,7 @@ def launch(pages: Sequence, params: dict, scratch: dict, rotate: bool = True, pi
     import torch
 
     from . import _lib, imaging
-    from .jpeg import _grown
+    from .devpages import LUMA_PLANE, PACKED_ROWS, SUMMED_AREA, grown, to_pinned
 
     lib, device, n = _lib.load(), pages[0].device, len(pages)
     assert lib.ymk_dsk_page_words() == PAGE_WORDS
@@ -201,11 +199,11 @@ def launch(pages: Sequence, params: dict, scratch: dict, rotate: bool = True, pi
     rec = page_table(pages, corrected if rotate else [None] * n)
     if edit_table is not None:
         edit_table(rec)
-    luma = _grown(scratch, "dsk_luma", max(luma_b, 16), torch.uint8, device)
-    sat = _grown(scratch, "bin_sat", sat_b // 4, torch.int32, device)
-    packed = _grown(scratch, "g4_packed", packed_b // 4, torch.int32, device)
-    scores = _grown(scratch, "dsk_scores", scores_b // 8, torch.int64, device)
-    answer = _grown(scratch, "dsk_answer", n * (CHOICE_WORDS + PAGE_WORDS), torch.int32, device)  # the choice words, then the planes' table
+    luma = grown(scratch, LUMA_PLANE, max(luma_b, 16), torch.uint8, device)
+    sat = grown(scratch, SUMMED_AREA, sat_b // 4, torch.int32, device)
+    packed = grown(scratch, PACKED_ROWS, packed_b // 4, torch.int32, device)
+    scores = grown(scratch, "dsk_scores", scores_b // 8, torch.int64, device)
+    answer = grown(scratch, "dsk_answer", n * (CHOICE_WORDS + PAGE_WORDS), torch.int32, device)  # the choice words, then the planes' table
     blob = np.concatenate([rec.reshape(-1), table.reshape(-1)])
     blob_dev = imaging._stage_blob(blob, device)
     table_ptr = blob_dev.data_ptr() + 4 * rec.size
@@ -214,8 +212,7 @@ def launch(pages: Sequence, params: dict, scratch: dict, rotate: bool = True, pi
                                  luma.data_ptr(), luma_b, sat.data_ptr(), sat_b, packed.data_ptr(), packed_b, planes_ptr, table_ptr, len(table),
                                  s_max, dead, scores.data_ptr(), answer.data_ptr(), 1 if rotate else 0, _lib.current_stream_ptr()),
                "ymk_dsk_pages")
-    pin = _grown(scratch if pin_scratch is None else pin_scratch, "dsk_pin_choice", n * CHOICE_WORDS, torch.int32, pinned=True)
-    pin[: n * CHOICE_WORDS].copy_(answer[: n * CHOICE_WORDS], non_blocking=True)
+    pin = to_pinned(scratch if pin_scratch is None else pin_scratch, "dsk_pin_choice", answer, n * CHOICE_WORDS)
     buffers = {"luma": luma, "packed": packed, "scores": scores, "choice": answer, "blob": blob_dev}
     return _Launched([(int(p.shape[0]), int(p.shape[1])) for p in pages], corrected, params, table, pin, buffers)
 
@@ -223,29 +220,14 @@ def launch(pages: Sequence, params: dict, scratch: dict, rotate: bool = True, pi
 def _run(pages: Sequence, deskew, stream, scratch, rotate: bool):
     import torch
 
-    from . import _lib
-    from .jpeg import _as_device_page
+    from .devpages import entered
 
     params = check_deskew(deskew)
     if params is None:
         raise ValueError("deskew=False: there is nothing to estimate")
-    out_pages: list = [None] * len(pages)
-    out_skews: list = [None] * len(pages)
-    if not pages:
-        return out_pages, out_skews
-    if not torch.cuda.is_available():
-        raise _lib.YmkError("page skew needs a HIP device (there is no host fallback)")
-    device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.device.type == "cuda"),
-                  torch.device("cuda", torch.cuda.current_device()))
     scratch = {} if scratch is None else scratch
-    with torch.cuda.device(device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device)):
-        live, devs = [], []
-        for k, page in enumerate(pages):
-            try:
-                devs.append(_as_device_page(page, device))
-                live.append(k)
-            except Exception as exc:  # noqa: BLE001 - only this page fails
-                out_pages[k] = out_skews[k] = exc
+    with entered(pages, stream, "page skew needs") as (_, live, devs, out_skews):
+        out_pages = list(out_skews)  # a page's exception stands in both
         if live:
             done = launch(devs, params, scratch, rotate=rotate)
             torch.cuda.current_stream().synchronize()

@@ -117,12 +117,11 @@ class OCR(StageAnalyzer):
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
         without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"), `jpeg_mrc`
         (False, True or the cells), `deskew`: as DocumentAnalyzer.serve."""
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
-        check_deskew(deskew)
+        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
+        deskew = check_deskew(deskew) or False
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew, jpeg_mrc=jpeg_mrc)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, files=files, deskew=deskew)
 
 
 # ---------------------------------------------------------------------------------------------- layout
@@ -622,12 +621,11 @@ class DocumentAnalyzer(StageAnalyzer):
         which `searchable_pdf_bytes` embeds as three images, the foreground painted through the mask.  Such a page is never
         resized (`scale` 1.0); `jpeg_optimize` and `jpeg_subsampling` apply to its two layer files, `jpeg_grey` does not.  A blank
         page, or one that is all ink, keeps its plain file.  OCR and layout see the page as it arrived; only the file changes."""
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
-        check_deskew(deskew)
+        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
+        deskew = check_deskew(deskew) or False
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                           jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew, jpeg_mrc=jpeg_mrc)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, files=files, deskew=deskew)
 
     def __call__(self, img):
         self.img = img

@@ -32,6 +32,10 @@ or a gradient of light, but a grey photograph too - and codes the result the sam
 `mrc=True` (serve: `jpeg_mrc=True`) writes every remaining page that has ink and paper as a layered page, an `EncodedMrc` of
 yomitoku_amd/mrc.py: its ink mask as a Group 4 file and two low-resolution pictures - the paper, the ink's colour - as JPEG files
 from this encoder, which takes the layers as pages like any other.
+
+The options are checked in one place, `page_files`, which makes a `PageFiles` of them (serve: `check_jpeg_preset`, the job's
+`wave.job.files`); `encode_page_files(pages, files)` is the worker behind every entry, the list of its phases: sort the pages,
+make up the JPEG batch, launch JPEG, launch Group 4, one wait and one gather.
 """
 
 from __future__ import annotations
@@ -44,11 +48,13 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _lib, imaging
+from . import _lib, ccitt, imaging
+from . import mrc as layered
+from .devpages import addr_words, entered, gather_files, grown, shape_args, to_pinned
+from .devpages import addr_words as _addr_words  # noqa: F401 - tools/jpeg_serve_timing.py takes it from here
 from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
 
 PAGE_WORDS, RESIZE_WORDS = 16, 16  # YMK_JPEG_PAGE_WORDS, YMK_PIL_RESIZE_U8_WORDS
-MAX_SIDE = 16383
 SUBSAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}  # word 15 of a page's record: YMK_JPEG_MODE_420 / _422 / _444
 MODE_GREY = 4  # YMK_JPEG_MODE_GREY: channel 0 of a three-channel page as a one-component file
 _SAMPLING = {0: (2, 2), 1: (2, 1), 2: (1, 1)}  # mode -> the luminance sampling factors (hs, vs)
@@ -128,21 +134,16 @@ def scratch_sizes(shapes: Sequence, optimize: bool = False, modes: Optional[Sequ
     pages of `shapes` = (h, w, channels) and `modes` (word 15 of their records; default 0 each); optimize: the stream bytes of
     that path, and behind the six the bytes of the histograms, the code tables and the DHT records."""
     n = len(shapes)
-    arr = ctypes.c_int * max(1, n)
     sizes = (ctypes.c_int64 * (9 if optimize else 6))()
     name = "ymk_jpeg_scratch_bytes_opt_mode" if optimize else "ymk_jpeg_scratch_bytes_mode"
-    _lib.check(getattr(_lib.load(), name)(arr(*[s[0] for s in shapes]), arr(*[s[1] for s in shapes]), arr(*[s[2] for s in shapes]),
-                                          None if modes is None else arr(*[int(m) for m in modes]), n, sizes), name)
+    _lib.check(getattr(_lib.load(), name)(*shape_args(shapes, channels=True),
+                                          None if modes is None else (ctypes.c_int * max(1, n))(*[int(m) for m in modes]), n, sizes), name)
     return tuple(int(v) for v in sizes)
 
 
 @functools.lru_cache(maxsize=64)
 def _lanczos(in_size: int, out_size: int):
     return imaging.pil_lanczos_coeffs(in_size, out_size)  # ~10 ms of host time per new (in, out) pair: the pages of a job share theirs
-
-
-def _addr_words(ptr: int):
-    return np.array([ptr & 0xFFFFFFFF, ptr >> 32], dtype=np.uint32).view(np.int32)
 
 
 def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]] = None, optimize: bool = False,
@@ -169,9 +170,9 @@ def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional
         ch = 1 if p.dim() == 2 else 3
         tiles, blocks, rows = _geometry(h, w, ch, modes[k])
         cap = int(capacities[k]) if capacities is not None else h * w * ch
-        rec[k, 0:2] = _addr_words(p.data_ptr())
+        rec[k, 0:2] = addr_words(p.data_ptr())
         rec[k, 2:8] = (h, w, ch, mcu, blk, iv)
-        rec[k, 8:10] = _addr_words(out_at)
+        rec[k, 8:10] = addr_words(out_at)
         rec[k, 10:13] = (cap, at, len(headers[k]))
         offsets.append(out_at)
         mcu, blk, iv = mcu + tiles, blk + blocks, iv + rows
@@ -187,16 +188,6 @@ def page_table(pages: Sequence[torch.Tensor], quality: int, capacities: Optional
     return blob, offsets, out_at
 
 
-def _grown(scratch: dict, key: str, count: int, dtype, device=None, pinned=False) -> torch.Tensor:
-    """scratch[key] with room for `count` elements: kept between calls, replaced (never resized) when it is too small."""
-    t = scratch.get(key)
-    if t is None or t.numel() < count or (not pinned and t.device != device):
-        count = max(int(count * 1.25), 1024)
-        t = torch.empty(count, dtype=dtype, pin_memory=True) if pinned else torch.empty(count, dtype=dtype, device=device)
-        scratch[key] = t
-    return t
-
-
 def resize_pages(pages: Sequence[torch.Tensor], sizes: Sequence) -> List[torch.Tensor]:
     """Pillow's `resize((ow, oh), LANCZOS)` of uint8 device pages (H x W x 3 or H x W), all in one launch on the current
     stream; sizes: (oh, ow) per page."""
@@ -209,36 +200,19 @@ def resize_pages(pages: Sequence[torch.Tensor], sizes: Sequence) -> List[torch.T
         out = torch.empty((oh, ow) if ch == 1 else (oh, ow, 3), dtype=torch.uint8, device=dev)
         xb, xk, ksx = _lanczos(w, ow)
         yb, yk, ksy = _lanczos(h, oh)
-        recs[k, 0:2] = _addr_words(p.data_ptr())
+        recs[k, 0:2] = addr_words(p.data_ptr())
         recs[k, 2:9] = (h, w, ch, oh, ow, ksx, ksy)
         for j, t in enumerate((xb, xk, yb, yk)):
             recs[k, 9 + j] = at
             tables.append(t.reshape(-1))
             at += t.size
-        recs[k, 13:15] = _addr_words(out.data_ptr())
+        recs[k, 13:15] = addr_words(out.data_ptr())
         outs.append(out)
     blob = np.concatenate([recs.reshape(-1)] + tables).astype(np.int32, copy=False)
     blob_dev = imaging._stage_blob(blob, dev)
     _lib.check(_lib.load().ymk_pil_resize_u8(blob_dev.data_ptr(), blob.size, len(pages), max(s[0] for s in sizes),
                                              max(s[1] for s in sizes), _lib.current_stream_ptr()), "ymk_pil_resize_u8")
     return outs
-
-
-def _as_device_page(page, device) -> torch.Tensor:
-    if isinstance(page, torch.Tensor):
-        t = page
-    else:
-        arr = np.ascontiguousarray(np.asarray(page))
-        if arr.dtype != np.uint8:
-            raise ValueError(f"a page is uint8, got {arr.dtype}")
-        t = torch.from_numpy(arr)
-    if t.dtype != torch.uint8 or not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 3)):
-        raise ValueError(f"a page is uint8 H x W x 3 (B G R) or H x W, got {t.dtype} {tuple(t.shape)}")
-    if min(t.shape[:2]) < 1 or max(t.shape[:2]) > MAX_SIDE:
-        raise ValueError(f"a page has 1..{MAX_SIDE} pixels on a side, got {tuple(t.shape[:2])}")
-    if t.device.type != "cuda":
-        t = t.to(device, non_blocking=False)
-    return t.contiguous()
 
 
 def _grey_launch(pages: Sequence[torch.Tensor], scratch: dict):
@@ -250,15 +224,13 @@ def _grey_launch(pages: Sequence[torch.Tensor], scratch: dict):
     device = pages[cand[0]].device
     rec = np.zeros((len(cand), PAGE_WORDS), np.int32)
     for j, k in enumerate(cand):
-        rec[j, 0:2] = _addr_words(pages[k].data_ptr())
+        rec[j, 0:2] = addr_words(pages[k].data_ptr())
         rec[j, 2:5] = (int(pages[k].shape[0]), int(pages[k].shape[1]), 3)
     blob_dev = imaging._stage_blob(rec.reshape(-1), device)
-    diff = _grown(scratch, "grey", len(cand), torch.int32, device)
+    diff = grown(scratch, "grey", len(cand), torch.int32, device)
     _lib.check(_lib.load().ymk_jpeg_pages_grey(blob_dev.data_ptr(), rec.size, len(cand), max(int(pages[k].shape[0]) * int(pages[k].shape[1]) for k in cand),
                                                diff.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_pages_grey")
-    pin = _grown(scratch, "pin_grey", len(cand), torch.int32, pinned=True)
-    pin[: len(cand)].copy_(diff[: len(cand)], non_blocking=True)
-    return cand, pin
+    return cand, to_pinned(scratch, "pin_grey", diff, len(cand))
 
 
 def _grey_answers(n: int, launched) -> List[bool]:
@@ -282,22 +254,227 @@ def grey_pages(pages: Sequence[torch.Tensor], scratch: Optional[dict] = None) ->
     return _grey_answers(len(pages), launched)
 
 
-def _gather_files(parts: Sequence, scratch: dict, key: str = "pin_bytes") -> list:
-    """parts: (device buffer, byte offset, length or -1) per file -> their bytes (None for -1): packed on the device, then one
-    copy through pinned memory and one wait."""
-    good = [(buf, at, n) for buf, at, n in parts if n >= 0]
-    total = sum(n for _, _, n in good)
-    host = None
-    if total:
-        packed = torch.cat([buf[at : at + n] for buf, at, n in good])
-        pin = _grown(scratch, key, total, torch.uint8, pinned=True)
-        pin[:total].copy_(packed, non_blocking=True)
+@dataclass(frozen=True)
+class PageFiles:
+    """What a job wants of its page files: the checked form of `encode_jpeg_pages`' and `serve`'s six options (`page_files`)."""
+
+    preset: str  # a name of IMAGE_QUALITY_PRESETS
+    optimize: bool
+    subsampling: str  # "4:2:0" | "4:2:2" | "4:4:4"
+    grey: Union[bool, str]  # False | "auto"
+    bilevel: Union[bool, str]  # False | "auto" | "otsu" | "adaptive"
+    mrc: Optional[dict]  # None, or check_mrc's full dict
+
+
+def page_files(preset, optimize=False, subsampling="4:2:0", grey=False, bilevel=False, mrc=False, serve=False) -> Optional[PageFiles]:
+    """The PageFiles of a call's options - the one place they are checked; every refusal is a ValueError.  serve: the reading of
+    the `serve()` entries - `preset` None: no page files (-> None), which every other option then has to agree with by
+    standing at its default; `subsampling` None: 4:2:0."""
+    given = subsampling
+    if serve:
+        if preset is not None and (not isinstance(preset, str) or preset not in IMAGE_QUALITY_PRESETS):
+            raise ValueError(f"unknown jpeg preset {preset!r}: None or one of {sorted(IMAGE_QUALITY_PRESETS)}")
+        if optimize and preset is None:
+            raise ValueError("jpeg_optimize=True needs jpeg=...: there is no JPEG file to optimise")
+        subsampling = "4:2:0" if given is None else given
+    else:
+        jpeg_preset(preset)
+    check_modes(subsampling, grey)
+    if preset is None and given is not None:
+        raise ValueError(f"jpeg_subsampling={given!r} needs jpeg=...: there is no JPEG file to write that way")
+    if preset is None and grey is not False:
+        raise ValueError(f"jpeg_grey={grey!r} needs jpeg=...: there is no JPEG file to write that way")
+    if ccitt.check_bilevel(bilevel) and preset is None:
+        raise ValueError(f"jpeg_bilevel={bilevel!r} needs jpeg=...: there are no page files to write that way")
+    cells = layered.check_mrc(mrc)
+    if cells is not None and preset is None:
+        raise ValueError(f"jpeg_mrc={mrc!r} needs jpeg=...: there are no page files to write that way")
+    return None if preset is None else PageFiles(preset, bool(optimize), subsampling, grey, bilevel, cells)
+
+
+def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, jpeg_mrc=False):
+    """`jpeg` of a serve() call: None (-> None) or a preset name of the searchable PDF (-> the job's PageFiles); anything else is
+    a ValueError - raised by the public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0",
+    "4:2:2", "4:4:4"), `jpeg_grey` (False, "auto"), `jpeg_bilevel` (False, "auto", "otsu", "adaptive") and `jpeg_mrc` (False, True
+    or a dict of cells: yomitoku_amd/mrc.py, check_mrc) ask for something of those files: a value that is none of these is a
+    ValueError, and so is any of the five without `jpeg`."""
+    return page_files(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, serve=True)
+
+
+def launch_encode(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]], optimize: bool,
+                  modes: Sequence[int], scratch: dict):
+    """Launch the coding of device pages on the current stream (ymk_jpeg_encode_pages, or - optimize - ymk_jpeg_encode_pages_opt).
+    modes: word 15 per page.  -> (the buffer of the files, per page its byte offset there, the files' lengths on the device)."""
+    lib, device, n = _lib.load(), pages[0].device, len(pages)
+    if not any(modes):
+        modes = None  # the defaults: the table and the sizes of every call before there were modes
+    blob, offsets, out_bytes = page_table(pages, quality, capacities, optimize, modes)
+    sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in pages], optimize, modes)
+    mcus, blocks, intervals, coef_b, stream_b, iv_b = sized[:6]
+    coef = grown(scratch, "coef", coef_b // 2, torch.int16, device)
+    bits = grown(scratch, "stream", stream_b // 4, torch.int32, device)
+    ivals = grown(scratch, "intervals", iv_b // 4, torch.int32, device)
+    files = grown(scratch, "out", out_bytes, torch.uint8, device)
+    lengths = grown(scratch, "lengths", n, torch.int32, device)
+    blob_dev = imaging._stage_blob(blob, device)
+    if optimize:
+        hist = grown(scratch, "hist", sized[6] // 4, torch.int32, device)
+        tables = grown(scratch, "tables", sized[7] // 4, torch.int32, device)
+        dht = grown(scratch, "dht", sized[8] // 4, torch.int32, device)
+        _lib.check(lib.ymk_jpeg_encode_pages_opt(blob_dev.data_ptr(), blob.size, n, mcus, blocks, intervals, coef.data_ptr(),
+                                                 hist.data_ptr(), tables.data_ptr(), dht.data_ptr(), bits.data_ptr(), stream_b,
+                                                 ivals.data_ptr(), files.data_ptr(), out_bytes, lengths.data_ptr(),
+                                                 _lib.current_stream_ptr()), "ymk_jpeg_encode_pages_opt")
+    else:
+        _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, n, mcus, blocks, intervals, coef.data_ptr(),
+                                             bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
+                                             lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
+    return files, offsets, lengths
+
+
+@dataclass
+class _Page:
+    """One live page of a call on its way to its entry."""
+
+    k: int  # its index in the call
+    dev: torch.Tensor  # on the device; the resized page once the preset has shrunk it
+    large: bool  # its long side exceeds the preset's
+    kind: str = "jpeg"  # what it becomes: "jpeg" | "group4" | "layered"
+    scale: float = 1.0
+    threshold: Optional[int] = None  # Otsu's, of a thresholded page
+    layer: Optional[int] = None  # a layered page's place in the separation
+    jpeg_at: Optional[int] = None  # its place in the JPEG batch; a layered page: its foreground's, the background follows
+    g4_at: Optional[int] = None  # its - or its mask's - place in the Group 4 batch
+
+
+def _sort(batch: List[_Page], files: PageFiles, scratch: dict):
+    """Phase 1: say of every page what it becomes.  -> (the bilevel test or None, the separation or None, the grey test where it
+    was launched early or None).  One wait with `bilevel`, one with `mrc`."""
+    devs = [p.dev for p in batch]
+    test = sep = early_grey = None
+    if files.bilevel is not False:
+        # on the pages as they arrived: the preset's resample would leave a two-valued page grey-valued.  Where no page can be
+        # resized the grey test sees the same pixels before and after that step: it is launched here and shares the wait
+        # "otsu" / "adaptive": the launches that threshold every page in place of the test; two-valued is then "grey-valued"
+        test = ccitt.start_test(devs, scratch) if files.bilevel == "auto" else ccitt.start_binarize(devs, scratch, files.bilevel)
+        if files.grey == "auto" and not any(p.large for p in batch):
+            early_grey = _grey_launch(devs, scratch)
         torch.cuda.current_stream().synchronize()
-        host = pin[:total].numpy()
-    out, at = [], 0
-    for _, _, n in parts:
-        out.append(None if n < 0 else host[at : at + n].tobytes())
-        at += max(n, 0)
+        thresholds = test.thresholds() if files.bilevel != "auto" else [None] * len(batch)
+        for p, two, threshold in zip(batch, test.answers(), thresholds):
+            if two:
+                p.kind, p.threshold = "group4", threshold
+    cand = [j for j, p in enumerate(batch) if p.kind == "jpeg"]
+    if files.mrc is not None and cand:
+        # with `bilevel` the ink goes where the test packed these pages' rows, which nothing reads any more: one buffer of
+        # packed rows for the one set of Group 4 launches
+        shared = None if test is None else (test.packed, [test.packed_at[j] for j in cand], test.packed_bytes)
+        sep = layered.launch([devs[j] for j in cand], files.mrc, scratch, packed=shared)
+        torch.cuda.current_stream().synchronize()
+        for i, (j, flag) in enumerate(zip(cand, sep.flags())):
+            if flag == 1:
+                batch[j].kind, batch[j].layer = "layered", i
+    return test, sep, early_grey
+
+
+def _jpeg_batch(batch: List[_Page], files: PageFiles, long_side, sep, early_grey, capacities, scratch: dict):
+    """Phase 2: -> (the pages of the JPEG launches, their capacities or None, per page whether it is written as a grey file): the
+    pages that stay JPEG, shrunk to the preset and tested for grey, then the two layers of every layered page."""
+    todo = []
+    for p in batch:
+        h, w = int(p.dev.shape[0]), int(p.dev.shape[1])
+        if p.kind == "jpeg" and p.large:
+            p.scale = long_side / max(w, h)
+            todo.append((p, (max(int(h * p.scale), 1), max(int(w * p.scale), 1))))
+    if todo:
+        for (p, _), small in zip(todo, resize_pages([p.dev for p, _ in todo], [s for _, s in todo])):
+            p.dev = small
+    plain = [p for p in batch if p.kind == "jpeg"]  # all of them without `bilevel` and `mrc`
+    jdevs = [p.dev for p in plain]
+    caps = None if capacities is None else [int(capacities[p.k]) for p in plain]
+    if early_grey is not None:
+        as_grey = [g for p, g in zip(batch, _grey_answers(len(batch), early_grey)) if p.kind == "jpeg"]
+    else:
+        as_grey = grey_pages(jdevs, scratch) if files.grey == "auto" and jdevs else [False] * len(jdevs)
+    for i, p in enumerate(plain):
+        p.jpeg_at = i
+    lay = [p for p in batch if p.kind == "layered"]
+    if lay:  # behind the plain pages the two layers of every layered page, foreground first: pages like any other
+        if caps is None:
+            caps = [d.numel() for d in jdevs]
+        for p in lay:
+            p.jpeg_at = len(jdevs)
+            jdevs += [sep.foreground(p.layer), sep.background(p.layer)]
+        caps += [d.numel() + layered.LAYER_ROOM for d in jdevs[len(plain):]]
+        as_grey = list(as_grey) + [False] * (len(jdevs) - len(plain))
+    return jdevs, caps, as_grey
+
+
+def _group4_batch(batch: List[_Page], test, sep):
+    """Phase 4's pages: -> (what holds their packed rows, their indices there): the two-valued pages, then the masks."""
+    two = [j for j, p in enumerate(batch) if p.kind == "group4"]
+    lay = [j for j, p in enumerate(batch) if p.kind == "layered"]
+    for i, j in enumerate(two + lay):
+        batch[j].g4_at = i
+    # with `bilevel` the masks lie in the test's buffer, at their pages' places
+    return (test, two + lay) if test is not None else (sep, [batch[j].layer for j in lay])
+
+
+def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_grey, sizes, datas):
+    """Phase 5's end: every live page's entry into `out`, from the files' bytes - the JPEG batch's, then the Group 4 batch's."""
+    def jpeg_entry(i, k, scale, what="the JPEG file"):
+        d = jdevs[i]
+        if sizes[i] < 0:
+            cap = caps[i] if caps is not None else d.numel()
+            return _lib.YmkError(f"page {k}: {what} does not fit its capacity of {cap} bytes")
+        one = d.dim() == 2 or as_grey[i]
+        return EncodedJpeg(datas[i], int(d.shape[1]), int(d.shape[0]), one, float(scale), bool(files.optimize), None if one else files.subsampling)
+
+    for p in batch:
+        if p.kind == "jpeg":
+            out[p.k] = jpeg_entry(p.jpeg_at, p.k, p.scale)
+        elif p.kind == "group4":
+            out[p.k] = ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, files.bilevel, p.threshold)
+        else:
+            parts = [ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, "adaptive"),
+                     jpeg_entry(p.jpeg_at, p.k, 1.0, "the foreground's file"), jpeg_entry(p.jpeg_at + 1, p.k, 1.0, "the background's file")]
+            failed = [e for e in parts if isinstance(e, BaseException)]
+            out[p.k] = failed[0] if failed else layered.EncodedMrc(parts[0], parts[2], parts[1], int(p.dev.shape[1]), int(p.dev.shape[0]), 1.0,
+                                                                  files.mrc["bg_cell"], files.mrc["fg_cell"])
+
+
+def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: Optional[dict] = None,
+                      capacities: Optional[Sequence[int]] = None) -> list:
+    """`encode_jpeg_pages` with its options as a PageFiles (serve: the job's): one entry per page, in order."""
+    preset = IMAGE_QUALITY_PRESETS[files.preset]
+    quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
+    scratch = {} if scratch is None else scratch
+    with entered(pages, stream, "encode_jpeg_pages needs") as (_, live, devs, out):
+        if not live:
+            return out
+        batch = [_Page(k, dev, long_side is not None and max(int(dev.shape[0]), int(dev.shape[1])) > long_side) for k, dev in zip(live, devs)]
+        # 1. sort: `bilevel`'s test (and the grey test, where no page is resized) and its wait; `mrc`'s separation and its wait
+        test, sep, early_grey = _sort(batch, files, scratch)
+        # 2. the JPEG batch: resize, the grey test (its own wait unless it ran early), the layers behind the plain pages
+        jdevs, caps, as_grey = _jpeg_batch(batch, files, long_side, sep, early_grey, capacities, scratch)
+        # 3. launch JPEG; the lengths go to the host first (one small copy), the bytes, packed on the device, in the gather
+        if jdevs:
+            colour = SUBSAMPLINGS[files.subsampling]
+            modes = [0 if d.dim() == 2 else (MODE_GREY if g else colour) for d, g in zip(jdevs, as_grey)]
+            jpegs, offsets, lengths = launch_encode(jdevs, quality, caps, files.optimize, modes, scratch)
+            pin_len = to_pinned(scratch, "pin_lengths", lengths, len(jdevs))
+        # 4. launch Group 4 behind the JPEG stages: the two-valued pages, then the masks
+        coded, which = _group4_batch(batch, test, sep)
+        if which:
+            g4s, g4_offsets, g4_lengths = ccitt.launch_encode(coded, which, scratch)
+            g4_pin = to_pinned(scratch, "g4_pin_lengths", g4_lengths, len(which))
+        # 5. one wait for the lengths, one gather of the bytes (its own wait), the entries
+        torch.cuda.current_stream().synchronize()
+        sizes = pin_len[: len(jdevs)].tolist() if jdevs else []
+        parts = [(jpegs, offsets[i], sizes[i]) for i in range(len(jdevs))]
+        if which:
+            parts += [(g4s, g4_offsets[i], n) for i, n in enumerate(g4_pin[: len(which)].tolist())]
+        _entries(batch, files, out, jdevs, caps, as_grey, sizes, gather_files(parts, scratch))
     return out
 
 
@@ -332,155 +509,7 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     further wait; the layers then join the JPEG launches and the masks the Group 4 launches, and the files come back in the same
     two copies.
     Anything else is a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
-    preset = jpeg_preset(image_quality)
-    colour_mode = check_modes(subsampling, grey)
-    mrc_params = None
-    if mrc is not False:
-        from . import ccitt
-        from . import mrc as layered  # imports this module
-
-        mrc_params = layered.check_mrc(mrc)
-    if bilevel is not False:
-        from . import ccitt  # imports this module
-
-        ccitt.check_bilevel(bilevel)
-    quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
-    out: list = [None] * len(pages)
-    if not pages:
-        return out
-    if not torch.cuda.is_available():
-        raise _lib.YmkError("encode_jpeg_pages needs a HIP device (there is no host fallback)")
-    device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.device.type == "cuda"),
-                  torch.device("cuda", torch.cuda.current_device()))
-    scratch = {} if scratch is None else scratch
-    lib = _lib.load()
-    with torch.cuda.device(device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device)):
-        live, devs = [], []
-        for k, page in enumerate(pages):
-            try:
-                devs.append(_as_device_page(page, device))
-                live.append(k)
-            except Exception as exc:  # noqa: BLE001 - only this page fails
-                out[k] = exc
-        if not live:
-            return out
-        large = [long_side is not None and max(int(p.shape[0]), int(p.shape[1])) > long_side for p in devs]
-        two, test, early_grey, thresholds = [False] * len(devs), None, None, [None] * len(devs)
-        if bilevel is not False:
-            # on the pages as they arrived: the preset's resample would leave a two-valued page grey-valued.  Where no page can be
-            # resized the grey test sees the same pixels before and after that step: it is launched here and shares the wait
-            # "otsu" / "adaptive": the launches that threshold every page in place of the test; `two` is then "grey-valued"
-            test = ccitt.start_test(devs, scratch) if bilevel == "auto" else ccitt.start_binarize(devs, scratch, bilevel)
-            if grey == "auto" and not any(large):
-                early_grey = _grey_launch(devs, scratch)
-            torch.cuda.current_stream().synchronize()
-            two = test.answers()
-            thresholds = test.thresholds() if bilevel != "auto" else [None] * len(devs)
-        sep, sep_of = None, {}  # the separation of the pages `bilevel` left, and page -> its index there where its flag is 1
-        if mrc_params is not None:
-            cand = [j for j in range(len(devs)) if not two[j]]
-            if cand:
-                # with `bilevel` the ink goes where the test packed these pages' rows, which nothing reads any more: one buffer
-                # of packed rows for the one set of Group 4 launches
-                shared = None if test is None else (test.packed, [test.packed_at[j] for j in cand], test.packed_bytes)
-                sep = layered.launch([devs[j] for j in cand], mrc_params, scratch, packed=shared)
-                torch.cuda.current_stream().synchronize()
-                sep_of = {j: i for i, (j, flag) in enumerate(zip(cand, sep.flags())) if flag == 1}
-        scales = [1.0] * len(live)
-        todo = []
-        for j, p in enumerate(devs):
-            h, w = int(p.shape[0]), int(p.shape[1])
-            if large[j] and not two[j] and j not in sep_of:
-                scales[j] = long_side / max(w, h)
-                todo.append((j, (max(int(h * scales[j]), 1), max(int(w * scales[j]), 1))))
-        if todo:
-            for (j, _), small in zip(todo, resize_pages([devs[j] for j, _ in todo], [s for _, s in todo])):
-                devs[j] = small
-        rest = [j for j in range(len(devs)) if not two[j] and j not in sep_of]  # the pages that get a JPEG file: all of them without `bilevel`
-        jdevs = [devs[j] for j in rest]
-        caps = None if capacities is None else [int(capacities[live[j]]) for j in rest]
-        n_plain = len(jdevs)
-        if early_grey is not None:
-            all_grey = _grey_answers(len(devs), early_grey)
-            as_grey = [all_grey[j] for j in rest]
-        else:
-            as_grey = grey_pages(jdevs, scratch) if grey == "auto" and jdevs else [False] * len(jdevs)
-        if sep_of:  # behind the plain pages the two layers of every layered page, foreground first: pages like any other
-            if caps is None:
-                caps = [p.numel() for p in jdevs]
-            for j, i in sep_of.items():
-                jdevs += [sep.foreground(i), sep.background(i)]
-            caps += [p.numel() + layered.LAYER_ROOM for p in jdevs[n_plain:]]
-            as_grey = list(as_grey) + [False] * (len(jdevs) - n_plain)
-        sizes = []
-        if jdevs:
-            modes = [0 if p.dim() == 2 else (MODE_GREY if g else colour_mode) for p, g in zip(jdevs, as_grey)]
-            if not any(modes):
-                modes = None  # the defaults: the table and the sizes of every call before there were modes
-            blob, offsets, out_bytes = page_table(jdevs, quality, caps, optimize, modes)
-            sized = scratch_sizes([(int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3) for p in jdevs], optimize, modes)
-            mcus, blocks, intervals, coef_b, stream_b, iv_b = sized[:6]
-            coef = _grown(scratch, "coef", coef_b // 2, torch.int16, device)
-            bits = _grown(scratch, "stream", stream_b // 4, torch.int32, device)
-            ivals = _grown(scratch, "intervals", iv_b // 4, torch.int32, device)
-            files = _grown(scratch, "out", out_bytes, torch.uint8, device)
-            lengths = _grown(scratch, "lengths", len(jdevs), torch.int32, device)
-            blob_dev = imaging._stage_blob(blob, device)
-            if optimize:
-                hist = _grown(scratch, "hist", sized[6] // 4, torch.int32, device)
-                tables = _grown(scratch, "tables", sized[7] // 4, torch.int32, device)
-                dht = _grown(scratch, "dht", sized[8] // 4, torch.int32, device)
-                _lib.check(lib.ymk_jpeg_encode_pages_opt(blob_dev.data_ptr(), blob.size, len(jdevs), mcus, blocks, intervals, coef.data_ptr(),
-                                                         hist.data_ptr(), tables.data_ptr(), dht.data_ptr(), bits.data_ptr(), stream_b,
-                                                         ivals.data_ptr(), files.data_ptr(), out_bytes, lengths.data_ptr(),
-                                                         _lib.current_stream_ptr()), "ymk_jpeg_encode_pages_opt")
-            else:
-                _lib.check(lib.ymk_jpeg_encode_pages(blob_dev.data_ptr(), blob.size, len(jdevs), mcus, blocks, intervals, coef.data_ptr(),
-                                                     bits.data_ptr(), stream_b, ivals.data_ptr(), files.data_ptr(), out_bytes,
-                                                     lengths.data_ptr(), _lib.current_stream_ptr()), "ymk_jpeg_encode_pages")
-            # the lengths first (one small copy), then the files' bytes, packed on the device, in one copy
-            pin_len = _grown(scratch, "pin_lengths", len(jdevs), torch.int32, pinned=True)
-            pin_len[: len(jdevs)].copy_(lengths[: len(jdevs)], non_blocking=True)
-        which = [j for j in range(len(devs)) if two[j]]
-        if sep_of:  # the masks behind the two-valued pages; `coded` is what holds the packed rows of both
-            if test is None:
-                coded, which = sep, list(sep_of.values())
-            else:
-                coded, which = test, which + list(sep_of)
-        else:
-            coded = test
-        if which:  # the Group 4 files: launched behind the JPEG stages, their lengths and bytes in the same two copies' waits
-            g4_files, g4_offsets, g4_lengths = ccitt.launch_encode(coded, which, scratch)
-            g4_pin = _grown(scratch, "g4_pin_lengths", len(which), torch.int32, pinned=True)
-            g4_pin[: len(which)].copy_(g4_lengths[: len(which)], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        parts = []
-        if jdevs:
-            sizes = pin_len[: len(jdevs)].tolist()
-            parts += [(files, offsets[i], sizes[i]) for i in range(len(jdevs))]
-        if which:
-            parts += [(g4_files, g4_offsets[i], n) for i, n in enumerate(g4_pin[: len(which)].tolist())]
-        datas = _gather_files(parts, scratch)
-        def jpeg_entry(i, p, k, scale, what="the JPEG file"):
-            if sizes[i] < 0:
-                cap = caps[i] if caps is not None else p.numel()
-                return _lib.YmkError(f"page {k}: {what} does not fit its capacity of {cap} bytes")
-            one = p.dim() == 2 or as_grey[i]
-            return EncodedJpeg(datas[i], int(p.shape[1]), int(p.shape[0]), one, float(scale), bool(optimize), None if one else subsampling)
-
-        for i, j in enumerate(rest):
-            out[live[j]] = jpeg_entry(i, devs[j], live[j], scales[j])
-        n_two = len(which) - len(sep_of)
-        for i, j in enumerate(which[:n_two]):
-            out[live[j]] = ccitt.bilevel_entry(devs[j], datas[len(jdevs) + i], live[j], bilevel, thresholds[j])
-        for i, j in enumerate(sep_of):
-            k, at = live[j], n_plain + 2 * i
-            parts3 = [ccitt.bilevel_entry(devs[j], datas[len(jdevs) + n_two + i], k, "adaptive"),
-                      jpeg_entry(at, jdevs[at], k, 1.0, "the foreground's file"), jpeg_entry(at + 1, jdevs[at + 1], k, 1.0, "the background's file")]
-            failed = [e for e in parts3 if isinstance(e, BaseException)]
-            out[k] = failed[0] if failed else layered.EncodedMrc(parts3[0], parts3[2], parts3[1], int(devs[j].shape[1]), int(devs[j].shape[0]), 1.0,
-                                                                mrc_params["bg_cell"], mrc_params["fg_cell"])
-    return out
+    return encode_page_files(pages, page_files(image_quality, optimize, subsampling, grey, bilevel, mrc), stream, scratch, capacities)
 
 
 def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False, subsampling: str = "4:2:0",

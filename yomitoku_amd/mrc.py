@@ -79,34 +79,32 @@ def scratch_sizes(shapes: Sequence, bg_cell: int, fg_cell: int):
     """((bytes of the planes, the summed-area tables, the packed rows, the pyramids, the layers, the flags), per page (word 5 of
     its record, the byte offsets of its foreground and background in the layers)) of pages of `shapes` = (h, w) or (h, w, 3)."""
     from . import _lib
+    from .devpages import shape_args
 
     n = len(shapes)
-    arr = ctypes.c_int * max(1, n)
     sizes, places = (ctypes.c_int64 * 6)(), (ctypes.c_int64 * max(1, 3 * n))()
-    _lib.check(_lib.load().ymk_mrc_scratch_bytes(arr(*[int(s[0]) for s in shapes]), arr(*[int(s[1]) for s in shapes]),
-                                                 arr(*[1 if len(s) == 2 else 3 for s in shapes]), n, bg_cell, fg_cell, sizes, places),
-               "ymk_mrc_scratch_bytes")
+    _lib.check(_lib.load().ymk_mrc_scratch_bytes(*shape_args(shapes, channels=True), n, bg_cell, fg_cell, sizes, places), "ymk_mrc_scratch_bytes")
     return tuple(int(v) for v in sizes), [tuple(int(places[3 * k + i]) for i in range(3)) for k in range(n)]
 
 
 def page_table(pages: Sequence, packed_at: Sequence[int], places: Sequence) -> np.ndarray:
     """int32 [n][16]: the page table of include/ymk.h ("Layered pages") - the planes and summed-area tables one page behind the
     other, the packed rows at `packed_at`, pyramids and layers at `places`."""
-    from .jpeg import _addr_words
+    from .devpages import addr_words
 
     rec = np.zeros((len(pages), PAGE_WORDS), np.int32)
     luma = sat = 0
     for k, p in enumerate(pages):
         h, w, ch = int(p.shape[0]), int(p.shape[1]), 1 if p.dim() == 2 else 3
-        rec[k, 0:2] = _addr_words(p.data_ptr())
+        rec[k, 0:2] = addr_words(p.data_ptr())
         rec[k, 2:5] = (h, w, ch)
         rec[k, 5] = places[k][0]
-        rec[k, 6:8] = _addr_words(int(packed_at[k]))
+        rec[k, 6:8] = addr_words(int(packed_at[k]))
         if ch == 3:
-            rec[k, 8:10] = _addr_words(luma)
+            rec[k, 8:10] = addr_words(luma)
             luma += -(-(h * w) // 16) * 16
-        rec[k, 11:13] = _addr_words(places[k][1])
-        rec[k, 14:16] = _addr_words(sat)
+        rec[k, 11:13] = addr_words(places[k][1])
+        rec[k, 14:16] = addr_words(sat)
         sat += h * w
     return rec
 
@@ -169,7 +167,7 @@ def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequenc
     import torch
 
     from . import _lib, imaging
-    from .jpeg import _grown
+    from .devpages import LUMA_PLANE, PACKED_ROWS, SUMMED_AREA, grown, to_pinned
 
     lib, device, n = _lib.load(), pages[0].device, len(pages)
     assert lib.ymk_mrc_page_words() == PAGE_WORDS
@@ -180,20 +178,20 @@ def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequenc
         for p in pages:
             packed_at.append(at)
             at += int(p.shape[0]) * (-(-int(p.shape[1]) // 32))
-        packed_dev = _grown(scratch, "g4_packed", packed_b // 4, torch.int32, device)
+        packed_dev = grown(scratch, PACKED_ROWS, packed_b // 4, torch.int32, device)
     else:
         packed_dev, packed_at, packed_b = packed
     rec = page_table(pages, packed_at, places)
     if edit_table is not None:
         edit_table(rec)
-    pyr = _grown(scratch, "mrc_pyramids", pyr_b // 4, torch.int32, device)
+    pyr = grown(scratch, "mrc_pyramids", pyr_b // 4, torch.int32, device)
     if layers is None:
         layers = torch.empty(max(layers_b, 16), dtype=torch.uint8, device=device)
-    answer = _grown(scratch, "mrc_answer", n * (1 + PAGE_WORDS), torch.int32, device)  # the flags, then the planes' table
+    answer = grown(scratch, "mrc_answer", n * (1 + PAGE_WORDS), torch.int32, device)  # the flags, then the planes' table
     luma = sat = None
     if masks is None:
-        luma = _grown(scratch, "dsk_luma", max(luma_b, 16), torch.uint8, device)
-        sat = _grown(scratch, "bin_sat", sat_b // 4, torch.int32, device)
+        luma = grown(scratch, LUMA_PLANE, max(luma_b, 16), torch.uint8, device)
+        sat = grown(scratch, SUMMED_AREA, sat_b // 4, torch.int32, device)
     else:
         for j, m in enumerate(masks):
             rows = pack_mask(m, device).reshape(-1)
@@ -203,8 +201,7 @@ def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequenc
                                  bg_cell, fg_cell, None if luma is None else luma.data_ptr(), luma_b, None if sat is None else sat.data_ptr(), sat_b,
                                  packed_dev.data_ptr(), packed_b, None if masks is not None else answer.data_ptr() + 4 * n, pyr.data_ptr(), pyr_b,
                                  layers.data_ptr(), layers_b, answer.data_ptr(), _lib.current_stream_ptr()), "ymk_mrc_pages")
-    pin = _grown(scratch, "mrc_pin_flags", n, torch.int32, pinned=True)
-    pin[:n].copy_(answer[:n], non_blocking=True)
+    pin = to_pinned(scratch, "mrc_pin_flags", answer, n)
     buffers = {"pyramids": pyr, "flags": answer, "blob": blob_dev, "sizes": (luma_b, sat_b, packed_b, pyr_b, layers_b)}
     return _Separated(list(pages), dict(params), packed_dev, list(packed_at), packed_b, layers, places, pin, buffers)
 
@@ -218,33 +215,20 @@ def separate_pages(pages: Sequence, mrc=True, masks: Optional[Sequence] = None, 
     torch stream to launch on (default: the current one); scratch: a dict the caller keeps between calls.  One wait, for the flags."""
     import torch
 
-    from . import _lib
-    from .jpeg import _as_device_page
+    from .devpages import entered
 
     params = check_mrc(mrc)
     if params is None:
         raise ValueError("mrc=False: there is nothing to separate")
     if masks is not None and len(masks) != len(pages):
         raise ValueError(f"{len(masks)} masks for {len(pages)} pages")
-    out: list = [None] * len(pages)
-    if not pages:
-        return out
-    if not torch.cuda.is_available():
-        raise _lib.YmkError("layered pages need a HIP device (there is no host fallback)")
-    device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.device.type == "cuda"),
-                  torch.device("cuda", torch.cuda.current_device()))
+
+    def mask_fits(k, page, dev):
+        if masks is not None and tuple(np.shape(masks[k])) != tuple(dev.shape[:2]):
+            raise ValueError(f"a mask has its page's H x W, got {tuple(np.shape(masks[k]))} for {tuple(page.shape[:2])}")
+
     scratch = {} if scratch is None else scratch
-    with torch.cuda.device(device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(device)):
-        live, devs = [], []
-        for k, page in enumerate(pages):
-            try:
-                devs.append(_as_device_page(page, device))
-                if masks is not None and tuple(np.shape(masks[k])) != tuple(devs[-1].shape[:2]):
-                    devs.pop()
-                    raise ValueError(f"a mask has its page's H x W, got {tuple(np.shape(masks[k]))} for {tuple(page.shape[:2])}")
-                live.append(k)
-            except Exception as exc:  # noqa: BLE001 - only this page fails
-                out[k] = exc
+    with entered(pages, stream, "layered pages need", mask_fits) as (_, live, devs, out):
         if live:
             done = launch(devs, params, scratch, None if masks is None else [masks[k] for k in live])
             torch.cuda.current_stream().synchronize()

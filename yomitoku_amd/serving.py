@@ -31,9 +31,9 @@ memory.
 `render` is not one of the nine: its thread and stream are started by the first job that asks for overlays or JPEG files, and
 only the waves of such a job visit it - after `finish` has aggregated them, before their slot is handed back.  It draws all
 canvases of a wave (as many per page as the analyzer draws: two, OCR one) with two launches (utils/visualizer.py: render_wave) and / or encodes the wave's clean pages
-as JPEG files with three - five with the job's `jpeg_optimize` - (yomitoku_amd/jpeg.py: encode_jpeg_pages), its two-valued pages as Group 4 files with four
-more where the job says `jpeg_bilevel="auto"` (yomitoku_amd/ccitt.py) - or its grey-valued pages, thresholded, with `"otsu"` (six
-more) or `"adaptive"` (seven more); `jpeg_mrc` separates the pages that leaves into an ink mask and two layers in front of those
+as the job's PageFiles (`wave.job.files`; yomitoku_amd/jpeg.py: encode_page_files) says: as JPEG files with three launches - five with `optimize` -, its two-valued pages as Group 4 files with four
+more under `bilevel="auto"` (yomitoku_amd/ccitt.py) - or its grey-valued pages, thresholded, with `"otsu"` (six
+more) or `"adaptive"` (seven more); `mrc` separates the pages that leaves into an ink mask and two layers in front of those
 launches (yomitoku_amd/mrc.py: the page-skew step's luminance and ink, cells, a pull per level, flags, push) and hands the layers
 to the JPEG launches and the masks to the Group 4 launches; a job with neither runs exactly the stages above.
 
@@ -79,6 +79,7 @@ import torch
 
 from . import imaging
 from .data.staging import PageStager
+from .jpeg import check_jpeg_preset, encode_page_files  # noqa: F401 - check_jpeg_preset: the public entries and the tests take it from here
 
 logger = logging.getLogger(__name__)
 
@@ -116,18 +117,12 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False, options=None, jpeg=None, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False,
-                 jpeg_bilevel=False, deskew=None, jpeg_mrc=False):
+    def __init__(self, n_hint=0, overlays=False, options=None, files=None, deskew=None):
         self.results = {}
         self.deskew = deskew  # None, or the parameters of check_deskew: the pages are turned upright behind their upload
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, the analyzer's pictures...): the waves visit the render stage
-        self.jpeg = jpeg  # None or a preset name: the entries end with the page's EncodedJpeg, made in the render stage too
-        self.jpeg_optimize = bool(jpeg_optimize)  # those files with Huffman tables of their own (encode_jpeg_pages(optimize=True))
-        self.jpeg_subsampling = jpeg_subsampling  # None (4:2:0) or the chroma of those files (encode_jpeg_pages(subsampling=...))
-        self.jpeg_grey = jpeg_grey  # False, or "auto": grey-valued colour pages become grey files (encode_jpeg_pages(grey="auto"))
-        self.jpeg_bilevel = jpeg_bilevel  # False, "auto": two-valued pages get Group 4 files; "otsu" / "adaptive": grey-valued ones, thresholded
-        self.jpeg_mrc = jpeg_mrc  # False, True or the cells: pages with ink and paper get an EncodedMrc (encode_jpeg_pages(mrc=...))
+        self.files = files  # None, or the PageFiles of check_jpeg_preset: the entries end with the page's file, made in the render stage too
         self.cond = threading.Condition()
         self.outstanding = 0
         self.retries: "deque" = deque()  # (page id, host page) to re-run alone
@@ -178,32 +173,6 @@ def _switch_interval(seconds):
             if _switch_users == 0 and _switch_saved is not None:
                 sys.setswitchinterval(_switch_saved)
                 _switch_saved = None
-
-
-def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, jpeg_mrc=False):
-    """`jpeg` of a serve() call: None or a preset name of the searchable PDF; anything else is a ValueError - raised by the
-    public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0", "4:2:2", "4:4:4"),
-    `jpeg_grey` (False, "auto") and `jpeg_bilevel` (False, "auto", "otsu", "adaptive") ask for something of those files: a value that is none of
-    these is a ValueError, and so is any of the four without `jpeg`.  `jpeg_mrc` (False, True or a dict of cells: yomitoku_amd/mrc.py,
-    check_mrc) likewise."""
-    from .ccitt import check_bilevel
-    from .jpeg import check_modes
-    from .mrc import check_mrc
-    from .utils.searchable_pdf import IMAGE_QUALITY_PRESETS
-
-    if jpeg is not None and (not isinstance(jpeg, str) or jpeg not in IMAGE_QUALITY_PRESETS):
-        raise ValueError(f"unknown jpeg preset {jpeg!r}: None or one of {sorted(IMAGE_QUALITY_PRESETS)}")
-    if jpeg_optimize and jpeg is None:
-        raise ValueError("jpeg_optimize=True needs jpeg=...: there is no JPEG file to optimise")
-    check_modes("4:2:0" if jpeg_subsampling is None else jpeg_subsampling, jpeg_grey)
-    if jpeg is None and jpeg_subsampling is not None:
-        raise ValueError(f"jpeg_subsampling={jpeg_subsampling!r} needs jpeg=...: there is no JPEG file to write that way")
-    if jpeg is None and jpeg_grey is not False:
-        raise ValueError(f"jpeg_grey={jpeg_grey!r} needs jpeg=...: there is no JPEG file to write that way")
-    if check_bilevel(jpeg_bilevel) and jpeg is None:
-        raise ValueError(f"jpeg_bilevel={jpeg_bilevel!r} needs jpeg=...: there are no page files to write that way")
-    if check_mrc(jpeg_mrc) is not None and jpeg is None:
-        raise ValueError(f"jpeg_mrc={jpeg_mrc!r} needs jpeg=...: there are no page files to write that way")
 
 
 def _run_stage(stream, wave, fn, *args):
@@ -372,7 +341,7 @@ class PagePipeline:
             try:
                 skews = self._skews(wave)
                 products = []  # per product of the job, per page: a tuple of entry members, or the exception
-                for wanted, fn in ((job.overlays, "_stage_render"), (job.jpeg, "_stage_jpeg")):
+                for wanted, fn in ((job.overlays, "_stage_render"), (job.files is not None, "_stage_jpeg")):
                     if not wanted:
                         continue
                     try:
@@ -428,7 +397,7 @@ class PagePipeline:
                 except Exception as exc:  # noqa: BLE001 - aggregation is per page: only this page fails
                     logger.error("page %d failed in aggregation: %s: %s", idx, type(exc).__name__, exc)
                     done.append(exc)
-            if job.overlays or job.jpeg:  # the render stage writes the entries and hands the slot back
+            if job.overlays or job.files is not None:  # the render stage writes the entries and hands the slot back
                 wave.results = done
                 self._render_q.put(wave)
                 return
@@ -483,9 +452,8 @@ class PagePipeline:
         for name in self._entries:
             self._q[name].put(wave)
 
-    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, jpeg=None,
-              jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False,
-              jpeg_mrc=False) -> List:
+    def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, files=None,
+              deskew=False) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -494,19 +462,10 @@ class PagePipeline:
         `analyze_pages` returns for the page with visualize=True everywhere, as arrays the caller owns; a failed page's entry
         stays the bare exception.  The waves of such a job pass through the render stage, whose thread the first such job
         starts; a job without overlays runs what it always ran.
-        jpeg: None, or a preset name of the searchable PDF ("high", "middle", "low"; anything else is a ValueError before a
-        source is read): a page's entry ends with its EncodedJpeg (yomitoku_amd/jpeg.py) - (schema, EncodedJpeg), or (schema, ocr
-        overlay, layout overlay, EncodedJpeg) - encoded in the render stage from the clean page, never from a canvas.
-        jpeg_optimize: those files with Huffman tables made for each page (smaller, the same pixels); a ValueError without `jpeg`.
-        jpeg_subsampling: None (4:2:0), "4:2:0", "4:2:2" or "4:4:4" - the chroma of those files; jpeg_grey: False, or "auto" - a page
-        whose pixels all have B == G == R becomes a grey file.  Other values, and either without `jpeg`, are a ValueError.
-        jpeg_bilevel: False, or "auto" - a two-valued page (every sample 0 or 255) gets an EncodedBilevel (yomitoku_amd/ccitt.py), a
-        lossless Group 4 file of the full-size page, in place of the EncodedJpeg; "otsu" or "adaptive" - every grey-valued page
-        (one channel, or B == G == R everywhere) is thresholded on the device, by one threshold per page or by a locally adaptive
-        one, and gets such a file; the same refusals.
-        jpeg_mrc: False, True, or a dict with any of bg_cell, fg_cell (each 1, 2, 4, 8 or 16; yomitoku_amd/mrc.py: check_mrc) - of the
-        pages `jpeg_bilevel` leaves, every page with ink and with paper gets an EncodedMrc - its ink mask as a Group 4 file and two
-        low-resolution JPEG layers - in place of the EncodedJpeg; the same refusals.
+        files: None, or the PageFiles of the job (yomitoku_amd/jpeg.py: check_jpeg_preset makes it of the public entries' `jpeg...`
+        options): a page's entry ends with its page file - (schema, EncodedJpeg), or (schema, ocr overlay, layout overlay,
+        EncodedJpeg); an EncodedBilevel or an EncodedMrc where the record gives the page one - encoded in the render stage from
+        the clean page, never from a canvas.
         deskew: False, True, or a dict with any of max_angle, step, min_angle in degrees (yomitoku_amd/deskew.py: check_deskew;
         anything else is a ValueError before a source is read): every page's skew is estimated and undone on the device behind
         its upload, so words, boxes, overlays and page files are those of the corrected page, and a page's entry ends with its
@@ -517,15 +476,12 @@ class PagePipeline:
         from .data.functions import load_image
         from .deskew import check_deskew
 
-        check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)
         deskew = check_deskew(deskew)
         if deskew is not None and not self._gpu:
             raise ValueError("deskew needs a HIP device: this pipeline has none (there is no host fallback)")
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job(overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                                   jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew,
-                                   jpeg_mrc=jpeg_mrc)
-            if job.overlays or job.jpeg:
+            job = self._job = _Job(overlays=overlays, options=options, files=files, deskew=deskew)
+            if job.overlays or job.files is not None:
                 self._start_render()
             n = 0
             origin = []  # page id -> (source index, frame index)
@@ -665,7 +621,7 @@ class StageAnalyzer:
     (`wave.job.options`, `wave.job.overlays`); `_stage_render(wave, results)` (GPU, here; overlays jobs only) returns per page
     its pictures - pictures per page: as many as `_page_drawings(wave, k, results)` (subclass) records, the same for every page
     of an analyzer (DocumentAnalyzer and TableSemanticParser two, OCR one) -, from those drawings and `wave.pages`; `_stage_jpeg(wave, results)` (GPU,
-    here; jpeg jobs only) returns per page a 1-tuple with its EncodedJpeg, from `wave.pages`, `wave.job.jpeg` and `wave.job.jpeg_optimize`.  `_nets()`
+    here; jobs with page files only) returns per page a 1-tuple with its page file, from `wave.pages` and `wave.job.files`.  `_nets()`
     (subclass): the modules whose `model.close()` releases the analyzer's device memory.
 
     `handover`: None, or an object that sees - and may replace - what one stage hands to the next, AFTER the stage has
@@ -787,24 +743,17 @@ class StageAnalyzer:
         return out
 
     def _stage_jpeg(self, wave, results, scratch=None):
-        """JPEG files: per page of the wave a 1-tuple with its EncodedJpeg (preset `wave.job.jpeg`, tables `wave.job.jpeg_optimize`,
-        chroma `wave.job.jpeg_subsampling`, grey files `wave.job.jpeg_grey`; an EncodedBilevel or an EncodedMrc where
-        `wave.job.jpeg_bilevel` / `wave.job.jpeg_mrc` give the page one), an exception for a page
+        """Page files: per page of the wave a 1-tuple with its EncodedJpeg (an EncodedBilevel or an EncodedMrc where
+        `wave.job.files`, the job's PageFiles, gives the page one), an exception for a page
         that could not be encoded, None for a page that had already failed.  All pages of the wave are encoded together on
-        the calling thread's stream (yomitoku_amd/jpeg.py: encode_jpeg_pages) from `wave.pages` - the clean pages: the
+        the calling thread's stream (yomitoku_amd/jpeg.py: encode_page_files) from `wave.pages` - the clean pages: the
         overlays are drawn on copies - with `scratch`, by default the wave slot's."""
-        from .jpeg import encode_jpeg_pages
-
         out = [None] * len(wave)
         live = [k for k in range(len(wave)) if not isinstance(results[k], BaseException)]
         if live:
             if scratch is None:
                 scratch = self._jpeg_scratch.setdefault(wave.ring, {})
-            files = encode_jpeg_pages([wave.pages[k] for k in live], wave.job.jpeg, scratch=scratch,
-                                      optimize=getattr(wave.job, "jpeg_optimize", False),
-                                      subsampling=getattr(wave.job, "jpeg_subsampling", None) or "4:2:0",
-                                      grey=getattr(wave.job, "jpeg_grey", False), bilevel=getattr(wave.job, "jpeg_bilevel", False),
-                                      mrc=getattr(wave.job, "jpeg_mrc", False))
+            files = encode_page_files([wave.pages[k] for k in live], wave.job.files, scratch=scratch)
             for k, made in zip(live, files):
                 out[k] = made if isinstance(made, BaseException) else (made,)
         return out
@@ -841,8 +790,7 @@ class StageAnalyzer:
         return wave
 
     # ---- the pipeline of this analyzer
-    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, jpeg=None, jpeg_optimize=False,
-               jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, deskew=False, jpeg_mrc=False):
+    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, files=None, deskew=False):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -850,8 +798,7 @@ class StageAnalyzer:
                 pipe.close()
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, jpeg=jpeg, jpeg_optimize=jpeg_optimize,
-                          jpeg_subsampling=jpeg_subsampling, jpeg_grey=jpeg_grey, jpeg_bilevel=jpeg_bilevel, deskew=deskew, jpeg_mrc=jpeg_mrc)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, files=files, deskew=deskew)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -
