@@ -549,6 +549,39 @@ int ymk_mrc_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_
                   int* planes_dev, uint32_t* pyr_dev, int64_t pyr_bytes, unsigned char* layers_dev, int64_t layers_bytes, int* flags_dev,
                   void* stream);
 
+/* ---- Despeckled pages: connected-component labelling of packed rows, and the removal of every component below a size, opt-in
+ * (yomitoku_amd/csrc/ymk_cc.hip; yomitoku_amd/despeckle.py; despeckle_masks, encode_g4_pages(despeckle=...), serve(jpeg=...,
+ * jpeg_despeckle=...)).  DESIGN.md, "Despeckled pages"; tests/despeckle_ref.py is the definition, and the rows and the counts
+ * equal it exactly.  The page table is the Group 4 encoder's; of it this call reads words 2-3 (h, w), 6-7 (the packed rows, which
+ * are rewritten in place: 1 = black, the leftmost pixel of a word in its bit 31; the bits behind column w stay 0 and are pixels
+ * of neither colour) and
+ *     word 14-15 WORD offset (low, high) in labels_dev and in areas_dev of the page's h w words (where the binariser's
+ *                summed-area table would be: ccitt.page_table(tables=True))
+ * A record that does not fit the sizes the caller states - the buffers', or max_h, max_w, the largest of the table - is taken as
+ * absent: its rows and its scratch are not touched, its counts are 0.  Buffers 4-byte aligned.
+ * ymk_cc_scratch_bytes: HOST arrays h, w -> sizes2_out = the bytes of labels_dev and of areas_dev, int32 each: 8 bytes a pixel.
+ * ymk_cc_despeckle_pages: counts_dev int32 [n_pages][4] zeroed on `stream`; then, n_black > 0: every 8-connected component of 1
+ *   bits with fewer than n_black pixels is cleared, counts [0], [1] += such components, their pixels; then, n_white > 0, on the
+ *   result: every 4-connected component of 0 bits with fewer than n_white pixels is set, counts [2], [3] likewise.  A component
+ *   that touches the page's edge is no exception.  n_black, n_white: 0..65535, 0 = that colour is left alone (no launch).
+ *   Four launches a colour - label the YMK_CC_TILE_W x YMK_CC_TILE_H tiles, merge across their seams, areas, apply -, in order
+ *   on `stream`; no kernel waits for another thread's progress (the argument is in ymk_cc.hip).  Nothing is allocated, nothing
+ *   waited for.  The result depends on the rows alone, not on timing.
+ * ymk_cc_stage: one of a colour's four launches alone - stage 0 label, 1 merge, 2 areas, 3 apply; white: 0 = the black pass, else
+ *   the white one; n: that colour's size; counts_dev is added to, not zeroed.  For tools/despeckle_serve_timing.py: the stages of
+ *   a colour in order are that colour's pass. */
+#define YMK_CC_TILE_W 64
+#define YMK_CC_TILE_H 16
+int ymk_cc_tile_w(void);
+int ymk_cc_tile_h(void);
+int ymk_cc_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes2_out);
+int ymk_cc_despeckle_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
+                           int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int n_black,
+                           int n_white, int* counts_dev, void* stream);
+int ymk_cc_stage(int stage, int white, const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
+                 int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int n, int* counts_dev,
+                 void* stream);
+
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,
  * polygon-mean score, unclip, scaling to the original page).  prob_host: fp32 [h][w] HOST pointer

@@ -119,6 +119,13 @@ SIGNATURES = {
                              c_void_p]),
     "ymk_mrc_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                               c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ymk_cc_tile_w": (c_int, []),
+    "ymk_cc_tile_h": (c_int, []),
+    "ymk_cc_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_cc_despeckle_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                       c_int, c_void_p, c_void_p]),
+    "ymk_cc_stage": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                             c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import ctypes
 import struct
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import ClassVar, List, Optional, Sequence, Union
 
 import numpy as np
@@ -44,7 +44,10 @@ class EncodedBilevel:
     """One two-valued page as a raw T.6 stream: the codes MSB first in each byte, rows not byte-aligned, EOFB at the end,
     zero-padded to a byte; 0 bits of the decoded image are white (`BlackIs1 false`, TIFF's MinIsWhite).  `scale` is 1.0: a
     two-valued page is never resized.  `method`: "auto" for a page that arrived two-valued, "otsu" / "adaptive" for one that was
-    thresholded; `threshold`: Otsu's t* (black iff p <= t*), None for the other two."""
+    thresholded; `threshold`: Otsu's t* (black iff p <= t*), None for the other two; `despeckled`: what despeckling removed
+    before the page was coded (yomitoku_amd/despeckle.py: Despeckled), None where it did not run.  It is the constructor's last
+    argument and an attribute, not a dataclass field: `==` and `repr` ignore it, `dataclasses.fields()` does not list it, and
+    `dataclasses.replace()` gives a copy whose `despeckled` is None unless it is passed again."""
 
     data: bytes
     width: int
@@ -53,6 +56,12 @@ class EncodedBilevel:
     method: str = "auto"
     threshold: Optional[int] = None
     bilevel: ClassVar[bool] = True  # what utils/searchable_pdf.py recognises the object by
+    # the last argument, kept as an attribute and not among dataclasses.fields(): an entry's fields, its equality and its recorded
+    # form (tools/record_page_files_golden.py) are those of an entry made before there was despeckling
+    despeckled: InitVar[Optional["Despeckled"]] = None  # noqa: F821 - yomitoku_amd/despeckle.py
+
+    def __post_init__(self, despeckled=None):
+        self.despeckled = despeckled
 
     def to_tiff(self) -> bytes:
         """A minimal little-endian TIFF with the stream as its single Group 4 strip."""
@@ -229,13 +238,20 @@ def launch_encode(test: _Test, which: Sequence[int], scratch: dict, capacities: 
 
 
 def encode_g4_pages(pages: Sequence, stream=None, scratch: Optional[dict] = None,
-                    binarize: Optional[str] = None) -> List[Union[EncodedBilevel, Exception]]:
+                    binarize: Optional[str] = None, despeckle=False) -> List[Union[EncodedBilevel, Exception]]:
     """One entry per page, in order: its EncodedBilevel, or the exception that page raised - a ValueError for a page that is not
     uint8 H x W x 3 / H x W, or not two-valued.  pages: device tensors and / or host arrays.  stream: the torch stream to launch
     on (default: the current one); scratch: a dict the caller keeps between calls to reuse the device and pinned buffers.  The
     file's capacity is `file_capacity`, which no file exceeds: a two-valued page cannot fail for room.
     binarize: None, or "otsu" / "adaptive" - every grey-valued page (one channel, or B == G == R everywhere) is thresholded on
-    the device and coded; a page that is not grey-valued gets a ValueError entry."""
+    the device and coded; a page that is not grey-valued gets a ValueError entry.
+    despeckle: False, True, an int or {"black": n, "white": n} (yomitoku_amd/despeckle.py: check_despeckle) - the specks and
+    pinholes below that size are removed from every page's bits on the device before they are coded, and the entry's
+    `despeckled` says how many; anything else is a ValueError before any device work.  With it a two-valued page's file is no
+    longer lossless."""
+    from . import despeckle as specks
+
+    clean = specks.check_despeckle(despeckle)
     if binarize is not None and not (isinstance(binarize, str) and binarize in BINARIZE_MODES):
         raise ValueError(f"unknown bilevel method {binarize!r}: None, 'otsu' or 'adaptive'")
     scratch = {} if scratch is None else scratch
@@ -255,19 +271,22 @@ def encode_g4_pages(pages: Sequence, stream=None, scratch: Optional[dict] = None
         which = [j for j in range(len(devs)) if two[j]]
         if not which:
             return out
-        # launch Group 4, then one wait, one gather, the entries
+        # despeckle the pages that qualify in place; launch Group 4; then one wait, one gather, the entries
+        if clean is not None:
+            pin_cc = to_pinned(scratch, "cc_pin_counts", specks.launch(test, which, clean, scratch), 4 * len(which))
         files, offsets, lengths = launch_encode(test, which, scratch)
         pin_len = to_pinned(scratch, "g4_pin_lengths", lengths, len(which))
         torch.cuda.current_stream().synchronize()
         sizes = pin_len[: len(which)].tolist()
-        for (j, data) in zip(which, gather_files([(files, offsets[i], sizes[i]) for i in range(len(which))], scratch, "g4_pin_bytes")):
-            out[live[j]] = bilevel_entry(devs[j], data, live[j], binarize or "auto", thresholds[j])
+        went = [None] * len(which) if clean is None else [specks.result(clean, four) for four in pin_cc[: 4 * len(which)].view(-1, 4).tolist()]
+        for i, (j, data) in enumerate(zip(which, gather_files([(files, offsets[i], sizes[i]) for i in range(len(which))], scratch, "g4_pin_bytes"))):
+            out[live[j]] = bilevel_entry(devs[j], data, live[j], binarize or "auto", thresholds[j], went[i])
     return out
 
 
-def bilevel_entry(page: torch.Tensor, data: Optional[bytes], k: int, method: str = "auto", threshold: Optional[int] = None):
+def bilevel_entry(page: torch.Tensor, data: Optional[bytes], k: int, method: str = "auto", threshold: Optional[int] = None, despeckled=None):
     """A page's entry from its file's bytes; None (a length of -1: by the slot bound that cannot be) is a YmkError."""
     if data is None:
         return _lib.YmkError(f"page {k}: the Group 4 file does not fit its capacity")
-    return EncodedBilevel(data, int(page.shape[1]), int(page.shape[0]), 1.0, method, threshold)
+    return EncodedBilevel(data, int(page.shape[1]), int(page.shape[0]), 1.0, method, threshold, despeckled)
 

@@ -1,4 +1,4 @@
-"""What the page-file modules (jpeg.py, ccitt.py, mrc.py, deskew.py) share: how a call's pages get onto the device, the scratch
+"""What the page-file modules (jpeg.py, ccitt.py, mrc.py, deskew.py, despeckle.py) share: how a call's pages get onto the device, the scratch
 buffers a caller keeps between calls, and the way an answer or the files' bytes reach the host - through pinned memory, behind
 one wait."""
 
@@ -18,7 +18,8 @@ MAX_SIDE = 16383
 # The scratch keys that more than one module uses.  A scratch dict belongs to one stream at a time (serve: one per wave slot,
 # used by the render thread; the page-skew step: one, on the copy stream), so the steps that share a buffer are serialised:
 #   PACKED_ROWS  the pages' rows as bits.  Written by ccitt.start_test / start_binarize, by mrc.launch (the ink - under `bilevel`
-#                into the test's own buffer, behind its wait) and by deskew.launch; read by ccitt.launch_encode.
+#                into the test's own buffer, behind its wait) and by deskew.launch; rewritten in place by despeckle.launch (whose
+#                labels and areas are keys of its own); read by ccitt.launch_encode.
 #   SUMMED_AREA  the "adaptive" rule's summed-area tables.  Written and read inside ccitt.start_binarize, mrc.launch and
 #                deskew.launch, each done with it before the next launch of the stream starts.
 #   LUMA_PLANE   the luminance planes of colour pages.  Written and read inside mrc.launch and deskew.launch, likewise.

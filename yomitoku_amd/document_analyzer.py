@@ -99,7 +99,7 @@ class OCR(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False, jpeg_mrc=False):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False):
         """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
         arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
         yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
@@ -116,8 +116,8 @@ class OCR(StageAnalyzer):
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
         without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"), `jpeg_mrc`
-        (False, True or the cells), `deskew`: as DocumentAnalyzer.serve."""
-        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
+        (False, True or the cells), `jpeg_despeckle` (False, True, an int or the sizes), `deskew`: as DocumentAnalyzer.serve."""
+        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle)  # before the pipeline is built or a source read
         deskew = check_deskew(deskew) or False
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
@@ -566,7 +566,7 @@ class DocumentAnalyzer(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False, jpeg_mrc=False):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -620,8 +620,15 @@ class DocumentAnalyzer(StageAnalyzer):
         page, the paper as a JPEG of one pixel per `bg_cell` x `bg_cell` pixels, the ink's colour as one per `fg_cell` x `fg_cell` -
         which `searchable_pdf_bytes` embeds as three images, the foreground painted through the mask.  Such a page is never
         resized (`scale` 1.0); `jpeg_optimize` and `jpeg_subsampling` apply to its two layer files, `jpeg_grey` does not.  A blank
-        page, or one that is all ink, keeps its plain file.  OCR and layout see the page as it arrived; only the file changes."""
-        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc)  # before the pipeline is built or a source read
+        page, or one that is all ink, keeps its plain file.  OCR and layout see the page as it arrived; only the file changes.
+        `jpeg_despeckle`: False, True (4 and 4), an int n, or a dict with `black` and / or `white` (a missing one is 0), each
+        0..65535 and not both 0; anything else, the switch without `jpeg`, and the switch with `jpeg_bilevel=False` (there is no
+        Group 4 file to clean) is a ValueError before a source is read.  Every page that gets a Group 4 file of its own has its
+        8-connected black components of fewer than `black` pixels cleared, then its 4-connected white components of fewer than
+        `white` pixels filled, on the device before it is coded (yomitoku_amd/despeckle.py; DESIGN.md, "Despeckled pages"):
+        paper grain and dust cost T.6 most of a noisy page's bytes.  `EncodedBilevel.despeckled` says what went.  With
+        `jpeg_bilevel="auto"` the file is then no longer lossless.  OCR and layout see the page as it arrived."""
+        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle)  # before the pipeline is built or a source read
         deskew = check_deskew(deskew) or False
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)

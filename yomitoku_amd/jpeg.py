@@ -36,6 +36,9 @@ from this encoder, which takes the layers as pages like any other.
 The options are checked in one place, `page_files`, which makes a `PageFiles` of them (serve: `check_jpeg_preset`, the job's
 `wave.job.files`); `encode_page_files(pages, files)` is the worker behind every entry, the list of its phases: sort the pages,
 make up the JPEG batch, launch JPEG, launch Group 4, one wait and one gather.
+
+`despeckle=True` (serve: `jpeg_despeckle=True`) removes the specks and pinholes of fewer than 4 pixels from every page that gets a
+Group 4 file, on the device, before it is coded (yomitoku_amd/despeckle.py); `EncodedBilevel.despeckled` says what went.
 """
 
 from __future__ import annotations
@@ -49,6 +52,7 @@ import numpy as np
 import torch
 
 from . import _lib, ccitt, imaging
+from . import despeckle as specks
 from . import mrc as layered
 from .devpages import addr_words, entered, gather_files, grown, shape_args, to_pinned
 from .devpages import addr_words as _addr_words  # noqa: F401 - tools/jpeg_serve_timing.py takes it from here
@@ -256,7 +260,7 @@ def grey_pages(pages: Sequence[torch.Tensor], scratch: Optional[dict] = None) ->
 
 @dataclass(frozen=True)
 class PageFiles:
-    """What a job wants of its page files: the checked form of `encode_jpeg_pages`' and `serve`'s six options (`page_files`)."""
+    """What a job wants of its page files: the checked form of `encode_jpeg_pages`' and `serve`'s seven options (`page_files`)."""
 
     preset: str  # a name of IMAGE_QUALITY_PRESETS
     optimize: bool
@@ -264,9 +268,11 @@ class PageFiles:
     grey: Union[bool, str]  # False | "auto"
     bilevel: Union[bool, str]  # False | "auto" | "otsu" | "adaptive"
     mrc: Optional[dict]  # None, or check_mrc's full dict
+    despeckle: Optional[dict] = None  # None, or check_despeckle's {"black": n, "white": n}
 
 
-def page_files(preset, optimize=False, subsampling="4:2:0", grey=False, bilevel=False, mrc=False, serve=False) -> Optional[PageFiles]:
+def page_files(preset, optimize=False, subsampling="4:2:0", grey=False, bilevel=False, mrc=False, serve=False,
+               despeckle=False) -> Optional[PageFiles]:
     """The PageFiles of a call's options - the one place they are checked; every refusal is a ValueError.  serve: the reading of
     the `serve()` entries - `preset` None: no page files (-> None), which every other option then has to agree with by
     standing at its default; `subsampling` None: 4:2:0."""
@@ -289,16 +295,24 @@ def page_files(preset, optimize=False, subsampling="4:2:0", grey=False, bilevel=
     cells = layered.check_mrc(mrc)
     if cells is not None and preset is None:
         raise ValueError(f"jpeg_mrc={mrc!r} needs jpeg=...: there are no page files to write that way")
-    return None if preset is None else PageFiles(preset, bool(optimize), subsampling, grey, bilevel, cells)
+    clean = specks.check_despeckle(despeckle)
+    if clean is not None and preset is None:
+        raise ValueError(f"jpeg_despeckle={despeckle!r} needs jpeg=...: there are no page files to write that way")
+    if clean is not None and bilevel is False:
+        raise ValueError(f"jpeg_despeckle={despeckle!r} needs jpeg_bilevel=...: there is no Group 4 file to clean")
+    return None if preset is None else PageFiles(preset, bool(optimize), subsampling, grey, bilevel, cells, clean)
 
 
-def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, jpeg_mrc=False):
+def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, jpeg_mrc=False,
+                      jpeg_despeckle=False):
     """`jpeg` of a serve() call: None (-> None) or a preset name of the searchable PDF (-> the job's PageFiles); anything else is
     a ValueError - raised by the public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0",
     "4:2:2", "4:4:4"), `jpeg_grey` (False, "auto"), `jpeg_bilevel` (False, "auto", "otsu", "adaptive") and `jpeg_mrc` (False, True
     or a dict of cells: yomitoku_amd/mrc.py, check_mrc) ask for something of those files: a value that is none of these is a
-    ValueError, and so is any of the five without `jpeg`."""
-    return page_files(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, serve=True)
+    ValueError, and so is any of the five without `jpeg`.  `jpeg_despeckle` (False, True, an int or a dict of sizes:
+    yomitoku_amd/despeckle.py, check_despeckle) cleans the Group 4 files' bits: a value that is none of these, the switch without
+    `jpeg`, and the switch with `jpeg_bilevel=False` - there is no Group 4 file to clean - are ValueErrors."""
+    return page_files(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, serve=True, despeckle=jpeg_despeckle)
 
 
 def launch_encode(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]], optimize: bool,
@@ -342,6 +356,7 @@ class _Page:
     kind: str = "jpeg"  # what it becomes: "jpeg" | "group4" | "layered"
     scale: float = 1.0
     threshold: Optional[int] = None  # Otsu's, of a thresholded page
+    despeckled: Optional[specks.Despeckled] = None  # of a despeckled Group 4 page
     layer: Optional[int] = None  # a layered page's place in the separation
     jpeg_at: Optional[int] = None  # its place in the JPEG batch; a layered page: its foreground's, the background follows
     g4_at: Optional[int] = None  # its - or its mask's - place in the Group 4 batch
@@ -434,7 +449,7 @@ def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_gr
         if p.kind == "jpeg":
             out[p.k] = jpeg_entry(p.jpeg_at, p.k, p.scale)
         elif p.kind == "group4":
-            out[p.k] = ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, files.bilevel, p.threshold)
+            out[p.k] = ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, files.bilevel, p.threshold, p.despeckled)
         else:
             parts = [ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, "adaptive"),
                      jpeg_entry(p.jpeg_at, p.k, 1.0, "the foreground's file"), jpeg_entry(p.jpeg_at + 1, p.k, 1.0, "the background's file")]
@@ -445,7 +460,9 @@ def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_gr
 
 def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: Optional[dict] = None,
                       capacities: Optional[Sequence[int]] = None) -> list:
-    """`encode_jpeg_pages` with its options as a PageFiles (serve: the job's): one entry per page, in order."""
+    """`encode_jpeg_pages` with its options as a PageFiles (serve: the job's): one entry per page, in order.  `files.despeckle`
+    cleans every page of kind "group4", the "auto" pages included: the switch is the caller's decision about the job, and "auto"
+    with it is no longer lossless."""
     preset = IMAGE_QUALITY_PRESETS[files.preset]
     quality, long_side = int(preset["jpeg_quality"]), preset["max_long_side"]
     scratch = {} if scratch is None else scratch
@@ -455,6 +472,10 @@ def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: O
         batch = [_Page(k, dev, long_side is not None and max(int(dev.shape[0]), int(dev.shape[1])) > long_side) for k, dev in zip(live, devs)]
         # 1. sort: `bilevel`'s test (and the grey test, where no page is resized) and its wait; `mrc`'s separation and its wait
         test, sep, early_grey = _sort(batch, files, scratch)
+        # 1b. `despeckle`: the Group 4 pages' bits cleaned in place, behind the wait that says which they are; no wait of its own
+        two = [j for j, p in enumerate(batch) if p.kind == "group4"] if files.despeckle is not None else []
+        if two:
+            cc_pin = to_pinned(scratch, "cc_pin_counts", specks.launch(test, two, files.despeckle, scratch), 4 * len(two))
         # 2. the JPEG batch: resize, the grey test (its own wait unless it ran early), the layers behind the plain pages
         jdevs, caps, as_grey = _jpeg_batch(batch, files, long_side, sep, early_grey, capacities, scratch)
         # 3. launch JPEG; the lengths go to the host first (one small copy), the bytes, packed on the device, in the gather
@@ -471,6 +492,8 @@ def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: O
         # 5. one wait for the lengths, one gather of the bytes (its own wait), the entries
         torch.cuda.current_stream().synchronize()
         sizes = pin_len[: len(jdevs)].tolist() if jdevs else []
+        for j, four in zip(two, cc_pin[: 4 * len(two)].view(-1, 4).tolist() if two else []):
+            batch[j].despeckled = specks.result(files.despeckle, four)
         parts = [(jpegs, offsets[i], sizes[i]) for i in range(len(jdevs))]
         if which:
             parts += [(g4s, g4_offsets[i], n) for i, n in enumerate(g4_pin[: len(which)].tolist())]
@@ -480,7 +503,7 @@ def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: O
 
 def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
                       capacities: Optional[Sequence[int]] = None, optimize: bool = False, subsampling: str = "4:2:0",
-                      grey=False, bilevel=False, mrc=False) -> list:
+                      grey=False, bilevel=False, mrc=False, despeckle=False) -> list:
     """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
     file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
     stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
@@ -508,8 +531,15 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     separation is launched behind `bilevel`'s wait and has one wait of its own, for its flags: with both switches on that is one
     further wait; the layers then join the JPEG launches and the masks the Group 4 launches, and the files come back in the same
     two copies.
+    despeckle: False, True (4 and 4), an int or {"black": n, "white": n} (yomitoku_amd/despeckle.py: check_despeckle) - every
+    page that gets a Group 4 file of its own, the "auto" pages included, has its 8-connected black components of fewer than
+    `black` pixels cleared and then its 4-connected white components of fewer than `white` pixels filled, on the device,
+    between the threshold and the coder; the entry's `despeckled` says how many.  It is the caller's decision about the job:
+    bilevel="auto" with the switch is no longer lossless.  It needs `bilevel`; the masks of layered pages are not touched.  Four
+    launches a colour behind `bilevel`'s wait, no wait of its own: the counts come back with the files' lengths.
     Anything else is a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
-    return encode_page_files(pages, page_files(image_quality, optimize, subsampling, grey, bilevel, mrc), stream, scratch, capacities)
+    return encode_page_files(pages, page_files(image_quality, optimize, subsampling, grey, bilevel, mrc, despeckle=despeckle), stream, scratch,
+                             capacities)
 
 
 def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False, subsampling: str = "4:2:0",
