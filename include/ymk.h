@@ -111,7 +111,20 @@ int ymk_dbnet_forward(ymk_model* m, const float* x_dev, int n, int h, int w, flo
  * step loop, no mapped flag, no copy back: in this mode ymk_parseq_forward[_groups] only queues work on the stream and
  * returns without having waited on anything.  (The grouped call hands its row tables to the device through one of 64 slots
  * of pinned memory; it waits - counted in "syncs_in_forward" - only if the copy out of the slot it is about to reuse, issued
- * 64 grouped calls earlier, has still not run.) */
+ * 64 grouped calls earlier, has still not run.)
+ *
+ * Retired rows - the model parameter "retire_rows" = 1 (default 0; any other value is refused by ymk_model_finalize): a row
+ * leaves the greedy loop after the step whose raw arg-max is ITS <eos>, instead of running until the slowest row of its
+ * mini-batch stops: it is no longer embedded, attended, fed forward or multiplied by the vocabulary head.  The refinement
+ * masks every context token from a row's first <eos> on, so with the switch on these are what they are with it off: the token
+ * ids up to and including each row's first <eos>, the score over them, *out_len and *ar_steps.  What changes: the repetition
+ * detector no longer runs on a row behind its <eos>, so logits behind a row's first <eos> carry no repetition cut (the +-30
+ * row); and the tokens behind an <eos> enter the max|x| record of the refinement's K|V projection, so refined logits may
+ * differ in their last bits (the 2^-21 of the fp16-plane products).  A row the repetition detector stopped is not retired:
+ * its arg-maxes stay context of the refinement, as before.  The switch acts where the loop's only products are its tokens:
+ * the fused decoder step (decoder width <= 256) with refine_iters >= 1 and the row-max head.  It is accepted and ignored with
+ * refine_iters = 0, under ymk_debug_option("parseq_no_rowmax", 1), on the per-operator decoder path of the wider models and
+ * with "decode_ar" = 0. */
 int ymk_parseq_dims(ymk_model* m, int* num_steps, int* num_classes);
 int ymk_parseq_forward(ymk_model* m, const float* x_dev, int b, int w, float* logits_dev, int* out_len, int* ar_steps,
                        void* stream);
@@ -835,7 +848,18 @@ int ymk_op_dbnet_asf(const float* ax_dev, const float* fuse_dev, int n, int h, i
  *   ld_b floats; partials = 1: c <= 256 (max, column-as-int-bits) pairs, lowest column among equal maxima) -> raw[i][step]; for
  *   step + 1 < num_steps the next context token tok[i][step + 1] - <eos> instead when the repetition detector (rep_on, periods
  *   1..period_max, a run of min_run_p1 for period 1, min_repeats units otherwise) fires on tok[i][1..step + 1]; state [b][4] =
- *   {has_eos, rep_done, rep_cut (-1 none), unused}.  prev_not_done / gid / gopen as above (a frozen row only gets raw = eos).
+ *   {has_eos, rep_done, rep_cut (-1 none), retired}.  prev_not_done / gid / gopen as above (a frozen row only gets raw = eos).
+ * greedy_step_retire: the same launch with the model parameter "retire_rows" as an argument (0: greedy_step).  1: a row whose
+ *   raw arg-max of this step is <eos> gets state[i][3] = 1 and is frozen from the next step on, whatever its mini-batch does:
+ *   raw = eos, no token, no repetition-detector advance, no vote in *not_done / gopen.  A row that only the repetition detector
+ *   stopped (has_eos set, arg-max not <eos>) is not retired.
+ * parseq_dec_step_state: parseq_dec_step with the greedy kernel's state [b][4] (may be null): a row whose state[i][3] != 0 is
+ *   treated as a frozen row is (neither out nor skv written; a block of such rows only returns).
+ * rowmax_head: the greedy loop's vocabulary head, pairs [m][2 * ceil(cout / 64)] = per 64-column tile (max, column-as-int-bits)
+ *   of x [m][k] . w_host[cout][k]^T + bias_host (may be null); k % 4 == 0.  split 0: exact fp32 (64-row tiles); 16: the fp16-split
+ *   form with amax_in_dev = the record of x (128-row tiles where the launch fills the chip).  An M tile is skipped (its pairs
+ *   keep their contents) when none of its rows is needed: row i is needed when group_open[row_group[i]] != 0 (both or neither;
+ *   absent = needed) and row_dead[i * row_dead_ld] == 0 (may be null).  Uploads the weights and waits for the stream.
  * refine_prep: tok2[i][t] = t == 0 ? bos : raw[i][t - 1], kpm[i][t] = an <eos> at or before t in tok2, or t >= gsteps[gid[i]]
  *   (gid / gsteps: both or neither), for t < s_len <= ld_tok; kpm is [b][ld_tok] bytes.
  * rep_cut: for rows with 0 <= state[i][2] < s_len: logits[i][cut][:] = -30, [eos_id] = +30 (logits [b][ld_b], ld_b >= s_len * c).
@@ -857,6 +881,22 @@ int ymk_op_parseq_dec_step(int d, int heads, int f, const float* sa_in_w_host, c
 int ymk_op_greedy_step(const float* logits_dev, int64_t ld_b, int c, int step, int num_steps, int* tok_dev, int* raw_dev, int ld_tok,
                        int* state_dev, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats, int* not_done_dev,
                        const int* prev_not_done_dev, const int* gid_dev, int* gopen_dev, int ng, int partials, int b, void* stream);
+int ymk_op_greedy_step_retire(const float* logits_dev, int64_t ld_b, int c, int step, int num_steps, int* tok_dev, int* raw_dev,
+                              int ld_tok, int* state_dev, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats,
+                              int* not_done_dev, const int* prev_not_done_dev, const int* gid_dev, int* gopen_dev, int ng, int partials,
+                              int retire_rows, int b, void* stream);
+int ymk_op_parseq_dec_step_state(int d, int heads, int f, const float* sa_in_w_host, const float* sa_in_b_host,
+                                 const float* sa_out_w_host, const float* sa_out_b_host, const float* ca_in_w_host,
+                                 const float* ca_in_b_host, const float* ca_out_w_host, const float* ca_out_b_host,
+                                 const float* lin1_w_host, const float* lin1_b_host, const float* lin2_w_host, const float* lin2_b_host,
+                                 const float* const* ln_host, const float* emb_host, int ntok, const float* posq_host,
+                                 const float* qsa_host, const int* tok_dev, float* skv_dev, const float* memkv_dev,
+                                 const int* mem_off_dev, const int* mem_len_dev, const int* prev_not_done_dev, const int* gid_dev,
+                                 const int* gopen_dev, int ng, const int* state_dev, int step, int b, int l, int ns, float* out_dev,
+                                 void* stream);
+int ymk_op_rowmax_head(const float* x_dev, int m, int k, const float* w_host, int cout, const float* bias_host, int split,
+                       const int* row_group_dev, const int* group_open_dev, const int* row_dead_dev, int row_dead_ld,
+                       const unsigned* amax_in_dev, float* pairs_dev, void* stream);
 int ymk_op_refine_prep(const int* raw_dev, int ld_tok, int s_len, int bos_id, int eos_id, int* tok2_dev, unsigned char* kpm_dev, int b,
                        const int* gid_dev, const int* gsteps_dev, void* stream);
 int ymk_op_rep_cut(float* logits_dev, int64_t ld_b, int c, int s_len, const int* state_dev, int eos_id, int b, void* stream);

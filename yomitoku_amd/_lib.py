@@ -220,6 +220,20 @@ SIGNATURES = {
         [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
          c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p],
     ),
+    "ymk_op_greedy_step_retire": (
+        c_int,
+        [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    ),
+    "ymk_op_parseq_dec_step_state": (
+        c_int,
+        [c_int, c_int, c_int] + [c_void_p] * 12 + [POINTER(c_void_p), c_void_p, c_int, c_void_p, c_void_p]
+        + [c_void_p] * 8 + [c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    ),
+    "ymk_op_rowmax_head": (
+        c_int,
+        [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    ),
     "ymk_op_refine_prep": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ymk_op_rep_cut": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "ymk_op_row_argmax": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -796,6 +796,21 @@ int ymk_op_parseq_dec_step(int d, int heads, int f, const float* sa_in_w_host, c
                            const float* memkv_dev, const int* mem_off_dev, const int* mem_len_dev, const int* prev_not_done_dev,
                            const int* gid_dev, const int* gopen_dev, int ng, int step, int b, int l, int ns, float* out_dev,
                            void* stream) {
+  return ymk_op_parseq_dec_step_state(d, heads, f, sa_in_w_host, sa_in_b_host, sa_out_w_host, sa_out_b_host, ca_in_w_host, ca_in_b_host,
+                                      ca_out_w_host, ca_out_b_host, lin1_w_host, lin1_b_host, lin2_w_host, lin2_b_host, ln_host, emb_host,
+                                      ntok, posq_host, qsa_host, tok_dev, skv_dev, memkv_dev, mem_off_dev, mem_len_dev, prev_not_done_dev,
+                                      gid_dev, gopen_dev, ng, /*state_dev=*/nullptr, step, b, l, ns, out_dev, stream);
+}
+
+int ymk_op_parseq_dec_step_state(int d, int heads, int f, const float* sa_in_w_host, const float* sa_in_b_host,
+                                 const float* sa_out_w_host, const float* sa_out_b_host, const float* ca_in_w_host,
+                                 const float* ca_in_b_host, const float* ca_out_w_host, const float* ca_out_b_host,
+                                 const float* lin1_w_host, const float* lin1_b_host, const float* lin2_w_host, const float* lin2_b_host,
+                                 const float* const* ln_host, const float* emb_host, int ntok, const float* posq_host,
+                                 const float* qsa_host, const int* tok_dev, float* skv_dev, const float* memkv_dev,
+                                 const int* mem_off_dev, const int* mem_len_dev, const int* prev_not_done_dev, const int* gid_dev,
+                                 const int* gopen_dev, int ng, const int* state_dev, int step, int b, int l, int ns, float* out_dev,
+                                 void* stream) {
   YMK_API_BEGIN
   using namespace ymk;
   // refused before anything is uploaded or launched (parseq_dec_step checks again)
@@ -823,7 +838,7 @@ int ymk_op_parseq_dec_step(int d, int heads, int f, const float* sa_in_w_host, c
   w.n2g = pool.upload(ln_host[6], d); w.n2b = pool.upload(ln_host[7], d);
   w.dng = pool.upload(ln_host[8], d); w.dnb = pool.upload(ln_host[9], d);
   parseq_dec_step(s, w, tok_dev, ns, step, skv_dev, ns, memkv_dev, l, mem_off_dev, mem_len_dev, out_dev, prev_not_done_dev, b, gid_dev,
-                  gopen_dev, ng);
+                  gopen_dev, ng, state_dev);
   YMK_HIP(hipStreamSynchronize(s));  // pool frees the weights on return
   YMK_API_END
 }
@@ -831,7 +846,17 @@ int ymk_op_parseq_dec_step(int d, int heads, int f, const float* sa_in_w_host, c
 int ymk_op_greedy_step(const float* logits_dev, int64_t ld_b, int c, int step, int num_steps, int* tok_dev, int* raw_dev, int ld_tok,
                        int* state_dev, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats, int* not_done_dev,
                        const int* prev_not_done_dev, const int* gid_dev, int* gopen_dev, int ng, int partials, int b, void* stream) {
+  return ymk_op_greedy_step_retire(logits_dev, ld_b, c, step, num_steps, tok_dev, raw_dev, ld_tok, state_dev, eos_id, rep_on, period_max,
+                                   min_run_p1, min_repeats, not_done_dev, prev_not_done_dev, gid_dev, gopen_dev, ng, partials,
+                                   /*retire_rows=*/0, b, stream);
+}
+
+int ymk_op_greedy_step_retire(const float* logits_dev, int64_t ld_b, int c, int step, int num_steps, int* tok_dev, int* raw_dev,
+                              int ld_tok, int* state_dev, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats,
+                              int* not_done_dev, const int* prev_not_done_dev, const int* gid_dev, int* gopen_dev, int ng, int partials,
+                              int retire_rows, int b, void* stream) {
   YMK_API_BEGIN
+  YMK_CHECK(retire_rows == 0 || retire_rows == 1, "greedy_step: retire_rows is 0 or 1");
   YMK_CHECK(logits_dev && tok_dev && raw_dev && state_dev && not_done_dev && b >= 1 && c >= 1, "greedy_step: bad argument");
   YMK_CHECK(step >= 0 && step < num_steps && num_steps <= ld_tok, "greedy_step: 0 <= step < num_steps <= ld_tok");
   YMK_CHECK(ld_b >= (int64_t)c * (partials ? 2 : 1), "greedy_step: rows overlap");
@@ -840,7 +865,28 @@ int ymk_op_greedy_step(const float* logits_dev, int64_t ld_b, int c, int step, i
   YMK_CHECK(period_max >= 0, "greedy_step: period_max >= 0");
   ymk::greedy_step((hipStream_t)stream, logits_dev, (long)ld_b, c, step, num_steps, tok_dev, raw_dev, ld_tok, state_dev, eos_id, rep_on,
                    period_max, min_run_p1, min_repeats, not_done_dev, prev_not_done_dev, /*arrived=*/nullptr, /*host_flag=*/nullptr, b,
-                   gid_dev, gopen_dev, ng, partials);
+                   gid_dev, gopen_dev, ng, partials, retire_rows);
+  YMK_API_END
+}
+
+int ymk_op_rowmax_head(const float* x_dev, int m, int k, const float* w_host, int cout, const float* bias_host, int split,
+                       const int* row_group_dev, const int* group_open_dev, const int* row_dead_dev, int row_dead_ld,
+                       const unsigned* amax_in_dev, float* pairs_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_dev && w_host && pairs_dev && m > 0 && k > 0 && k % 4 == 0 && cout > 0, "rowmax_head: bad argument");
+  YMK_CHECK((row_group_dev == nullptr) == (group_open_dev == nullptr), "rowmax_head: row_group and group_open come in pairs");
+  YMK_CHECK(row_dead_dev == nullptr || row_dead_ld >= 1, "rowmax_head: row_dead_ld >= 1");
+  YMK_CHECK(split == 0 || (split == SPLIT_F16X2 && amax_in_dev != nullptr), "rowmax_head: split is 0 or 16 (with the input's record)");
+  hipStream_t s = (hipStream_t)stream;
+  DevicePool pool;
+  const ConvW cw = op_conv_weight(pool, w_host, cout, k, 1, 1, false, nullptr, bias_host);
+  SplitCtxOwner split_ctx;
+  ConvSplitScope scope(split, split_ctx.get(), 0);
+  const int tiles = (cout + ROWMAX_TILE_N - 1) / ROWMAX_TILE_N;
+  gemm(s, x_dev, m, k, k, cw, ACT_NONE, nullptr, 0, pairs_dev, 2 * tiles, row_group_dev, group_open_dev, EPI_ROWMAX, amax_in_dev, nullptr,
+       row_dead_dev, row_dead_ld);
+  YMK_HIP(hipStreamSynchronize(s));  // pool frees the weights on return
   YMK_API_END
 }
 

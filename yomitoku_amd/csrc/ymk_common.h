@@ -262,6 +262,10 @@ struct ConvArgs {
   // all of whose rows sit in groups with group_open[g] == 0 is not computed (its outputs keep their old contents)
   const int* row_group = nullptr;
   const int* group_open = nullptr;
+  // ... and rows that are not needed on their own account (PARSeq "retire_rows"): row m with row_dead[m * row_dead_ld] != 0
+  // counts as not needed whatever its group says; either predicate may come alone
+  const int* row_dead = nullptr;
+  int row_dead_ld = 1;
   // max|x| records for callers without Tensor objects (gemm): of the input (filled by its producer) / to fill for the output
   const unsigned* amax_in = nullptr;
   unsigned* amax_out = nullptr;
@@ -331,7 +335,7 @@ bool conv_planes_pair_ok(const Tensor& in, const ConvW& w1, const ConvArgs& a1, 
 // `res_ld == 0` broadcasts one residual row to every m.
 void gemm(hipStream_t s, const float* A, int M, int K, int lda, const ConvW& w, int act, const float* res, int res_ld,
           float* out, int out_ld, const int* row_group = nullptr, const int* group_open = nullptr, int epi = EPI_STORE,
-          const unsigned* amax_in = nullptr, unsigned* amax_out = nullptr);
+          const unsigned* amax_in = nullptr, unsigned* amax_out = nullptr, const int* row_dead = nullptr, int row_dead_ld = 1);
 
 // out[m][:] = act(LayerNorm(X[m][:]; gamma, beta, eps) . W^T * scale + bias + res[m][:]) in ONE launch, the normalised rows never
 // written (conv_f16_astat<.., LN>, ymk_conv_astat.hip: fp16-split mode, K = 128 / 192, a launch that fills the chip).

@@ -729,6 +729,8 @@ static bool conv2d_impl(hipStream_t s, const Tensor& in, const ConvW& w, const C
   k.epi = a.epi;
   k.row_group = a.row_group;
   k.group_open = a.group_open;
+  k.row_dead = a.row_dead;
+  k.row_dead_ld = a.row_dead_ld;
   k.amax = in.amax ? in.amax : a.amax_in;
   k.amax_out = a.epi == EPI_ROWMAX ? nullptr : (out.amax ? out.amax : a.amax_out);
   YMK_CHECK((a.row_group == nullptr) == (a.group_open == nullptr), "conv: row_group and group_open come together");
@@ -822,7 +824,7 @@ static bool conv2d_impl(hipStream_t s, const Tensor& in, const ConvW& w, const C
 bool conv_planes_pair_ok(const Tensor& in, const ConvW& w1, const ConvArgs& a1, const ConvW& w2, const ConvArgs& a2) {
   if (conv_effective_split() != SPLIT_F16X2 || t_split_ctx == nullptr) return false;
   if (w1.mode != 0 || w2.mode != 0 || a1.epi != EPI_STORE || a2.epi != EPI_STORE || a1.res != nullptr) return false;
-  if (a1.row_group != nullptr || a2.row_group != nullptr || a1.ln_g != nullptr) return false;
+  if (a1.row_group != nullptr || a2.row_group != nullptr || a1.row_dead != nullptr || a2.row_dead != nullptr || a1.ln_g != nullptr) return false;
   if (a1.act != ACT_NONE && a1.act != ACT_RELU && a1.act != ACT_SILU && a1.act != ACT_GELU) return false;
   if (w1.cout % 32 != 0 || w2.cin != w1.cout || w2.kh * w2.kw <= 1 || in.planes) return false;
   const int sw1 = a1.stride_w > 0 ? a1.stride_w : a1.stride, sw2 = a2.stride_w > 0 ? a2.stride_w : a2.stride;
@@ -866,7 +868,8 @@ bool vit_mlp_fused(hipStream_t s, float* x, int M, int ld, const float* ln_g, co
 }
 
 void gemm(hipStream_t s, const float* A, int M, int K, int lda, const ConvW& w, int act, const float* res, int res_ld,
-          float* out, int out_ld, const int* row_group, const int* group_open, int epi, const unsigned* amax_in, unsigned* amax_out) {
+          float* out, int out_ld, const int* row_group, const int* group_open, int epi, const unsigned* amax_in, unsigned* amax_out,
+          const int* row_dead, int row_dead_ld) {
   YMK_CHECK(K == w.cin, "gemm: K " + std::to_string(K) + " != weight in-features " + std::to_string(w.cin));
   // The kernels address their A operand through a buffer descriptor with 32-bit byte offsets (conv2d: "input view must stay
   // below 4 GiB"); a row-major GEMM has no such natural bound - the fc2 input of a 2048-line PARSeq forward is 1.6 M rows x
@@ -886,6 +889,8 @@ void gemm(hipStream_t s, const float* A, int M, int K, int lda, const ConvW& w, 
     a.res = res ? &r : nullptr;
     a.row_group = row_group ? row_group + m0 : nullptr;
     a.group_open = group_open;
+    a.row_dead = row_dead ? row_dead + m0 * (size_t)row_dead_ld : nullptr;
+    a.row_dead_ld = row_dead_ld;
     a.epi = epi;
     a.amax_in = amax_in;
     a.amax_out = amax_out;

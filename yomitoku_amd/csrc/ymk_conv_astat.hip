@@ -150,7 +150,7 @@ __device__ __forceinline__ void astat_rowmax(const ConvK& p, const f32x16 (&acc)
 // a row lives in the two lanes li and li + 32 of its wave, so mean and variance are one xor-shuffle away) - what
 // k_layernorm + this kernel computed through a [M][C] round trip; p.amax is then the LayerNorm's static output bound.
 // RM (BN = 128): the row-max epilogue above instead of stores (the greedy loop's vocabulary head, EPI_ROWMAX), and a block whose
-// 128 rows all belong to finished groups (p.row_group / p.group_open) returns at once
+// 128 rows all belong to finished groups (p.row_group / p.group_open) or are dead themselves (p.row_dead) returns at once
 template <int BN, int KT, bool LN = false, bool RM = false>
 __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* __restrict__ wsplit, unsigned w_bytes) {
   constexpr int TN = BN / 32;
@@ -370,7 +370,7 @@ bool conv2d_f16_astat_can(const ConvK& k, size_t w_bytes) {
   if (k.KH != 1 || k.KW != 1 || k.stride != 1 || k.stride_w != 1 || k.pad != 0) return false;
   if (k.epi == EPI_ROWMAX) {  // the pair table instead of the tile: 128-column blocks, K <= 192, nothing else in the epilogue
     if (k.Kpad > 192 || k.res != nullptr || k.ln_g != nullptr || k.act != ACT_NONE || k.Cout <= 64) return false;
-  } else if (k.epi != EPI_STORE || k.row_group != nullptr) {
+  } else if (k.epi != EPI_STORE || has_row_predicate(k)) {
     return false;
   }
   if (k.Kpad % 32 != 0 || k.Kpad < 32 || k.Kpad > 256 || k.C % 4 != 0 || k.M <= 0) return false;

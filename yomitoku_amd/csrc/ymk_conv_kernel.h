@@ -26,6 +26,8 @@ struct ConvK {
   int vec;      // 1: Cout, leading dims and pointers allow 16 B epilogue accesses
   const int* row_group;   // optional (ConvArgs): row m -> group id ...
   const int* group_open;  // ... and the per-group "still needed" word; M tiles without a needed row return at once
+  const int* row_dead;    // optional (ConvArgs): row m is not needed either when row_dead[m * row_dead_ld] != 0
+  int row_dead_ld;
   int fast;     // ymk_debug_option("conv_fast"), default 27: bit 0 pointwise index shortcut, bit 1 residual prefetch,
                 // bit 2 direct epilogue for every plain store (A/B runs; slower than the staged one where 16-byte stores
                 // are possible), bit 3 swizzled K tiles / three 128 x 64 blocks per CU, bit 4 direct epilogue for the
@@ -47,14 +49,18 @@ struct ConvK {
 // true when some row of the block's M tile [m0, m0 + BM) is still needed (or no row predicate was given); block-uniform
 template <int BM, int NT>
 __device__ __forceinline__ bool tile_needed(const ConvK& p, int m0, int t) {
-  if (!p.row_group) return true;
+  if (!p.row_group && !p.row_dead) return true;
   int live = 0;
   for (int r = t; r < BM; r += NT) {
     const int m = m0 + r;
-    if (m < p.M && p.group_open[p.row_group[m]] != 0) live = 1;
+    if (m < p.M && (!p.row_group || p.group_open[p.row_group[m]] != 0) &&
+        (!p.row_dead || p.row_dead[(size_t)m * p.row_dead_ld] == 0))
+      live = 1;
   }
   return __syncthreads_or(live) != 0;
 }
+// a launch with a row predicate goes to the kernels that test it (tile_needed)
+inline bool has_row_predicate(const ConvK& k) { return k.row_group != nullptr || k.row_dead != nullptr; }
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {

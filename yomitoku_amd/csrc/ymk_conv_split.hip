@@ -748,7 +748,7 @@ bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* c
   bool narrow = false;
   SplitRoute route = ROUTE_STAGED;
   if (code == SPLIT_F16X2) {
-    route = route_f16(RouteQuery{k.M, w.cout, k.Kpad, k.KH * k.KW, rowmax, k.row_group != nullptr, conv2d_f16_astat_can(k, w_bytes_f16),
+    route = route_f16(RouteQuery{k.M, w.cout, k.Kpad, k.KH * k.KW, rowmax, has_row_predicate(k), conv2d_f16_astat_can(k, w_bytes_f16),
                                  k.ln_g != nullptr, planes_io}, tile, narrow);
   } else {  // bf16 evaluation forms: the register-staged kernel, for launches that fill the chip
     const long mt128 = (k.M + 127) / 128;

@@ -30,7 +30,9 @@ bool parseq_dec_step_supported(int D, int H, int F, int L, int NS);
 // longest sample of a ragged batch
 void parseq_dec_step(hipStream_t s, const DecStepW& W, const int* tok, int ld_tok, int step, float* skv, int NS,
                      const float* memkv, int L, const int* mem_off, const int* mem_len, float* out, const int* prev_not_done,
-                     int B, const int* gid = nullptr, const int* gopen = nullptr, int ng = 1);
+                     int B, const int* gid = nullptr, const int* gopen = nullptr, int ng = 1, const int* state = nullptr);
+// state (optional, the greedy kernel's [B][4] words, "retire_rows"): a row whose state[b][3] != 0 has been retired - it is
+// treated as a row of a closed mini-batch is (neither skv nor out written; a block of such rows only returns)
 bool decstep_debug_option(const std::string& key, int value);
 
 }  // namespace ymk

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(NT) void k_parseq_dec_step_rows(DecStepW W, const i
                                                              const int* __restrict__ mem_len, float* __restrict__ out,
                                                              const int* __restrict__ prev_not_done,
                                                              const int* __restrict__ gid, const int* __restrict__ gopen, int ng,
-                                                             int B) {
+                                                             const int* __restrict__ state, int B) {
   if (prev_not_done && *prev_not_done == 0) return;  // speculative step after the batch finished
   constexpr int WPR = NWV / R;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -249,6 +249,9 @@ __global__ __launch_bounds__(NT) void k_parseq_dec_step_rows(DecStepW W, const i
     int live = b < B;
     // grouped forward: the row's mini-batch finished at an earlier step - its own loop would not run this step at all
     if (live && gid && step > 0 && gopen[(size_t)(step - 1) * ng + gid[b]] == 0) live = 0;
+    // "retire_rows": the row's own arg-max was <eos> at an earlier step (k_greedy_step set state[b][3]) - nothing it would
+    // compute from here on reaches a result
+    if (live && state && state[(size_t)b * 4 + 3] != 0) live = 0;
     live_s[t] = live;
   }
   __syncthreads();
@@ -334,7 +337,7 @@ static size_t rows_smem_bytes(int D, int F) {
 template <int R>
 static bool launch_rows(hipStream_t s, const DecStepW& W, const int* tok, int ld_tok, int step, float* skv, int NS,
                         const float* memkv, int L, const int* mem_off, const int* mem_len, float* out, const int* prev_not_done,
-                        int B, const int* gid, const int* gopen, int ng) {
+                        int B, const int* gid, const int* gopen, int ng, const int* state) {
   const size_t bytes = rows_smem_bytes<R>(W.D, W.F);
   // per device: the LDS a workgroup may declare (gfx950: 160 KB; asked of the device, not assumed) minus live_s and
   // alignment slack; 0 = not asked yet, -1 = the attribute could not be raised -> fewer rows per block serve the forward
@@ -355,14 +358,14 @@ static bool launch_rows(hipStream_t s, const DecStepW& W, const int* tok, int ld
   }
   if (cap < 0 || bytes > (size_t)cap) return false;
   hipLaunchKernelGGL(k_parseq_dec_step_rows<R>, dim3((B + R - 1) / R), dim3(NT), bytes, s, W, tok, ld_tok, step, skv, NS, memkv,
-                     L, mem_off, mem_len, out, prev_not_done, gid, gopen, ng, B);
+                     L, mem_off, mem_len, out, prev_not_done, gid, gopen, ng, state, B);
   YMK_HIP(hipGetLastError());
   return true;
 }
 
 void parseq_dec_step(hipStream_t s, const DecStepW& W, const int* tok, int ld_tok, int step, float* skv, int NS,
                      const float* memkv, int L, const int* mem_off, const int* mem_len, float* out, const int* prev_not_done,
-                     int B, const int* gid, const int* gopen, int ng) {
+                     int B, const int* gid, const int* gopen, int ng, const int* state) {
   YMK_CHECK(parseq_dec_step_supported(W.D, W.H, W.F, L, NS), "fused decoder step: unsupported geometry");
   // rows per block, by measurement (one launch per step of the bench's recogniser forwards, rocprofv3; us per step):
   //   rows   150 / 300     655           1234                  2048
@@ -377,7 +380,7 @@ void parseq_dec_step(hipStream_t s, const DecStepW& W, const int* tok, int ld_to
   if (rows <= 0) rows = B > 1536 ? 4 : (B > 320 ? 2 : 1);
   rows = std::min(rows, MAX_ROWS);
 #define YMK_TRY_ROWS(R) \
-  if (rows >= R && launch_rows<R>(s, W, tok, ld_tok, step, skv, NS, memkv, L, mem_off, mem_len, out, prev_not_done, B, gid, gopen, ng)) return
+  if (rows >= R && launch_rows<R>(s, W, tok, ld_tok, step, skv, NS, memkv, L, mem_off, mem_len, out, prev_not_done, B, gid, gopen, ng, state)) return
   YMK_TRY_ROWS(4);
   YMK_TRY_ROWS(3);
   YMK_TRY_ROWS(2);

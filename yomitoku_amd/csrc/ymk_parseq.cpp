@@ -92,6 +92,8 @@ class ParseqModel : public Model {
     YMK_CHECK((int)param("dec_depth", 1) == 1, "only decoder depth 1 is implemented (all shipped configs)");
     decode_ar_ = (int)param("decode_ar", 1);
     YMK_CHECK(decode_ar_ == 0 || decode_ar_ == 1, "decode_ar must be 0 (non-autoregressive) or 1 (greedy autoregressive)");
+    retire_rows_ = (int)param("retire_rows", 0);
+    YMK_CHECK(retire_rows_ == 0 || retire_rows_ == 1, "retire_rows must be 0 (rows run until their mini-batch stops) or 1");
     YMK_CHECK(D_ == Dd_, "encoder and decoder widths must match (cross attention has no kdim)");
     YMK_CHECK(D_ % eh_ == 0 && Dd_ % dh_ == 0, "embed dim must divide by heads");
     C_ = ntok_ - 2;
@@ -455,6 +457,10 @@ class ParseqModel : public Model {
     const bool fused = !nar && parseq_dec_step_supported(D, dh_, lin1_.cout, Lmax, NS) && !parseq_unfused();
     const bool ar_rowmax = fused && refine_ > 0 && !parseq_no_rowmax();
     const int head_tiles = (C + ROWMAX_TILE_N - 1) / ROWMAX_TILE_N;
+    // "retire_rows": a row leaves the greedy loop once its own raw arg-max is <eos> (k_greedy_step).  Only where the loop's sole
+    // products are the `raw` tokens - the fused step with the row-max head and a refinement to follow; elsewhere the steps'
+    // logits are outputs (or there is no loop) and the parameter is ignored.
+    const bool retire = ar_rowmax && retire_rows_ != 0;
     float *qsa = nullptr, *posq_t = nullptr, *cn = nullptr, *skv = nullptr, *qcur = nullptr, *t1 = nullptr, *t2 = nullptr, *hdec = nullptr;
     float *arlog = nullptr, *armax = nullptr;
     int *tok = nullptr, *raw = nullptr, *tok2 = nullptr, *state = nullptr, *not_done = nullptr;
@@ -676,11 +682,13 @@ class ParseqModel : public Model {
         // the whole query stream of step i in one launch, then the vocabulary head as a GEMM
         DecStepW w = fw_;
         w.qsa = qsa;
-        parseq_dec_step(s, w, tok, NS, i, skv, NS, memkv, L, mem_tab.koff, mem_tab.klen, t1, prev, B, gid, gop, ng);
-        // the vocabulary head skips the M tiles whose rows all sit in mini-batches that finished at an earlier step
+        parseq_dec_step(s, w, tok, NS, i, skv, NS, memkv, L, mem_tab.koff, mem_tab.klen, t1, prev, B, gid, gop, ng, retire ? state : nullptr);
+        // the vocabulary head skips the M tiles whose rows all sit in mini-batches that finished at an earlier step or have
+        // been retired (state[b][3]; no row is before step 1)
         const int* open_prev = (gop && i > 0) ? gop + (size_t)(i - 1) * ng : nullptr;
         if (ar_rowmax)
-          gemm(s, t1, B, D, D, head_, ACT_NONE, nullptr, 0, armax, 2 * head_tiles, open_prev ? gid : nullptr, open_prev, EPI_ROWMAX, dn_rec_);
+          gemm(s, t1, B, D, D, head_, ACT_NONE, nullptr, 0, armax, 2 * head_tiles, open_prev ? gid : nullptr, open_prev, EPI_ROWMAX, dn_rec_,
+               nullptr, (retire && i > 0) ? state + 3 : nullptr, 4);
         else
           gemm(s, t1, B, D, D, head_, ACT_NONE, nullptr, 0, arlog + (size_t)i * C, NS * C, open_prev ? gid : nullptr, open_prev, EPI_STORE, dn_rec_);
       } else {
@@ -698,7 +706,7 @@ class ParseqModel : public Model {
       int* in_kernel_flag = (!publish_launch && i + 1 < NS) ? host_flags_dev_ + i : nullptr;
       if (ar_rowmax)
         greedy_step(s, armax, (long)2 * head_tiles, head_tiles, i, NS, tok, raw, NS, state, eos_, rep_on_, rep_pmax_, rep_p1_, rep_min_,
-                    not_done + i, prev, arrived + i, in_kernel_flag, B, gid, gop, ng, 1);
+                    not_done + i, prev, arrived + i, in_kernel_flag, B, gid, gop, ng, 1, retire ? 1 : 0);
       else
         greedy_step(s, arlog + (size_t)i * C, (long)NS * C, C, i, NS, tok, raw, NS, state, eos_, rep_on_, rep_pmax_, rep_p1_,
                     rep_min_, not_done + i, prev, arrived + i, in_kernel_flag, B, gid, gop, ng);
@@ -753,6 +761,7 @@ class ParseqModel : public Model {
   int ph_ = 4, pw_ = 8, img_h_ = 32, img_w_ = 800, D_ = 192, eh_ = 6, depth_ = 12, Dd_ = 192, dh_ = 6;
   static constexpr int NAR_SLOTS = 64;
   int decode_ar_ = 1;
+  int retire_rows_ = 0;
   float *nar_x_ = nullptr, *nar_q_ = nullptr;  // decode_ar = 0: [NS][D] query stream before / queries of the cross attention
   std::array<hipEvent_t, NAR_SLOTS> nar_ev_{};  // decode_ar = 0: behind the table copy out of staging slot i
   std::array<bool, NAR_SLOTS> nar_ev_used_{};

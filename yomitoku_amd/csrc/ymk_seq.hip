@@ -721,7 +721,11 @@ __device__ __forceinline__ void row_reduce_256(const float* __restrict__ row, in
 
 // greedy step (models/parseq.py:222-250): argmax over C of logits[b][step][:], write the raw argmax,
 // the context token for position step+1 (forced to <eos> when a repetition loop is detected), and the
-// per-sample flags; one block per sample.  state[b] = {has_eos, rep_done, rep_cut(-1 = none)}.
+// per-sample flags; one block per sample.  state[b] = {has_eos, rep_done, rep_cut(-1 = none), retired}.
+// retire ("retire_rows"): a row whose RAW arg-max is <eos> at this step is marked retired and is frozen from the next step on,
+// as the rows of a closed mini-batch are.  Everything it would still produce lies behind its first <eos> in `raw`, which the
+// refinement masks (k_refine_prep).  has_eos is NOT the condition: a row the repetition detector stopped holds <eos> in tok but
+// an arg-max in raw, and its later arg-maxes are unmasked context of the refinement - it runs on until its group closes.
 __global__ __launch_bounds__(256) void k_greedy_step(const float* __restrict__ logits, long ld_b, int C, int step,
                                                      int num_steps, int* __restrict__ tok, int* __restrict__ raw,
                                                      int ld_tok, int* __restrict__ state, int eos_id, int rep_on,
@@ -729,14 +733,14 @@ __global__ __launch_bounds__(256) void k_greedy_step(const float* __restrict__ l
                                                      int* __restrict__ not_done, const int* __restrict__ prev_not_done,
                                                      int* __restrict__ arrived, int* __restrict__ host_flag,
                                                      const int* __restrict__ gid, int* __restrict__ gopen, int ng, int partials,
-                                                     int flags) {
+                                                     int flags, int retire) {
   const int b = blockIdx.x, t = threadIdx.x;
   // speculative step issued after every row already held an <eos>: change nothing (not_done stays 0)
   if (prev_not_done && *prev_not_done == 0) return;
   // grouped forward: a row whose mini-batch finished at an earlier step is frozen - its own loop would have stopped
   // there (models/parseq.py:245-250), so neither tokens nor the repetition detector may advance any further
   const int g = gid ? gid[b] : 0;
-  const bool frozen = gid && step > 0 && gopen[(size_t)(step - 1) * ng + g] == 0;
+  const bool frozen = (gid && step > 0 && gopen[(size_t)(step - 1) * ng + g] == 0) || (retire && state[b * 4 + 3] != 0);
   __shared__ float sv[256];
   __shared__ int si[256];
   if (!frozen && !partials) {  // block-uniform
@@ -786,6 +790,7 @@ __global__ __launch_bounds__(256) void k_greedy_step(const float* __restrict__ l
   if (!frozen) {
     const int am = si[0];
     raw[(size_t)b * ld_tok + step] = am;
+    if (retire && am == eos_id) st[3] = 1;
     const int j = step + 1;
     if (j < num_steps) {
       int* trow = tok + (size_t)b * ld_tok;
@@ -863,12 +868,12 @@ void publish_open(hipStream_t s, const int* not_done, const int* prev_not_done, 
 void greedy_step(hipStream_t s, const float* logits, long ld_b, int C, int step, int num_steps, int* tok, int* raw,
                  int ld_tok, int* state, int eos_id, int rep_on, int period_max, int min_run_p1, int min_repeats,
                  int* not_done, const int* prev_not_done, int* arrived, int* host_flag, int B, const int* gid, int* gopen,
-                 int ng, int partials) {
+                 int ng, int partials, int retire_rows) {
   // host_flag null: the open-row words are flags and publish_open reports the step; non-null: they count and the kernel reports
   YMK_CHECK(!partials || C <= 256, "greedy step: at most 256 partial (max, column) pairs per row");
   hipLaunchKernelGGL(k_greedy_step, dim3(B), dim3(256), 0, s, logits, ld_b, C, step, num_steps, tok, raw, ld_tok, state,
                      eos_id, rep_on, period_max, min_run_p1, min_repeats, not_done, prev_not_done, arrived, host_flag, gid,
-                     gopen, ng, partials, host_flag == nullptr ? 1 : 0);
+                     gopen, ng, partials, host_flag == nullptr ? 1 : 0, retire_rows);
   YMK_HIP(hipGetLastError());
 }
 

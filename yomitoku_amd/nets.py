@@ -255,6 +255,10 @@ class PARSeq(HipNet):
         self.tokenizer = None
         self.export_onnx = False
         self.refine_iters = int(_cfg_get(cfg, "refine_iters", 1))
+        # 1: a row leaves the greedy loop once its own arg-max is <eos> (include/ymk.h, "retire_rows").  Logits behind a row's
+        # first <eos> then carry no repetition cut, so a net built directly keeps 0; TextRecognizer, which reads token ids and
+        # scores up to the first <eos> only, turns it on before the handle is built
+        self.retire_rows = int(_cfg_get(cfg, "retire_rows", 0))
         self.last_ar_steps = 0
 
     def params(self) -> dict:
@@ -269,6 +273,7 @@ class PARSeq(HipNet):
             "dec_depth": _cfg_get(c, "decoder.depth", 1),
             "num_tokens": _cfg_get(c, "num_tokens", 7121), "max_label_length": _cfg_get(c, "max_label_length", 100),
             "refine_iters": self.refine_iters, "decode_ar": _cfg_get(c, "decode_ar", 1),
+            "retire_rows": self.retire_rows,
             "repetition_stop": int(bool(_cfg_get(c, "repetition_stop", True))),
             "rep_period_max": _cfg_get(c, "rep_period_max", 8), "rep_min_run_p1": _cfg_get(c, "rep_min_run_p1", 8),
             "rep_min_repeats": _cfg_get(c, "rep_min_repeats", 3),

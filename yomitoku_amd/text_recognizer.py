@@ -117,11 +117,14 @@ class TextRecognizer(BaseModule):
     def __init__(self, model_name="parseq-large-v4_1", path_cfg=None, device="cuda", visualize=False, from_pretrained=True,
                  infer_onnx=False, rec_orientation_fallback=False, rec_orientation_fallback_thresh=0.75,
                  batch_bucketing=False, dynamic_width=False, num_parallel_batches=1, source_downscale=False,
-                 workspace_reuse=False):
+                 workspace_reuse=False, retire_rows=True):
         super().__init__()
         if infer_onnx:
             raise NotImplementedError("the ONNX backend is out of scope of the MI355X path (infer_onnx=False only)")
         self.load_model(model_name, path_cfg, from_pretrained=from_pretrained)
+        # the greedy loop drops a row once its own <eos> is out (include/ymk.h, "retire_rows"): this module reads token ids and
+        # scores up to each row's first <eos> only, which are what they are with the switch off
+        self.model.retire_rows = int(bool(retire_rows))
         if workspace_reuse:  # planned workspace (include/ymk.h, "workspace_reuse"); False leaves the process-wide default in force
             self.model.set_workspace_reuse(True)
         self.charset = load_charset(self._cfg.charset)
@@ -387,6 +390,7 @@ class TextRecognizer(BaseModule):
                 if rep is not None:
                     rep.close()
                 rep = type(self.model)(self.model.cfg).load_state_dict(self.model._sd)
+                rep.retire_rows = self.model.retire_rows
                 rep.set_workspace_reuse(self.model._workspace_reuse)  # before the handle exists: its first reservation is in the mode
                 rep.to(self.device)
                 rep._source_sd = self.model._sd
