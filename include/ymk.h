@@ -582,7 +582,20 @@ int ymk_mrc_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_
  *   waited for.  The result depends on the rows alone, not on timing.
  * ymk_cc_stage: one of a colour's four launches alone - stage 0 label, 1 merge, 2 areas, 3 apply; white: 0 = the black pass, else
  *   the white one; n: that colour's size; counts_dev is added to, not zeroed.  For tools/despeckle_serve_timing.py: the stages of
- *   a colour in order are that colour's pass. */
+ *   a colour in order are that colour's pass.
+ * Filtered ink (yomitoku_amd/despeckle.py: filter_masks; yomitoku_amd/mrc.py: the ink masks of layered pages with "despeckle" or
+ * "blobs"; tests/ink_filter_ref.py is the definition, and the rows and the six counts equal it exactly):
+ * ymk_cc_filter_scratch_bytes: sizes3_out = the bytes of labels_dev, areas_dev and boxes_dev (int32; three words a pixel, plane k of
+ *   a page at word 3 (words 14-15) + k h w): 20 bytes a pixel in all.
+ * ymk_cc_filter_pages: counts_dev int32 [n_pages][6] zeroed on `stream`; the two passes of ymk_cc_despeckle_pages, counts [0]-[3];
+ *   then, side > 0, on their result a third, the blob pass: every 8-connected component of 1 bits with area a and bounding box bh x
+ *   bw (inclusive extents) is cleared where bh >= side, bw >= side and 256 a >= fill bh bw (in 64 bits), counts [4], [5] += such
+ *   components, their pixels.  side: 0 (no blob pass; boxes_dev is not read) or 2..16383; fill: 1..256, in 256ths of the box.  The
+ *   blob pass is four launches - label, merge, boxes (every component's exact area and box), apply -; a record that does not fit
+ *   boxes_bytes is absent like one that does not fit the labels.  Nothing is allocated, nothing waited for; the result depends on
+ *   the rows alone.
+ * ymk_cc_filter_stage: one of the blob pass's four launches alone - stage 0 label, 1 merge, 2 boxes, 3 apply; counts_dev
+ *   ([n_pages][6]) is added to, not zeroed.  For tools/mrc_filter_timing.py. */
 #define YMK_CC_TILE_W 64
 #define YMK_CC_TILE_H 16
 int ymk_cc_tile_w(void);
@@ -594,6 +607,13 @@ int ymk_cc_despeckle_pages(const int* blob_dev, int64_t blob_words, int n_pages,
 int ymk_cc_stage(int stage, int white, const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
                  int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int n, int* counts_dev,
                  void* stream);
+int ymk_cc_filter_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes3_out);
+int ymk_cc_filter_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
+                        int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int* boxes_dev,
+                        int64_t boxes_bytes, int n_black, int n_white, int side, int fill, int* counts_dev, void* stream);
+int ymk_cc_filter_stage(int stage, const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
+                        int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int* boxes_dev,
+                        int64_t boxes_bytes, int side, int fill, int* counts_dev, void* stream);
 
 /* ---- DB post-processing on the host (replaces DBnetPostProcessor.boxes_from_bitmap,
  * postprocessor/dbnet_postporcessor.py:32-82: threshold, border following, min-area rectangles,

@@ -126,6 +126,11 @@ SIGNATURES = {
                                        c_int, c_void_p, c_void_p]),
     "ymk_cc_stage": (c_int, [c_int, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
                              c_void_p, c_void_p]),
+    "ymk_cc_filter_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_cc_filter_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                    c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_cc_filter_stage": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "ymk_db_postprocess": (

@@ -45,7 +45,8 @@ class EncodedBilevel:
     zero-padded to a byte; 0 bits of the decoded image are white (`BlackIs1 false`, TIFF's MinIsWhite).  `scale` is 1.0: a
     two-valued page is never resized.  `method`: "auto" for a page that arrived two-valued, "otsu" / "adaptive" for one that was
     thresholded; `threshold`: Otsu's t* (black iff p <= t*), None for the other two; `despeckled`: what despeckling removed
-    before the page was coded (yomitoku_amd/despeckle.py: Despeckled), None where it did not run.  It is the constructor's last
+    before the page was coded (yomitoku_amd/despeckle.py: Despeckled; of a layered page's mask whose ink was filtered, an
+    InkFiltered), None where it did not run.  It is the constructor's last
     argument and an attribute, not a dataclass field: `==` and `repr` ignore it, `dataclasses.fields()` does not list it, and
     `dataclasses.replace()` gives a copy whose `despeckled` is None unless it is passed again."""
 

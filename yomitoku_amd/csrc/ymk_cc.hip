@@ -4,7 +4,8 @@
 // which no order of addition changes.
 //
 // One pass per colour - black under 8-connectivity, then, on its result, white under 4 -, four launches each.  A page's pixel
-// (y, x) has the index i = y w + x < 2^28 and two words of scratch, label[i] and area[i].
+// (y, x) has the index i = y w + x < 2^28 and two words of scratch, label[i] and area[i] (8 bytes a pixel; the blob pass of
+// ymk_cc_filter_pages, below, has three more: 20 bytes a pixel).
 //
 //   k_cc_label   one block per 64 x 16 pixel tile: union-find over the tile's pixels of the colour in LDS (a pixel is united with
 //                the run above it - by the first pixel at which the two runs overlap -, under 8-connectivity with the upper diagonals
@@ -28,9 +29,36 @@
 // an older parent, still a smaller index in what will be the same component once every unite() has returned.  There is no
 // barrier across blocks: the launch boundaries are the barriers.
 //
-// Determinism.  Which pixel a component's root is may depend on timing between k_cc_merge's threads; its area, and with it
-// every output bit and every count, does not.
-
+// The root.  Every parent link goes from a larger index to a smaller one, so a tree's root is below every other pixel of the
+// tree; once every unite() of a pass has returned a component is one tree; so after k_cc_merge a component's root is the smallest
+// index of the component, whatever the timing - which pixels stand between a pixel and its root is what may differ from run to
+// run, and k_cc_areas / k_cc_boxes store the root itself.  Row-major order makes the root's row the component's first row.
+//
+// Determinism.  A component's root is its smallest index, and its area is a sum of ones: every output bit and every count is
+// independent of timing.
+//
+// Filtered ink (ymk_cc_filter_pages; tests/ink_filter_ref.py is the definition): behind the two passes a third, the blob pass,
+// over the black components under 8-connectivity again - k_cc_label and k_cc_merge as they are, then
+//
+//   k_cc_boxes   one block per tile: a pixel stands for the pixel its label names where that is one of this tile - its tile's
+//                root, which k_cc_label left and k_cc_merge did not touch: it only stores into roots' slots -, else for itself;
+//                area and extents per such pixel in LDS, a run of lanes along a tile's row at a time (a wave is one row of the
+//                tile, so a run never spans two rows); then one find, one add of the true area - not stopped at any n - and at
+//                most three atomicMax into the root's words per pixel that stands for any; label[i] = that root.
+//   k_cc_blob_apply  one thread per pixel: the pixel is cleared where its root's box has bh >= side, bw >= side and
+//                256 area >= fill bh bw (64 bits); the ballot is the words' change, the two counts go to the page's counters.
+//
+// A pixel then has five words of scratch, 20 bytes: label, area, and three box words in boxes_dev, plane k of a page at
+// 3 label_at + k h w.  The box words only ever grow, by atomicMax, from the 0 that k_cc_label stores at every pixel that is its
+// tile's root (a component's root is one of them): plane 0 max(w - x) = w - x_min, plane 1 max(x + 1) = x_max + 1, plane 2
+// max(y + 1) = y_max + 1; y_min is the root's row (above).  A maximum and a sum do not depend on the order of their terms, and
+// the load that spares an atomicMax can only read a value that is at most the final one: skipped or not, the final word is the
+// same.  Both kernels are straight-line code behind cc_find, which ends as argued above: what k_cc_boxes stores into the label slot
+// of pixel i is find(rep) <= rep <= i, rep the pixel that i stands for - a pixel of i's own component, because a label only ever
+// names one -, so the store keeps the invariant like k_cc_areas' does, and a find of another block that passes through the slot
+// meanwhile reads an older parent or the root.  The barriers are __syncthreads inside a block, reached by all of its threads or
+// by none.  Still no loop waits for another thread's progress.
+//
 #include "ymk_common.h"
 
 #include <algorithm>
@@ -112,7 +140,8 @@ __device__ __forceinline__ void cc_unite(int* L, int a, int b) {
 
 // ------------------------------------------------------------------------------------------------ label
 __global__ __launch_bounds__(CC_THREADS) void k_cc_label(const int* __restrict__ blob, CcLimits lim, unsigned invert, int eight,
-                                                         const unsigned* __restrict__ packed, int* __restrict__ labels, int* __restrict__ areas) {
+                                                         const unsigned* __restrict__ packed, int* __restrict__ labels, int* __restrict__ areas,
+                                                         int* __restrict__ boxes) {
   __shared__ unsigned long long s_row[CC_TILE_H + 1];  // s_row[r + 1]: row y0 + r of the tile, pixel x0 + c in bit 63 - c; s_row[0] = 0
   __shared__ int s_lab[CC_TILE];
   const CcPage g = cc_page(blob, blockIdx.z, lim);
@@ -171,6 +200,11 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_label(const int* __restrict__
     }
     lab[y * g.w + x] = v;
     area[y * g.w + x] = 0;
+    if (boxes && v == y * g.w + x) {  // the blob pass: a tile's root may be its component's
+      int* b = boxes + 3 * g.label_at + v;
+      const long long plane = (long long)g.h * g.w;
+      b[0] = b[plane] = b[2 * plane] = 0;
+    }
   }
 }
 
@@ -252,7 +286,7 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_areas(const int* __restrict__
 
 __global__ __launch_bounds__(CC_THREADS) void k_cc_apply(const int* __restrict__ blob, CcLimits lim, unsigned invert, int n,
                                                          unsigned* __restrict__ packed, const int* __restrict__ labels,
-                                                         const int* __restrict__ areas, int* __restrict__ counts) {
+                                                         const int* __restrict__ areas, int* __restrict__ counts, int per_page) {
   const CcPage g = cc_page(blob, blockIdx.z, lim);
   const long long t = (long long)blockIdx.x * CC_THREADS + threadIdx.x;
   if (!g.ok) return;
@@ -275,10 +309,124 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_apply(const int* __restrict__
     if (half) rows[t >> 5] ^= __brev(half);
   }
   if (lane == 0) {
-    int* c = counts + 4 * (int)blockIdx.z + (invert ? 2 : 0);
+    int* c = counts + per_page * (int)blockIdx.z + (invert ? 2 : 0);  // per_page: 4, or the filter's 6
     if (roots) atomicAdd(c, __popcll(roots));
     atomicAdd(c + 1, __popcll(flips));
   }
+}
+
+// ------------------------------------------------------------------------------------------------ boxes and blob apply
+// The blob pass (black, 8-connected).  A root's box words: see the file's header; `plane` = h w.
+__device__ __forceinline__ void cc_raise(int* slot, int v) {
+  // a word that has reached v stays at least v: a page-sized component costs a load, not an atomic on one word
+  if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < v) atomicMax(slot, v);
+}
+
+// One block per tile, as k_cc_label.  What that launch left and k_cc_merge kept: the label of a pixel that is not its tile's root
+// is its tile's root, a pixel of this tile; k_cc_merge has only ever stored into the slots of roots.  So a pixel stands for
+// rep = label[i] where that lies in this tile and for itself otherwise (a tile's root, hung below a pixel elsewhere or below
+// nothing) - either way a pixel of its own component, in this tile, and not larger than i.  The tile's pixels are summed per rep
+// in LDS - per run of one rep along a tile row first -, and each rep that stands for any pixel takes its sums to its component's
+// root once: a frame or a grid costs the root's words an atomic per tile it crosses, not one per run of every row.
+__global__ __launch_bounds__(CC_THREADS) void k_cc_boxes(const int* __restrict__ blob, CcLimits lim, const unsigned* __restrict__ packed,
+                                                         int* __restrict__ labels, int* __restrict__ areas, int* __restrict__ boxes) {
+  __shared__ int s_area[CC_TILE], s_left[CC_TILE], s_right[CC_TILE], s_low[CC_TILE], s_root[CC_TILE];
+  constexpr int PER = CC_TILE / CC_THREADS;
+  const CcPage g = cc_page(blob, blockIdx.z, lim);
+  const int x0 = (int)blockIdx.x * CC_TILE_W, y0 = (int)blockIdx.y * CC_TILE_H, tid = threadIdx.x;
+  if (!g.ok || x0 >= g.w || y0 >= g.h) return;  // the whole block
+  int* lab = labels + g.label_at;
+  int rep[PER];  // the tile-local place (row * 64 + column) of what the pixel stands for; -1: no pixel of the colour
+  bool any = false;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    const int t = tid + k * CC_THREADS, y = y0 + (t >> 6), x = x0 + (t & 63);
+    rep[k] = -1;
+    if (cc_is(packed + g.packed_at, g, 0u, y, x)) {
+      const int i = y * g.w + x, v = lab[i];
+      const int ry = v >= 0 ? v / g.w - y0 : -1, rx = v >= 0 ? v % g.w - x0 : -1;
+      rep[k] = ry >= 0 && ry < CC_TILE_H && rx >= 0 && rx < CC_TILE_W && v <= i ? ry * CC_TILE_W + rx : t;
+      any = true;
+    }
+  }
+  if (!__syncthreads_or(any)) return;  // paper
+  for (int t = tid; t < CC_TILE; t += CC_THREADS) s_area[t] = s_left[t] = s_right[t] = s_low[t] = 0;
+  __syncthreads();
+  const int lane = tid & 63;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {  // a wave's 64 lanes are one row of the tile
+    const int t = tid + k * CC_THREADS, y = y0 + (t >> 6), x = x0 + lane;
+    const int before = __shfl_up(rep[k], 1);
+    const bool head = lane == 0 || before != rep[k];
+    const unsigned long long heads = __ballot(head);
+    if (rep[k] >= 0 && head) {
+      const unsigned long long rest = lane == 63 ? 0ull : heads >> (lane + 1);
+      const int len = rest ? __ffsll((long long)rest) : 64 - lane;  // the run is columns x .. x + len - 1 of row y
+      atomicAdd(&s_area[rep[k]], len);
+      atomicMax(&s_left[rep[k]], g.w - x);
+      atomicMax(&s_right[rep[k]], x + len);
+      atomicMax(&s_low[rep[k]], y + 1);
+    }
+  }
+  __syncthreads();
+  const long long plane = (long long)g.h * g.w;
+  for (int t = tid; t < CC_TILE; t += CC_THREADS) {
+    if (s_area[t] == 0) continue;
+    const int root = cc_find<true>(lab, (y0 + (t >> 6)) * g.w + x0 + (t & 63));
+    s_root[t] = root;
+    atomicAdd(areas + g.label_at + root, s_area[t]);
+    int* b = boxes + 3 * g.label_at + root;
+    cc_raise(b, s_left[t]);
+    cc_raise(b + plane, s_right[t]);
+    cc_raise(b + 2 * plane, s_low[t]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    if (rep[k] < 0) continue;
+    const int t = tid + k * CC_THREADS;
+    __hip_atomic_store(lab + (y0 + (t >> 6)) * g.w + x0 + (t & 63), s_root[rep[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // <= rep <= i
+  }
+}
+
+// Thread t of a page is bit t & 31 of packed word t >> 5, as in k_cc_apply; the two counts are summed over the block first.
+__global__ __launch_bounds__(CC_THREADS) void k_cc_blob_apply(const int* __restrict__ blob, CcLimits lim, int side, int fill,
+                                                              unsigned* __restrict__ packed, const int* __restrict__ labels,
+                                                              const int* __restrict__ areas, const int* __restrict__ boxes,
+                                                              int* __restrict__ counts, int per_page) {
+  __shared__ int s_count[2];
+  const CcPage g = cc_page(blob, blockIdx.z, lim);
+  const long long t = (long long)blockIdx.x * CC_THREADS + threadIdx.x;
+  if (!g.ok) return;  // the whole grid row of the page
+  if (threadIdx.x < 2) s_count[threadIdx.x] = 0;
+  __syncthreads();
+  unsigned* rows = packed + g.packed_at;
+  int y = 0, x = 0;
+  const bool mine = cc_pixel(g, t, y, x) && cc_is(rows, g, 0u, y, x);
+  bool flip = false, root = false;
+  if (mine) {
+    const int i = y * g.w + x, r = labels[g.label_at + i];
+    if (r >= 0 && r <= i) {  // what k_cc_boxes left: the root
+      const long long plane = (long long)g.h * g.w;
+      const int* b = boxes + 3 * g.label_at + r;
+      const int bw = b[0] + b[plane] - g.w;         // (x_max + 1) - x_min
+      const int bh = b[2 * plane] - r / g.w;        // (y_max + 1) - y_min: the root's row is the first
+      flip = bh >= side && bw >= side && 256LL * areas[g.label_at + r] >= (long long)fill * bh * bw;
+      root = flip && r == i;
+    }
+  }
+  const unsigned long long flips = __ballot(flip), roots = __ballot(root);
+  const int lane = threadIdx.x & 63;
+  if (flips && (lane & 31) == 0) {
+    const unsigned half = lane ? (unsigned)(flips >> 32) : (unsigned)flips;  // lane b of the half is bit 31 - b of the word
+    if (half) rows[t >> 5] ^= __brev(half);
+  }
+  if (flips && lane == 0) {
+    if (roots) atomicAdd(&s_count[0], __popcll(roots));
+    atomicAdd(&s_count[1], __popcll(flips));
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && s_count[threadIdx.x]) atomicAdd(counts + per_page * (int)blockIdx.z + 4 + threadIdx.x, s_count[threadIdx.x]);
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -288,11 +436,12 @@ static unsigned cc_blocks(long long threads, long long most) {
 
 // One colour's launches on `s`; stages: bit k = launch k (label, merge, areas, apply) - all four but for the timing tool.
 static void cc_pass(hipStream_t s, const int* blob, int n_pages, int max_h, int max_w, const CcLimits& lim, unsigned invert, int eight, int n,
-                    uint32_t* packed, int* labels, int* areas, int* counts, int stages = 15) {
+                    uint32_t* packed, int* labels, int* areas, int* counts, int stages = 15, int per_page = 4, int* boxes = nullptr, int side = 0,
+                    int fill = 0) {
   const unsigned pages = (unsigned)n_pages;
   const dim3 tiles((unsigned)((max_w + CC_TILE_W - 1) / CC_TILE_W), (unsigned)((max_h + CC_TILE_H - 1) / CC_TILE_H), pages);
   if (stages & 1) {
-    hipLaunchKernelGGL(k_cc_label, tiles, dim3(CC_THREADS), 0, s, blob, lim, invert, eight, (const unsigned*)packed, labels, areas);
+    hipLaunchKernelGGL(k_cc_label, tiles, dim3(CC_THREADS), 0, s, blob, lim, invert, eight, (const unsigned*)packed, labels, areas, boxes);
     YMK_HIP(hipGetLastError());
   }
   const long long seams = (long long)((max_h - 1) / CC_TILE_H) * max_w + (long long)((max_w - 1) / CC_TILE_W) * max_h;
@@ -303,13 +452,25 @@ static void cc_pass(hipStream_t s, const int* blob, int n_pages, int max_h, int 
   }
   const long long bits = (long long)max_h * ((max_w + 31) >> 5) * 32;  // below 2^28 + 2^19: fewer than 2^21 blocks
   const dim3 words(cc_blocks(bits, 1LL << 22), 1u, pages);
+  if (boxes) {  // the blob pass: the third and fourth launch are its own
+    if (stages & 4) {
+      hipLaunchKernelGGL(k_cc_boxes, tiles, dim3(CC_THREADS), 0, s, blob, lim, (const unsigned*)packed, labels, areas, boxes);
+      YMK_HIP(hipGetLastError());
+    }
+    if (stages & 8) {
+      hipLaunchKernelGGL(k_cc_blob_apply, words, dim3(CC_THREADS), 0, s, blob, lim, side, fill, (unsigned*)packed, (const int*)labels,
+                         (const int*)areas, (const int*)boxes, counts, per_page);
+      YMK_HIP(hipGetLastError());
+    }
+    return;
+  }
   if (stages & 4) {
     hipLaunchKernelGGL(k_cc_areas, words, dim3(CC_THREADS), 0, s, blob, lim, invert, n, (const unsigned*)packed, labels, areas);
     YMK_HIP(hipGetLastError());
   }
   if (stages & 8) {
     hipLaunchKernelGGL(k_cc_apply, words, dim3(CC_THREADS), 0, s, blob, lim, invert, n, (unsigned*)packed, (const int*)labels, (const int*)areas,
-                       counts);
+                       counts, per_page);
     YMK_HIP(hipGetLastError());
   }
 }
@@ -330,6 +491,16 @@ static CcCall cc_check(const int* blob_dev, int64_t blob_words, int n_pages, int
   YMK_CHECK(n_black >= 0 && n_black <= 65535 && n_white >= 0 && n_white <= 65535, "n is 0..65535");
   YMK_CHECK(counts_dev && ((uintptr_t)counts_dev & 3) == 0, "null or misaligned counts");
   return CcCall{(hipStream_t)stream, CcLimits{packed_bytes / 4, std::min(labels_bytes, areas_bytes) / 4, max_h, max_w}};
+}
+
+// What the filter's entries check beyond cc_check: the blob rule's two numbers, and - side > 0 - the box words, three a pixel, which
+// then bound a page's place like the labels and the areas do.
+static void cc_check_blobs(CcCall& c, int side, int fill, const int* boxes_dev, int64_t boxes_bytes) {
+  YMK_CHECK(side == 0 || (side >= 2 && side <= CC_MAX_SIDE), "side is 0 or 2..16383");
+  if (side == 0) return;
+  YMK_CHECK(fill >= 1 && fill <= 256, "fill is 1..256, in 256ths of the box");
+  YMK_CHECK(boxes_dev && ((uintptr_t)boxes_dev & 3) == 0 && boxes_bytes >= 0, "boxes: null, misaligned or a negative size");
+  c.lim.label_words = std::min<long long>(c.lim.label_words, boxes_bytes / 12);
 }
 
 }  // namespace ymk
@@ -365,6 +536,51 @@ int ymk_cc_despeckle_pages(const int* blob_dev, int64_t blob_words, int n_pages,
     YMK_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pages * 4 * sizeof(int), c.s));
     if (n_black > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, n_black, packed_dev, labels_dev, areas_dev, counts_dev);
     if (n_white > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, ~0u, 0, n_white, packed_dev, labels_dev, areas_dev, counts_dev);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_cc_filter_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes3_out) {
+  if (ymk_cc_scratch_bytes(h, w, n_pages, sizes3_out) != 0) return 1;  // sizes3_out is checked there
+  sizes3_out[2] = 3 * sizes3_out[0];
+  return 0;
+}
+
+int ymk_cc_filter_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev, int64_t packed_bytes,
+                        int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int* boxes_dev, int64_t boxes_bytes, int n_black,
+                        int n_white, int side, int fill, int* counts_dev, void* stream) {
+  try {
+    if (n_pages == 0) return 0;
+    ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
+                                  areas_bytes, n_black, n_white, counts_dev, stream);
+    ymk::cc_check_blobs(c, side, fill, boxes_dev, boxes_bytes);
+    YMK_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pages * 6 * sizeof(int), c.s));
+    if (n_black > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, n_black, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6);
+    if (n_white > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, ~0u, 0, n_white, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6);
+    if (side > 0)
+      ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, 0, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6, boxes_dev, side, fill);
+    return 0;
+  } catch (const std::exception& e) {
+    ymk::set_error(e.what());
+    return 1;
+  }
+}
+
+int ymk_cc_filter_stage(int stage, const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
+                        int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int* boxes_dev,
+                        int64_t boxes_bytes, int side, int fill, int* counts_dev, void* stream) {
+  try {
+    if (n_pages == 0) return 0;
+    YMK_CHECK(stage >= 0 && stage <= 3, "a stage is 0 (label), 1 (merge), 2 (boxes) or 3 (apply)");
+    YMK_CHECK(side >= 2, "the blob pass needs a side");
+    ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
+                                  areas_bytes, 0, 0, counts_dev, stream);
+    ymk::cc_check_blobs(c, side, fill, boxes_dev, boxes_bytes);
+    ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, 0, packed_dev, labels_dev, areas_dev, counts_dev, 1 << stage, 6, boxes_dev, side,
+                 fill);
     return 0;
   } catch (const std::exception& e) {
     ymk::set_error(e.what());

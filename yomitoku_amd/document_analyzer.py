@@ -621,6 +621,11 @@ class DocumentAnalyzer(StageAnalyzer):
         which `searchable_pdf_bytes` embeds as three images, the foreground painted through the mask.  Such a page is never
         resized (`scale` 1.0); `jpeg_optimize` and `jpeg_subsampling` apply to its two layer files, `jpeg_grey` does not.  A blank
         page, or one that is all ink, keeps its plain file.  OCR and layout see the page as it arrived; only the file changes.
+        The dict may also hold `despeckle` (what `jpeg_despeckle` takes) and `blobs` (False, True, or a dict with `side` (128),
+        2..16383, and / or `fill` (64), 1..256), both False by default: the ink filtered before it is used - specks and pinholes
+        removed, and every ink component at least `side` pixels high and wide that fills `fill` / 256 of its bounding box, the dark
+        part of a picture, left to the background layer (yomitoku_amd/despeckle.py: check_blobs; DESIGN.md, "Layered pages: the
+        ink filtered ...").  The page's `EncodedMrc.mask.despeckled` then says what went.
         `jpeg_despeckle`: False, True (4 and 4), an int n, or a dict with `black` and / or `white` (a missing one is 0), each
         0..65535 and not both 0; anything else, the switch without `jpeg`, and the switch with `jpeg_bilevel=False` (there is no
         Group 4 file to clean) is a ValueError before a source is read.  Every page that gets a Group 4 file of its own has its

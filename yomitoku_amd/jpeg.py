@@ -356,7 +356,7 @@ class _Page:
     kind: str = "jpeg"  # what it becomes: "jpeg" | "group4" | "layered"
     scale: float = 1.0
     threshold: Optional[int] = None  # Otsu's, of a thresholded page
-    despeckled: Optional[specks.Despeckled] = None  # of a despeckled Group 4 page
+    despeckled: Optional[object] = None  # of a despeckled Group 4 page its Despeckled; of a layered page with a filtered mask its InkFiltered
     layer: Optional[int] = None  # a layered page's place in the separation
     jpeg_at: Optional[int] = None  # its place in the JPEG batch; a layered page: its foreground's, the background follows
     g4_at: Optional[int] = None  # its - or its mask's - place in the Group 4 batch
@@ -386,9 +386,9 @@ def _sort(batch: List[_Page], files: PageFiles, scratch: dict):
         shared = None if test is None else (test.packed, [test.packed_at[j] for j in cand], test.packed_bytes)
         sep = layered.launch([devs[j] for j in cand], files.mrc, scratch, packed=shared)
         torch.cuda.current_stream().synchronize()
-        for i, (j, flag) in enumerate(zip(cand, sep.flags())):
+        for i, (j, flag, filtered) in enumerate(zip(cand, sep.flags(), sep.filtered())):
             if flag == 1:
-                batch[j].kind, batch[j].layer = "layered", i
+                batch[j].kind, batch[j].layer, batch[j].despeckled = "layered", i, filtered  # the mask's InkFiltered, or None
     return test, sep, early_grey
 
 
@@ -451,7 +451,7 @@ def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_gr
         elif p.kind == "group4":
             out[p.k] = ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, files.bilevel, p.threshold, p.despeckled)
         else:
-            parts = [ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, "adaptive"),
+            parts = [ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, "adaptive", None, p.despeckled),
                      jpeg_entry(p.jpeg_at, p.k, 1.0, "the foreground's file"), jpeg_entry(p.jpeg_at + 1, p.k, 1.0, "the background's file")]
             failed = [e for e in parts if isinstance(e, BaseException)]
             out[p.k] = failed[0] if failed else layered.EncodedMrc(parts[0], parts[2], parts[1], int(p.dev.shape[1]), int(p.dev.shape[0]), 1.0,
@@ -530,7 +530,10 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     capacity is its raw bytes plus 2048).  A page without ink or without paper goes the way it goes without the switch.  The
     separation is launched behind `bilevel`'s wait and has one wait of its own, for its flags: with both switches on that is one
     further wait; the layers then join the JPEG launches and the masks the Group 4 launches, and the files come back in the same
-    two copies.
+    two copies.  The dict may also hold "despeckle" (as `despeckle` below takes it) and "blobs" (False, True or {"side": 128,
+    "fill": 64}: yomitoku_amd/despeckle.py, check_blobs): the ink filtered on the device before the separation - specks and
+    pinholes removed, and every component at least `side` high and wide that fills `fill` / 256 of its box, the dark part of a
+    picture, left to the background; the mask's `despeckled` is then an InkFiltered.  No further wait.
     despeckle: False, True (4 and 4), an int or {"black": n, "white": n} (yomitoku_amd/despeckle.py: check_despeckle) - every
     page that gets a Group 4 file of its own, the "auto" pages included, has its 8-connected black components of fewer than
     `black` pixels cleared and then its 4-connected white components of fewer than `white` pixels filled, on the device,

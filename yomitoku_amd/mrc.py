@@ -21,7 +21,19 @@ through the mask (utils/searchable_pdf.py).  A page without ink, or without pape
 plain file it is without the switch.  Like a two-valued page a layered page is never resized: the preset gives the quality.
 There is no host fallback.
 
-Out: JBIG2 and JPEG 2000 layers, a choice of cells per page, smoothing of the fills, `serve_sharded`.
+    encode_jpeg_pages(pages, "high", mrc={"despeckle": True, "blobs": {"side": 48}})  # the ink filtered before it is used
+    analyzer.serve(sources, jpeg="high", jpeg_mrc={"despeckle": True, "blobs": True})
+
+The ink is the adaptive rule's as it is unless the dict asks for the ink filter (yomitoku_amd/despeckle.py; tests/ink_filter_ref.py
+is the definition; DESIGN.md, "Layered pages: the ink filtered ..."): "despeckle" - False, True, an int or sizes, as
+`check_despeckle` takes them - removes the specks and pinholes the mask's file pays for; "blobs" - False, True or a dict with
+`side` and / or `fill`, as `check_blobs` takes them - sends every ink component that is large and fills its box, the dark part of
+a picture, back to the paper, where it is a picture in the background layer and not a stencil over a mean colour.  The filter runs
+on the device between the ink and the cells; the page's `EncodedMrc.mask.despeckled` is its `InkFiltered`.  A page whose ink is
+all removed has flag 0.  Without the two keys every launch and byte is what it was.
+
+Out: JBIG2 and JPEG 2000 layers, a choice of cells or of the filter's parameters per page, picture regions from the layout model,
+smoothing of the fills, `serve_sharded`.
 """
 
 from __future__ import annotations
@@ -34,24 +46,35 @@ import numpy as np
 
 CELLS = (1, 2, 4, 8, 16)
 DEFAULTS = {"bg_cell": 2, "fg_cell": 8}
+FILTERS = ("despeckle", "blobs")  # the ink filter's keys: on only where asked for
 PAGE_WORDS = 16  # YMK_MRC_PAGE_WORDS
 LAYER_ROOM = 2048  # a layer's file may take its raw bytes and this: the header fits a tiny layer
 
 
 def check_mrc(mrc=False) -> Optional[dict]:
     """`mrc` of a call: False -> None; True -> the defaults; a dict with any of bg_cell, fg_cell, each one of 1, 2, 4, 8, 16 -> the
-    defaults with those.  Anything else is a ValueError."""
+    defaults with those.  The dict may also hold "despeckle" (what yomitoku_amd/despeckle.py's check_despeckle takes) and "blobs"
+    (what its check_blobs takes), both False by default: the ink filter of the mask.  One that is on is in the result under its
+    key, as that function's dict; without either the result is the cells alone.  Anything else is a ValueError."""
+    from .despeckle import check_blobs, check_despeckle
+
     if mrc is False:
         return None
     if mrc is True:
         return dict(DEFAULTS)
-    if not isinstance(mrc, dict) or any(k not in DEFAULTS for k in mrc):
-        raise ValueError(f"unknown jpeg mrc {mrc!r}: False, True or a dict with any of {sorted(DEFAULTS)}")
+    if not isinstance(mrc, dict) or any(k not in DEFAULTS and k not in FILTERS for k in mrc):
+        raise ValueError(f"unknown jpeg mrc {mrc!r}: False, True or a dict with any of {sorted(DEFAULTS) + list(FILTERS)}")
     out = dict(DEFAULTS)
     for key, value in mrc.items():
+        if key in FILTERS:
+            continue
         if isinstance(value, bool) or not isinstance(value, int) or value not in CELLS:
             raise ValueError(f"jpeg mrc[{key!r}] is one of {CELLS}, got {value!r}")
         out[key] = int(value)
+    for key, check in (("despeckle", check_despeckle), ("blobs", check_blobs)):
+        checked = check(mrc.get(key, False))
+        if checked is not None:
+            out[key] = checked
     return out
 
 
@@ -128,13 +151,24 @@ class _Separated:
     test - the masks are coded by the Group 4 launches as they are.  `layers`: the buffer of the layer images; `pin`: the flags
     on their way to pinned memory; `buffers`: what the stages wrote, for the tests."""
 
-    def __init__(self, pages, params, packed, packed_at, packed_bytes, layers, places, pin, buffers):
+    def __init__(self, pages, params, packed, packed_at, packed_bytes, layers, places, pin, buffers, ink_filter=None):
         self.pages, self.params, self.packed, self.packed_at, self.packed_bytes = pages, params, packed, packed_at, packed_bytes
-        self.layers, self.places, self.pin, self.buffers = layers, places, pin, buffers
+        self.layers, self.places, self.pin, self.buffers, self.ink_filter = layers, places, pin, buffers, ink_filter
 
     def flags(self) -> List[int]:
         """Per page 1 (layered), 0 (no ink, or no paper: no layers) or -1 (no page) - once the stream has been waited for."""
         return self.pin[: len(self.pages)].tolist()
+
+    def filtered(self) -> list:
+        """Per page the InkFiltered of its mask (yomitoku_amd/despeckle.py), or None where the ink filter did not run - once
+        the stream has been waited for.  The six counts lie behind the flags and the planes' table in `pin`."""
+        from .despeckle import filter_result
+
+        n = len(self.pages)
+        if self.ink_filter is None:
+            return [None] * n
+        at = n * (1 + PAGE_WORDS)
+        return [filter_result(self.ink_filter, six) for six in self.pin[at : at + 6 * n].view(n, 6).tolist()]
 
     def _layer(self, j: int, at: int, cell: int):
         p = self.pages[j]
@@ -155,11 +189,22 @@ class _Separated:
         return self.packed[self.packed_at[j] : self.packed_at[j] + h * rw].view(h, rw)
 
 
+class _Ink:
+    """What despeckle.launch_filter reads of a test: the pages (their shapes) and where their packed ink lies."""
+
+    def __init__(self, pages, packed, packed_at, packed_bytes):
+        self.pages, self.packed, self.packed_at, self.packed_bytes = pages, packed, packed_at, packed_bytes
+
+
 def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequence] = None, packed=None, layers=None,
            edit_table=None) -> _Separated:
     """Queue the separation of device pages (uint8 H x W x 3 or H x W, contiguous) on the current stream: luminance and ink (the
     page-skew step's two calls; with `masks` - per page a bool H x W array or tensor - those are packed in their place), cells,
-    pull, flags and push, and the copy of the flags to pinned memory.  Waits for nothing.  scratch: the device and pinned buffers,
+    pull, flags and push, and the copy of the flags to pinned memory.  Waits for nothing.  With "despeckle" or "blobs" in
+    `params` the ink filter (yomitoku_amd/despeckle.py: launch_filter) is queued between the ink and the cells, in place on the
+    packed rows - the ink then comes from ymk_dsk_luma and ymk_bin_adaptive_pack called here, and ymk_mrc_pages takes it as the
+    caller's -, and its six counts a page go to pinned memory behind the flags, in the same copy; without them the call is the
+    one it was.  scratch: the device and pinned buffers,
     kept between calls - but the layers are a fresh tensor per call, which the returned object holds.  packed: (buffer, word
     offsets per page, bytes) of packed rows the ink is to be written to (default: scratch's, one page behind the other); layers: a
     caller's uint8 buffer for the layer images (the tests' poisoned one); edit_table: a function that may change the int32 [n][16]
@@ -167,6 +212,7 @@ def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequenc
     import torch
 
     from . import _lib, imaging
+    from . import despeckle as specks
     from .devpages import LUMA_PLANE, PACKED_ROWS, SUMMED_AREA, grown, to_pinned
 
     lib, device, n = _lib.load(), pages[0].device, len(pages)
@@ -187,7 +233,11 @@ def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequenc
     pyr = grown(scratch, "mrc_pyramids", pyr_b // 4, torch.int32, device)
     if layers is None:
         layers = torch.empty(max(layers_b, 16), dtype=torch.uint8, device=device)
-    answer = grown(scratch, "mrc_answer", n * (1 + PAGE_WORDS), torch.int32, device)  # the flags, then the planes' table
+    ink_filter = None
+    if any(key in params for key in FILTERS):
+        ink_filter = specks.filter_params(params.get("despeckle"), params.get("blobs"))
+    # the flags, then the planes' table, then - the ink filter - its six counts a page
+    answer = grown(scratch, "mrc_answer", n * (1 + PAGE_WORDS + (6 if ink_filter else 0)), torch.int32, device)
     luma = sat = None
     if masks is None:
         luma = grown(scratch, LUMA_PLANE, max(luma_b, 16), torch.uint8, device)
@@ -197,13 +247,26 @@ def launch(pages: Sequence, params: dict, scratch: dict, masks: Optional[Sequenc
             rows = pack_mask(m, device).reshape(-1)
             packed_dev[packed_at[j] : packed_at[j] + rows.numel()].copy_(rows)
     blob_dev = imaging._stage_blob(rec.reshape(-1), device)
-    _lib.check(lib.ymk_mrc_pages(blob_dev.data_ptr(), rec.size, n, max(int(p.shape[0]) for p in pages), max(int(p.shape[1]) for p in pages),
+    max_h, max_w, stream = max(int(p.shape[0]) for p in pages), max(int(p.shape[1]) for p in pages), _lib.current_stream_ptr()
+    planes = None if masks is not None else answer.data_ptr() + 4 * n
+    if ink_filter is not None:
+        # the ink by the two entries ymk_mrc_pages would call, the filter in place on the packed rows, then the separation of
+        # what is the caller's ink now.  A caller's masks are filtered like the pages' own ink.
+        if planes is not None:
+            _lib.check(lib.ymk_dsk_luma(blob_dev.data_ptr(), rec.size, n, max_h * max_w, luma.data_ptr(), luma_b, packed_b, sat_b, planes, stream),
+                       "ymk_dsk_luma")
+            _lib.check(lib.ymk_bin_adaptive_pack(planes, n * PAGE_WORDS, n, max_h, max_w, sat.data_ptr(), sat_b, packed_dev.data_ptr(), packed_b,
+                                                 stream), "ymk_bin_adaptive_pack")
+            planes = None
+        ink = _Ink(pages, packed_dev, packed_at, packed_b)
+        specks.launch_filter(ink, list(range(n)), ink_filter, scratch, counts=answer[n * (1 + PAGE_WORDS) : n * (7 + PAGE_WORDS)])
+    _lib.check(lib.ymk_mrc_pages(blob_dev.data_ptr(), rec.size, n, max_h, max_w,
                                  bg_cell, fg_cell, None if luma is None else luma.data_ptr(), luma_b, None if sat is None else sat.data_ptr(), sat_b,
-                                 packed_dev.data_ptr(), packed_b, None if masks is not None else answer.data_ptr() + 4 * n, pyr.data_ptr(), pyr_b,
-                                 layers.data_ptr(), layers_b, answer.data_ptr(), _lib.current_stream_ptr()), "ymk_mrc_pages")
-    pin = to_pinned(scratch, "mrc_pin_flags", answer, n)
+                                 packed_dev.data_ptr(), packed_b, planes, pyr.data_ptr(), pyr_b,
+                                 layers.data_ptr(), layers_b, answer.data_ptr(), stream), "ymk_mrc_pages")
+    pin = to_pinned(scratch, "mrc_pin_flags", answer, n * (1 + PAGE_WORDS + 6) if ink_filter else n)
     buffers = {"pyramids": pyr, "flags": answer, "blob": blob_dev, "sizes": (luma_b, sat_b, packed_b, pyr_b, layers_b)}
-    return _Separated(list(pages), dict(params), packed_dev, list(packed_at), packed_b, layers, places, pin, buffers)
+    return _Separated(list(pages), dict(params), packed_dev, list(packed_at), packed_b, layers, places, pin, buffers, ink_filter)
 
 
 def separate_pages(pages: Sequence, mrc=True, masks: Optional[Sequence] = None, stream=None, scratch: Optional[dict] = None) -> list:
@@ -211,7 +274,9 @@ def separate_pages(pages: Sequence, mrc=True, masks: Optional[Sequence] = None, 
     int32 [h][ceil(w / 32)] (1 = ink, the leftmost pixel of a word in bit 31) and uint8 [ceil(h / fg_cell)][ceil(w / fg_cell)]
     (x 3 for a colour page), likewise bg_cell; flag 0 (no ink, or no paper outside the dilated ink): the layers are None -, or the
     exception that page raised (not uint8, not H x W x 3 / H x W).  pages: device tensors and / or host arrays; mrc: True or the
-    dict `check_mrc` takes; masks: per page a bool H x W ink mask to use instead of the adaptive one, or None for all; stream: the
+    dict `check_mrc` takes - with "despeckle" or "blobs" in it the mask returned, and the layers, are those of the filtered ink, and
+    a page whose ink is all removed has flag 0; masks: per page a bool H x W ink mask to use instead of the adaptive one (filtered
+    like it), or None for all; stream: the
     torch stream to launch on (default: the current one); scratch: a dict the caller keeps between calls.  One wait, for the flags."""
     import torch
 
