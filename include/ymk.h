@@ -831,6 +831,26 @@ int ymk_op_deform_sample(const float* offs_dev, const float* attw_dev, const flo
 /* NHWC fp32, c a multiple of 4: AvgPool2d(2, 2, 0, ceil_mode=True) -> [n][(h+1)/2][(w+1)/2][c]; nearest x2 -> [n][2h][2w][c] */
 int ymk_op_avgpool2x2_ceil(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream);
 int ymk_op_upsample_nearest2x(const float* x_dev, int n, int h, int w, int c, float* y_dev, void* stream);
+/* Test-only entries for the memory-bound kernels between the convolutions and for the max|x| passes, in the forms the models
+ * launch them (tests/test_glue_views_gpu.py).  Each is one call of the launch function the models call; none allocates or waits.
+ * *_view: the operators above with the caller's pixel strides - x_dev / y_dev / add_dev point at the first channel of the view
+ *   inside pixels of in_ld / out_ld / add_ld floats (multiples of 4, >= c; the pointers 16-byte aligned), as Tensor::slice_c makes
+ *   them.  The pooling and nearest entries derive the output size; bilinear takes any oh, ow >= 1, add_dev may be null.
+ * nchw3_to_nhwc4: x [n][3][h][w] -> y [n][h][w][4], channel 3 zero (the first kernel of every forward).
+ * add_bcast: out[r][:] = a[r][:] + b[r % rows_mod][:] over m rows of d floats (d a multiple of 4), contiguous.
+ * absmax: one launch of k_absmax with the library's grid rule over `pixels` pixels of c floats at pixel stride ld: atomicMax of
+ *   the fp32 bit pattern of max|x| into word 0 of slot_dev, and word 0 of next_dev cleared.
+ * amax_merge: word 0 of each of the 32 lines of the record dst_dev = the larger of dst's and src's (1024 words each); a null
+ *   record makes it a no-op. */
+int ymk_op_maxpool3x3s2_view(const float* x_dev, int n, int h, int w, int c, int in_ld, float* y_dev, int out_ld, void* stream);
+int ymk_op_avgpool2x2_ceil_view(const float* x_dev, int n, int h, int w, int c, int in_ld, float* y_dev, int out_ld, void* stream);
+int ymk_op_upsample_nearest2x_view(const float* x_dev, int n, int h, int w, int c, int in_ld, float* y_dev, int out_ld, void* stream);
+int ymk_op_upsample_bilinear_view(const float* x_dev, int n, int h, int w, int c, int in_ld, int oh, int ow, const float* add_dev,
+                                  int add_ld, float* y_dev, int out_ld, void* stream);
+int ymk_op_nchw3_to_nhwc4(const float* x_nchw_dev, int n, int h, int w, float* y_dev, void* stream);
+int ymk_op_add_bcast(const float* a_dev, const float* b_dev, int rows_mod, int m, int d, float* out_dev, void* stream);
+int ymk_op_absmax(const float* x_dev, int64_t pixels, int c, int ld, unsigned* slot_dev, unsigned* next_dev, void* stream);
+int ymk_op_amax_merge(unsigned* dst_dev, const unsigned* src_dev, void* stream);
 
 /* ---- single operators of the DBNet++ head (ymk_dbnet.cpp).
  * deconv2x2: act(ConvTranspose2d(cin, cout, 2, stride 2)(x) * scale + bias) through the convolution path's EPI_DECONV2X2

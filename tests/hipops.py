@@ -771,3 +771,142 @@ def add_pos_embed(x, pos, full_gw):
         _lib.check(lib.ymk_op_add_pos_embed(y.data_ptr(), pos.data_ptr(), B, gh, gw, full_gw, D, _lib.current_stream_ptr()),
                    "ymk_op_add_pos_embed")
     return y
+
+
+# ---- the NHWC glue kernels and the max|x| passes in the forms the models launch them (include/ymk.h: "*_view", ymk_op_absmax ..)
+GLUE_VIEW_OPS = {  # kind -> (entry, output size of an h x w input)
+    "maxpool": ("ymk_op_maxpool3x3s2_view", lambda h, w: ((h - 1) // 2 + 1, (w - 1) // 2 + 1)),
+    "avgpool": ("ymk_op_avgpool2x2_ceil_view", lambda h, w: ((h + 1) // 2, (w + 1) // 2)),
+    "nearest": ("ymk_op_upsample_nearest2x_view", lambda h, w: (2 * h, 2 * w)),
+}
+
+
+def _glue_in(t_nhwc, view, unchecked):
+    """_into_view; `unchecked`: a view the entry has to refuse (c0 + c > ld, ld % 4, c0 % 4) is declared as it stands, inside a
+    NaN buffer wide enough that a launch that went through anyway would stay inside it."""
+    if not unchecked:
+        return _into_view(t_nhwc, view)
+    c0, ld = view
+    wide = (max(ld, c0 + t_nhwc.shape[-1]) + 7) // 4 * 4
+    buf = torch.full(t_nhwc.shape[:-1] + (wide,), float("nan"), dtype=torch.float32, device=t_nhwc.device)
+    buf[..., c0:c0 + t_nhwc.shape[-1]] = t_nhwc
+    return buf, buf.data_ptr() + 4 * c0
+
+
+def _glue_out(shape, c, view, device, unchecked, into=None):
+    """-> (the whole output buffer [.., ld], every word SENTINEL - or `into`, a buffer of an earlier launch -, the view's address)"""
+    c0, ld = view
+    if not unchecked:
+        assert 0 <= c0 and c0 + c <= ld
+    wide = ld if not unchecked else (max(ld, c0 + c) + 7) // 4 * 4
+    if into is not None:
+        assert tuple(into.shape) == tuple(shape) + (wide,) and into.is_contiguous()
+        return into, into.data_ptr() + 4 * c0
+    buf = torch.empty(tuple(shape) + (wide,), dtype=torch.float32, device=device)
+    buf.view(torch.int32).fill_(SENTINEL)
+    return buf, buf.data_ptr() + 4 * c0
+
+
+def _glue_call(lib, name, unchecked, *args):
+    status = getattr(lib, name)(*args, _lib.current_stream_ptr())
+    if not unchecked:
+        _lib.check(status, name)
+        return None
+    msg = lib.ymk_last_error() if status != 0 else None
+    return None if status == 0 else (msg.decode("utf-8", "replace") if msg else str(status))
+
+
+def pool_view(kind, x, in_view=None, out_view=None, unchecked=False):
+    """ymk_op_maxpool3x3s2_view / ymk_op_avgpool2x2_ceil_view / ymk_op_upsample_nearest2x_view (kind "maxpool" / "avgpool" /
+    "nearest"): x NCHW on the device.  *_view = (first channel, leading dimension) inside a wider NHWC buffer allocated here
+    (default: contiguous): NaN beside the input view, SENTINEL in every word of the output buffer.
+    -> (y NCHW: the output view, the whole output buffer [n, oh, ow, out_ld]); unchecked: (the entry's error message or None,
+    the whole output buffer) for views the entry has to refuse."""
+    lib = _lib.load()
+    assert x.is_cuda
+    n, c, h, w = x.shape
+    name, size = GLUE_VIEW_OPS[kind]
+    oh, ow = size(h, w)
+    xbuf, xptr = _glue_in(_nhwc(x.float()), in_view or (0, c), unchecked)
+    oc0, out_ld = out_view or (0, c)
+    ybuf, yptr = _glue_out((n, oh, ow), c, (oc0, out_ld), x.device, unchecked)
+    with torch.cuda.device(x.device):
+        err = _glue_call(lib, name, unchecked, xptr, n, h, w, c, (in_view or (0, c))[1], yptr, out_ld)
+    if unchecked:
+        return err, ybuf
+    return _nchw(ybuf[..., oc0:oc0 + c]), ybuf
+
+
+def upsample_bilinear_view(x, size, add=None, in_view=None, out_view=None, add_view=None, into=None, unchecked=False):
+    """ymk_op_upsample_bilinear_view: x NCHW on the device -> size = (oh, ow), `add` NCHW of the output's shape or None; views as
+    pool_view (NaN beside x and add).  into: the whole output buffer of an earlier launch, to write another slice of it.
+    -> (y NCHW: the output view, the whole output buffer); unchecked: (error message or None, the whole output buffer)."""
+    lib = _lib.load()
+    assert x.is_cuda
+    n, c, h, w = x.shape
+    oh, ow = size
+    xbuf, xptr = _glue_in(_nhwc(x.float()), in_view or (0, c), unchecked)
+    abuf, aptr, add_ld = None, None, 0
+    if add is not None:
+        assert tuple(add.shape) == (n, c, oh, ow)
+        abuf, aptr = _glue_in(_nhwc(add.float().to(x.device)), add_view or (0, c), unchecked)
+        add_ld = (add_view or (0, c))[1]
+    oc0, out_ld = out_view or (0, c)
+    ybuf, yptr = _glue_out((n, max(oh, 0), max(ow, 0)), c, (oc0, out_ld), x.device, unchecked, into)
+    with torch.cuda.device(x.device):
+        err = _glue_call(lib, "ymk_op_upsample_bilinear_view", unchecked, xptr, n, h, w, c, (in_view or (0, c))[1], oh, ow, aptr, add_ld,
+                         yptr, out_ld)
+    if unchecked:
+        return err, ybuf
+    return _nchw(ybuf[..., oc0:oc0 + c]), ybuf
+
+
+def nchw3_to_nhwc4(x, unchecked=False, offset=0):
+    """ymk_op_nchw3_to_nhwc4: x [n, 3, h, w] fp32 on the device -> y [n, h, w, 4] (NHWC as the kernel leaves it, SENTINEL before
+    the launch).  unchecked: (error message or None, y), the output pointer `offset` floats into its buffer."""
+    lib = _lib.load()
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 3
+    n, _, h, w = x.shape
+    y = torch.empty((n, h, w, 4 + (4 if unchecked else 0)), dtype=torch.float32, device=x.device)
+    y.view(torch.int32).fill_(SENTINEL)
+    with torch.cuda.device(x.device):
+        err = _glue_call(lib, "ymk_op_nchw3_to_nhwc4", unchecked, x.data_ptr(), n, h, w, y.data_ptr() + 4 * offset)
+    return (err, y) if unchecked else y
+
+
+def add_bcast(a, b, unchecked=False, offset=0, d=None):
+    """ymk_op_add_bcast: a [m, d], b [rows_mod, d] fp32 on the device -> out [m, d] = a[r] + b[r % rows_mod] (SENTINEL before the
+    launch).  unchecked: (error message or None, out), the row length declared as `d`, the output `offset` floats in."""
+    lib = _lib.load()
+    assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    m, da = a.shape
+    assert b.shape[1] == da
+    out = torch.empty((m, da + (8 if unchecked else 0)), dtype=torch.float32, device=a.device)
+    out.view(torch.int32).fill_(SENTINEL)
+    with torch.cuda.device(a.device):
+        err = _glue_call(lib, "ymk_op_add_bcast", unchecked, a.data_ptr(), b.data_ptr(), b.shape[0], m, da if d is None else d,
+                         out.data_ptr() + 4 * offset)
+    return (err, out) if unchecked else out
+
+
+def absmax(buf, pixels, c, view, slot, nxt, unchecked=False):
+    """ymk_op_absmax: one launch of k_absmax over `pixels` pixels of c floats at view = (first channel, leading dimension) of the
+    flat fp32 device buffer `buf`, IN PLACE on the records slot / nxt (int32 [1024], device).  unchecked: -> error message or None."""
+    lib = _lib.load()
+    c0, ld = view
+    assert buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()
+    assert unchecked or (0 <= c0 and c0 + c <= ld and (pixels - 1) * ld + c0 + c <= buf.numel())
+    for rec in (slot, nxt):
+        assert rec.is_cuda and rec.dtype == torch.int32 and rec.numel() == AMAX_REC_WORDS and rec.is_contiguous()
+    with torch.cuda.device(buf.device):
+        return _glue_call(lib, "ymk_op_absmax", unchecked, buf.data_ptr() + 4 * c0, pixels, c, ld, slot.data_ptr(), nxt.data_ptr())
+
+
+def amax_merge(dst, src):
+    """ymk_op_amax_merge IN PLACE on dst: records int32 [1024] on the device, or None (= a null record)."""
+    lib = _lib.load()
+    for rec in (dst, src):
+        assert rec is None or (rec.is_cuda and rec.dtype == torch.int32 and rec.numel() == AMAX_REC_WORDS and rec.is_contiguous())
+    dev = (dst if dst is not None else src).device
+    with torch.cuda.device(dev):
+        _glue_call(lib, "ymk_op_amax_merge", False, _lib.ptr(dst), _lib.ptr(src))

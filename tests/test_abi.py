@@ -27,11 +27,15 @@ def test_ctypes_table_matches_header():
 
 
 def test_view_entries_of_the_sequence_kernels_have_as_many_ctypes_arguments_as_the_header():
-    """ymk_op_attention_view / ymk_op_layernorm_view: one ctypes argument per declared parameter, the batch strides as int64"""
+    """ymk_op_attention_view / ymk_op_layernorm_view: one ctypes argument per declared parameter, the batch strides as int64;
+    the same for the glue kernels' entries (the pooling / resize views, the layout change, the broadcast add, the max|x| passes)"""
     import ctypes
 
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ymk.h")).read(), flags=re.S)
-    for name, count in (("ymk_op_attention_view", 31), ("ymk_op_layernorm_view", 11)):
+    for name, count in (("ymk_op_attention_view", 31), ("ymk_op_layernorm_view", 11), ("ymk_op_maxpool3x3s2_view", 9),
+                        ("ymk_op_avgpool2x2_ceil_view", 9), ("ymk_op_upsample_nearest2x_view", 9),
+                        ("ymk_op_upsample_bilinear_view", 13), ("ymk_op_nchw3_to_nhwc4", 6), ("ymk_op_add_bcast", 7),
+                        ("ymk_op_absmax", 7), ("ymk_op_amax_merge", 3)):
         params = re.search(r"\bint\s+" + name + r"\s*\((.*?)\)", src, flags=re.S).group(1).split(",")
         res, args = _lib.SIGNATURES[name]
         assert res is ctypes.c_int and len(args) == len(params) == count, name

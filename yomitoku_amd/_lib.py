@@ -206,6 +206,17 @@ SIGNATURES = {
     ),
     "ymk_op_avgpool2x2_ceil": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ymk_op_upsample_nearest2x": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_maxpool3x3s2_view": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ymk_op_avgpool2x2_ceil_view": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ymk_op_upsample_nearest2x_view": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "ymk_op_upsample_bilinear_view": (
+        c_int,
+        [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    ),
+    "ymk_op_nchw3_to_nhwc4": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_add_bcast": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ymk_op_absmax": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ymk_op_amax_merge": (c_int, [c_void_p, c_void_p, c_void_p]),
     "ymk_op_deconv2x2": (
         c_int,
         [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p],

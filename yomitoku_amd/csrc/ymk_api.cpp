@@ -727,6 +727,105 @@ int ymk_op_upsample_nearest2x(const float* x_dev, int n, int h, int w, int c, fl
   YMK_API_END
 }
 
+// ---- the NHWC glue kernels and the max|x| passes in the forms the models launch them (tests/test_glue_views_gpu.py): the
+// caller's leading dimensions into the launch functions the models call; nothing allocated, nothing waited for
+namespace {
+// what every kernel of ymk_elem.hip trusts of a view, said once more here so that a test gets the message of the entry it called
+void glue_view_arg(const char* op, const char* what, const float* p, int c, int ld) {
+  const std::string at = std::string(op) + ": " + what;
+  YMK_CHECK(p != nullptr, at + " is null");
+  YMK_CHECK(c >= 4 && c % 4 == 0, at + ": c must be a positive multiple of 4");
+  YMK_CHECK(ld % 4 == 0 && ld >= c, at + ": ld must be a multiple of 4, at least c");
+  YMK_CHECK(aligned16(p), at + " must be 16 B aligned");
+}
+ymk::Tensor glue_tensor(const float* p, int n, int h, int w, int c, int ld) {
+  ymk::Tensor t;
+  t.p = const_cast<float*>(p);
+  t.n = n;
+  t.h = h;
+  t.w = w;
+  t.c = c;
+  t.ld = ld;
+  return t;
+}
+}  // namespace
+
+int ymk_op_maxpool3x3s2_view(const float* x_dev, int n, int h, int w, int c, int in_ld, float* y_dev, int out_ld, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(n >= 1 && h >= 1 && w >= 1, "maxpool_view: n, h, w >= 1");
+  glue_view_arg("maxpool_view", "x", x_dev, c, in_ld);
+  glue_view_arg("maxpool_view", "y", y_dev, c, out_ld);
+  maxpool3x3s2((hipStream_t)stream, glue_tensor(x_dev, n, h, w, c, in_ld), glue_tensor(y_dev, n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, c, out_ld));
+  YMK_API_END
+}
+
+int ymk_op_avgpool2x2_ceil_view(const float* x_dev, int n, int h, int w, int c, int in_ld, float* y_dev, int out_ld, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(n >= 1 && h >= 1 && w >= 1, "avgpool_view: n, h, w >= 1");
+  glue_view_arg("avgpool_view", "x", x_dev, c, in_ld);
+  glue_view_arg("avgpool_view", "y", y_dev, c, out_ld);
+  avgpool2x2_ceil((hipStream_t)stream, glue_tensor(x_dev, n, h, w, c, in_ld), glue_tensor(y_dev, n, (h + 1) / 2, (w + 1) / 2, c, out_ld));
+  YMK_API_END
+}
+
+int ymk_op_upsample_nearest2x_view(const float* x_dev, int n, int h, int w, int c, int in_ld, float* y_dev, int out_ld, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(n >= 1 && h >= 1 && w >= 1, "nearest2x_view: n, h, w >= 1");
+  glue_view_arg("nearest2x_view", "x", x_dev, c, in_ld);
+  glue_view_arg("nearest2x_view", "y", y_dev, c, out_ld);
+  upsample_nearest2x((hipStream_t)stream, glue_tensor(x_dev, n, h, w, c, in_ld), glue_tensor(y_dev, n, 2 * h, 2 * w, c, out_ld));
+  YMK_API_END
+}
+
+int ymk_op_upsample_bilinear_view(const float* x_dev, int n, int h, int w, int c, int in_ld, int oh, int ow, const float* add_dev,
+                                  int add_ld, float* y_dev, int out_ld, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(n >= 1 && h >= 1 && w >= 1 && oh >= 1 && ow >= 1, "bilinear_view: n, h, w, oh, ow >= 1");
+  glue_view_arg("bilinear_view", "x", x_dev, c, in_ld);
+  glue_view_arg("bilinear_view", "y", y_dev, c, out_ld);
+  if (add_dev) glue_view_arg("bilinear_view", "add", add_dev, c, add_ld);
+  const Tensor add = glue_tensor(add_dev, n, oh, ow, c, add_ld);
+  upsample_bilinear((hipStream_t)stream, glue_tensor(x_dev, n, h, w, c, in_ld), glue_tensor(y_dev, n, oh, ow, c, out_ld), add_dev ? &add : nullptr);
+  YMK_API_END
+}
+
+int ymk_op_nchw3_to_nhwc4(const float* x_nchw_dev, int n, int h, int w, float* y_dev, void* stream) {
+  YMK_API_BEGIN
+  using namespace ymk;
+  YMK_CHECK(x_nchw_dev && y_dev && n >= 1 && h >= 1 && w >= 1, "nchw3_to_nhwc4: null argument or an empty image");
+  YMK_CHECK(aligned16(y_dev), "nchw3_to_nhwc4: y must be 16 B aligned");
+  nchw3_to_nhwc4((hipStream_t)stream, x_nchw_dev, n, h, w, glue_tensor(y_dev, n, h, w, 4, 4));
+  YMK_API_END
+}
+
+int ymk_op_add_bcast(const float* a_dev, const float* b_dev, int rows_mod, int m, int d, float* out_dev, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(a_dev && b_dev && out_dev, "add_bcast: null argument");
+  YMK_CHECK(m >= 1 && rows_mod >= 1 && d >= 4 && d % 4 == 0, "add_bcast: m, rows_mod >= 1, d a positive multiple of 4");
+  YMK_CHECK(aligned16(a_dev) && aligned16(b_dev) && aligned16(out_dev), "add_bcast: rows must be 16 B aligned");
+  ymk::add_bcast((hipStream_t)stream, a_dev, b_dev, rows_mod, out_dev, m, d);
+  YMK_API_END
+}
+
+int ymk_op_absmax(const float* x_dev, int64_t pixels, int c, int ld, unsigned* slot_dev, unsigned* next_dev, void* stream) {
+  YMK_API_BEGIN
+  YMK_CHECK(slot_dev && next_dev && pixels >= 1, "absmax: null record or no pixels");
+  glue_view_arg("absmax", "x", x_dev, c, ld);
+  ymk::absmax_launch((hipStream_t)stream, x_dev, (size_t)pixels, c, ld, slot_dev, next_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
+}
+
+int ymk_op_amax_merge(unsigned* dst_dev, const unsigned* src_dev, void* stream) {
+  YMK_API_BEGIN
+  ymk::amax_merge((hipStream_t)stream, dst_dev, src_dev);  // a null record is "no record": nothing is launched
+  YMK_API_END
+}
+
 int ymk_op_deconv2x2(const float* x_dev, int n, int h, int w, int cin, const float* w_host, int cout, const float* scale_host,
                      const float* bias_host, int act, float* y_dev, void* stream) {
   YMK_API_BEGIN

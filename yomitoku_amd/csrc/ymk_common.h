@@ -320,6 +320,9 @@ class ConvSplitTileScope {
 int conv_effective_split();
 // max|x| over n floats (n % 4 == 0, 16-byte aligned) into word 0 of the zeroed record rec (ymk_conv_split.hip; tests / tools)
 void absmax_record(hipStream_t s, const float* x, size_t n, unsigned* rec);
+// the one launch of k_absmax: max|x| over `pixels` pixels of c floats, pixel stride ld (c, ld multiples of 4, ld >= c, 16-byte
+// aligned), folded into word 0 of `slot`; clears word 0 of `next`.  absmax_record and the split context's pass both call it
+void absmax_launch(hipStream_t s, const float* x, size_t pixels, int c, int ld, unsigned* slot, unsigned* next);
 
 // out must be pre-shaped (n, oh, ow, cout[, ld]); for EPI_DECONV2X2 out is (n, 2h, 2w, cout/4).
 void conv2d(hipStream_t s, const Tensor& in, const ConvW& w, const ConvArgs& a, const Tensor& out);
@@ -369,7 +372,6 @@ void avgpool2x2_ceil(hipStream_t s, const Tensor& in, const Tensor& out);
 // per-image per-channel mean over h*w: out[n][c]; scratch = GAP_CHUNKS*n*c floats
 constexpr int GAP_CHUNKS = 256;
 void global_avgpool(hipStream_t s, const Tensor& in, float* scratch, float* out_nc);
-void add_act(hipStream_t s, const Tensor& a, const Tensor& b, int act, const Tensor& out);
 // dst record = max(dst record, src record), line by line (a tensor that also holds values copied from src's tensor)
 void amax_merge(hipStream_t s, unsigned* dst, const unsigned* src);
 

@@ -385,10 +385,13 @@ __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ in, si
   if (t == 0) atomicMax(slot, max(max(red[0], red[1]), max(red[2], red[3])));
 }
 
-void absmax_record(hipStream_t s, const float* x, size_t n, unsigned* rec) {
-  const size_t items = n / 4;
+void absmax_launch(hipStream_t s, const float* x, size_t pixels, int c, int ld, unsigned* slot, unsigned* next) {
+  const size_t items = pixels * (size_t)(c / 4);
   const int blocks = (int)std::min<size_t>(1024, (items + 1023) / 1024);
-  hipLaunchKernelGGL(k_absmax, dim3(blocks), dim3(256), 0, s, x, items, 1, 4, rec, rec + AMAX_LINE_WORDS);  // (clears a word nobody reads)
+  hipLaunchKernelGGL(k_absmax, dim3(blocks), dim3(256), 0, s, x, items, c / 4, ld, slot, next);
+}
+void absmax_record(hipStream_t s, const float* x, size_t n, unsigned* rec) {
+  absmax_launch(s, x, n / 4, 4, 4, rec, rec + AMAX_LINE_WORDS);  // (clears a word nobody reads)
   YMK_HIP(hipGetLastError());
 }
 
@@ -466,10 +469,8 @@ class SplitCtx {
     stream_ = s;
     have_stream_ = true;
     const size_t pixels = (size_t)(k.in_bytes / 4 - k.C) / k.in_ld + 1;
-    const size_t items = pixels * (size_t)(k.C / 4);
-    const int blocks = (int)std::min<size_t>(1024, (items + 1023) / 1024);
     unsigned* cur = slots_ + parity_ * AMAX_REC_WORDS;
-    hipLaunchKernelGGL(k_absmax, dim3(blocks), dim3(256), 0, s, k.in, items, k.C / 4, k.in_ld, cur, slots_ + (parity_ ^ 1) * AMAX_REC_WORDS);
+    absmax_launch(s, k.in, pixels, k.C, k.in_ld, cur, slots_ + (parity_ ^ 1) * AMAX_REC_WORDS);
     parity_ ^= 1;
     return cur;
   }

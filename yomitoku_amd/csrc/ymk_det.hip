@@ -36,6 +36,9 @@ __global__ void k_add_bcast(const float4* __restrict__ a, const float4* __restri
 void add_bcast(hipStream_t s, const float* a, const float* b, int rows_mod, float* out, int M, int D) {
   const size_t total = (size_t)M * D / 4;
   if (total == 0) return;
+  YMK_CHECK(D % 4 == 0 && rows_mod >= 1, "add_bcast: D a multiple of 4, rows_mod >= 1");
+  YMK_CHECK(a && b && out && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+            "add_bcast: null or not 16-byte aligned");
   hipLaunchKernelGGL(k_add_bcast, dim3(gridsz(total)), dim3(256), 0, s, (const float4*)a, (const float4*)b, (float4*)out,
                      D / 4, (size_t)rows_mod * D / 4, total);
   YMK_HIP(hipGetLastError());

@@ -12,6 +12,14 @@ static inline int grid_for(size_t work, int block = 256, int cap = 256 * 16) {
   return (int)g;
 }
 
+// what the 16-byte loads and stores below trust of an NHWC view: a pointer on a 16-byte boundary, channels and pixel stride in
+// whole float4 words, the view inside its pixel stride
+static void check_view(const Tensor& t, const char* what) {
+  YMK_CHECK(t.p != nullptr && (reinterpret_cast<uintptr_t>(t.p) & 15) == 0, std::string(what) + ": null or not 16-byte aligned");
+  YMK_CHECK(t.n >= 1 && t.h >= 1 && t.w >= 1, std::string(what) + ": empty tensor");
+  YMK_CHECK(t.c >= 4 && t.c % 4 == 0 && t.ld % 4 == 0 && t.ld >= t.c, std::string(what) + ": c and ld must be multiples of 4, ld >= c");
+}
+
 // ---------------------------------------------------------------- NCHW(3) -> NHWC(4)
 __global__ void k_nchw3_to_nhwc4(const float* __restrict__ in, float4* __restrict__ out, size_t hw, size_t total) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -22,6 +30,8 @@ __global__ void k_nchw3_to_nhwc4(const float* __restrict__ in, float4* __restric
 }
 void nchw3_to_nhwc4(hipStream_t s, const float* in, int n, int h, int w, const Tensor& out) {
   YMK_CHECK(out.c == 4 && out.ld == 4, "nchw3_to_nhwc4 wants packed 4-channel output");
+  YMK_CHECK(in != nullptr && n >= 1 && h >= 1 && w >= 1 && out.n == n && out.h == h && out.w == w, "nchw3_to_nhwc4: shape");
+  check_view(out, "nchw3_to_nhwc4: out");
   const size_t hw = (size_t)h * w, total = hw * n;
   hipLaunchKernelGGL(k_nchw3_to_nhwc4, dim3(grid_for(total)), dim3(256), 0, s, in, (float4*)out.p, hw, total);
   YMK_HIP(hipGetLastError());
@@ -55,7 +65,9 @@ __global__ void k_maxpool3x3s2(const float* __restrict__ in, float* __restrict__
   }
 }
 void maxpool3x3s2(hipStream_t s, const Tensor& in, const Tensor& out) {
-  YMK_CHECK(in.c % 4 == 0 && out.c == in.c, "maxpool: channels");
+  YMK_CHECK(in.c % 4 == 0 && out.c == in.c && out.n == in.n, "maxpool: channels");
+  check_view(in, "maxpool: in");
+  check_view(out, "maxpool: out");
   YMK_CHECK(out.h == (in.h + 2 - 3) / 2 + 1 && out.w == (in.w + 2 - 3) / 2 + 1, "maxpool: shape");
   const size_t total = out.pixels() * (in.c / 4);
   hipLaunchKernelGGL(k_maxpool3x3s2, dim3(grid_for(total)), dim3(256), 0, s, in.p, out.p, in.h, in.w, in.c / 4, in.ld,
@@ -93,7 +105,9 @@ __global__ void k_avgpool2(const float* __restrict__ in, float* __restrict__ out
   }
 }
 void avgpool2x2_ceil(hipStream_t s, const Tensor& in, const Tensor& out) {
-  YMK_CHECK(in.c % 4 == 0 && out.c == in.c, "avgpool: channels");
+  YMK_CHECK(in.c % 4 == 0 && out.c == in.c && out.n == in.n, "avgpool: channels");
+  check_view(in, "avgpool: in");
+  check_view(out, "avgpool: out");
   YMK_CHECK(out.h == (in.h + 1) / 2 && out.w == (in.w + 1) / 2, "avgpool: shape");
   const size_t total = out.pixels() * (in.c / 4);
   hipLaunchKernelGGL(k_avgpool2, dim3(grid_for(total)), dim3(256), 0, s, in.p, out.p, in.h, in.w, in.c / 4, in.ld, out.h,
@@ -113,8 +127,14 @@ __global__ void k_bilinear(const float* __restrict__ in, const float* __restrict
     pix /= OW;
     const int oh = (int)(pix % OH);
     const int n = (int)(pix / OH);
-    float fy = ((float)oh + 0.5f) * sh - 0.5f;
-    float fx = ((float)ow + 0.5f) * sw - 0.5f;
+    float fy, fx;
+    {
+      // the product and the difference each rounded, as the formula is written and as ATen computes it on the host: contracted
+      // into one FMA the coordinate moves by up to an ulp of its value (8e-6 of a pixel near row 64), 1e-6 max|x| in the result
+#pragma clang fp contract(off)
+      fy = ((float)oh + 0.5f) * sh - 0.5f;
+      fx = ((float)ow + 0.5f) * sw - 0.5f;
+    }
     fy = fy < 0.f ? 0.f : fy;
     fx = fx < 0.f ? 0.f : fx;
     const int y0 = (int)fy, x0 = (int)fx;
@@ -143,6 +163,12 @@ __global__ void k_bilinear(const float* __restrict__ in, const float* __restrict
 void upsample_bilinear(hipStream_t s, const Tensor& in, const Tensor& out, const Tensor* add) {
   YMK_CHECK(in.c % 4 == 0 && out.c == in.c && in.n == out.n, "bilinear: channels");
   YMK_CHECK(out.ld % 4 == 0 && in.ld % 4 == 0, "bilinear: ld");
+  check_view(in, "bilinear: in");
+  check_view(out, "bilinear: out");
+  if (add) {
+    YMK_CHECK(add->c == out.c && add->n == out.n && add->h == out.h && add->w == out.w, "bilinear: add has the output's shape");
+    check_view(*add, "bilinear: add");
+  }
   const size_t total = out.pixels() * (in.c / 4);
   const float sh = (float)in.h / (float)out.h, sw = (float)in.w / (float)out.w;
   hipLaunchKernelGGL(k_bilinear, dim3(grid_for(total)), dim3(256), 0, s, in.p, add ? add->p : nullptr, out.p, in.h,
@@ -166,33 +192,11 @@ __global__ void k_nearest2(const float* __restrict__ in, float* __restrict__ out
   }
 }
 void upsample_nearest2x(hipStream_t s, const Tensor& in, const Tensor& out) {
-  YMK_CHECK(in.c % 4 == 0 && out.c == in.c && out.h == 2 * in.h && out.w == 2 * in.w, "nearest2x: shape");
+  YMK_CHECK(in.c % 4 == 0 && out.c == in.c && out.n == in.n && out.h == 2 * in.h && out.w == 2 * in.w, "nearest2x: shape");
+  check_view(in, "nearest2x: in");
+  check_view(out, "nearest2x: out");
   const size_t total = out.pixels() * (in.c / 4);
   hipLaunchKernelGGL(k_nearest2, dim3(grid_for(total)), dim3(256), 0, s, in.p, out.p, in.h, in.w, in.c / 4, in.ld, out.ld,
-                     total);
-  YMK_HIP(hipGetLastError());
-}
-
-// ---------------------------------------------------------------- a + b (+act)
-__global__ void k_add_act(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int C4,
-                          int a_ld, int b_ld, int out_ld, int act, size_t total) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % C4);
-    const size_t pix = i / C4;
-    float4 x = *reinterpret_cast<const float4*>(a + pix * a_ld + c4 * 4);
-    const float4 y = *reinterpret_cast<const float4*>(b + pix * b_ld + c4 * 4);
-    x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
-    if (act == ACT_RELU) {
-      x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f);
-    }
-    *reinterpret_cast<float4*>(out + pix * out_ld + c4 * 4) = x;
-  }
-}
-void add_act(hipStream_t s, const Tensor& a, const Tensor& b, int act, const Tensor& out) {
-  YMK_CHECK(a.c % 4 == 0 && a.c == b.c && a.c == out.c, "add: channels");
-  YMK_CHECK(act == ACT_NONE || act == ACT_RELU, "add: act");
-  const size_t total = out.pixels() * (a.c / 4);
-  hipLaunchKernelGGL(k_add_act, dim3(grid_for(total)), dim3(256), 0, s, a.p, b.p, out.p, a.c / 4, a.ld, b.ld, out.ld, act,
                      total);
   YMK_HIP(hipGetLastError());
 }
