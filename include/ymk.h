@@ -384,6 +384,18 @@ int ymk_jpeg_pages_grey(const int* blob_dev, int64_t blob_words, int n_pages, in
 #define YMK_PIL_RESIZE_U8_WORDS 16
 int ymk_pil_resize_u8_record_words(void);
 int ymk_pil_resize_u8(const int* blob_dev, int64_t blob_words, int n, int max_oh, int max_ow, void* stream);
+/* ymk_crop_u8: n axis-aligned rectangles of uint8 pages copied into contiguous [ch][cw][C] destinations in one launch
+ *   (yomitoku_amd/csrc/ymk_crop.hip; yomitoku_amd/figures.py: the figure crops of serve(figures=...)).  The pages are [H][W][C],
+ *   C 1 | 3, contiguous, at any address; a destination is 16-byte aligned.  blob_dev: n records of YMK_CROP_U8_WORDS int32 words
+ *   {source address low, high; H; W; C; x0; y0; cw; ch; destination address low, high; index of the crop's first 16-byte
+ *   destination chunk in the launch; 0 ...}: a crop has ceil(ch cw C / 16) chunks, the crops' chunks follow one another and
+ *   total_chunks is their sum (sizes the launch).  A record that does not fit - a side outside 1..16383, C not 1 | 3,
+ *   x0 + cw > W, y0 + ch > H, a negative origin, a misaligned destination, chunks outside 0..total_chunks - is ignored:
+ *   nothing is read or written for it.  Exactly ch cw C bytes are written per crop, none behind them; no load leaves
+ *   [source, source + H W C).  n == 0 queues nothing.  Nothing is allocated, nothing waited for. */
+#define YMK_CROP_U8_WORDS 16
+int ymk_crop_u8_record_words(void);
+int ymk_crop_u8(const int* blob_dev, int64_t blob_words, int n, int64_t total_chunks, void* stream);
 
 /* ---- Group 4 encoder: CCITT T.6 files of the two-valued pages of a wave, opt-in (yomitoku_amd/csrc/ymk_ccitt.hip;
  * yomitoku_amd/ccitt.py; encode_jpeg_pages(bilevel="auto"), serve(jpeg=..., jpeg_bilevel="auto")).  DESIGN.md, "Two-valued

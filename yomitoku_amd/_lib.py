@@ -133,6 +133,8 @@ SIGNATURES = {
                                     c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "ymk_pil_resize_u8_record_words": (c_int, []),
     "ymk_pil_resize_u8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "ymk_crop_u8_record_words": (c_int, []),
+    "ymk_crop_u8": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p]),
     "ymk_db_postprocess": (
         c_int,
         [c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_int,

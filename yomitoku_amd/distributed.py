@@ -414,6 +414,9 @@ class ShardedServer:
         if serve_kwargs.get("deskew", False) is not False:
             raise NotImplementedError("deskew=... is not supported by serve_sharded: the ranks' PageSkew entries are not gathered "
                                       "(DocumentAnalyzer.serve(..., deskew=True) corrects on one GPU)")
+        if serve_kwargs.get("figures") not in (None, False):
+            raise NotImplementedError("figures=... is not supported by serve_sharded: the ranks' figure files are not gathered "
+                                      "(DocumentAnalyzer.serve(..., figures=True) cuts and encodes on one GPU)")
         serve_kwargs.setdefault("rec_lanes", self.budget["rec_lanes"])
         self._jobs += 1  # run() is called by every rank for every job: the job number is the same everywhere
         if assign == "static":

@@ -28,6 +28,7 @@ from .schemas import (
     ParagraphSchema,
 )
 from .deskew import check_deskew
+from .figures import check_figures
 from .serving import StageAnalyzer, check_jpeg_preset
 from .table_structure_recognizer import TableStructureRecognizer
 from .text_detector import TextDetector
@@ -566,7 +567,7 @@ class DocumentAnalyzer(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False, figures=None):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -632,12 +633,22 @@ class DocumentAnalyzer(StageAnalyzer):
         8-connected black components of fewer than `black` pixels cleared, then its 4-connected white components of fewer than
         `white` pixels filled, on the device before it is coded (yomitoku_amd/despeckle.py; DESIGN.md, "Despeckled pages"):
         paper grain and dust cost T.6 most of a noisy page's bytes.  `EncodedBilevel.despeckled` says what went.  With
-        `jpeg_bilevel="auto"` the file is then no longer lossless.  OCR and layout see the page as it arrived."""
+        `jpeg_bilevel="auto"` the file is then no longer lossless.  OCR and layout see the page as it arrived.
+        `figures`: None / False, True, an int 1..100 (the JPEG quality), or a dict with any of `quality` (95), `subsampling`
+        ("4:2:0"), `optimize` (False) and `max_side` (None, or 16..16383: a crop whose long side exceeds it is shrunk to it);
+        anything else is a ValueError before a source is read.  The crops of the page's `schema.figures` - the only pixels the
+        Markdown / HTML / JSON / CSV exporters write - are cut on the device from the clean page (with `deskew` the corrected
+        one, whose boxes the schema holds; full size whatever the `jpeg` preset) and coded as JPEG files in the render stage
+        (yomitoku_amd/figures.py; DESIGN.md, "Figure crops"): the entry gets a PageFigures behind the page file and in front of
+        the PageSkew - (schema, PageFigures), (schema, ocr overlay, layout overlay, EncodedJpeg, PageFigures, PageSkew) -, one
+        EncodedJpeg per figure in `schema.figures` order (None for an empty box), which `schema.to_markdown(path,
+        figures=entry[...])` and the other exporters write in place of crops of a host image."""
         files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle)  # before the pipeline is built or a source read
         deskew = check_deskew(deskew) or False
+        figures = check_figures(figures)
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
-        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, files=files, deskew=deskew)
+        return self._serve(sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, files=files, deskew=deskew, figures=figures)
 
     def __call__(self, img):
         self.img = img

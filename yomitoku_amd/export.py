@@ -38,16 +38,42 @@ def save_image(img, path):
         f.write(buf.getvalue())
 
 
-def _save_figures(figures, img, out_path, figure_dir):
-    """The figure crops next to `out_path`; yields (index, figure, name relative to figure_dir)."""
-    assert img is not None, "img is required for saving figures"
+def _figure_bytes(files, count):
+    """`figures=` of an exporter as one slot per figure: a PageFigures (yomitoku_amd/figures.py: what `serve(figures=...)` hands
+    back) or a sequence of EncodedJpeg / bytes, `count` of them; any other length is a ValueError."""
+    files = list(getattr(files, "files", files))
+    if len(files) != count:
+        raise ValueError(f"figures holds {len(files)} files, the page has {count} figures")
+    return files
+
+
+def _write_figure(file, path):
+    """The file of one figure as it was given; a slot without a file - an empty crop, a crop that failed - raises what
+    `save_image` raises for an image it cannot encode."""
+    data = getattr(file, "data", file)
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise ValueError("Failed to encode image") from (file if isinstance(file, BaseException) else None)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def _save_figures(figures, img, out_path, figure_dir, files=None):
+    """The figure crops next to `out_path`; yields (index, figure, name relative to figure_dir).  files: the crops as encoded
+    files, one per figure (`_figure_bytes`) - written as they are under the same names, `img` is then not looked at."""
+    if files is not None:
+        files = _figure_bytes(files, len(figures))
+    else:
+        assert img is not None, "img is required for saving figures"
     out = []
     for i, figure in enumerate(figures):
         x1, y1, x2, y2 = map(int, figure.box)
         save_dir = os.path.join(os.path.dirname(out_path), figure_dir)
         os.makedirs(save_dir, exist_ok=True)
         name = f"{os.path.splitext(os.path.basename(out_path))[0]}_figure_{i}.png"
-        save_image(img[y1:y2, x1:x2, :], os.path.join(save_dir, name))
+        if files is not None:
+            _write_figure(files[i], os.path.join(save_dir, name))
+        else:
+            save_image(img[y1:y2, x1:x2, :], os.path.join(save_dir, name))
         out.append((i, figure, name))
     return out
 
@@ -66,7 +92,7 @@ def table_to_json(table, ignore_line_break):
             cell.contents = cell.contents.replace("\n", "")
 
 
-def convert_json(inputs, out_path, ignore_line_break, img, export_figure, figure_dir):
+def convert_json(inputs, out_path, ignore_line_break, img, export_figure, figure_dir, figures=None):
     from .schemas import DocumentAnalyzerSchema
 
     if isinstance(inputs, DocumentAnalyzerSchema):
@@ -75,7 +101,7 @@ def convert_json(inputs, out_path, ignore_line_break, img, export_figure, figure
         for paragraph in inputs.paragraphs:
             paragraph_to_json(paragraph, ignore_line_break)
         if export_figure:
-            for _, figure, name in _save_figures(inputs.figures, img, out_path, figure_dir):
+            for _, figure, name in _save_figures(inputs.figures, img, out_path, figure_dir, files=figures):
                 figure.figure_path = os.path.join(figure_dir, name)
     return inputs
 
@@ -86,8 +112,11 @@ def save_json(data, out_path, encoding):
 
 
 def export_json(inputs, out_path, ignore_line_break=False, encoding: str = "utf-8", img=None, export_figure=False,
-                figure_dir="figures"):
-    inputs = convert_json(inputs, out_path, ignore_line_break, img, export_figure, figure_dir)
+                figure_dir="figures", figures=None):
+    """figures (every exporter takes it): the figure crops as encoded files - the PageFigures `DocumentAnalyzer.serve(figures=...)`
+    hands back for the page, or a sequence of EncodedJpeg / bytes with one entry per `inputs.figures` - written as they are under
+    the names the crops of `img` get; `img` is then neither needed nor looked at."""
+    inputs = convert_json(inputs, out_path, ignore_line_break, img, export_figure, figure_dir, figures=figures)
     save_json(inputs.model_dump(), out_path, encoding)
     return inputs
 
@@ -108,7 +137,7 @@ def paragraph_to_csv(paragraph, ignore_line_break):
 
 
 def convert_csv(inputs, out_path, ignore_line_break, img=None, export_figure: bool = True, export_figure_letter: bool = False,
-                figure_dir="figures"):
+                figure_dir="figures", figures=None):
     elements = [{"type": "table", "box": t.box, "element": table_to_csv(t, ignore_line_break), "order": t.order} for t in inputs.tables]
     elements += [{"type": "paragraph", "box": p.box, "element": paragraph_to_csv(p, ignore_line_break), "order": p.order}
                  for p in inputs.paragraphs]
@@ -119,7 +148,7 @@ def convert_csv(inputs, out_path, ignore_line_break, img=None, export_figure: bo
                                  "order": figure.order})
     elements = sorted(elements, key=lambda x: x["order"])
     if export_figure:
-        _save_figures(inputs.figures, img, out_path, figure_dir)
+        _save_figures(inputs.figures, img, out_path, figure_dir, files=figures)
     return elements
 
 
@@ -135,8 +164,8 @@ def save_csv(elements, out_path, encoding):
 
 
 def export_csv(inputs, out_path: str, ignore_line_break: bool = False, encoding: str = "utf-8", img=None, export_figure: bool = True,
-               export_figure_letter: bool = False, figure_dir="figures"):
-    elements = convert_csv(inputs, out_path, ignore_line_break, img, export_figure, export_figure_letter, figure_dir)
+               export_figure_letter: bool = False, figure_dir="figures", figures=None):
+    elements = convert_csv(inputs, out_path, ignore_line_break, img, export_figure, export_figure_letter, figure_dir, figures=figures)
     save_csv(elements, out_path, encoding)
     return elements
 
@@ -173,9 +202,10 @@ def table_to_md(table, ignore_line_break):
     return {"order": table.order, "box": table.box, "md": md}
 
 
-def figure_to_md(figures, img, out_path, export_figure_letter=False, ignore_line_break=False, width=200, figure_dir="figures"):
+def figure_to_md(figures, img, out_path, export_figure_letter=False, ignore_line_break=False, width=200, figure_dir="figures", files=None):
+    """files: what the exporters call `figures=` - the name is taken here by the page's figure elements."""
     elements = []
-    for _, figure, name in _save_figures(figures, img, out_path, figure_dir):
+    for _, figure, name in _save_figures(figures, img, out_path, figure_dir, files=files):
         elements.append({"order": figure.order, "md": f'<img src="{figure_dir}/{name}" width="{width}px"><br>'})
         if export_figure_letter:
             for paragraph in sorted(figure.paragraphs, key=lambda x: x.order):
@@ -184,11 +214,12 @@ def figure_to_md(figures, img, out_path, export_figure_letter=False, ignore_line
 
 
 def convert_markdown(inputs, out_path, ignore_line_break=False, img=None, export_figure_letter=False, export_figure=True,
-                     figure_width=200, figure_dir="figures"):
+                     figure_width=200, figure_dir="figures", figures=None):
     elements = [table_to_md(t, ignore_line_break) for t in inputs.tables]
     elements += [paragraph_to_md(p, ignore_line_break) for p in inputs.paragraphs]
     if export_figure:
-        elements.extend(figure_to_md(inputs.figures, img, out_path, export_figure_letter, ignore_line_break, figure_width, figure_dir=figure_dir))
+        elements.extend(figure_to_md(inputs.figures, img, out_path, export_figure_letter, ignore_line_break, figure_width, figure_dir=figure_dir,
+                                     files=figures))
     elements = sorted(elements, key=lambda x: x["order"])
     return "\n".join(e["md"] for e in elements), elements
 
@@ -199,8 +230,9 @@ def save_markdown(markdown, out_path, encoding):
 
 
 def export_markdown(inputs, out_path: str, ignore_line_break: bool = False, img=None, export_figure_letter=False, export_figure=True,
-                    figure_width=200, figure_dir="figures", encoding: str = "utf-8"):
-    markdown, _ = convert_markdown(inputs, out_path, ignore_line_break, img, export_figure_letter, export_figure, figure_width, figure_dir)
+                    figure_width=200, figure_dir="figures", encoding: str = "utf-8", figures=None):
+    markdown, _ = convert_markdown(inputs, out_path, ignore_line_break, img, export_figure_letter, export_figure, figure_width, figure_dir,
+                                   figures=figures)
     save_markdown(markdown, out_path, encoding)
     return markdown
 
@@ -237,9 +269,10 @@ def paragraph_to_html(paragraph, ignore_line_break):
     return {"box": paragraph.box, "order": paragraph.order, "html": f"<p>{contents}</p>"}
 
 
-def figure_to_html(figures, img, out_path, export_figure_letter=False, ignore_line_break=False, figure_dir="figures", width=200):
+def figure_to_html(figures, img, out_path, export_figure_letter=False, ignore_line_break=False, figure_dir="figures", width=200, files=None):
+    """files: what the exporters call `figures=`, as in figure_to_md."""
     elements = []
-    for _, figure, name in _save_figures(figures, img, out_path, figure_dir):
+    for _, figure, name in _save_figures(figures, img, out_path, figure_dir, files=files):
         elements.append({"order": figure.order, "html": f'<img src="{figure_dir}/{name}" width="{width}"><br>'})
         if export_figure_letter:
             for paragraph in sorted(figure.paragraphs, key=lambda x: x.order):
@@ -248,12 +281,12 @@ def figure_to_html(figures, img, out_path, export_figure_letter=False, ignore_li
 
 
 def convert_html(inputs, out_path, ignore_line_break, export_figure, export_figure_letter, img=None, figure_width=200,
-                 figure_dir="figures"):
+                 figure_dir="figures", figures=None):
     elements = [table_to_html(t, ignore_line_break) for t in inputs.tables]
     elements += [paragraph_to_html(p, ignore_line_break) for p in inputs.paragraphs]
     if export_figure:
         elements.extend(figure_to_html(inputs.figures, img, out_path, export_figure_letter, ignore_line_break, width=figure_width,
-                                       figure_dir=figure_dir))
+                                       figure_dir=figure_dir, files=figures))
     elements = sorted(elements, key=lambda x: x["order"])
     html_string = "".join(e["html"] for e in elements)
     if html_string:
@@ -274,8 +307,9 @@ def save_html(html, out_path, encoding):
 
 
 def export_html(inputs, out_path: str, ignore_line_break: bool = False, export_figure: bool = True, export_figure_letter: bool = False,
-                img=None, figure_width=200, figure_dir="figures", encoding: str = "utf-8"):
-    formatted, _ = convert_html(inputs, out_path, ignore_line_break, export_figure, export_figure_letter, img, figure_width, figure_dir)
+                img=None, figure_width=200, figure_dir="figures", encoding: str = "utf-8", figures=None):
+    formatted, _ = convert_html(inputs, out_path, ignore_line_break, export_figure, export_figure_letter, img, figure_width, figure_dir,
+                                figures=figures)
     save_html(formatted, out_path, encoding)
     return formatted
 

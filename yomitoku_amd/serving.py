@@ -35,7 +35,9 @@ as the job's PageFiles (`wave.job.files`; yomitoku_amd/jpeg.py: encode_page_file
 more under `bilevel="auto"` (yomitoku_amd/ccitt.py) - or its grey-valued pages, thresholded, with `"otsu"` (six
 more) or `"adaptive"` (seven more); `mrc` separates the pages that leaves into an ink mask and two layers in front of those
 launches (yomitoku_amd/mrc.py: the page-skew step's luminance and ink, cells, a pull per level, flags, push) and hands the layers
-to the JPEG launches and the masks to the Group 4 launches; a job with neither runs exactly the stages above.
+to the JPEG launches and the masks to the Group 4 launches; a job with `figures` has the crops of every page's `schema.figures` cut
+from the wave's pages by one launch and coded by the JPEG launches as pages of their own (yomitoku_amd/figures.py:
+crop_figure_files), the stage's third product; a job with none of the three runs exactly the stages above.
 
 `serve(deskew=...)` adds no stage either: the skew of every page of a wave is estimated and undone on the copy stream, behind the
 wave's uploads and before the event every stage waits for (yomitoku_amd/deskew.py: launch; five launches and the binariser's three),
@@ -117,8 +119,9 @@ class Wave:
 class _Job:
     """One serve() call: where results go and how many waves are still out."""
 
-    def __init__(self, n_hint=0, overlays=False, options=None, files=None, deskew=None):
+    def __init__(self, n_hint=0, overlays=False, options=None, files=None, deskew=None, figures=None):
         self.results = {}
+        self.figures = figures  # None, or the record of check_figures: the entries get the page's PageFigures, made in the render stage too
         self.deskew = deskew  # None, or the parameters of check_deskew: the pages are turned upright behind their upload
         self.options = options  # what the analyzer's serve() wants its stages to know about THIS job (read through wave.job)
         self.overlays = bool(overlays)  # entries are (schema, the analyzer's pictures...): the waves visit the render stage
@@ -326,7 +329,7 @@ class PagePipeline:
     def _render_loop(self):
         """The render stage: waves of overlays and / or jpeg jobs, after aggregation.  Turns every page's schema into (schema,
         the analyzer's pictures...) - ocr and layout overlay; OCR: the ocr overlay alone -, (schema, EncodedJpeg) or (schema,
-        pictures..., EncodedJpeg); a page whose
+        pictures..., EncodedJpeg), each with the page's PageFigures behind it in a figures job; a page whose
         drawing or encoding fails - or every page of the wave, when the launches fail - gets the exception."""
         stream = None
         if self._gpu:
@@ -341,7 +344,8 @@ class PagePipeline:
             try:
                 skews = self._skews(wave)
                 products = []  # per product of the job, per page: a tuple of entry members, or the exception
-                for wanted, fn in ((job.overlays, "_stage_render"), (job.files is not None, "_stage_jpeg")):
+                for wanted, fn in ((job.overlays, "_stage_render"), (job.files is not None, "_stage_jpeg"),
+                                   (job.figures is not None, "_stage_figures")):
                     if not wanted:
                         continue
                     try:
@@ -397,7 +401,7 @@ class PagePipeline:
                 except Exception as exc:  # noqa: BLE001 - aggregation is per page: only this page fails
                     logger.error("page %d failed in aggregation: %s: %s", idx, type(exc).__name__, exc)
                     done.append(exc)
-            if job.overlays or job.files is not None:  # the render stage writes the entries and hands the slot back
+            if job.overlays or job.files is not None or job.figures is not None:  # the render stage writes the entries and hands the slot back
                 wave.results = done
                 self._render_q.put(wave)
                 return
@@ -453,7 +457,7 @@ class PagePipeline:
             self._q[name].put(wave)
 
     def serve(self, sources: Iterable, with_source: bool = False, overlays: bool = False, options=None, files=None,
-              deskew=False) -> List:
+              deskew=False, figures=None) -> List:
         """sources: uint8 H x W x 3 BGR arrays and / or image file paths (a multi-frame file contributes one entry per
         frame).  Returns one entry per page, in order: the DocumentAnalyzerSchema, or the exception that page (or
         file) raised.  with_source=True: (source index, frame index within the source, entry) triples instead - what a
@@ -471,6 +475,10 @@ class PagePipeline:
         its upload, so words, boxes, overlays and page files are those of the corrected page, and a page's entry ends with its
         PageSkew - (schema, PageSkew), (schema, ..., EncodedJpeg, PageSkew); a failed page's entry stays the bare exception.  A
         page that is re-run alone is estimated again from its host original.  Needs a HIP device.
+        figures: None, or the record of the job's figure crops (yomitoku_amd/figures.py: check_figures makes it of the public
+        entry's `figures`): the crops of the page's `schema.figures` are cut from the clean - with deskew: corrected - page in the
+        render stage and coded as JPEG files, and the entry gets the page's PageFigures behind the page file and in front of
+        the PageSkew - (schema, PageFigures), (schema, ocr overlay, layout overlay, EncodedJpeg, PageFigures, PageSkew).
         options: carried on the job for the analyzer's own stages (TableSemanticParser: template / grid_only / kv_only); the
         pipeline does not look at it."""
         from .data.functions import load_image
@@ -480,8 +488,8 @@ class PagePipeline:
         if deskew is not None and not self._gpu:
             raise ValueError("deskew needs a HIP device: this pipeline has none (there is no host fallback)")
         with self._serve_lock, _full_gc_deferred(self.defer_full_gc), _switch_interval(self.switch_interval):
-            job = self._job = _Job(overlays=overlays, options=options, files=files, deskew=deskew)
-            if job.overlays or job.files is not None:
+            job = self._job = _Job(overlays=overlays, options=options, files=files, deskew=deskew, figures=figures)
+            if job.overlays or job.files is not None or job.figures is not None:
                 self._start_render()
             n = 0
             origin = []  # page id -> (source index, frame index)
@@ -621,7 +629,9 @@ class StageAnalyzer:
     (`wave.job.options`, `wave.job.overlays`); `_stage_render(wave, results)` (GPU, here; overlays jobs only) returns per page
     its pictures - pictures per page: as many as `_page_drawings(wave, k, results)` (subclass) records, the same for every page
     of an analyzer (DocumentAnalyzer and TableSemanticParser two, OCR one) -, from those drawings and `wave.pages`; `_stage_jpeg(wave, results)` (GPU,
-    here; jobs with page files only) returns per page a 1-tuple with its page file, from `wave.pages` and `wave.job.files`.  `_nets()`
+    here; jobs with page files only) returns per page a 1-tuple with its page file, from `wave.pages` and `wave.job.files`;
+    `_stage_figures(wave, results)` (GPU, here; figures jobs only) per page a 1-tuple with its PageFigures, from `wave.pages`,
+    `results[k].figures` and `wave.job.figures`.  `_nets()`
     (subclass): the modules whose `model.close()` releases the analyzer's device memory.
 
     `handover`: None, or an object that sees - and may replace - what one stage hands to the next, AFTER the stage has
@@ -644,6 +654,7 @@ class StageAnalyzer:
         self.handover = None
         self._render_pinned = {}  # wave slot -> [pinned buffer the slot's canvases come back through] (serve(overlays=True))
         self._jpeg_scratch = {}  # wave slot -> the encoder's device and pinned buffers, made when the slot first needs them (serve(jpeg=...))
+        self._figures_scratch = {}  # wave slot -> the figure crops' and their encoder's buffers, likewise (serve(figures=...))
         self._pipeline = None
 
     # ---- the two concurrent chains, each on its own HIP stream
@@ -758,6 +769,24 @@ class StageAnalyzer:
                 out[k] = made if isinstance(made, BaseException) else (made,)
         return out
 
+    def _stage_figures(self, wave, results, scratch=None):
+        """Figure crops: per page of the wave a 1-tuple with its PageFigures - the crops of `results[k].figures`, cut from
+        `wave.pages[k]` (the clean and, with deskew, corrected page) and coded as `wave.job.figures` says -, an exception for a page
+        that is no page, None for a page that had already failed.  All pages of the wave go through one call on the calling
+        thread's stream (yomitoku_amd/figures.py: crop_figure_files) with `scratch`, by default the wave slot's own."""
+        from .figures import crop_figure_files
+
+        out = [None] * len(wave)
+        live = [k for k in range(len(wave)) if not isinstance(results[k], BaseException)]
+        if live:
+            if scratch is None:
+                scratch = self._figures_scratch.setdefault(wave.ring, {})
+            made = crop_figure_files([wave.pages[k] for k in live], [[f.box for f in results[k].figures] for k in live],
+                                     wave.job.figures, scratch=scratch)
+            for k, one in zip(live, made):
+                out[k] = one if isinstance(one, BaseException) else (one,)
+        return out
+
     # ---- one wave at a time (`analyze_pages`, `parse_pages`): the same stage methods as two concurrent chains
     def _recognize_wave(self, wave):
         self._stage_crops(wave)
@@ -790,7 +819,8 @@ class StageAnalyzer:
         return wave
 
     # ---- the pipeline of this analyzer
-    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, files=None, deskew=False):
+    def _serve(self, sources, wave, in_flight, defer_full_gc, with_source, rec_lanes, overlays, options=None, files=None, deskew=False,
+               figures=None):
         """What the public `serve()`s share: the pipeline is built on first use and rebuilt when its shape changes."""
         pipe = self._pipeline
         if pipe is None or (pipe.wave, pipe.in_flight, pipe.rec_lanes_asked) != (max(1, int(wave)), max(1, int(in_flight)), int(rec_lanes)):
@@ -798,7 +828,7 @@ class StageAnalyzer:
                 pipe.close()
             pipe = self._pipeline = PagePipeline(self, wave=wave, in_flight=in_flight, rec_lanes=rec_lanes)
         pipe.defer_full_gc = bool(defer_full_gc)
-        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, files=files, deskew=deskew)
+        return pipe.serve(sources, with_source=with_source, overlays=overlays, options=options, files=files, deskew=deskew, figures=figures)
 
     def close(self, release_models: bool = True):
         """Stop the pipeline threads, drop the render buffers, release the extra recogniser handles and - `release_models` -
@@ -809,6 +839,7 @@ class StageAnalyzer:
             self._pipeline = None
         self._render_pinned.clear()
         self._jpeg_scratch.clear()
+        self._figures_scratch.clear()
         self.text_recognizer.close_replicas()
         if release_models:
             for module in self._nets():
