@@ -650,8 +650,8 @@ int ymk_table_hole_rects(int h, int w, const int* cell_boxes, int n, int pad, in
 int ymk_prof_begin(void);
 /* Test / measurement knobs, process-wide (never touched by the product path; defaults in parentheses):
  *   "splitk_force" (-1)  >= 0: that split-K tile shape for every eligible launch      "no_splitk" (0)  1: conv_igemm only
- *   "conv_variant" (0)   alternative conv_igemm schedules for A/B runs (tools/conv_sweep.py)       "prof_dump" (0)  1: ymk_prof_end
- *   prints one line per launch      "parseq_unfused" (0)  1: per-op PARSeq decoder step at every width
+ *   "conv_variant" (0)   alternative conv_igemm schedules for A/B runs (tools/conv_sweep.py): 0-4, 7, 8; any other value is an error
+ *   "prof_dump" (0)      1: ymk_prof_end prints one line per launch      "parseq_unfused" (0)  1: per-op PARSeq decoder step at every width
  *   "conv_fast" (27)     bit 0: index shortcut of 1x1 / stride-1 layers, bit 1: residual rows fetched ahead, bit 3: K-tile rows of the
  *                        128 x 64 tile XOR-swizzled instead of padded (48 KB of LDS: three blocks per CU) and that tile for every
  *                        launch with K <= 512, bit 4: accumulators of ragged-Cout launches stored straight from registers;
@@ -661,9 +661,8 @@ int ymk_prof_begin(void);
  *   "parseq_no_rowmax" (0)  1: the fused greedy loop writes every step's logits and arg-maxes them from memory (round-2 form);
  *                        0: the vocabulary head's epilogue reduces each 64-column tile to (max, column) and no AR logits exist
  *   "rowmax_tile" (0)    the kernel of that head where 128 x 128 tiles fill the chip: 0 = the A-stationary kernel, one column block
- *                        per block (K <= 192; else the 128 x 64 tile), 1 / 2 / 3 = 128 x 128 x 16 waves / 128 x 128 x 8 waves / 256 x 128,
- *                        4 = the A-stationary kernel with dealt column groups, 6 = 128 x 64 always (rounds 3-5) - the same pair
- *                        table, bit for bit, from each (tests/test_routes_gpu.py)
+ *                        per block (K <= 192; else the 128 x 64 tile), 6 = 128 x 64 always (rounds 3-5) - the same pair table,
+ *                        bit for bit, from each (tests/test_routes_gpu.py).  Any other value is an error and changes nothing
  * GELU: every kernel of the library (the exact-fp32 mode "conv_split" = 0 included, and the greedy decoder step) evaluates
  *   0.5 v (1 + erf(v / sqrt 2)) through one branch-free function (csrc/ymk_common.h gelu_f32: a rational erfc form on v_rcp_f32 /
  *   v_exp_f32) since round 5: absolute error < 5e-7 over the whole line (tests/test_ops_gpu.py), the size of the rounding of
@@ -673,10 +672,10 @@ int ymk_prof_begin(void);
  *                        ymk_op_conv2d: 0 = exact fp32 MFMA, 16 = two fp16 planes, 2 / 3 = bf16 planes (ymk_model_set_param above);
  *                        -1 = unset: models run their default (16), ymk_op_conv2d exact fp32.  Also set for a whole process by
  *                        the environment variable YMK_CONV_SPLIT (yomitoku_amd/_lib.py).
- *   "conv_split_tile" (0) tile shape of that path for A/B runs: 0 = by format, 1 = 128 x 64, 2 = 256 x 128 (16 waves),
- *                        3 = 128 x 128 (16 waves), 4 = 128 x 128 (8 waves), 11 = 256 x 256 (16 waves; two planes); two fp16
- *                        planes only: 20 / 21 = the LDS-DMA kernel (256- / 128-row tiles), 30 = the A-stationary kernel ("astat"
- *                        below).  Accepted: 0, 1, 2, 3, 4, 11, 20, 21, 30; any other value is an error and changes nothing
+ *   "conv_split_tile" (0) forces one product kernel of that path (tests): 0 = each launch by the routing rule, 1 = the
+ *                        register-staged kernel's 128 x 64 tile, 3 = its wide tile for the format (256 x 128 for three bf16
+ *                        planes, else 128 x 128 x 16 waves); two fp16 planes only: 21 = the LDS-DMA kernel, 30 = the A-stationary
+ *                        kernel ("astat" below).  Accepted: 0, 1, 3, 21, 30; any other value is an error and changes nothing
  *   "gemm_row_limit" (0) > 0: linear layers cut their rows into chunks of at most this many (rounded down to 1024s) - the chunking
  *                        that keeps an A operand view below the 4 GiB a buffer descriptor addresses, forced at test sizes
  *   "astat" (1)          1: chip-filling pointwise layers with K <= 192 and Cout > 64 run on the A-stationary kernel (K = 256 stays on

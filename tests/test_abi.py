@@ -66,13 +66,25 @@ def test_debug_options_exist_and_their_documented_defaults_agree():
     # "conv_split_tile" takes the selectors the routing code knows and nothing else: a retired or mistyped one is an error,
     # never a run of the default tile under another label
     try:
-        for tile in (0, 1, 2, 3, 4, 11, 20, 21, 30):
+        for tile in (0, 1, 3, 21, 30):
             assert lib.ymk_debug_option(b"conv_split_tile", tile) == 0, tile
-        for tile in (5, 10, 12, 14, 99):
+        for tile in (2, 4, 11, 20, 5, 10, 12, 14, 99, -1):
             assert lib.ymk_debug_option(b"conv_split_tile", tile) != 0, tile
+            assert lib.ymk_last_error(), tile
+        for variant in (0, 1, 2, 3, 4, 7, 8):
+            assert lib.ymk_debug_option(b"conv_variant", variant) == 0, variant
+        for variant in (5, 6, 9, -1):  # 5 / 6: the two-tiles-ahead loads, retired
+            assert lib.ymk_debug_option(b"conv_variant", variant) != 0, variant
+            assert lib.ymk_last_error(), variant
+        for tile in (0, 6):
+            assert lib.ymk_debug_option(b"rowmax_tile", tile) == 0, tile
+        for tile in (1, 2, 3, 4, 5, 7, -1):
+            assert lib.ymk_debug_option(b"rowmax_tile", tile) != 0, tile
             assert lib.ymk_last_error(), tile
     finally:
         assert lib.ymk_debug_option(b"conv_split_tile", 0) == 0
+        assert lib.ymk_debug_option(b"rowmax_tile", 0) == 0
+        assert lib.ymk_debug_option(b"conv_variant", 0) == 0
     src = open(os.path.join(ROOT, "yomitoku_amd", "csrc", "ymk_conv.hip")).read()
     assert int(re.search(r"g_conv_fast\{(\d+)\}", src).group(1)) == _lib.CONV_FAST_DEFAULT
     header = open(os.path.join(ROOT, "include", "ymk.h")).read()

@@ -97,10 +97,9 @@ SPLIT_SHAPE = (1, 150, 220)  # M = 33 000
 SPLIT_CASES = [  # tile, kernel, shape, cin, in view, cout, out view, res view
     (3, "1x1", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
     (3, "3x3p1", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
-    (20, "1x1", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
-    (20, "3x3d2", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
     (21, "1x1", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
     (21, "3x3p1", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
+    (21, "3x3d2", SPLIT_SHAPE, 64, (32, 128), 64, (64, 256), (4, 72)),
     (21, "3x3s2", (1, 300, 440), 32, (32, 96), 64, (64, 256), (4, 72)),   # 150 x 220 outputs again
     (21, "3x3p1", SPLIT_SHAPE, 36, (4, 96), 36, (4, 256), (8, 48)),        # a partial channel tile in every tap
     (3, "1x1", SPLIT_SHAPE, 36, (4, 96), 36, (0, 37), (1, 41)),            # scalar stores on a strided output

@@ -42,17 +42,16 @@ def test_deconv2x2_epilogue_small_m_exact_fp32(dev, cout):
 
 
 # conv_split code, conv_split_tile, mfma products per fp32-grade product of the launch that must have run, tolerance / max|y|
-BIG_RUNS = ([(0, 0, 0.0, 3e-6)] + [(16, t, 3.0, 4e-6) for t in (0, 1, 2, 3, 4, 11, 20, 21, 30)]
-            + [(3, 0, 6.0, 4e-6), (2, 0, 3.0, 2.0 ** -14)]
-            + [run for t in (1, 2, 4, 11) for run in ((3, t, 6.0, 4e-6), (2, t, 3.0, 2.0 ** -14))])
+BIG_RUNS = ([(0, 0, 0.0, 3e-6)] + [(16, t, 3.0, 4e-6) for t in (0, 1, 3, 21, 30)]
+            + [(3, 0, 6.0, 4e-6), (2, 0, 3.0, 2.0 ** -14), (3, 1, 6.0, 4e-6), (2, 1, 3.0, 2.0 ** -14)])
 
 
 def test_deconv2x2_epilogue_chip_filling_every_route(dev):
     """The binarize head's shape at a chip-filling M (2 x 150 x 201 = 60 300 rows, odd width; cin = 64, cout = 64: a 256-column
     panel) under every operand precision and forced tile of the split path: exact fp32 ("conv_split" 0), two fp16 planes (16)
-    on the automatic tile and on tiles 1, 2, 3, 4, 11, 20, 21 and 30 - which the A-stationary kernel refuses for this epilogue, so
+    on the automatic tile and on tiles 1, 3, 21 and 30 - which the A-stationary kernel refuses for this epilogue, so
     the launch falls back to the register-staged kernel - and three / two bf16 planes (3 / 2) on the automatic tile and on
-    tiles 1, 2, 4 and 11 (256 x 256 with two planes, the 128 x 128 fallback with three).  ymk_prof_launch_table names the
+    tile 1.  ymk_prof_launch_table names the
     kernel family that ran.  Tolerances as tests/test_conv_split_gpu.py asserts them: 3e-6 of max|y| for exact fp32, 4e-6 for
     two fp16 planes and three bf16 planes, 2^-14 for two bf16 planes (products to 2^-16)."""
     import ctypes

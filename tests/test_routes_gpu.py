@@ -113,9 +113,9 @@ def test_parseq_layernorm_fusion_and_astat_routing_on_and_off(dev):
 
 def test_row_max_head_on_every_kernel_it_can_run_on_changes_no_bit(dev):
     """"rowmax_tile": the greedy loop's vocabulary head (1300 rows x 7119 columns x K = 192, (max, column) per 64-column sub-tile
-    in its epilogue) on the A-stationary kernel (0: the default since round 6; 4: its column blocks dealt to groups) and on
-    128 x 128 / 256 x 128 tiles (1-3) against the 128 x 64 tile of rounds 3-5 (6) - the same planes, products and K order per
-    accumulator and the same pair table, so tokens, step counts and the refined logits are the same bits."""
+    in its epilogue) on the A-stationary kernel (0: the default since round 6) against the 128 x 64 tile of rounds 3-5 (6) - the
+    same planes, products and K order per accumulator and the same pair table, so tokens, step counts and the refined logits
+    are the same bits."""
     from tests.test_parseq_gpu import _net
     from yomitoku_amd import _lib
     from yomitoku_amd.utils.synth import parseq_state_dict, synthetic_line_batch
@@ -124,19 +124,18 @@ def test_row_max_head_on_every_kernel_it_can_run_on_changes_no_bit(dev):
     _, net = _net(dev, sd)
     x = synthetic_line_batch(31, 1300, 64).to(dev)
     outs = {}
-    for tile in (6, 0, 1, 2, 3, 4):
+    for tile in (6, 0):
         with _Option("rowmax_tile", tile, 0):
             w0, a0 = _lib.stat("rowmax_wide_launches"), _lib.stat("astat_launches")
             outs[tile] = (net(x).cpu(), net.last_ar_steps)
             wide, astat = _lib.stat("rowmax_wide_launches") - w0, _lib.stat("astat_launches") - a0
             assert (wide == 0) if tile == 6 else (wide >= outs[tile][1]), (tile, wide)
-            if tile in (0, 4):
+            if tile == 0:
                 assert astat - astat_other >= outs[tile][1], (tile, astat, astat_other)  # the head's launches on top of the encoder's
             else:
                 astat_other = astat
     assert outs[6][1] >= 2
-    for tile in (0, 1, 2, 3, 4):
-        assert outs[tile][1] == outs[6][1] and torch.equal(outs[tile][0], outs[6][0]), tile
+    assert outs[0][1] == outs[6][1] and torch.equal(outs[0][0], outs[6][0])
 
 
 def test_whole_pages_with_every_route_on_and_off(dev):

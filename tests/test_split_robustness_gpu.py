@@ -156,7 +156,7 @@ def test_an_all_zero_input_takes_the_clamped_scale(dev):
     x = torch.zeros(2, 64, 160, 160)
     try:
         _lib.debug_option("conv_split", 16)
-        for tile in (0, 3, 20, 21):
+        for tile in (0, 3, 21):
             _lib.debug_option("conv_split_tile", tile)
             y = hipops.conv2d(x.to(dev), wt, sc, bi, None, 1, 1, 1, "none").cpu()
             assert torch.equal(y, bi.view(1, -1, 1, 1).expand_as(y)), tile

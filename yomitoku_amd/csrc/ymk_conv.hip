@@ -34,15 +34,12 @@
 
 namespace ymk {
 
-// PF: K tiles the global loads run ahead of the MFMAs (1: the tile consumed next; 2: one more - two register sets, so a
-// load has two compute phases to come back from MALL / HBM before its ds_write waits for it)
 // OPT bit 0: accumulators go straight to global memory (every wave on its own: no LDS staging, no block barrier in the
 //            epilogue; a half-wave writes 128 contiguous bytes of an output row per store) - EPI_STORE launches only
 // OPT bit 1: K-tile rows of 32 floats with the 16-byte slots XOR-swizzled over row pairs instead of rows padded to 36:
 //            the 128 x 64 tile then takes 48 KB of LDS and THREE blocks share a CU
-template <int BM, int BN, int WM, int WN, int MODE, int PF = 1, int OPT = 0>
+template <int BM, int BN, int WM, int WN, int MODE, int OPT = 0>
 __global__ __launch_bounds__(64 * WM * WN, ((OPT & 2) ? blocks_per_cu(BM, BN, OPT) : 2 * (BM + BN) * LDK * 4 <= 80 * 1024 ? 2 : 1) * WM * WN / 4) void conv_igemm(ConvK p) {
-  static_assert(PF == 1 || PF == 2, "prefetch distance 1 or 2");
   constexpr int LDR = lds_row(OPT);
   static_assert(!(OPT & 2) || (64 * WM * WN / 8) % 16 == 0, "swizzle: staging passes must keep (row >> 1) & 7");
   constexpr int NT = 64 * WM * WN;             // 4, 8 or 16 waves
@@ -99,7 +96,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((OPT & 2) ? blocks_per_cu(BM, BN, OP
   const float* wrow = p.w + (size_t)(n0 + rowb) * p.Kpad + colq * 4;
 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
-  f32x4 ra[PF][APASS], rb[PF][BPASS];
+  f32x4 ra[APASS], rb[BPASS];
 
   // K-tile cursor (wave-uniform, kept in scalar registers): tap (kh, kw) and channel tile cc
   int cur_kh = 0, cur_kw = 0, cur_cc = 0;
@@ -112,7 +109,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((OPT & 2) ? blocks_per_cu(BM, BN, OP
   for (int i = 0; i < APASS; ++i) voff[i] = OOB_OFFSET;
 
   // branch-free gather of one K tile: out-of-image / padded taps read a safe address and are zeroed
-  auto load_tile = [&](int kt, int set) {
+  auto load_tile = [&](int kt) {
     if (MODE == 0) {
       if (cur_cc == 0) {  // wave-uniform: a new filter tap
         const int dh = cur_kh * p.dil, dw = cur_kw * p.dil;
@@ -129,7 +126,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((OPT & 2) ? blocks_per_cu(BM, BN, OP
 #pragma unroll
       for (int i = 0; i < APASS; ++i) {
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(chan_ok ? voff[i] : OOB_OFFSET), soff, 0);
-        ra[set][i] = __builtin_bit_cast(f32x4, v);
+        ra[i] = __builtin_bit_cast(f32x4, v);
       }
       if (++cur_cc == p.ctiles) {
         cur_cc = 0;
@@ -149,24 +146,24 @@ __global__ __launch_bounds__(64 * WM * WN, ((OPT & 2) ? blocks_per_cu(BM, BN, OP
         const bool ok = tapok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
         const unsigned off = ((unsigned)(pixb[i] + ih * p.W + iw) * (unsigned)p.in_ld) * 4u;
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(ok ? off : OOB_OFFSET), 0, 0);
-        ra[set][i] = __builtin_bit_cast(f32x4, v);
+        ra[i] = __builtin_bit_cast(f32x4, v);
       }
     }
 #pragma unroll
     for (int j = 0; j < BPASS; ++j)
-      rb[set][j] = *reinterpret_cast<const f32x4*>(wrow + (size_t)(RPP * j) * p.Kpad + kt * 32);
+      rb[j] = *reinterpret_cast<const f32x4*>(wrow + (size_t)(RPP * j) * p.Kpad + kt * 32);
   };
 
   const int st_off = lds_slot<OPT>(rowb, colq);  // RPP is a multiple of 16 rows: the passes only add whole lines
-  auto store_tile = [&](int buf, int set) {
+  auto store_tile = [&](int buf) {
     float* As = lds + buf * STAGE + st_off;
     float* Bs = As + BM * LDR;
 #pragma unroll
     for (int i = 0; i < APASS; ++i)
-      *reinterpret_cast<f32x4*>(As + RPP * i * LDR) = ra[set][i];
+      *reinterpret_cast<f32x4*>(As + RPP * i * LDR) = ra[i];
 #pragma unroll
     for (int j = 0; j < BPASS; ++j)
-      *reinterpret_cast<f32x4*>(Bs + RPP * j * LDR) = rb[set][j];
+      *reinterpret_cast<f32x4*>(Bs + RPP * j * LDR) = rb[j];
   };
 
   // ---- MFMA coordinates
@@ -213,37 +210,21 @@ __global__ __launch_bounds__(64 * WM * WN, ((OPT & 2) ? blocks_per_cu(BM, BN, OP
     }
   };
 
-  load_tile(0, 0);
-  store_tile(0, 0);
-  if (PF == 2 && ktiles > 1) load_tile(1, 1);
+  load_tile(0);
+  store_tile(0);
   __syncthreads();
 
   using Epi = EpiRows<EROWS, BN, NT>;
-  constexpr bool CAN_PRE = PF == 1 && EROWS == BM && Epi::NR <= 8 && NT <= 512;  // the 16-wave tiles have no registers to spare
+  constexpr bool CAN_PRE = EROWS == BM && Epi::NR <= 8 && NT <= 512;  // the 16-wave tiles have no registers to spare
   const bool pre_res = CAN_PRE && (p.fast & 2) && p.res != nullptr && p.vec && p.epi == EPI_STORE;  // block-uniform
   float4 rpre[CAN_PRE ? Epi::NR : 1];
-  if (PF == 1) {
-    for (int kt = 0; kt < ktiles; ++kt) {
-      const int buf = kt & 1;
-      if (kt + 1 < ktiles) load_tile(kt + 1, 0);
-      if (CAN_PRE && kt + 1 == ktiles && pre_res) prefetch_residual<EROWS, BN, NT>(p, m0, n0, t, rpre);
-      compute(buf);
-      if (kt + 1 < ktiles) store_tile(buf ^ 1, 0);
-      if (!(OPT & 1) || kt + 1 < ktiles) __syncthreads();  // the direct epilogue does not reuse the LDS
-    }
-  } else {
-    // tile t travels in register set t & 1: loaded at the top of step t - 2, written to LDS[t & 1] at the end of step t - 1
-    for (int kt = 0; kt < ktiles; kt += 2) {
-      if (kt + 2 < ktiles) load_tile(kt + 2, 0);
-      compute(0);
-      if (kt + 1 < ktiles) store_tile(1, PF - 1);
-      __syncthreads();
-      if (kt + 1 >= ktiles) break;
-      if (kt + 3 < ktiles) load_tile(kt + 3, PF - 1);
-      compute(1);
-      if (kt + 2 < ktiles) store_tile(0, 0);
-      __syncthreads();
-    }
+  for (int kt = 0; kt < ktiles; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < ktiles) load_tile(kt + 1);
+    if (CAN_PRE && kt + 1 == ktiles && pre_res) prefetch_residual<EROWS, BN, NT>(p, m0, n0, t, rpre);
+    compute(buf);
+    if (kt + 1 < ktiles) store_tile(buf ^ 1);
+    if (!(OPT & 1) || kt + 1 < ktiles) __syncthreads();  // the direct epilogue does not reuse the LDS
   }
 
   if (OPT & 1) {
@@ -489,7 +470,10 @@ int conv_effective_split() {
 bool conv_debug_option(const std::string& key, int value) {
   if (key == "splitk_force") g_splitk_force = value;
   else if (key == "no_splitk") g_no_splitk = value;
-  else if (key == "conv_variant") g_conv_variant = value;
+  else if (key == "conv_variant") {
+    YMK_CHECK((value >= 0 && value <= 4) || value == 7 || value == 8, "conv_variant " + std::to_string(value) + " is no selector; accepted: 0 1 2 3 4 7 8");
+    g_conv_variant = value;
+  }
   else if (key == "conv_fast") g_conv_fast = value;
   else if (key == "prof_dump") g_prof_dump = value;
   else if (key == "conv_split") g_conv_split = value;
@@ -627,7 +611,7 @@ static bool try_splitk(hipStream_t s, ConvK& k) {
   return true;
 }
 
-template <int BM, int BN, int WM, int WN, int MODE = 0, int PF = 1>
+template <int BM, int BN, int WM, int WN, int MODE = 0>
 static void launch(hipStream_t s, ConvK& k) {
   const int mt = (k.M + BM - 1) / BM, nt = (k.Cout + BN - 1) / BN;
   k.ntiles_n = nt;
@@ -635,20 +619,20 @@ static void launch(hipStream_t s, ConvK& k) {
   // ConvK::fast bits 2 / 4: direct epilogue (plain stores only; everywhere / ragged Cout); bit 3: swizzled K tiles.
   // (A persistent tile loop over the swizzled tile - next tile's first loads issued before this tile's epilogue - was
   // measured in round 4 and removed: bit-identical, 5-30 % slower on 15 of 17 shapes, profiles/r04_conv_sweep_persistent_tile_loop.txt)
-  constexpr bool HAS_OPT = MODE == 0 && PF == 1;
+  constexpr bool HAS_OPT = MODE == 0;
   constexpr bool HAS_SWZ = HAS_OPT && BM == 128 && BN == 64 && WM * WN == 8;
   const bool direct = HAS_OPT && k.epi == EPI_STORE && ((k.fast & 4) || ((k.fast & 16) && !k.vec));
   const bool swz = HAS_SWZ && (k.fast & 8);
   auto* e = conv_prof_open(s, k, BM, BN, mt * nt, 1);
   const dim3 grid(mt * nt), block(64 * WM * WN);
   if constexpr (HAS_SWZ) {
-    if (swz && direct) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, PF, 3>), grid, block, 0, s, k);
-    else if (swz) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, PF, 2>), grid, block, 0, s, k);
+    if (swz && direct) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, 3>), grid, block, 0, s, k);
+    else if (swz) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, 2>), grid, block, 0, s, k);
   }
   if constexpr (HAS_OPT) {
-    if (direct && !swz) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, PF, 1>), grid, block, 0, s, k);
+    if (direct && !swz) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, 1>), grid, block, 0, s, k);
   }
-  if (!direct && !swz) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE, PF>), grid, block, 0, s, k);
+  if (!direct && !swz) hipLaunchKernelGGL((conv_igemm<BM, BN, WM, WN, MODE>), grid, block, 0, s, k);
   if (e) YMK_HIP(hipEventRecord(e->second, s));
 }
 
@@ -661,14 +645,15 @@ static void launch(hipStream_t s, ConvK& k) {
 // epilogue) and lose a little on the long-K layers; the 128 x 64 tile likewise gains from eight waves.  Interleaving the
 // MFMA order across accumulators, s_setprio around the MFMA cluster and a 256 x 128 tile changed nothing or lost.
 // conv_variant (ymk_debug_option) keeps the alternatives reachable for A/B runs:
-//   wide path (Cout > 64):  0 = by K (default)   1 = 4 waves (round 1)   2 = 16 waves   4 = 8 waves   5 = 8 waves, loads 2 K tiles ahead   8 = 128 x 64 tiles
-//   narrow path (128 x 64): 0 = 8 waves (default)   3 = 4 waves (round 1)   6 = 8 waves, loads 2 K tiles ahead
+//   wide path (Cout > 64):  0 = by K (default)   1 = 4 waves (round 1)   2 = 16 waves   4 = 8 waves   8 = 128 x 64 tiles
+//   narrow path (128 x 64): 0 = 8 waves (default)   3 = 4 waves (round 1)
+//   any shape: 7 = 64 x 64 tiles.  5 and 6 (eight waves with the loads two K tiles ahead, a second register set: level or behind
+//   on every layer, profiles/r02_conv_sweep_c_prefetch.txt) are retired and refused
 static void launch_wide(hipStream_t s, ConvK& k) {
   switch (g_conv_variant.load(std::memory_order_relaxed)) {
     case 1: launch<128, 128, 2, 2>(s, k); break;
     case 2: launch<128, 128, 4, 4>(s, k); break;
     case 4: launch<128, 128, 4, 2>(s, k); break;
-    case 5: launch<128, 128, 4, 2, 0, 2>(s, k); break;
     case 8: launch<128, 64, 4, 2>(s, k); break;  // A/B runs: 64-wide tiles whatever Cout
     default:
       if (k.Kpad <= 512) launch<128, 128, 4, 4>(s, k);
@@ -679,7 +664,6 @@ static void launch_wide(hipStream_t s, ConvK& k) {
 static void launch_n64(hipStream_t s, ConvK& k) {
   switch (g_conv_variant.load(std::memory_order_relaxed)) {
     case 3: launch<128, 64, 2, 2>(s, k); break;
-    case 6: launch<128, 64, 4, 2, 0, 2>(s, k); break;
     default: launch<128, 64, 4, 2>(s, k); break;
   }
 }
@@ -782,7 +766,7 @@ static bool conv2d_impl(hipStream_t s, const Tensor& in, const ConvW& w, const C
     const int mt = (k.M + 63) / 64, nt = (k.Cout + ROWMAX_TILE_N - 1) / ROWMAX_TILE_N;
     k.ntiles_n = nt;
     auto* e = conv_prof_open(s, k, 64, 64, mt * nt, 1);
-    hipLaunchKernelGGL((conv_igemm<64, 64, 2, 2, 0, 1>), dim3(mt * nt), dim3(256), 0, s, k);
+    hipLaunchKernelGGL((conv_igemm<64, 64, 2, 2, 0>), dim3(mt * nt), dim3(256), 0, s, k);
     if (e) YMK_HIP(hipEventRecord(e->second, s));
     YMK_HIP(hipGetLastError());
     return true;

@@ -24,7 +24,6 @@
 //     sequence over (column block, K tile) - the pipeline does not drain between column blocks;
 //   * a column block's accumulators go out straight from registers, four rows at a time through buffer descriptors; with two
 //     blocks per CU (K = 192 at 128 columns: 255 VGPRs, 48 KB of LDS) the other block's MFMAs cover this one's epilogue.
-#include <atomic>
 #include <string>
 
 #include "ymk_conv_kernel.h"
@@ -349,9 +348,6 @@ __global__ __launch_bounds__(256, 2) void conv_f16_astat(ConvK p, const uint4* _
 }
 
 
-static std::atomic<int> g_astat_rowmax_dealt{0};  // "rowmax_tile" 4 (A/B runs): the head's column blocks dealt to groups as a store launch's are
-void astat_rowmax_dealt(int on) { g_astat_rowmax_dealt = on; }
-
 template <int BN, int KT, bool LN, bool RM = false>
 static void launch_astat(hipStream_t s, ConvK& k, const void* planes, size_t w_bytes, int groups) {
   hipLaunchKernelGGL((conv_f16_astat<BN, KT, LN, RM>), dim3((k.M + 127) / 128, groups), dim3(256), 0, s, k, reinterpret_cast<const uint4*>(planes), (unsigned)w_bytes);
@@ -404,7 +400,7 @@ bool conv2d_f16_astat(hipStream_t s, ConvK& k, const void* planes, size_t w_byte
   while (mblocks * groups < 512 && groups * 2 <= k.ntiles_n) groups *= 2;
   // the row-max head: ONE column block per block (job AE, 655 / 1234 / 2048 rows x 7119 columns: 24.3 / 28.2 / 38.8 us against 33.4 /
   // 38.1 / 43.8 with two per block) - its blocks are short and latency-bound, the more of them in flight the better
-  if (k.epi == EPI_ROWMAX && !g_astat_rowmax_dealt.load(std::memory_order_relaxed)) groups = k.ntiles_n;
+  if (k.epi == EPI_ROWMAX) groups = k.ntiles_n;
   const int kt = k.Kpad / 32;
   if (k.epi == EPI_ROWMAX) {
     switch (kt) {

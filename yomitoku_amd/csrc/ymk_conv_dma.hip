@@ -8,11 +8,11 @@
 //   * both operands travel global -> LDS by `buffer_load_dwordx4 ... lds` (no staging registers, no ds_write, no VALU): the
 //     weight planes are stored in LDS layout already; the ACTIVATIONS land in LDS as the fp32 they are in HBM - a padding tap
 //     or a row past M is an out-of-range buffer offset, for which the DMA writes zeros;
-//   * a wave owns 32 rows x BN columns of a 256 x BN block tile (8 waves): it converts the fp32 A fragment it reads into the
+//   * a wave owns 32 rows x BN columns of a 128 x BN block tile (4 waves): it converts the fp32 A fragment it reads into the
 //     two fp16 planes IN REGISTERS, once per 16-k step, for BN / 32 column tiles x 3 MFMAs (no other wave converts the same
 //     rows), and it DMA-loads exactly the 32 A rows it will read itself;
-//   * three LDS stages of one 32-k tile each (48 KB: 144 KB per block, one block per CU), loads two tiles ahead, ONE raw
-//     s_barrier per K tile, counted `s_waitcnt vmcnt` (the DMA of tiles t+1 / t+2 stays in flight across the barrier);
+//   * two LDS stages of one 32-k tile each (68 KB per block at BN = 128: TWO blocks per CU - another block's main loop covers
+//     a block's prologue and epilogue, what the short-K layers need), loads one tile ahead, ONE raw s_barrier per K tile;
 //   * LDS rows are 128 B (32 fp32 of A; 2 planes x 32 halves of B) with the 16-byte slot index XOR-ed by (row >> 1) & 7 -
 //     applied on the DMA's SOURCE address (the destination of a wave's DMA is linear) and on the fragment reads - so that
 //     the 16 rows a ds_read_b128 phase touches fall on 16 different slots of the 256-byte bank line.
@@ -25,16 +25,17 @@ namespace ymk {
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-// DMA_WAVES waves of 32 rows x BN columns (block tile 32 DMA_WAVES x BN), DMA_NST LDS stages of one 32-k tile, loads
-// DMA_NST - 1 tiles ahead.  <BN, 8, 3>: 256-row tiles, 144 KB, one block per CU.  <BN, 4, 2>: 128-row tiles, 68 KB, TWO blocks
-// per CU - another block's main loop covers a block's prologue and epilogue (what the short-K layers need).
+constexpr int DMA_WAVES = 4;  // a wave owns 32 rows x BN columns: 128-row block tiles
+
+// (A 256-row form - eight waves, three stages, loads two tiles ahead, one block per CU - measured level on the long-K layers and
+// behind wherever a block's prologue / epilogue weighs, as did a three-stage 128 x 64 form: profiles/r04_conv_sweep_f16_lds_dma.txt.)
 // APL: the ACTIVATIONS are fp16 planes in HBM already (Tensor::planes, layout in ymk_f16_planes.h: the 128 bytes of a pixel's
 // 32-channel slice are 32 high halves then 32 low halves, written by the producing convolution's epilogue under p.amax): the
 // fragment read is two ds_read_b128 straight into the MFMA operands - no fp32 -> (h, l) conversion in the loop, where the fp32
 // form spends 12 VALU instructions per 16-k step and tap (6.8 VALU per MFMA on the 3 x 3 layers, the MFMA pipe 0.47 busy:
 // profiles/r04_conv_f16_short_k_pmc_pass*.csv).  Same DMA addressing, same swizzle, same products in the same order.
 // OPL: the epilogue writes planes (epilogue_tile<.., PL>).
-template <int BN, int DMA_WAVES, int DMA_NST, bool APL = false, bool OPL = false>
+template <int BN, bool APL = false, bool OPL = false>
 __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const uint4* __restrict__ wsplit, unsigned w_bytes) {
   constexpr int DMA_BM = 32 * DMA_WAVES, DMA_NT = 64 * DMA_WAVES;
   constexpr int TN = BN / 32;                 // 32-column MFMA tiles of a wave
@@ -43,12 +44,10 @@ __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const
   constexpr int STAGE_B = A_STAGE + B_STAGE;
   constexpr int BROWS = BN / DMA_WAVES;       // B rows a wave loads per K tile
   constexpr int BI = BROWS / 8;               // B DMA instructions per wave per K tile (8 rows each)
-  constexpr int NLOAD = 4 + BI;               // DMA instructions a wave issues per K tile
   constexpr int LDC = BN + 4;
-  constexpr int PD = DMA_NST - 1;             // prefetch distance in K tiles
   constexpr int EPI_B = DMA_BM * LDC * 4;     // the fp32 output tile of the epilogue
-  constexpr int LDS_B = DMA_NST * STAGE_B > EPI_B ? DMA_NST * STAGE_B : EPI_B;
-  static_assert(BROWS % 8 == 0 && PD >= 1 && PD <= 2, "shape");
+  constexpr int LDS_B = 2 * STAGE_B > EPI_B ? 2 * STAGE_B : EPI_B;
+  static_assert(BROWS % 8 == 0, "shape");
   __shared__ __attribute__((aligned(16))) char lds[LDS_B];
 
   const int t = threadIdx.x, wv = t >> 6, lane = t & 63, li = lane & 31, lh = lane >> 5;
@@ -178,23 +177,20 @@ __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const
   };
 
   issue(0, 0);
-  if (PD > 1 && ktiles > 1) issue(1, 1);
-  int st = 0, stp = PD;  // stage of tile kt / of tile kt + PD
+  int st = 0, stp = 1;  // stage of tile kt / of tile kt + 1
   for (int kt = 0; kt < ktiles; ++kt) {
-    // tile kt has landed once this wave's own DMAs of it have (a younger tile's may stay in flight) and every wave has
-    // said so; the same barrier tells that every wave is done reading the stage tile kt + PD is about to overwrite
-    if (PD > 1 && kt + 1 < ktiles) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLOAD) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // tile kt has landed once this wave's own DMAs of it have and every wave has said so; the same barrier tells that every
+    // wave is done reading the stage tile kt + 1 is about to overwrite
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (PD == 1 && kt + 1 < ktiles) issue(kt + 1, stp);  // one tile ahead: as early as the barrier allows
+    if (kt + 1 < ktiles) issue(kt + 1, stp);  // one tile ahead: as early as the barrier allows
     compute(st, 0);
-    if (PD > 1 && kt + PD < ktiles) issue(kt + PD, stp);  // behind the first step's MFMAs: the address arithmetic rides in their shadow
     compute(st, 1);
-    st = st == DMA_NST - 1 ? 0 : st + 1;
-    stp = stp == DMA_NST - 1 ? 0 : stp + 1;
+    st = st == 1 ? 0 : st + 1;  // (two counters, not `kt & 1`: that form gives every kernel another register allocation)
+    stp = stp == 1 ? 0 : stp + 1;
   }
 
-  // ---- epilogue: accumulators (times 1 / sa: exact) -> LDS as [256][BN + 4] fp32 -> the shared coalesced epilogue
+  // ---- epilogue: accumulators (times 1 / sa: exact) -> LDS as [128][BN + 4] fp32 -> the shared coalesced epilogue
   __syncthreads();
   float* Cs = reinterpret_cast<float*>(lds);
 #pragma unroll
@@ -208,39 +204,26 @@ __global__ __launch_bounds__(64 * DMA_WAVES, 2) void conv_f16_dma(ConvK p, const
   epilogue_tile<DMA_BM, BN, DMA_NT, false, 4, OPL>(p, Cs, m0, n0, t);
 }
 
-template <int BN, int WAVES, int NST, bool APL = false, bool OPL = false>
+template <int BN, bool APL = false, bool OPL = false>
 static void launch_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes) {
-  const int mt = (k.M + 32 * WAVES - 1) / (32 * WAVES), nt = (k.Cout + BN - 1) / BN;
+  const int mt = (k.M + 32 * DMA_WAVES - 1) / (32 * DMA_WAVES), nt = (k.Cout + BN - 1) / BN;
   k.ntiles_n = nt;
-  hipLaunchKernelGGL((conv_f16_dma<BN, WAVES, NST, APL, OPL>), dim3(mt * nt), dim3(64 * WAVES), 0, s, k, reinterpret_cast<const uint4*>(wsplit), (unsigned)w_bytes);
+  hipLaunchKernelGGL((conv_f16_dma<BN, APL, OPL>), dim3(mt * nt), dim3(64 * DMA_WAVES), 0, s, k, reinterpret_cast<const uint4*>(wsplit), (unsigned)w_bytes);
 }
 
 template <int BN>
-static void launch_dma_planes(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes) {
-  if (k.in_planes && k.out_planes) launch_dma<BN, 4, 2, true, true>(s, k, wsplit, w_bytes);
-  else if (k.in_planes) launch_dma<BN, 4, 2, true, false>(s, k, wsplit, w_bytes);
-  else launch_dma<BN, 4, 2, false, true>(s, k, wsplit, w_bytes);
+static void launch_dma_bn(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes) {
+  if (k.in_planes && k.out_planes) launch_dma<BN, true, true>(s, k, wsplit, w_bytes);
+  else if (k.in_planes) launch_dma<BN, true, false>(s, k, wsplit, w_bytes);
+  else if (k.out_planes) launch_dma<BN, false, true>(s, k, wsplit, w_bytes);
+  else launch_dma<BN>(s, k, wsplit, w_bytes);
 }
 
-// the caller (conv2d_split) has resolved the panel and the input's max|x| record.  rows: 128 (4 waves, two stages, two or three
-// blocks per CU: the form the dispatch uses) or 256 (8 waves, three stages, one block per CU: kept for A/B runs - level on the
-// long-K layers, behind wherever a block's prologue / epilogue weighs, profiles/r04_conv_sweep_f16_lds_dma.txt; a three-stage
-// 128 x 64 form measured no better than the two-stage one and was dropped)
-bool conv2d_f16_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes, bool narrow, int rows) {
+// the caller (conv2d_split) has resolved the panel and the input's max|x| record
+bool conv2d_f16_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes, bool narrow) {
   if (w_bytes >= (size_t)OOB_OFFSET) return false;
-  if (k.in_planes || k.out_planes) {  // the plane forms exist for the dispatch's own tile (128 rows) only
-    if (rows != 128) return false;
-    if (narrow) launch_dma_planes<64>(s, k, wsplit, w_bytes);
-    else launch_dma_planes<128>(s, k, wsplit, w_bytes);
-    return true;
-  }
-  if (rows == 128) {
-    if (narrow) launch_dma<64, 4, 2>(s, k, wsplit, w_bytes);
-    else launch_dma<128, 4, 2>(s, k, wsplit, w_bytes);
-  } else {
-    if (narrow) launch_dma<64, 8, 3>(s, k, wsplit, w_bytes);
-    else launch_dma<128, 8, 3>(s, k, wsplit, w_bytes);
-  }
+  if (narrow) launch_dma_bn<64>(s, k, wsplit, w_bytes);
+  else launch_dma_bn<128>(s, k, wsplit, w_bytes);
   return true;
 }
 

@@ -339,11 +339,10 @@ int conv_split_route_with_planes(long M, int cout, int kpad, int taps, bool* aut
 bool vit_mlp_split_launch(hipStream_t s, SplitCtx* ctx, float* x, int M, int ld, const float* ln_g, const float* ln_b, float ln_eps,
                           float ln_bound, const ConvW& fc1, const ConvW& fc2);
 // LDS-DMA kernel (ymk_conv_dma.hip); the caller has resolved the panel and the input's max|x| record
-bool conv2d_f16_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes, bool narrow, int rows);
+bool conv2d_f16_dma(hipStream_t s, ConvK& k, const void* wsplit, size_t w_bytes, bool narrow);
 // A-stationary short-K 1 x 1 kernel (ymk_conv_astat.hip): false = this launch is not one it runs
 bool conv2d_f16_astat_can(const ConvK& k, size_t w_bytes);
 bool conv2d_f16_astat(hipStream_t s, ConvK& k, const void* planes, size_t w_bytes);
 int conv2d_f16_astat_columns(const ConvK& k);
-void astat_rowmax_dealt(int on);  // "rowmax_tile" 4: the row-max launch deals its column blocks to groups
 
 }  // namespace ymk

@@ -595,14 +595,13 @@ static void launch_split(hipStream_t s, ConvK& k, const void* wsplit, SplitCtx* 
   if (e) YMK_HIP(hipEventRecord(e->second, s));
 }
 
-// ymk_debug_option("conv_split_tile", v), for A/B runs; any other value is refused (SPLIT_TILES):
-//   0 = the measured best per format (profiles/r03_conv_sweep_bf16_split*.txt): 256 x 128 for three bf16 planes, else 128 x 128 x 16 waves
-//   shapes of the register-staged kernel (dispatch_staged), every format:
-//     1 = 128 x 64, 8 waves        2 = 256 x 128, 16 waves        3 = 128 x 128, 16 waves        4 = 128 x 128, 8 waves
-//     11 = 256 x 256, 16 waves (64 x 64 per wave) with two planes and Cout >= 256, else as 3
-//   other kernels, fp16 form only (the bf16 forms run as 3): 20 / 21 = the LDS-DMA kernel with 256- / 128-row tiles, 30 = the
-//     A-stationary kernel for every launch it can run (route_f16)
-static constexpr int SPLIT_TILES[] = {0, 1, 2, 3, 4, 11, 20, 21, 30};
+// ymk_debug_option("conv_split_tile", v): 0 = every launch by the rule (route_f16; the bf16 forms run the register-staged kernel);
+// the others force one of the product kernels, for tests that reach or compare them - any other value is refused (SPLIT_TILES):
+//   1 = the register-staged kernel, narrow tile (128 x 64)
+//   3 = the register-staged kernel, the format's own wide tile (256 x 128 for three bf16 planes, else 128 x 128 x 16 waves: the
+//       measured best per format, profiles/r03_conv_sweep_bf16_split*.txt)
+//   fp16 form only (the bf16 forms run as 3): 21 = the LDS-DMA kernel, 30 = the A-stationary kernel for every launch it can run
+static constexpr int SPLIT_TILES[] = {0, 1, 3, 21, 30};
 static std::atomic<int> g_split_tile{0};
 // ... or, for the calling thread only, a ConvSplitTileScope (single-operator entry points: the process-wide word would
 // reroute forwards that other threads have in flight)
@@ -611,7 +610,7 @@ static int split_tile_now() { return t_split_tile != 0 ? t_split_tile : g_split_
 ConvSplitTileScope::ConvSplitTileScope(int tile) : prev_(t_split_tile) { t_split_tile = tile; }
 ConvSplitTileScope::~ConvSplitTileScope() { t_split_tile = prev_; }
 // ymk_debug_option("astat", v): 1 (default) = the short-K pointwise layers the A-stationary kernel measured ahead on take it;
-// 0 = none does (the round-4 routing, for A/B runs); "conv_split_tile" 30 forces it for every launch it can run
+// 0 = none does (the round-4 routing, what the tests compare it with); "conv_split_tile" 30 forces it for every launch it can run
 static std::atomic<int> g_astat{1};
 // ymk_debug_option("act_planes", v): 1 (default) = the tensor between a bottleneck's 1 x 1 reduction and its 3 x 3 convolution
 // lives in HBM as the two fp16 planes the 3 x 3 multiplies with (written by the reduction's epilogue under a bound, read by
@@ -619,12 +618,13 @@ static std::atomic<int> g_astat{1};
 static std::atomic<int> g_act_planes{1};
 // ymk_debug_option("rowmax_tile", v): the kernel of a row-max launch (the greedy loop's vocabulary head) where 128 x 128 tiles fill
 // the chip: 0 = the A-stationary kernel, one column block per block, where it runs (K <= 192: ymk_conv_astat.hip astat_rowmax),
-// else the 128 x 64 x 8-wave tile; for A/B runs 1 = 128 x 128 x 16 waves, 2 = 128 x 128 x 8 waves, 3 = 256 x 128 x 16 waves, 4 = the
-// A-stationary kernel with its column blocks dealt to groups, 6 = 128 x 64 always (rounds 3-5) - the same (max, column) pairs per
-// 64-column sub-tile from each (ymk_conv_kernel.h, EPI_ROWMAX).  profiles/r06_rowmax_head_tiles.md: 35.2 us per step at 1234 rows
-// on 128 x 64, 36.3 / 44.4 / 55.5 on the wider tiles, 38.1 on (4), 28.2 on (0)
+// else the 128 x 64 x 8-wave tile; 6 = 128 x 64 always (the route of a head with K > 192, and what the A-stationary head is compared
+// with bit for bit) - the same (max, column) pairs per 64-column sub-tile from each (ymk_conv_kernel.h, EPI_ROWMAX).
+// profiles/r06_rowmax_head_tiles.md: 35.2 us per step at 1234 rows on 128 x 64, 28.2 on (0)
 static std::atomic<int> g_rowmax_tile{0};
-// launch counters since the process started (ymk_stat; tests assert that a route was really taken)
+// launch counters since the process started (ymk_stat; tests assert that a route was really taken).  "rowmax_wide_launches"
+// keeps its name from when the head also ran on wide tiles of the staged kernel: it counts the head's A-stationary launches
+// (128-column blocks), the only form wider than the 128 x 64 tile that is left
 static std::atomic<long long> g_n_astat{0}, g_n_ln_fused{0}, g_n_planes_read{0}, g_n_planes_written{0}, g_n_rowmax_wide{0}, g_n_mlp_fused{0};
 bool conv_split_stat(const std::string& key, long long* value) {
   if (key == "astat_launches") *value = g_n_astat.load();
@@ -648,8 +648,8 @@ bool conv_split_debug_option(const std::string& key, int value) {
   else if (key == "astat") g_astat = value;
   else if (key == "act_planes") g_act_planes = value;
   else if (key == "rowmax_tile") {
+    YMK_CHECK(value == 0 || value == 6, "rowmax_tile " + std::to_string(value) + " is no selector; accepted: 0 6");
     g_rowmax_tile = value;
-    astat_rowmax_dealt(value == 4);
   }
   else return false;
   return true;
@@ -657,27 +657,17 @@ bool conv_split_debug_option(const std::string& key, int value) {
 
 // the tile shapes of the register-staged kernel, for every format (FMT 0: NS bf16 planes, 1: two fp16 planes)
 template <int FMT, int NS>
-static void dispatch_staged(hipStream_t s, ConvK& k, const void* ws, int tile, bool narrow, SplitCtx* ctx) {
+static void dispatch_staged(hipStream_t s, ConvK& k, const void* ws, bool narrow, SplitCtx* ctx) {
   if constexpr (FMT == 1) {
-    if (k.out_planes) {  // plane-writing epilogues exist for the two shapes the automatic choice uses
+    if (k.out_planes) {
       if (narrow) launch_split<1, 128, 64, 4, 2, 2, true>(s, k, ws, ctx);
       else launch_split<1, 128, 128, 4, 4, 2, true>(s, k, ws, ctx);
       return;
     }
   }
-  if (narrow) {
-    launch_split<FMT, 128, 64, 4, 2, NS>(s, k, ws, ctx);
-    return;
-  }
-  switch (tile) {
-    case 2: launch_split<FMT, 256, 128, 4, 4, NS>(s, k, ws, ctx); break;
-    case 4: launch_split<FMT, 128, 128, 4, 2, NS>(s, k, ws, ctx); break;
-    case 11:  // 256 x 256, 16 waves of 64 x 64 (two planes only: three do not fit the LDS); Cout < 256 keeps 128-wide tiles
-      if (NS == 2 && k.Cout >= 256) launch_split<FMT, 256, 256, 4, 4, 2>(s, k, ws, ctx);
-      else launch_split<FMT, 128, 128, 4, 4, NS>(s, k, ws, ctx);
-      break;
-    default: launch_split<FMT, 128, 128, 4, 4, NS>(s, k, ws, ctx); break;
-  }
+  if (narrow) launch_split<FMT, 128, 64, 4, 2, NS>(s, k, ws, ctx);
+  else if constexpr (FMT == 0 && NS == 3) launch_split<0, 256, 128, 4, 4, 3>(s, k, ws, ctx);
+  else launch_split<FMT, 128, 128, 4, 4, NS>(s, k, ws, ctx);
 }
 
 // ---- which kernel an fp16-split launch runs on: ONE rule, asked by conv2d_split for the launch itself and by
@@ -701,42 +691,43 @@ struct RouteQuery {
   int cout, kpad, taps;
   bool rowmax, row_group, astat_can, ln, planes_io;
 };
-static SplitRoute route_f16(const RouteQuery& q, int& tile, bool& narrow) {
+static SplitRoute route_f16(const RouteQuery& q, bool& narrow) {
   const long mt128 = (q.M + 127) / 128;
   const long blocks128 = mt128 * ((q.cout + 127) / 128), blocks64 = mt128 * ((q.cout + 63) / 64);
-  tile = split_tile_now();
-  const bool auto_tile = tile == 0;
-  const bool astat_forced = tile == 30;  // tests: the A-stationary kernel at any size it can run
-  bool few = false;
-  if (blocks128 < 256 && !astat_forced) {
-    if (blocks64 < 256) return ROUTE_NONE;
-    few = true;
+  // ---- the forcing options (tests reach and compare the product kernels with them), each turned into one flag here.  With
+  // none set, `rule`, `astat_rule` and `head_astat` are true, the two `force_` flags false, and what follows is the rule above:
+  // the astat and dma conditions below choose a kernel BY THE RULE only under their flag, so "conv_split_tile" 1 and 3, which
+  // set no other flag, leave every launch on the staged kernel
+  const int force = split_tile_now();
+  const bool rule = force == 0;
+  const bool force_narrow = force == 1, force_dma = force == 21;
+  const bool astat_rule = rule && g_astat.load(std::memory_order_relaxed) != 0;           // "astat" 0
+  const bool head_astat = astat_rule && g_rowmax_tile.load(std::memory_order_relaxed) == 0;  // "rowmax_tile" 6
+  const bool astat_able = q.astat_can && !q.planes_io;
+  if (force == 30) {  // the A-stationary kernel at any size it can run; else the staged kernel, where 128 x 128 tiles fill the chip
+    narrow = q.cout <= 64 || q.rowmax;
+    if (astat_able && !q.rowmax) return ROUTE_ASTAT;
+    return q.ln || blocks128 < 256 ? ROUTE_NONE : ROUTE_STAGED;
   }
-  if (tile == 0) tile = 3;
-  const int rowmax_tile = q.rowmax && auto_tile && !few ? g_rowmax_tile.load(std::memory_order_relaxed) : 0;
-  if (rowmax_tile == 2) tile = 4;
-  if (rowmax_tile == 3) tile = 2;
-  narrow = q.cout <= 64 || tile == 1 || (q.rowmax && (rowmax_tile < 1 || rowmax_tile > 3)) || few;
-  if ((!q.rowmax || ((rowmax_tile == 0 || rowmax_tile == 4) && auto_tile)) && q.astat_can && !q.planes_io &&
-      (astat_forced || q.ln || (auto_tile && g_astat.load(std::memory_order_relaxed) != 0 && q.cout > 64 && !few && q.kpad <= 192)))
-    return ROUTE_ASTAT;
-  if (q.ln) return ROUTE_NONE;
-  if (tile == 30) {
-    if (blocks128 < 256) return ROUTE_NONE;  // forced, but not a launch the kernel runs: as without the option
-    tile = 3;
-  }
+
+  // none
+  if (blocks128 < 256 && blocks64 < 256) return ROUTE_NONE;
+  const bool few = blocks128 < 256;
+  narrow = q.cout <= 64 || q.rowmax || few || force_narrow;
+  // astat
+  if (q.ln) return astat_able ? ROUTE_ASTAT : ROUTE_NONE;
+  if (astat_able && (q.rowmax ? head_astat : astat_rule) && q.cout > 64 && !few && q.kpad <= 192) return ROUTE_ASTAT;
+  // dma (a row-max or row-predicated launch stays staged, and so does a few-row launch of more than 64 columns)
   const bool dma_shape = q.taps > 1 || (q.kpad >= 1024 && q.cout <= 512) || q.cout <= 64;
-  const bool dma_fills = blocks128 >= 256 || (q.cout <= 64 && mt128 >= 256);
-  if (!q.rowmax && !q.row_group && (tile == 20 || tile == 21 || (auto_tile && dma_shape && dma_fills))) return ROUTE_DMA;
-  if (tile == 20 || tile == 21) tile = 3;
+  const bool dma_runs = !q.rowmax && !q.row_group;
+  if (dma_runs && (force_dma || (rule && dma_shape && (!few || q.cout <= 64)))) return ROUTE_DMA;
   return ROUTE_STAGED;
 }
 
 int conv_split_route_with_planes(long M, int cout, int kpad, int taps, bool* auto_tile) {
-  int tile = 0;
   bool narrow = false;
   *auto_tile = split_tile_now() == 0 && g_act_planes.load(std::memory_order_relaxed) != 0;
-  return (int)route_f16(RouteQuery{M, cout, kpad, taps, false, false, false, false, true}, tile, narrow);
+  return (int)route_f16(RouteQuery{M, cout, kpad, taps, false, false, false, false, true}, narrow);
 }
 
 bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* ctx) {
@@ -745,25 +736,20 @@ bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* c
   if ((k.ln_g != nullptr || planes_io) && code != SPLIT_F16X2) return false;  // fused LayerNorm / planes in HBM: fp16 form only
   const bool rowmax = k.epi == EPI_ROWMAX;  // (max, column) per 64-column tile: the 128 x 64 tile
   const size_t w_bytes_f16 = (size_t)((w.cout + 255) / 256 * 256) * w.kpad * 2 * 2;
-  int tile = 0;
   bool narrow = false;
   SplitRoute route = ROUTE_STAGED;
   if (code == SPLIT_F16X2) {
     route = route_f16(RouteQuery{k.M, w.cout, k.Kpad, k.KH * k.KW, rowmax, has_row_predicate(k), conv2d_f16_astat_can(k, w_bytes_f16),
-                                 k.ln_g != nullptr, planes_io}, tile, narrow);
+                                 k.ln_g != nullptr, planes_io}, narrow);
   } else {  // bf16 evaluation forms: the register-staged kernel, for launches that fill the chip
     const long mt128 = (k.M + 127) / 128;
     const long blocks128 = mt128 * ((w.cout + 127) / 128), blocks64 = mt128 * ((w.cout + 63) / 64);
-    tile = split_tile_now();
-    if (tile == 0) tile = code == 3 ? 2 : 3;
-    if (tile == 20 || tile == 21 || tile == 30) tile = 3;
     if (blocks128 < 256 && blocks64 < 256) return false;
-    narrow = w.cout <= 64 || tile == 1 || rowmax || blocks128 < 256;
+    narrow = w.cout <= 64 || split_tile_now() == 1 || rowmax || blocks128 < 256;
   }
   if (route == ROUTE_NONE) return false;
-  YMK_CHECK(!k.in_planes || (route == ROUTE_DMA && tile != 20), "a tensor stored as fp16 planes reached a kernel that cannot read it");
-  YMK_CHECK(!k.out_planes || (route == ROUTE_DMA && tile != 20) || (route == ROUTE_STAGED && (narrow || tile == 3)),
-            "fp16 planes asked of a kernel that cannot write them");
+  YMK_CHECK(!k.in_planes || route == ROUTE_DMA, "a tensor stored as fp16 planes reached a kernel that cannot read it");
+  YMK_CHECK(!k.out_planes || route == ROUTE_DMA || route == ROUTE_STAGED, "fp16 planes asked of a kernel that cannot write them");
   const SplitCtx::Panels& pn = ctx->panels(s, w, code);
   if (k.in_planes) ++g_n_planes_read;
   if (k.out_planes) ++g_n_planes_written;
@@ -785,13 +771,12 @@ bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* c
   if (route == ROUTE_DMA) {
     k.scale = pn.scale;
     const bool nar = w.cout <= 64;
-    const int rows = tile == 20 ? 256 : 128;
     k.ntiles_n = (k.Cout + (nar ? 64 : 128) - 1) / (nar ? 64 : 128);
-    auto* e = conv_prof_open(s, k, rows, nar ? 64 : 128, ((k.M + rows - 1) / rows) * k.ntiles_n, 161);
+    auto* e = conv_prof_open(s, k, 128, nar ? 64 : 128, ((k.M + 127) / 128) * k.ntiles_n, 161);
     YMK_CHECK(!k.in_planes || k.amax != nullptr, "a tensor of fp16 planes without the record that holds its scale");
     if (k.amax == nullptr) k.amax = ctx->absmax(s, k);
     else if (g_amax_check.load(std::memory_order_relaxed) && !k.in_planes) amax_verify(s, k, ctx);
-    const bool taken = conv2d_f16_dma(s, k, pn.planes, w_bytes_f16, nar, rows);
+    const bool taken = conv2d_f16_dma(s, k, pn.planes, w_bytes_f16, nar);
     if (e) YMK_HIP(hipEventRecord(e->second, s));
     YMK_HIP(hipGetLastError());
     YMK_CHECK(taken, "conv_f16_dma refused a launch");
@@ -799,12 +784,11 @@ bool conv2d_split(hipStream_t s, ConvK& k, const ConvW& w, int code, SplitCtx* c
   }
   if (code == SPLIT_F16X2) {
     k.scale = pn.scale;
-    if (rowmax && !narrow) ++g_n_rowmax_wide;
-    dispatch_staged<1, 2>(s, k, pn.planes, tile, narrow, ctx);
+    dispatch_staged<1, 2>(s, k, pn.planes, narrow, ctx);
   } else if (code == 2) {
-    dispatch_staged<0, 2>(s, k, pn.planes, tile, narrow, ctx);
+    dispatch_staged<0, 2>(s, k, pn.planes, narrow, ctx);
   } else {
-    dispatch_staged<0, 3>(s, k, pn.planes, tile, narrow, ctx);
+    dispatch_staged<0, 3>(s, k, pn.planes, narrow, ctx);
   }
   YMK_HIP(hipGetLastError());
   return true;
