@@ -910,3 +910,101 @@ def amax_merge(dst, src):
     dev = (dst if dst is not None else src).device
     with torch.cuda.device(dev):
         _glue_call(lib, "ymk_op_amax_merge", False, _lib.ptr(dst), _lib.ptr(src))
+
+
+# ---- the page / text-line pre-processing kernels (csrc/ymk_image.hip) through their own entries, on guarded buffers
+IMAGE_GUARD = 256  # words (fp32 outputs) or bytes (uint8 outputs) behind every output, pre-filled like the output itself
+SCRATCH_FILL = 0xA5
+
+
+def _guarded(shape, dtype, device):
+    """A view of `shape` at the front of a buffer IMAGE_GUARD elements longer; every fp32 word SENTINEL, every byte SCRATCH_FILL."""
+    n = 1
+    for v in shape:
+        n *= int(v)
+    buf = torch.empty(n + IMAGE_GUARD, dtype=dtype, device=device)
+    if dtype == torch.float32:
+        buf.view(torch.int32).fill_(SENTINEL)
+    else:
+        buf.fill_(SCRATCH_FILL)
+    return buf[:n].view(*shape)
+
+
+def guard_tail(view):
+    """The IMAGE_GUARD elements behind a `_guarded` view."""
+    return view._base.view(-1)[view.numel():]
+
+
+def untouched(t):
+    """True when every element still holds what `_guarded` put there."""
+    if t.dtype == torch.float32:
+        return bool((t.contiguous().view(torch.int32) == SENTINEL).all().item())
+    return bool((t == SCRATCH_FILL).all().item())
+
+
+def det_preprocess(page_u8_dev, oh, ow, unchecked=False):
+    """ymk_det_preprocess at any output size: page uint8 [h, w, 3] BGR on the device -> y fp32 [3, oh, ow], a `_guarded` view.
+    unchecked: -> (the entry's error message or None, y) for sizes the entry has to refuse."""
+    lib = _lib.load()
+    assert page_u8_dev.is_cuda and page_u8_dev.dtype == torch.uint8 and page_u8_dev.is_contiguous() and page_u8_dev.shape[2] == 3
+    h, w = page_u8_dev.shape[:2]
+    y = _guarded((3, oh, ow), torch.float32, page_u8_dev.device)
+    with torch.cuda.device(page_u8_dev.device):
+        err = _glue_call(lib, "ymk_det_preprocess", unchecked, page_u8_dev.data_ptr(), h, w, oh, ow, y.data_ptr())
+    return (err, y) if unchecked else y
+
+
+def halve(page_u8_dev, unchecked=False):
+    """ymk_halve_u8c3: uint8 [h, w, 3] on the device -> [round-half-even(h / 2), round-half-even(w / 2), 3], a `_guarded` view.
+    unchecked: -> (error message or None, y)."""
+    lib = _lib.load()
+    assert page_u8_dev.is_cuda and page_u8_dev.dtype == torch.uint8 and page_u8_dev.is_contiguous() and page_u8_dev.shape[2] == 3
+    h, w = page_u8_dev.shape[:2]
+    dh, dw = int(round(h * 0.5)), int(round(w * 0.5))
+    y = _guarded((dh, dw, 3), torch.uint8, page_u8_dev.device)
+    with torch.cuda.device(page_u8_dev.device):
+        err = _glue_call(lib, "ymk_halve_u8c3", unchecked, page_u8_dev.data_ptr(), h, w, y.data_ptr(), dh, dw)
+    return (err, y) if unchecked else y
+
+
+def crop_batch(levels, descs, out_h, batch_w, slots=None, flip=False):
+    """ymk_crop_batch_levels: levels = the page and its pyramid levels (uint8 [h, w, 3] BGR device tensors, None for a level
+    not built); descs = a numpy record array of imaging.CropDesc (rows of a plan's `table`, fields edited at will).  warp_off
+    is laid out as imaging.build_crop_batch does (each crop's bytes start on a multiple of 16); slot = `slots` (a permutation;
+    default 0 .. n - 1); flip: one value or one per crop.
+    -> (out fp32 [n, 3, out_h, batch_w], scratch uint8 [bytes + IMAGE_GUARD], warp_off int64 [n]); out is a `_guarded` view,
+    the scratch held SCRATCH_FILL in every byte before the launch."""
+    import ctypes
+
+    import numpy as np
+
+    from yomitoku_amd import imaging
+
+    lib = _lib.load()
+    assert ctypes.sizeof(imaging.CropDesc) == lib.ymk_crop_desc_size() and descs.dtype == imaging._CROP_DTYPE
+    arr = np.array(descs, copy=True)
+    n = len(arr)
+    arr["slot"] = np.arange(n) if slots is None else np.asarray(slots)
+    assert sorted(arr["slot"].tolist()) == list(range(n))
+    arr["flip"] = np.asarray(flip, dtype=np.int32)
+    sizes = (arr["ww"].astype(np.int64) * arr["wh"] * 3 + 15) & ~15
+    ends = np.cumsum(sizes)
+    arr["warp_off"] = ends - sizes
+    dev = levels[0].device
+    for k in np.unique(arr["level"]).tolist():
+        assert k < len(levels) and levels[k] is not None
+    for d in arr:  # the kernels trust the descriptor: keep every box inside its level
+        lh, lw = levels[int(d["level"])].shape[:2]
+        assert 0 <= d["bx"] and 0 <= d["by"] and d["bx"] + d["bw"] <= lw and d["by"] + d["bh"] <= lh and d["nw"] <= batch_w and d["nh"] <= out_h
+    scratch = torch.full((int(ends[-1]) + IMAGE_GUARD,), SCRATCH_FILL, dtype=torch.uint8, device=dev)
+    out = _guarded((n, 3, out_h, batch_w), torch.float32, dev)
+    descs_dev = torch.from_numpy(arr.view(np.uint8).copy()).to(dev)
+    nl = len(levels)
+    ptrs = (ctypes.c_void_p * nl)(*[(t.data_ptr() if t is not None else None) for t in levels])
+    hs = (ctypes.c_int * nl)(*[(t.shape[0] if t is not None else 0) for t in levels])
+    ws = (ctypes.c_int * nl)(*[(t.shape[1] if t is not None else 0) for t in levels])
+    with torch.cuda.device(dev):
+        _glue_call(lib, "ymk_crop_batch_levels", False, ptrs, hs, ws, nl, descs_dev.data_ptr(), n, max(1, int(arr["ww"].max())),
+                   max(1, int(arr["wh"].max())), scratch.data_ptr(), out.data_ptr(), batch_w, out_h)
+        torch.cuda.synchronize()
+    return out, scratch, (ends - sizes).astype(np.int64)

@@ -15,11 +15,16 @@ def _page(seed, h, w):
     return synthetic_page(seed, h, w)
 
 
-@pytest.mark.parametrize("h,w", [(1600, 1200), (1200, 1600), (480, 640), (2100, 1500), (91, 38), (700, 2400)])
+@pytest.mark.parametrize("h,w", [(1600, 1200), (1200, 1600), (480, 640), (2100, 1500), (91, 38), (700, 2400), (1279, 1320)])
 def test_detector_preprocess(dev, h, w):
     from oracle.preprocess import detector_preprocess
     from yomitoku_amd import imaging
 
+    oh, ow = imaging.resize_shortest_edge_dims(h, w, 1280, 1600)
+    if (h, w) == (1279, 1320):  # each side is rounded to a multiple of 32 on its own: one axis grows, the other shrinks,
+        assert (oh, ow) == (1280, 1312) and h / oh < 1 < w / ow  # so both go through the linear rule; no other shape here does
+    else:
+        assert (h / oh >= 1 and w / ow >= 1) or (h / oh < 1 and w / ow < 1)
     img = np.ascontiguousarray(_page(h + w, max(h, 600), max(w, 600))[:h, :w])
     ref = detector_preprocess(img)
     out = imaging.detector_tensor(imaging.page_to_device(img, dev), 1280, 1600).cpu()
