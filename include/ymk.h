@@ -444,6 +444,65 @@ int ymk_g4_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, in
                         int64_t packed_bytes, uint32_t* slots_dev, int64_t slot_bytes, uint32_t* rowbits_dev, uint64_t* rowoff_dev,
                         unsigned char* out_dev, int64_t out_bytes, int64_t max_capacity, int* lengths_dev, void* stream);
 
+/* ---- Lossless pages: a zlib stream of the page's PNG-filtered rows in one dynamic-Huffman Deflate block, opt-in
+ * (yomitoku_amd/csrc/ymk_flate.hip; yomitoku_amd/flate.py; encode_lossless_pages, encode_jpeg_pages(lossless=...), serve(jpeg=...,
+ * jpeg_lossless=...)).  DESIGN.md, "Lossless pages"; tests/flate_ref.py is the definition, and every stage equals it byte for byte.
+ *
+ * Page table (DEVICE, int32 words): n_pages records of YMK_FLATE_PAGE_WORDS words.
+ *     word 0-1   address of the page's pixels (low, high), uint8 H x W x channels, B G R       word 2-4  h, w, channels (1 | 3)
+ *     word 5     index: the page's place in hist_dev, tables_dev, head_dev, sizes_dev (0 ... n_index - 1, in the order of 8-9)
+ *     word 6-7   BYTE offset (low, high) of the page's filtered bytes in filt_dev; its tokens start at the same uint16 of tokens_dev
+ *     word 8-9   the page's first segment in segtok_dev, segadler_dev, segbits_dev (its offsets: off_dev + that + 3 index)
+ *     word 10-11 WORD offset of the page's slots in slots_dev      word 12-13 BYTE offset of its file in out_dev, a multiple of 4
+ *     word 14    the file's capacity in bytes                      word 15  0, or 1 + the page's place in grey_dev
+ * All offsets are those of the page with the channels it arrived with.  grey_dev (ymk_jpeg_pages_grey's answers, or null): a
+ * three-channel page whose word there is 0 is coded as ONE channel - fewer segments of the same places, a smaller file.
+ * A record that does not fit the sizes the call names is no page: nothing of it is read or written.
+ *
+ * ymk_flate_file_capacity: the bytes no file of an h x w x channels page exceeds (the proof is in ymk_flate.hip).  HOST, -1 on a
+ *   bad size.
+ * ymk_flate_scratch_bytes: HOST arrays h, w, channels -> sizes8_out = the segments; then the bytes of filt_dev; tokens_dev; each of
+ *   segtok_dev, segadler_dev, segbits_dev; off_dev; slots_dev; each of hist_dev, tables_dev; head_dev.  sizes_dev: int32 [2 n_pages].
+ * Every phase takes the table, n_index (the pages the per-page buffers have room for; n_pages <= n_index: a later phase may be
+ * given some of the records of an earlier one) and the four sizes its records are checked against: the bytes of filt_dev (tokens_dev
+ * has twice as many), the segments, the bytes of slots_dev and of out_dev.
+ * ymk_flate_rows: hist_dev zeroed on `stream`, then one wave per row segment: the filtered bytes (a row: its type, then its bytes),
+ *   the tokens (uint16: a literal's byte, or 0x8000 | index of the distance << 9 | length - 3), their count, the segment's Adler
+ *   sums, and its symbol counts added to hist_dev [index][YMK_FLATE_HIST_WORDS] (286 literal / length symbols, 30 distance symbols).
+ * ymk_flate_tables: one wave per page: tables_dev [index][YMK_FLATE_HIST_WORDS] = (code length << 16 | the code, first bit lowest) per
+ *   symbol; head_dev [index][YMK_FLATE_HEAD_WORDS]: word 0 the file's bytes (-1: it exceeds the capacity), 1 the channels it is coded
+ *   with, 2 the bits of 78 9C and the block's header, 3 the bits of the tail (end-of-block, pad, Adler-32), 4 the Adler-32, 5-6
+ *   the tail's bit offset, 8-9 the tail's bits, 10.. the head's bits; sizes_dev [2 index] = word 0, [2 index + 1] = word 1.
+ * ymk_flate_code: one wave per segment of every page that has a file: its tokens' bits into its slot, their count into segbits_dev.
+ * ymk_flate_scan: one block per page: off_dev from segbits_dev; a page whose counts contradict its head gets -1 in both places.
+ * ymk_flate_gather: one thread per 32-bit word of every file; no byte behind a file's end is written.  out_dev 16-byte aligned.
+ * ymk_flate_encode_pages: the five in order on `stream`.  Nothing is allocated, nothing waited for. */
+#define YMK_FLATE_PAGE_WORDS 16
+#define YMK_FLATE_HIST_WORDS 320
+#define YMK_FLATE_HEAD_WORDS 160
+int ymk_flate_page_words(void);
+int64_t ymk_flate_file_capacity(int h, int w, int channels);
+int ymk_flate_scratch_bytes(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes8_out);
+int ymk_flate_rows(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
+                   int64_t out_bytes, int max_rows, int max_row_segments, const int* grey_dev, unsigned char* filt_dev, uint16_t* tokens_dev,
+                   uint32_t* segtok_dev, uint32_t* segadler_dev, int* hist_dev, void* stream);
+int ymk_flate_tables(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
+                     int64_t out_bytes, const int* grey_dev, const int* hist_dev, const uint32_t* segadler_dev, uint32_t* tables_dev,
+                     uint32_t* head_dev, int* sizes_dev, void* stream);
+int ymk_flate_code(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
+                   int64_t out_bytes, int max_rows, int max_row_segments, const uint16_t* tokens_dev, const uint32_t* segtok_dev,
+                   const uint32_t* tables_dev, const uint32_t* head_dev, uint32_t* slots_dev, uint32_t* segbits_dev, void* stream);
+int ymk_flate_scan(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
+                   int64_t out_bytes, const uint32_t* segbits_dev, uint32_t* head_dev, uint64_t* off_dev, int* sizes_dev, void* stream);
+int ymk_flate_gather(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
+                     int64_t out_bytes, const uint32_t* slots_dev, const uint32_t* head_dev, const uint64_t* off_dev, unsigned char* out_dev,
+                     int64_t max_capacity, void* stream);
+int ymk_flate_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs,
+                           int64_t slot_bytes, int64_t out_bytes, int max_rows, int max_row_segments, const int* grey_dev,
+                           unsigned char* filt_dev, uint16_t* tokens_dev, uint32_t* segtok_dev, uint32_t* segadler_dev, uint32_t* segbits_dev,
+                           int* hist_dev, uint32_t* tables_dev, uint32_t* head_dev, uint64_t* off_dev, uint32_t* slots_dev,
+                           unsigned char* out_dev, int64_t max_capacity, int* sizes_dev, void* stream);
+
 /* ---- Binariser: grey-valued pages of a wave thresholded into the packed rows of the Group 4 encoder, opt-in
  * (yomitoku_amd/csrc/ymk_binarize.hip; yomitoku_amd/ccitt.py; encode_jpeg_pages(bilevel="otsu" | "adaptive"), serve(jpeg=...,
  * jpeg_bilevel=...)).  DESIGN.md, "Thresholded pages"; tests/binarize_ref.py is the definition, and every stage equals it bit

@@ -97,6 +97,22 @@ SIGNATURES = {
                               c_void_p]),
     "ymk_g4_encode_pages": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                     c_int64, c_int64, c_void_p, c_void_p]),
+    "ymk_flate_page_words": (c_int, []),
+    "ymk_flate_file_capacity": (c_int64, [c_int, c_int, c_int]),
+    "ymk_flate_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
+    "ymk_flate_rows": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ymk_flate_tables": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "ymk_flate_code": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ymk_flate_scan": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "ymk_flate_gather": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_void_p]),
+    "ymk_flate_encode_pages": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_void_p, c_void_p]),
     "ymk_bin_scratch_bytes": (c_int, [POINTER(c_int), POINTER(c_int), c_int, POINTER(c_int64)]),
     "ymk_bin_test_hist": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "ymk_bin_otsu": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),

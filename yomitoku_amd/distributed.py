@@ -408,6 +408,9 @@ class ShardedServer:
         if serve_kwargs.get("overlays"):
             raise NotImplementedError("overlays=True is not supported by serve_sharded: the ranks' images are not gathered "
                                       "(DocumentAnalyzer.serve(..., overlays=True) draws on one GPU)")
+        if serve_kwargs.get("jpeg_lossless", False) is not False:
+            raise NotImplementedError("jpeg_lossless=... is not supported by serve_sharded: the ranks' encoded pages are not gathered "
+                                      "(DocumentAnalyzer.serve(..., jpeg=..., jpeg_lossless=...) encodes on one GPU)")
         if serve_kwargs.get("jpeg") is not None:
             raise NotImplementedError("jpeg=... is not supported by serve_sharded: the ranks' encoded pages are not gathered "
                                       "(DocumentAnalyzer.serve(..., jpeg=...) encodes on one GPU)")

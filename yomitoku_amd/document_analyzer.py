@@ -100,7 +100,7 @@ class OCR(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False, jpeg_lossless=False):
         """The multi-page entry point of a text-only job (searchable PDFs, full-text indexing): host pages (uint8 H x W x 3 BGR
         arrays) and / or image file paths in, one result per page out, in page order, through the stage pipeline of
         yomitoku_amd/serving.py with the OCR chain alone - detect, boxes, crops, recognize (two lanes), decode, finish; no
@@ -117,8 +117,9 @@ class OCR(StageAnalyzer):
             searchable_pdf_bytes([e[-1] for e in out], [e[0] for e in out])
         is the whole searchable-PDF job.  `jpeg_optimize`: those files with Huffman tables made for each page; a ValueError
         without `jpeg`.  `jpeg_subsampling`, `jpeg_grey`, `jpeg_bilevel` (False, "auto", "otsu", "adaptive"), `jpeg_mrc`
-        (False, True or the cells), `jpeg_despeckle` (False, True, an int or the sizes), `deskew`: as DocumentAnalyzer.serve."""
-        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle)  # before the pipeline is built or a source read
+        (False, True or the cells), `jpeg_despeckle` (False, True, an int or the sizes), `jpeg_lossless` (False, True or the budget),
+        `deskew`: as DocumentAnalyzer.serve."""
+        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle, jpeg_lossless)  # before the pipeline is built or a source read
         deskew = check_deskew(deskew) or False
         if self.visualize:
             raise NotImplementedError(_NO_VIS_SERVE)
@@ -567,7 +568,7 @@ class DocumentAnalyzer(StageAnalyzer):
 
     def serve(self, sources, wave: int = 16, in_flight: int = 4, defer_full_gc: bool = True, with_source: bool = False, rec_lanes: int = 2,
               overlays: bool = False, jpeg=None, jpeg_optimize: bool = False, jpeg_subsampling=None, jpeg_grey=False,
-              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False, figures=None):
+              jpeg_bilevel=False, deskew=False, jpeg_mrc=False, jpeg_despeckle=False, figures=None, jpeg_lossless=False):
         """The multi-page entry point: host pages (uint8 H x W x 3 BGR arrays) and / or image file paths in, one result
         per page out, in page order - the page loop of cli/main.py:105-137 as a stage pipeline on one GPU from one
         process (yomitoku_amd/serving.py): pinned staging + H2D on a copy stream, `wave` pages per device batch (16 measured best
@@ -642,8 +643,19 @@ class DocumentAnalyzer(StageAnalyzer):
         (yomitoku_amd/figures.py; DESIGN.md, "Figure crops"): the entry gets a PageFigures behind the page file and in front of
         the PageSkew - (schema, PageFigures), (schema, ocr overlay, layout overlay, EncodedJpeg, PageFigures, PageSkew) -, one
         EncodedJpeg per figure in `schema.figures` order (None for an empty box), which `schema.to_markdown(path,
-        figures=entry[...])` and the other exporters write in place of crops of a host image."""
-        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle)  # before the pipeline is built or a source read
+        figures=entry[...])` and the other exporters write in place of crops of a host image.
+        `jpeg_lossless`: False, True, or {"budget": b} with b a positive finite number of bytes a pixel; anything else, an unknown
+        key, and the switch without `jpeg`, is a ValueError before a source is read.  Every page `jpeg_bilevel` and `jpeg_mrc`
+        leave - one channel or three: a rasterised PDF, a screenshot, a slide, a form, a page with drawn graphics - is written as a
+        lossless file instead of a JPEG (yomitoku_amd/flate.py; DESIGN.md, "Lossless pages"): its entry ends with an
+        EncodedLossless - `data`, a zlib stream of the page's PNG-filtered rows made on the device, `width`, `height`, `channels`,
+        `scale` 1.0, `nbytes`, `to_png()` - which `searchable_pdf_bytes` embeds as a /FlateDecode image with /Predictor 15.  Such a
+        page is never resized; `jpeg_optimize` and `jpeg_subsampling` do not apply to it, `jpeg_grey="auto"` does (`channels` 1 for
+        a three-channel page that is grey); with `deskew` the file is of the corrected page.  With a budget a page goes lossless
+        only where its file takes at most b bytes a pixel (in integers: nbytes * 256 <= ceil(256 b) * height * width) and gets
+        exactly the JPEG of the job without the switch otherwise - a grainy scan is several times larger lossless.  OCR and layout
+        see the page as it arrived; only the file changes."""
+        files = check_jpeg_preset(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, jpeg_despeckle, jpeg_lossless)  # before the pipeline is built or a source read
         deskew = check_deskew(deskew) or False
         figures = check_figures(figures)
         if self.visualize:

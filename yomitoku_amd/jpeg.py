@@ -39,6 +39,11 @@ make up the JPEG batch, launch JPEG, launch Group 4, one wait and one gather.
 
 `despeckle=True` (serve: `jpeg_despeckle=True`) removes the specks and pinholes of fewer than 4 pixels from every page that gets a
 Group 4 file, on the device, before it is coded (yomitoku_amd/despeckle.py); `EncodedBilevel.despeckled` says what went.
+
+`lossless=True` (serve: `jpeg_lossless=True`) writes every page `bilevel` and `mrc` leave as a lossless file, an `EncodedLossless`
+of yomitoku_amd/flate.py - a zlib stream of the page's PNG-filtered rows, never resized - in place of the EncodedJpeg;
+`lossless={"budget": b}` only where that file takes at most b bytes a pixel: a page over the budget gets the JPEG it gets
+without the switch.
 """
 
 from __future__ import annotations
@@ -51,7 +56,7 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _lib, ccitt, imaging
+from . import _lib, ccitt, flate, imaging
 from . import despeckle as specks
 from . import mrc as layered
 from .devpages import addr_words, entered, gather_files, grown, shape_args, to_pinned
@@ -269,10 +274,11 @@ class PageFiles:
     bilevel: Union[bool, str]  # False | "auto" | "otsu" | "adaptive"
     mrc: Optional[dict]  # None, or check_mrc's full dict
     despeckle: Optional[dict] = None  # None, or check_despeckle's {"black": n, "white": n}
+    lossless: Optional[dict] = None  # None, or check_lossless's {"budget256": None or the budget in 1/256 byte a pixel}
 
 
 def page_files(preset, optimize=False, subsampling="4:2:0", grey=False, bilevel=False, mrc=False, serve=False,
-               despeckle=False) -> Optional[PageFiles]:
+               despeckle=False, lossless=False) -> Optional[PageFiles]:
     """The PageFiles of a call's options - the one place they are checked; every refusal is a ValueError.  serve: the reading of
     the `serve()` entries - `preset` None: no page files (-> None), which every other option then has to agree with by
     standing at its default; `subsampling` None: 4:2:0."""
@@ -300,19 +306,25 @@ def page_files(preset, optimize=False, subsampling="4:2:0", grey=False, bilevel=
         raise ValueError(f"jpeg_despeckle={despeckle!r} needs jpeg=...: there are no page files to write that way")
     if clean is not None and bilevel is False:
         raise ValueError(f"jpeg_despeckle={despeckle!r} needs jpeg_bilevel=...: there is no Group 4 file to clean")
-    return None if preset is None else PageFiles(preset, bool(optimize), subsampling, grey, bilevel, cells, clean)
+    flat = flate.check_lossless(lossless)
+    if flat is not None and preset is None:
+        raise ValueError(f"jpeg_lossless={lossless!r} needs jpeg=...: there are no page files to write that way")
+    return None if preset is None else PageFiles(preset, bool(optimize), subsampling, grey, bilevel, cells, clean, flat)
 
 
 def check_jpeg_preset(jpeg, jpeg_optimize=False, jpeg_subsampling=None, jpeg_grey=False, jpeg_bilevel=False, jpeg_mrc=False,
-                      jpeg_despeckle=False):
+                      jpeg_despeckle=False, jpeg_lossless=False):
     """`jpeg` of a serve() call: None (-> None) or a preset name of the searchable PDF (-> the job's PageFiles); anything else is
     a ValueError - raised by the public entry points before a source is read.  `jpeg_optimize`, `jpeg_subsampling` (None, "4:2:0",
     "4:2:2", "4:4:4"), `jpeg_grey` (False, "auto"), `jpeg_bilevel` (False, "auto", "otsu", "adaptive") and `jpeg_mrc` (False, True
     or a dict of cells: yomitoku_amd/mrc.py, check_mrc) ask for something of those files: a value that is none of these is a
     ValueError, and so is any of the five without `jpeg`.  `jpeg_despeckle` (False, True, an int or a dict of sizes:
     yomitoku_amd/despeckle.py, check_despeckle) cleans the Group 4 files' bits: a value that is none of these, the switch without
-    `jpeg`, and the switch with `jpeg_bilevel=False` - there is no Group 4 file to clean - are ValueErrors."""
-    return page_files(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, serve=True, despeckle=jpeg_despeckle)
+    `jpeg`, and the switch with `jpeg_bilevel=False` - there is no Group 4 file to clean - are ValueErrors.  `jpeg_lossless` (False,
+    True or {"budget": bytes per pixel}: yomitoku_amd/flate.py, check_lossless) writes the pages the other switches leave as lossless
+    files: any other value, an unknown key, a budget that is no positive finite number, and the switch without `jpeg` are ValueErrors."""
+    return page_files(jpeg, jpeg_optimize, jpeg_subsampling, jpeg_grey, jpeg_bilevel, jpeg_mrc, serve=True, despeckle=jpeg_despeckle,
+                      lossless=jpeg_lossless)
 
 
 def launch_encode(pages: Sequence[torch.Tensor], quality: int, capacities: Optional[Sequence[int]], optimize: bool,
@@ -353,13 +365,14 @@ class _Page:
     k: int  # its index in the call
     dev: torch.Tensor  # on the device; the resized page once the preset has shrunk it
     large: bool  # its long side exceeds the preset's
-    kind: str = "jpeg"  # what it becomes: "jpeg" | "group4" | "layered"
+    kind: str = "jpeg"  # what it becomes: "jpeg" | "group4" | "layered" | "lossless"
     scale: float = 1.0
     threshold: Optional[int] = None  # Otsu's, of a thresholded page
     despeckled: Optional[object] = None  # of a despeckled Group 4 page its Despeckled; of a layered page with a filtered mask its InkFiltered
     layer: Optional[int] = None  # a layered page's place in the separation
     jpeg_at: Optional[int] = None  # its place in the JPEG batch; a layered page: its foreground's, the background follows
     g4_at: Optional[int] = None  # its - or its mask's - place in the Group 4 batch
+    flat_at: Optional[int] = None  # its place among the pages the lossless coder was given
 
 
 def _sort(batch: List[_Page], files: PageFiles, scratch: dict):
@@ -435,8 +448,24 @@ def _group4_batch(batch: List[_Page], test, sep):
     return (test, two + lay) if test is not None else (sep, [batch[j].layer for j in lay])
 
 
-def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_grey, sizes, datas):
-    """Phase 5's end: every live page's entry into `out`, from the files' bytes - the JPEG batch's, then the Group 4 batch's."""
+def _lossless_batch(batch: List[_Page], files: PageFiles, scratch: dict):
+    """Phase 1c: the pages the sort left become lossless files - all of them, or, with a budget, those whose file fits it: the
+    first phase of the coder, ONE wait for the files' sizes, the rest for the pages that go on; a page over the budget stays
+    "jpeg".  `grey="auto"`: the device test runs in front, and the kernels read its answer - no wait of its own.
+    -> the coding, or None where no page was left."""
+    cand = [p for p in batch if p.kind == "jpeg"]
+    if not cand:
+        return None
+    coding, keep = flate.launch([p.dev for p in cand], scratch, files.lossless["budget256"], grey=files.grey == "auto")
+    for i, (p, go) in enumerate(zip(cand, keep)):
+        if go:
+            p.kind, p.flat_at = "lossless", i
+    return coding
+
+
+def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_grey, sizes, datas, flat=None):
+    """Phase 5's end: every live page's entry into `out`, from the files' bytes - the JPEG batch's, then the Group 4 batch's, then
+    the lossless pages' (`flat`: (the first of them in `datas`, per page its channels))."""
     def jpeg_entry(i, k, scale, what="the JPEG file"):
         d = jdevs[i]
         if sizes[i] < 0:
@@ -450,6 +479,8 @@ def _entries(batch: List[_Page], files: PageFiles, out: list, jdevs, caps, as_gr
             out[p.k] = jpeg_entry(p.jpeg_at, p.k, p.scale)
         elif p.kind == "group4":
             out[p.k] = ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, files.bilevel, p.threshold, p.despeckled)
+        elif p.kind == "lossless":
+            out[p.k] = flate.lossless_entry(p.dev, datas[flat[0] + p.flat_at], flat[1][p.flat_at], p.k)
         else:
             parts = [ccitt.bilevel_entry(p.dev, datas[len(jdevs) + p.g4_at], p.k, "adaptive", None, p.despeckled),
                      jpeg_entry(p.jpeg_at, p.k, 1.0, "the foreground's file"), jpeg_entry(p.jpeg_at + 1, p.k, 1.0, "the background's file")]
@@ -476,6 +507,8 @@ def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: O
         two = [j for j, p in enumerate(batch) if p.kind == "group4"] if files.despeckle is not None else []
         if two:
             cc_pin = to_pinned(scratch, "cc_pin_counts", specks.launch(test, two, files.despeckle, scratch), 4 * len(two))
+        # 1c. `lossless`: the pages that are left go to the lossless coder; with a budget one wait for the sizes, else none
+        coding = _lossless_batch(batch, files, scratch) if files.lossless is not None else None
         # 2. the JPEG batch: resize, the grey test (its own wait unless it ran early), the layers behind the plain pages
         jdevs, caps, as_grey = _jpeg_batch(batch, files, long_side, sep, early_grey, capacities, scratch)
         # 3. launch JPEG; the lengths go to the host first (one small copy), the bytes, packed on the device, in the gather
@@ -497,13 +530,18 @@ def encode_page_files(pages: Sequence, files: PageFiles, stream=None, scratch: O
         parts = [(jpegs, offsets[i], sizes[i]) for i in range(len(jdevs))]
         if which:
             parts += [(g4s, g4_offsets[i], n) for i, n in enumerate(g4_pin[: len(which)].tolist())]
-        _entries(batch, files, out, jdevs, caps, as_grey, sizes, gather_files(parts, scratch))
+        flat = None
+        if coding is not None:
+            answers, went = coding.answers(), {p.flat_at for p in batch if p.kind == "lossless"}
+            flat = (len(parts), [ch for _, ch in answers])
+            parts += [(coding.out, coding.offsets[i], n if i in went else -1) for i, (n, _) in enumerate(answers)]
+        _entries(batch, files, out, jdevs, caps, as_grey, sizes, gather_files(parts, scratch), flat)
     return out
 
 
 def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None, scratch: Optional[dict] = None,
                       capacities: Optional[Sequence[int]] = None, optimize: bool = False, subsampling: str = "4:2:0",
-                      grey=False, bilevel=False, mrc=False, despeckle=False) -> list:
+                      grey=False, bilevel=False, mrc=False, despeckle=False, lossless=False) -> list:
     """One entry per page, in order: its EncodedJpeg, or the exception that page raised (not uint8, not H x W x 3 / H x W; a
     file larger than its capacity - default: the page's raw byte count).  pages: device tensors and / or host arrays.
     stream: the torch stream to launch on (default: the current one).  scratch: a dict the caller keeps between calls to reuse
@@ -540,9 +578,15 @@ def encode_jpeg_pages(pages: Sequence, image_quality: str = "high", stream=None,
     between the threshold and the coder; the entry's `despeckled` says how many.  It is the caller's decision about the job:
     bilevel="auto" with the switch is no longer lossless.  It needs `bilevel`; the masks of layered pages are not touched.  Four
     launches a colour behind `bilevel`'s wait, no wait of its own: the counts come back with the files' lengths.
+    lossless: False, True or {"budget": bytes per pixel} (yomitoku_amd/flate.py: check_lossless) - of the pages `bilevel` and `mrc`
+    leave, one channel or three, every page gets an EncodedLossless in place of the EncodedJpeg: a zlib stream of its PNG-filtered
+    rows, full size whatever the preset (scale 1.0); `optimize`, `subsampling` and `capacities` do not apply to it, `grey="auto"`
+    does: a three-channel page with B == G == R everywhere is written as one channel.  Five launches behind the sort, no wait of
+    their own.  With a budget a page goes lossless only where its file takes at most that many bytes a pixel - the size is exact
+    after the first two launches, which one further wait follows - and otherwise gets exactly the JPEG it gets without the switch.
     Anything else is a ValueError before any device work.  A 4:4:4 file is larger: noise may no longer fit the default capacity."""
-    return encode_page_files(pages, page_files(image_quality, optimize, subsampling, grey, bilevel, mrc, despeckle=despeckle), stream, scratch,
-                             capacities)
+    return encode_page_files(pages, page_files(image_quality, optimize, subsampling, grey, bilevel, mrc, despeckle=despeckle, lossless=lossless),
+                             stream, scratch, capacities)
 
 
 def encode_jpeg(page, image_quality: str = "high", stream=None, optimize: bool = False, subsampling: str = "4:2:0",

@@ -754,8 +754,8 @@ class StageAnalyzer:
         return out
 
     def _stage_jpeg(self, wave, results, scratch=None):
-        """Page files: per page of the wave a 1-tuple with its EncodedJpeg (an EncodedBilevel or an EncodedMrc where
-        `wave.job.files`, the job's PageFiles, gives the page one), an exception for a page
+        """Page files: per page of the wave a 1-tuple with its EncodedJpeg (an EncodedBilevel, an EncodedMrc or an EncodedLossless
+        where `wave.job.files`, the job's PageFiles, gives the page one), an exception for a page
         that could not be encoded, None for a page that had already failed.  All pages of the wave are encoded together on
         the calling thread's stream (yomitoku_amd/jpeg.py: encode_page_files) from `wave.pages` - the clean pages: the
         overlays are drawn on copies - with `scratch`, by default the wave slot's."""

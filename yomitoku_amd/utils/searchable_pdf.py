@@ -328,6 +328,13 @@ def _is_bilevel(image) -> bool:
         hasattr(image, a) for a in ("width", "height", "scale"))
 
 
+def _is_lossless(image) -> bool:
+    """An entry that is a finished zlib stream of PNG-filtered rows: yomitoku_amd.flate.EncodedLossless, recognised by `lossless`
+    and its fields (`data` bytes, `width`, `height`, `channels`, `scale`), again without torch or the HIP library."""
+    return getattr(image, "lossless", False) is True and isinstance(getattr(image, "data", None), (bytes, bytearray)) and all(
+        hasattr(image, a) for a in ("width", "height", "channels", "scale"))
+
+
 def _is_mrc(image) -> bool:
     """An entry that is a layered page: yomitoku_amd.mrc.EncodedMrc, recognised by `mrc` and its fields - `mask` an
     EncodedBilevel, `background` and `foreground` EncodedJpegs, `width`, `height`, `scale`, `bg_cell`, `fg_cell` -, again without
@@ -383,8 +390,10 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
             kids.append(pdf.add((f"<< /Type /Page /Parent {pages} 0 R /MediaBox [0 0 {w} {h}] /Contents {contents} 0 R "
                                  f"/Resources << /XObject << /Im0 {fore} 0 R /Im1 {back} 0 R >> /Font << /F1 {font} 0 R >> >> >>").encode("ascii")))
             continue
-        bilevel = _is_bilevel(image)
-        if bilevel:  # a finished T.6 stream (yomitoku_amd.ccitt.EncodedBilevel): 1 bit a pixel, 0 = white (BlackIs1 false, the default)
+        bilevel, lossless = _is_bilevel(image), _is_lossless(image)
+        if lossless:  # a finished zlib stream of PNG-filtered rows (yomitoku_amd.flate.EncodedLossless): what /Predictor 15 expects
+            data, w, h, scale, channels = bytes(image.data), int(image.width), int(image.height), float(image.scale), int(image.channels)
+        elif bilevel:  # a finished T.6 stream (yomitoku_amd.ccitt.EncodedBilevel): 1 bit a pixel, 0 = white (BlackIs1 false, the default)
             data, w, h, scale = bytes(image.data), int(image.width), int(image.height), float(image.scale)
         elif _is_encoded(image):  # a finished JPEG (yomitoku_amd.jpeg.EncodedJpeg): embedded as it is, `image_quality` does not apply
             data, w, h, grey, scale = bytes(image.data), int(image.width), int(image.height), bool(image.grey), float(image.scale)
@@ -402,7 +411,11 @@ def searchable_pdf_bytes(images: Sequence, docs: Sequence, image_quality: str = 
             image.save(jpeg, format="JPEG", quality=preset["jpeg_quality"])
             data = jpeg.getvalue()
             w, h = image.size
-        if bilevel:
+        if lossless:
+            xobject = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ColorSpace /Device{'Gray' if channels == 1 else 'RGB'} "
+                                     f"/BitsPerComponent 8 /Filter /FlateDecode /DecodeParms << /Predictor 15 /Colors {channels} "
+                                     f"/BitsPerComponent 8 /Columns {w} >>", data, compress=False)
+        elif bilevel:
             xobject = pdf.add_stream(f"/Type /XObject /Subtype /Image /Width {w} /Height {h} /ColorSpace /DeviceGray /BitsPerComponent 1 "
                                      f"/Filter /CCITTFaxDecode /DecodeParms << /K -1 /Columns {w} /Rows {h} >>", data, compress=False)
         else:
@@ -424,7 +437,8 @@ def create_searchable_pdf(images: List, docs: List, output_path: str, font_path:
     from the object, the words are scaled by its `scale`, and `image_quality` is ignored for that entry.  An EncodedBilevel
     (yomitoku_amd/ccitt.py; `serve(jpeg=..., jpeg_bilevel="auto")` returns one for a two-valued page) is embedded as a 1-bit
     /CCITTFaxDecode image, K -1 (Group 4), likewise as it is.  An EncodedMrc (yomitoku_amd/mrc.py; `serve(jpeg=..., jpeg_mrc=True)`)
-    becomes three images: the background, and the foreground painted through the Group 4 mask."""
+    becomes three images: the background, and the foreground painted through the Group 4 mask.  An EncodedLossless
+    (yomitoku_amd/flate.py; `serve(jpeg=..., jpeg_lossless=True)`) is embedded as it is as a /FlateDecode image with /Predictor 15."""
     data = searchable_pdf_bytes(images, docs, image_quality)
     with open(output_path, "wb") as f:
         f.write(data)
