@@ -48,19 +48,6 @@ struct RoctxRange {
 };
 }  // namespace
 
-#define YMK_API_BEGIN try {
-#define YMK_API_END                                 \
-  return 0;                                         \
-  }                                                 \
-  catch (const std::exception& e) {                 \
-    ymk::set_error(e.what());                       \
-    return 1;                                       \
-  }                                                 \
-  catch (...) {                                     \
-    ymk::set_error("unknown C++ exception");        \
-    return 2;                                       \
-  }
-
 extern "C" {
 
 int ymk_version(void) { return 100; }
@@ -74,23 +61,20 @@ int ymk_device_count(void) {
 }
 
 ymk_model* ymk_model_create(const char* kind, int device) {
-  try {
-    YMK_CHECK(kind != nullptr, "kind is null");
-    YMK_HIP(hipSetDevice(device));
-    std::string k(kind);
-    ymk::Model* impl = nullptr;
-    if (k == "dbnet") impl = ymk::create_dbnet();
-    else if (k == "parseq") impl = ymk::create_parseq();
-    else if (k == "rtdetr") impl = ymk::create_rtdetr();
-    else throw ymk::Error("unknown model kind: " + k);
-    auto* m = new ymk_model();
-    m->impl = impl;
-    m->device = device;
-    return m;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return nullptr;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(kind != nullptr, "kind is null");
+  YMK_HIP(hipSetDevice(device));
+  std::string k(kind);
+  ymk::Model* impl = nullptr;
+  if (k == "dbnet") impl = ymk::create_dbnet();
+  else if (k == "parseq") impl = ymk::create_parseq();
+  else if (k == "rtdetr") impl = ymk::create_rtdetr();
+  else throw ymk::Error("unknown model kind: " + k);
+  auto* m = new ymk_model();
+  m->impl = impl;
+  m->device = device;
+  return m;
+  YMK_API_END_OR(nullptr)
 }
 
 void ymk_model_destroy(ymk_model* m) {

@@ -20,9 +20,7 @@
 // form is exact all the same: a window's sum is A11 - A01 - A10 + A00 modulo 2^32, and its true value is at most 255 * 2047^2
 // < 2^31 (r <= 16383 / 16), so the residue IS the value.  Half the bytes of an int64 table, on a stage that is all memory traffic.
 
-#include "ymk_common.h"
-
-#include <algorithm>
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -35,10 +33,6 @@ struct BzLimits {
   long long packed_words, sat_words;
 };
 
-__device__ __forceinline__ long long bz_word64(const int* r, int k) {
-  return (long long)(((unsigned long long)(unsigned)r[k + 1] << 32) | (unsigned long long)(unsigned)r[k]);
-}
-
 // A page's record, read and checked against the buffers' sizes, as g4_page of ymk_ccitt.hip does: a kernel takes a page whose
 // record fails the check for what it touches as absent.
 struct BzPage {
@@ -50,9 +44,9 @@ struct BzPage {
 __device__ __forceinline__ BzPage bz_page(const int* blob, int p, const BzLimits& lim) {
   const int* r = blob + (size_t)p * BZ_REC;
   BzPage g;
-  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)bz_word64(r, 0));
+  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
   g.h = r[2], g.w = r[3], g.ch = r[4];
-  g.packed_at = bz_word64(r, 6), g.sat_at = bz_word64(r, 14);
+  g.packed_at = page_word64(r, 6), g.sat_at = page_word64(r, 14);
   g.ok = g.h >= 1 && g.w >= 1 && g.h <= BZ_MAX_SIDE && g.w <= BZ_MAX_SIDE && g.src != nullptr && (g.ch == 1 || g.ch == 3);
   g.row_words = g.ok ? (g.w + 31) >> 5 : 0;
   g.pack_ok = g.ok && g.packed_at >= 0 && g.packed_at + (long long)g.h * g.row_words <= lim.packed_words;
@@ -253,10 +247,8 @@ __global__ __launch_bounds__(PK_THREADS) void k_bin_adaptive_pack(const int* __r
 }
 
 static void bz_check_table(const int* blob_dev, int64_t blob_words, int n_pages) {
-  YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n_pages * BZ_REC, "page table: n records");
+  check_page_table(blob_dev, blob_words, n_pages, BZ_REC, 3, 4096, "0..4096 pages", "page table: n records");
 }
-static void bz_aligned(const void* p, const char* what) { YMK_CHECK(p && ((uintptr_t)p & 7) == 0, what); }
 // a pixel per thread and step, sixteen steps where the largest page has that many; 512 blocks per page at the most
 static unsigned bz_pixel_blocks(int64_t max_pixels) {
   const int64_t per_block = (int64_t)PK_THREADS * 16;
@@ -268,102 +260,82 @@ static unsigned bz_pixel_blocks(int64_t max_pixels) {
 extern "C" {
 
 int ymk_bin_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes2_out) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes2_out && (n_pages == 0 || (h && w)), "bad argument");
-    int64_t cells = 0;
-    for (int k = 0; k < n_pages; ++k) {
-      YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::BZ_MAX_SIDE && w[k] <= ymk::BZ_MAX_SIDE, "a page has 1..16383 pixels on a side");
-      cells += (int64_t)h[k] * w[k];
-    }
-    sizes2_out[0] = (int64_t)n_pages * 256 * 4;
-    sizes2_out[1] = ((cells + 1) & ~1LL) * 4;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes2_out && (n_pages == 0 || (h && w)), "bad argument");
+  int64_t cells = 0;
+  for (int k = 0; k < n_pages; ++k) {
+    YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::BZ_MAX_SIDE && w[k] <= ymk::BZ_MAX_SIDE, "a page has 1..16383 pixels on a side");
+    cells += (int64_t)h[k] * w[k];
   }
+  sizes2_out[0] = (int64_t)n_pages * 256 * 4;
+  sizes2_out[1] = ((cells + 1) & ~1LL) * 4;
+  YMK_API_END
 }
 
 int ymk_bin_test_hist(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* flags_dev, uint32_t* hist_dev,
                       void* stream) {
-  try {
-    YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::bz_check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(flags_dev && ((uintptr_t)flags_dev & 3) == 0, "null or misaligned flags");
-    YMK_CHECK(((uintptr_t)hist_dev & 3) == 0, "misaligned histograms");
-    const hipStream_t s = (hipStream_t)stream;
-    YMK_HIP(hipMemsetAsync(flags_dev, 0, (size_t)n_pages * sizeof(int), s));
-    if (hist_dev) YMK_HIP(hipMemsetAsync(hist_dev, 0, (size_t)n_pages * 256 * sizeof(uint32_t), s));
-    hipLaunchKernelGGL(ymk::k_bin_test_hist, dim3(ymk::bz_pixel_blocks(max_pixels), (unsigned)n_pages), dim3(ymk::TH_THREADS), 0, s,
-                       blob_dev, flags_dev, (unsigned*)hist_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::bz_check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(flags_dev && ((uintptr_t)flags_dev & 3) == 0, "null or misaligned flags");
+  YMK_CHECK(((uintptr_t)hist_dev & 3) == 0, "misaligned histograms");
+  const hipStream_t s = (hipStream_t)stream;
+  YMK_HIP(hipMemsetAsync(flags_dev, 0, (size_t)n_pages * sizeof(int), s));
+  if (hist_dev) YMK_HIP(hipMemsetAsync(hist_dev, 0, (size_t)n_pages * 256 * sizeof(uint32_t), s));
+  hipLaunchKernelGGL(ymk::k_bin_test_hist, dim3(ymk::bz_pixel_blocks(max_pixels), (unsigned)n_pages), dim3(ymk::TH_THREADS), 0, s,
+                     blob_dev, flags_dev, (unsigned*)hist_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_bin_otsu(int n_pages, const uint32_t* hist_dev, int* thresholds_dev, void* stream) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
-    if (n_pages == 0) return 0;
-    YMK_CHECK(hist_dev && ((uintptr_t)hist_dev & 3) == 0 && thresholds_dev && ((uintptr_t)thresholds_dev & 3) == 0,
-              "null or misaligned histograms / thresholds");
-    hipLaunchKernelGGL(ymk::k_bin_otsu, dim3((unsigned)n_pages), dim3(ymk::OT_THREADS), 0, (hipStream_t)stream, (const unsigned*)hist_dev,
-                       thresholds_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
+  if (n_pages == 0) return 0;
+  YMK_CHECK(hist_dev && ((uintptr_t)hist_dev & 3) == 0 && thresholds_dev && ((uintptr_t)thresholds_dev & 3) == 0,
+            "null or misaligned histograms / thresholds");
+  hipLaunchKernelGGL(ymk::k_bin_otsu, dim3((unsigned)n_pages), dim3(ymk::OT_THREADS), 0, (hipStream_t)stream, (const unsigned*)hist_dev,
+                     thresholds_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_bin_otsu_pack(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, const int* thresholds_dev,
                       uint32_t* packed_dev, int64_t packed_bytes, void* stream) {
-  try {
-    YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL && packed_bytes >= 0, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::bz_check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(thresholds_dev && ((uintptr_t)thresholds_dev & 3) == 0, "null or misaligned thresholds");
-    ymk::bz_aligned(packed_dev, "packed rows: 8-byte aligned");
-    const ymk::BzLimits lim{packed_bytes / 4, 0};
-    hipLaunchKernelGGL(ymk::k_bin_otsu_pack, dim3(ymk::bz_pixel_blocks(max_pixels), (unsigned)n_pages), dim3(ymk::PK_THREADS), 0,
-                       (hipStream_t)stream, blob_dev, lim, thresholds_dev, (unsigned*)packed_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL && packed_bytes >= 0, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::bz_check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(thresholds_dev && ((uintptr_t)thresholds_dev & 3) == 0, "null or misaligned thresholds");
+  ymk::check_aligned8(packed_dev, "packed rows: 8-byte aligned");
+  const ymk::BzLimits lim{packed_bytes / 4, 0};
+  hipLaunchKernelGGL(ymk::k_bin_otsu_pack, dim3(ymk::bz_pixel_blocks(max_pixels), (unsigned)n_pages), dim3(ymk::PK_THREADS), 0,
+                     (hipStream_t)stream, blob_dev, lim, thresholds_dev, (unsigned*)packed_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_bin_adaptive_pack(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* sat_dev, int64_t sat_bytes,
                           uint32_t* packed_dev, int64_t packed_bytes, void* stream) {
-  try {
-    YMK_CHECK(max_h >= 1 && max_w >= 1 && max_h <= ymk::BZ_MAX_SIDE && max_w <= ymk::BZ_MAX_SIDE && sat_bytes >= 0 && packed_bytes >= 0,
-              "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::bz_check_table(blob_dev, blob_words, n_pages);
-    ymk::bz_aligned(sat_dev, "summed-area tables: 8-byte aligned");
-    ymk::bz_aligned(packed_dev, "packed rows: 8-byte aligned");
-    const ymk::BzLimits lim{packed_bytes / 4, sat_bytes / 4};
-    const hipStream_t s = (hipStream_t)stream;
-    const unsigned rows_x = (unsigned)((max_h + ymk::RS_THREADS / 64 - 1) / (ymk::RS_THREADS / 64));  // a wave per row
-    hipLaunchKernelGGL(ymk::k_bin_row_scan, dim3(rows_x, (unsigned)n_pages), dim3(ymk::RS_THREADS), 0, s, blob_dev, lim, (unsigned*)sat_dev);
-    YMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ymk::k_bin_col_scan, dim3((unsigned)((max_w + 63) / 64), (unsigned)n_pages), dim3(ymk::CS_THREADS), 0, s, blob_dev, lim,
-                       (unsigned*)sat_dev);
-    YMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ymk::k_bin_adaptive_pack, dim3(ymk::bz_pixel_blocks((int64_t)max_h * max_w), (unsigned)n_pages), dim3(ymk::PK_THREADS), 0, s,
-                       blob_dev, lim, (const unsigned*)sat_dev, (unsigned*)packed_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(max_h >= 1 && max_w >= 1 && max_h <= ymk::BZ_MAX_SIDE && max_w <= ymk::BZ_MAX_SIDE && sat_bytes >= 0 && packed_bytes >= 0,
+            "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::bz_check_table(blob_dev, blob_words, n_pages);
+  ymk::check_aligned8(sat_dev, "summed-area tables: 8-byte aligned");
+  ymk::check_aligned8(packed_dev, "packed rows: 8-byte aligned");
+  const ymk::BzLimits lim{packed_bytes / 4, sat_bytes / 4};
+  const hipStream_t s = (hipStream_t)stream;
+  const unsigned rows_x = (unsigned)((max_h + ymk::RS_THREADS / 64 - 1) / (ymk::RS_THREADS / 64));  // a wave per row
+  hipLaunchKernelGGL(ymk::k_bin_row_scan, dim3(rows_x, (unsigned)n_pages), dim3(ymk::RS_THREADS), 0, s, blob_dev, lim, (unsigned*)sat_dev);
+  YMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ymk::k_bin_col_scan, dim3((unsigned)((max_w + 63) / 64), (unsigned)n_pages), dim3(ymk::CS_THREADS), 0, s, blob_dev, lim,
+                     (unsigned*)sat_dev);
+  YMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ymk::k_bin_adaptive_pack, dim3(ymk::bz_pixel_blocks((int64_t)max_h * max_w), (unsigned)n_pages), dim3(ymk::PK_THREADS), 0, s,
+                     blob_dev, lim, (const unsigned*)sat_dev, (unsigned*)packed_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 }

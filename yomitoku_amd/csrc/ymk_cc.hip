@@ -59,9 +59,7 @@
 // meanwhile reads an older parent or the root.  The barriers are __syncthreads inside a block, reached by all of its threads or
 // by none.  Still no loop waits for another thread's progress.
 //
-#include "ymk_common.h"
-
-#include <algorithm>
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -78,10 +76,6 @@ struct CcLimits {
   int max_h, max_w;  // what the call's grids are sized by
 };
 
-__device__ __forceinline__ long long cc_word64(const int* r, int k) {
-  return (long long)(((unsigned long long)(unsigned)r[k + 1] << 32) | (unsigned long long)(unsigned)r[k]);
-}
-
 // A page's record (the Group 4 page table: h, w, words 6-7 the packed rows, words 14-15 the place of its h w labels and areas),
 // read and checked against the buffers' sizes and the call's max_h, max_w: every kernel takes a page whose record fails as absent.
 struct CcPage {
@@ -93,7 +87,7 @@ __device__ __forceinline__ CcPage cc_page(const int* blob, int p, const CcLimits
   const int* r = blob + (size_t)p * CC_REC;
   CcPage g;
   g.h = r[2], g.w = r[3];
-  g.packed_at = cc_word64(r, 6), g.label_at = cc_word64(r, 14);
+  g.packed_at = page_word64(r, 6), g.label_at = page_word64(r, 14);
   g.ok = g.h >= 1 && g.w >= 1 && g.h <= lim.max_h && g.w <= lim.max_w;  // a larger page the grids would cover in part only
   g.row_words = g.ok ? (g.w + 31) >> 5 : 0;
   g.ok = g.ok && g.packed_at >= 0 && g.packed_at + (long long)g.h * g.row_words <= lim.packed_words && g.label_at >= 0 &&
@@ -482,8 +476,7 @@ struct CcCall {
 static CcCall cc_check(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, const uint32_t* packed_dev, int64_t packed_bytes,
                        const int* labels_dev, int64_t labels_bytes, const int* areas_dev, int64_t areas_bytes, int n_black, int n_white,
                        const int* counts_dev, void* stream) {
-  YMK_CHECK(n_pages >= 1 && n_pages <= 4096, "0..4096 pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n_pages * CC_REC, "page table: n records");
+  check_page_table(blob_dev, blob_words, n_pages, CC_REC, 3, 4096, "0..4096 pages", "page table: n records");  // no caller comes with 0
   YMK_CHECK(max_h >= 1 && max_w >= 1 && max_h <= CC_MAX_SIDE && max_w <= CC_MAX_SIDE, "a page has 1..16383 pixels on a side");
   YMK_CHECK(packed_dev && ((uintptr_t)packed_dev & 3) == 0 && packed_bytes >= 0, "packed rows: null, misaligned or a negative size");
   YMK_CHECK(labels_dev && areas_dev && (((uintptr_t)labels_dev | (uintptr_t)areas_dev) & 3) == 0, "null or misaligned labels or areas");
@@ -511,36 +504,28 @@ int ymk_cc_tile_w(void) { return ymk::CC_TILE_W; }
 int ymk_cc_tile_h(void) { return ymk::CC_TILE_H; }
 
 int ymk_cc_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes2_out) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes2_out && (n_pages == 0 || (h && w)), "bad argument");
-    int64_t pixels = 0;
-    for (int k = 0; k < n_pages; ++k) {
-      YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::CC_MAX_SIDE && w[k] <= ymk::CC_MAX_SIDE, "a page has 1..16383 pixels on a side");
-      pixels += (int64_t)h[k] * w[k];
-    }
-    sizes2_out[0] = sizes2_out[1] = ((pixels + 1) & ~1LL) * 4;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes2_out && (n_pages == 0 || (h && w)), "bad argument");
+  int64_t pixels = 0;
+  for (int k = 0; k < n_pages; ++k) {
+    YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::CC_MAX_SIDE && w[k] <= ymk::CC_MAX_SIDE, "a page has 1..16383 pixels on a side");
+    pixels += (int64_t)h[k] * w[k];
   }
+  sizes2_out[0] = sizes2_out[1] = ((pixels + 1) & ~1LL) * 4;
+  YMK_API_END
 }
 
 int ymk_cc_despeckle_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev, int64_t packed_bytes,
                            int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int n_black, int n_white, int* counts_dev,
                            void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    const ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
-                                        areas_bytes, n_black, n_white, counts_dev, stream);
-    YMK_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pages * 4 * sizeof(int), c.s));
-    if (n_black > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, n_black, packed_dev, labels_dev, areas_dev, counts_dev);
-    if (n_white > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, ~0u, 0, n_white, packed_dev, labels_dev, areas_dev, counts_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  const ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
+                                      areas_bytes, n_black, n_white, counts_dev, stream);
+  YMK_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pages * 4 * sizeof(int), c.s));
+  if (n_black > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, n_black, packed_dev, labels_dev, areas_dev, counts_dev);
+  if (n_white > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, ~0u, 0, n_white, packed_dev, labels_dev, areas_dev, counts_dev);
+  YMK_API_END
 }
 
 int ymk_cc_filter_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes3_out) {
@@ -552,56 +537,44 @@ int ymk_cc_filter_scratch_bytes(const int* h, const int* w, int n_pages, int64_t
 int ymk_cc_filter_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev, int64_t packed_bytes,
                         int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int* boxes_dev, int64_t boxes_bytes, int n_black,
                         int n_white, int side, int fill, int* counts_dev, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
-                                  areas_bytes, n_black, n_white, counts_dev, stream);
-    ymk::cc_check_blobs(c, side, fill, boxes_dev, boxes_bytes);
-    YMK_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pages * 6 * sizeof(int), c.s));
-    if (n_black > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, n_black, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6);
-    if (n_white > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, ~0u, 0, n_white, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6);
-    if (side > 0)
-      ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, 0, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6, boxes_dev, side, fill);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
+                                areas_bytes, n_black, n_white, counts_dev, stream);
+  ymk::cc_check_blobs(c, side, fill, boxes_dev, boxes_bytes);
+  YMK_HIP(hipMemsetAsync(counts_dev, 0, (size_t)n_pages * 6 * sizeof(int), c.s));
+  if (n_black > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, n_black, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6);
+  if (n_white > 0) ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, ~0u, 0, n_white, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6);
+  if (side > 0)
+    ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, 0, packed_dev, labels_dev, areas_dev, counts_dev, 15, 6, boxes_dev, side, fill);
+  YMK_API_END
 }
 
 int ymk_cc_filter_stage(int stage, const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
                         int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int* boxes_dev,
                         int64_t boxes_bytes, int side, int fill, int* counts_dev, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    YMK_CHECK(stage >= 0 && stage <= 3, "a stage is 0 (label), 1 (merge), 2 (boxes) or 3 (apply)");
-    YMK_CHECK(side >= 2, "the blob pass needs a side");
-    ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
-                                  areas_bytes, 0, 0, counts_dev, stream);
-    ymk::cc_check_blobs(c, side, fill, boxes_dev, boxes_bytes);
-    ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, 0, packed_dev, labels_dev, areas_dev, counts_dev, 1 << stage, 6, boxes_dev, side,
-                 fill);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  YMK_CHECK(stage >= 0 && stage <= 3, "a stage is 0 (label), 1 (merge), 2 (boxes) or 3 (apply)");
+  YMK_CHECK(side >= 2, "the blob pass needs a side");
+  ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
+                                areas_bytes, 0, 0, counts_dev, stream);
+  ymk::cc_check_blobs(c, side, fill, boxes_dev, boxes_bytes);
+  ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, 0u, 1, 0, packed_dev, labels_dev, areas_dev, counts_dev, 1 << stage, 6, boxes_dev, side,
+               fill);
+  YMK_API_END
 }
 
 int ymk_cc_stage(int stage, int white, const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, uint32_t* packed_dev,
                  int64_t packed_bytes, int* labels_dev, int64_t labels_bytes, int* areas_dev, int64_t areas_bytes, int n, int* counts_dev,
                  void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    YMK_CHECK(stage >= 0 && stage <= 3, "a stage is 0 (label), 1 (merge), 2 (areas) or 3 (apply)");
-    const ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
-                                        areas_bytes, n, n, counts_dev, stream);
-    ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, white ? ~0u : 0u, white ? 0 : 1, n, packed_dev, labels_dev, areas_dev, counts_dev,
-                 1 << stage);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  YMK_CHECK(stage >= 0 && stage <= 3, "a stage is 0 (label), 1 (merge), 2 (areas) or 3 (apply)");
+  const ymk::CcCall c = ymk::cc_check(blob_dev, blob_words, n_pages, max_h, max_w, packed_dev, packed_bytes, labels_dev, labels_bytes, areas_dev,
+                                      areas_bytes, n, n, counts_dev, stream);
+  ymk::cc_pass(c.s, blob_dev, n_pages, max_h, max_w, c.lim, white ? ~0u : 0u, white ? 0 : 1, n, packed_dev, labels_dev, areas_dev, counts_dev,
+               1 << stage);
+  YMK_API_END
 }
 }

@@ -30,9 +30,7 @@
 // first step is either vertical or horizontal).  tests/test_ccitt_host.py checks the bound exhaustively for narrow rows.
 // k_g4_rows nevertheless never writes beyond a slot: a row that did not fit would be marked and its page get -1.
 
-#include "ymk_common.h"
-
-#include <algorithm>
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -91,10 +89,6 @@ __device__ const unsigned G4_TABLE[G4_TABLE_WORDS] = {
 constexpr unsigned G4_PASS = G4C(4, 1), G4_HORIZONTAL = G4C(3, 1);
 constexpr unsigned G4_EOFB_TOP = 0x00100100u;  // 000000000001 twice, in the upper 24 bits of a word
 
-__device__ __forceinline__ long long g4_word64(const int* r, int k) {
-  return (long long)(((unsigned long long)(unsigned)r[k + 1] << 32) | (unsigned long long)(unsigned)r[k]);
-}
-
 // A page's record, read and checked against the buffers' sizes: every kernel takes a page whose record fails as absent, so no
 // record, whatever it says, makes a kernel touch memory outside the buffers the caller named.
 struct G4Page {
@@ -106,9 +100,9 @@ struct G4Page {
 __device__ __forceinline__ G4Page g4_page(const int* blob, int p, const G4Limits& lim) {
   const int* r = blob + (size_t)p * G4_REC;
   G4Page g;
-  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)g4_word64(r, 0));
+  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
   g.h = r[2], g.w = r[3], g.ch = r[4], g.first_row = r[5];
-  g.packed_at = g4_word64(r, 6), g.out_at = g4_word64(r, 8), g.capacity = r[10], g.slot_at = g4_word64(r, 11);
+  g.packed_at = page_word64(r, 6), g.out_at = page_word64(r, 8), g.capacity = r[10], g.slot_at = page_word64(r, 11);
   g.ok = g.h >= 1 && g.w >= 1 && g.h <= G4_MAX_SIDE && g.w <= G4_MAX_SIDE;
   g.row_words = g.ok ? (g.w + 31) >> 5 : 0;
   g.slot_row_words = g.ok ? g4_slot_words(g.w) : 0;
@@ -311,12 +305,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_g4_scan(const int* __restrict__ 
   }
   part[t] = sum;
   __syncthreads();
-  for (int o = 1; o < SC_THREADS; o <<= 1) {  // inclusive scan of the threads' sums
-    const unsigned long long add = t >= o ? part[t - o] : 0ull;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
+  block_inclusive_scan_u64<SC_THREADS>(part, t);  // of the threads' sums
   bad = __syncthreads_or(bad);
   unsigned long long at = part[t] - sum;
   unsigned long long* off = rowoff + g.first_row + p;
@@ -350,11 +339,7 @@ __global__ __launch_bounds__(CC_THREADS) void k_g4_concat(const int* __restrict_
     unsigned acc = 0;
     int filled = 0;
     if (bit < total) {
-      int r = 0, hi = g.h - 1;  // the last row whose first bit is at or before `bit` (a row has at least one bit)
-      while (r < hi) {
-        const int mid = (r + hi + 1) >> 1;
-        if (off[mid] <= bit) r = mid; else hi = mid - 1;
-      }
+      int r = last_piece_at_or_before(off, g.h, bit);  // a row is a piece
       int s = (int)(bit - off[r]);
       while (filled < 32 && r < g.h) {
         const int nb = (int)(off[r + 1] - off[r]), take = min(32 - filled, nb - s);
@@ -382,40 +367,35 @@ static G4Limits g4_limits(int64_t total_rows, int64_t packed_bytes, int64_t slot
   return G4Limits{total_rows, packed_bytes / 4, slot_bytes / 4, out_bytes};
 }
 static void g4_check_table(const int* blob_dev, int64_t blob_words, int n_pages) {
-  YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n_pages * G4_REC, "page table: n records");
+  check_page_table(blob_dev, blob_words, n_pages, G4_REC, 3, 4096, "0..4096 pages", "page table: n records");
 }
-static void g4_aligned(const void* p, const char* what) { YMK_CHECK(p && ((uintptr_t)p & 7) == 0, what); }
 
 static void launch_g4_rows(hipStream_t s, const int* blob, int n_pages, const G4Limits& lim, int max_rows, const uint32_t* packed,
                            uint32_t* slots, uint32_t* rowbits) {
   YMK_CHECK(max_rows >= 1 && max_rows <= G4_MAX_SIDE, "max_rows: the largest page's rows");
-  g4_aligned(packed, "packed rows: 8-byte aligned");
-  g4_aligned(slots, "slots: 8-byte aligned");
-  g4_aligned(rowbits, "row bit counts: 8-byte aligned");
+  check_aligned8(packed, "packed rows: 8-byte aligned");
+  check_aligned8(slots, "slots: 8-byte aligned");
+  check_aligned8(rowbits, "row bit counts: 8-byte aligned");
   hipLaunchKernelGGL(k_g4_rows, dim3((unsigned)((max_rows + RC_ROWS - 1) / RC_ROWS), (unsigned)n_pages), dim3(RC_THREADS), 0, s, blob, lim, packed,
                      slots, rowbits);
   YMK_HIP(hipGetLastError());
 }
 static void launch_g4_scan(hipStream_t s, const int* blob, int n_pages, const G4Limits& lim, const uint32_t* rowbits, uint64_t* rowoff,
                            int* lengths) {
-  g4_aligned(rowbits, "row bit counts: 8-byte aligned");
-  g4_aligned(rowoff, "row offsets: 8-byte aligned");
+  check_aligned8(rowbits, "row bit counts: 8-byte aligned");
+  check_aligned8(rowoff, "row offsets: 8-byte aligned");
   YMK_CHECK(lengths && ((uintptr_t)lengths & 3) == 0, "null or misaligned lengths");
   hipLaunchKernelGGL(k_g4_scan, dim3((unsigned)n_pages), dim3(SC_THREADS), 0, s, blob, lim, rowbits, (unsigned long long*)rowoff, lengths);
   YMK_HIP(hipGetLastError());
 }
 static void launch_g4_concat(hipStream_t s, const int* blob, int n_pages, const G4Limits& lim, const uint32_t* slots, const uint64_t* rowoff,
                              const int* lengths, unsigned char* out, int64_t max_capacity) {
-  g4_aligned(slots, "slots: 8-byte aligned");
-  g4_aligned(rowoff, "row offsets: 8-byte aligned");
+  check_aligned8(slots, "slots: 8-byte aligned");
+  check_aligned8(rowoff, "row offsets: 8-byte aligned");
   YMK_CHECK(out && ((uintptr_t)out & 15) == 0 && lengths, "output: 16-byte aligned");
   YMK_CHECK(max_capacity >= 0 && max_capacity <= 0x7fffffffLL, "bad capacity");
-  // four words per thread where the largest file has that many; 1024 blocks per page at the most (the loop strides the rest)
-  const int64_t per_block = (int64_t)CC_THREADS * 4 * 4;
-  const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_capacity + per_block - 1) / per_block, 1), 1024);
-  hipLaunchKernelGGL(k_g4_concat, dim3(gx, (unsigned)n_pages), dim3(CC_THREADS), 0, s, blob, lim, slots, (const unsigned long long*)rowoff,
-                     lengths, out);
+  hipLaunchKernelGGL(k_g4_concat, dim3(file_word_grid(max_capacity, CC_THREADS), (unsigned)n_pages), dim3(CC_THREADS), 0, s, blob, lim, slots,
+                     (const unsigned long long*)rowoff, lengths, out);
   YMK_HIP(hipGetLastError());
 }
 
@@ -433,109 +413,85 @@ int64_t ymk_g4_file_capacity(int h, int w) {
 }
 
 int ymk_g4_scratch_bytes(const int* h, const int* w, int n_pages, int64_t* sizes5_out) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes5_out && (n_pages == 0 || (h && w)), "bad argument");
-    int64_t rows = 0, packed = 0, slots = 0;
-    for (int k = 0; k < n_pages; ++k) {
-      YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::G4_MAX_SIDE && w[k] <= ymk::G4_MAX_SIDE, "a page has 1..16383 pixels on a side");
-      rows += h[k];
-      packed += (int64_t)h[k] * ((w[k] + 31) >> 5);
-      slots += (int64_t)h[k] * ymk::g4_slot_words(w[k]);
-    }
-    sizes5_out[0] = rows;
-    sizes5_out[1] = ((packed + 1) & ~1LL) * 4;
-    sizes5_out[2] = ((slots + 1) & ~1LL) * 4;
-    sizes5_out[3] = ((rows + 1) & ~1LL) * 4;
-    sizes5_out[4] = (rows + n_pages) * 8;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes5_out && (n_pages == 0 || (h && w)), "bad argument");
+  int64_t rows = 0, packed = 0, slots = 0;
+  for (int k = 0; k < n_pages; ++k) {
+    YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::G4_MAX_SIDE && w[k] <= ymk::G4_MAX_SIDE, "a page has 1..16383 pixels on a side");
+    rows += h[k];
+    packed += (int64_t)h[k] * ((w[k] + 31) >> 5);
+    slots += (int64_t)h[k] * ymk::g4_slot_words(w[k]);
   }
+  sizes5_out[0] = rows;
+  sizes5_out[1] = ((packed + 1) & ~1LL) * 4;
+  sizes5_out[2] = ((slots + 1) & ~1LL) * 4;
+  sizes5_out[3] = ((rows + 1) & ~1LL) * 4;
+  sizes5_out[4] = (rows + n_pages) * 8;
+  YMK_API_END
 }
 
 int ymk_g4_test_pack(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* flags_dev, uint32_t* packed_dev,
                      int64_t packed_bytes, void* stream) {
-  try {
-    YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::g4_check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(flags_dev && ((uintptr_t)flags_dev & 3) == 0, "null or misaligned flags");
-    ymk::g4_aligned(packed_dev, "packed rows: 8-byte aligned");
-    const ymk::G4Limits lim = ymk::g4_limits(0, packed_bytes, 0, 0);
-    const hipStream_t s = (hipStream_t)stream;
-    YMK_HIP(hipMemsetAsync(flags_dev, 0, (size_t)n_pages * sizeof(int), s));
-    // 64 pixels per wave and step, sixteen steps per wave where the largest page has that many; 512 blocks per page at the most
-    const int64_t per_block = (int64_t)ymk::TP_THREADS * 16;
-    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_pixels + per_block - 1) / per_block, 1), 512);
-    hipLaunchKernelGGL(ymk::k_g4_test_pack, dim3(gx, (unsigned)n_pages), dim3(ymk::TP_THREADS), 0, s, blob_dev, lim, flags_dev, packed_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::g4_check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(flags_dev && ((uintptr_t)flags_dev & 3) == 0, "null or misaligned flags");
+  ymk::check_aligned8(packed_dev, "packed rows: 8-byte aligned");
+  const ymk::G4Limits lim = ymk::g4_limits(0, packed_bytes, 0, 0);
+  const hipStream_t s = (hipStream_t)stream;
+  YMK_HIP(hipMemsetAsync(flags_dev, 0, (size_t)n_pages * sizeof(int), s));
+  // 64 pixels per wave and step, sixteen steps per wave where the largest page has that many; 512 blocks per page at the most
+  const int64_t per_block = (int64_t)ymk::TP_THREADS * 16;
+  const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_pixels + per_block - 1) / per_block, 1), 512);
+  hipLaunchKernelGGL(ymk::k_g4_test_pack, dim3(gx, (unsigned)n_pages), dim3(ymk::TP_THREADS), 0, s, blob_dev, lim, flags_dev, packed_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_g4_code_rows(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int max_rows, const uint32_t* packed_dev,
                      int64_t packed_bytes, uint32_t* slots_dev, int64_t slot_bytes, int64_t out_bytes, uint32_t* rowbits_dev, void* stream) {
-  try {
-    if (n_pages == 0 || total_rows == 0) return 0;
-    ymk::g4_check_table(blob_dev, blob_words, n_pages);
-    const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
-    ymk::launch_g4_rows((hipStream_t)stream, blob_dev, n_pages, lim, max_rows, packed_dev, slots_dev, rowbits_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0 || total_rows == 0) return 0;
+  ymk::g4_check_table(blob_dev, blob_words, n_pages);
+  const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
+  ymk::launch_g4_rows((hipStream_t)stream, blob_dev, n_pages, lim, max_rows, packed_dev, slots_dev, rowbits_dev);
+  YMK_API_END
 }
 
 int ymk_g4_scan(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int64_t packed_bytes, int64_t slot_bytes,
                 int64_t out_bytes, const uint32_t* rowbits_dev, uint64_t* rowoff_dev, int* lengths_dev, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    ymk::g4_check_table(blob_dev, blob_words, n_pages);
-    const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
-    ymk::launch_g4_scan((hipStream_t)stream, blob_dev, n_pages, lim, rowbits_dev, rowoff_dev, lengths_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  ymk::g4_check_table(blob_dev, blob_words, n_pages);
+  const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
+  ymk::launch_g4_scan((hipStream_t)stream, blob_dev, n_pages, lim, rowbits_dev, rowoff_dev, lengths_dev);
+  YMK_API_END
 }
 
 int ymk_g4_concat(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int64_t packed_bytes, const uint32_t* slots_dev,
                   int64_t slot_bytes, const uint64_t* rowoff_dev, const int* lengths_dev, unsigned char* out_dev, int64_t out_bytes,
                   int64_t max_capacity, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    ymk::g4_check_table(blob_dev, blob_words, n_pages);
-    const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
-    ymk::launch_g4_concat((hipStream_t)stream, blob_dev, n_pages, lim, slots_dev, rowoff_dev, lengths_dev, out_dev, max_capacity);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  ymk::g4_check_table(blob_dev, blob_words, n_pages);
+  const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
+  ymk::launch_g4_concat((hipStream_t)stream, blob_dev, n_pages, lim, slots_dev, rowoff_dev, lengths_dev, out_dev, max_capacity);
+  YMK_API_END
 }
 
 int ymk_g4_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_rows, int max_rows, const uint32_t* packed_dev,
                         int64_t packed_bytes, uint32_t* slots_dev, int64_t slot_bytes, uint32_t* rowbits_dev, uint64_t* rowoff_dev,
                         unsigned char* out_dev, int64_t out_bytes, int64_t max_capacity, int* lengths_dev, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    ymk::g4_check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(total_rows > 0, "pages without rows");
-    const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
-    const hipStream_t s = (hipStream_t)stream;
-    ymk::launch_g4_rows(s, blob_dev, n_pages, lim, max_rows, packed_dev, slots_dev, rowbits_dev);
-    ymk::launch_g4_scan(s, blob_dev, n_pages, lim, rowbits_dev, rowoff_dev, lengths_dev);
-    ymk::launch_g4_concat(s, blob_dev, n_pages, lim, slots_dev, rowoff_dev, lengths_dev, out_dev, max_capacity);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  ymk::g4_check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(total_rows > 0, "pages without rows");
+  const ymk::G4Limits lim = ymk::g4_limits(total_rows, packed_bytes, slot_bytes, out_bytes);
+  const hipStream_t s = (hipStream_t)stream;
+  ymk::launch_g4_rows(s, blob_dev, n_pages, lim, max_rows, packed_dev, slots_dev, rowbits_dev);
+  ymk::launch_g4_scan(s, blob_dev, n_pages, lim, rowbits_dev, rowoff_dev, lengths_dev);
+  ymk::launch_g4_concat(s, blob_dev, n_pages, lim, slots_dev, rowoff_dev, lengths_dev, out_dev, max_capacity);
+  YMK_API_END
 }
 }

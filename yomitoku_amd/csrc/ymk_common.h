@@ -40,6 +40,26 @@ struct Error : public std::runtime_error {
     if (!(cond)) throw ::ymk::Error(std::string("check failed: ") + #cond + ": " + (msg)); \
   } while (0)
 
+// The guard of every extern "C" entry: no exception leaves the library.  The body stands between YMK_API_BEGIN and one of
+//   YMK_API_END           an entry that answers 0 / non-zero: falls off the end of its body as 0 (an early `return 0;` inside the
+//                         body means the same), 1 with the message in ymk_last_error, 2 for an exception that is no std::exception;
+//   YMK_API_END_OR(fail)  an entry whose body returns its own value (a size, a handle): `fail` for either kind of exception.
+#define YMK_API_BEGIN try {
+#define YMK_API_CATCH(fail_std, fail_other)         \
+  }                                                 \
+  catch (const std::exception& e) {                 \
+    ymk::set_error(e.what());                       \
+    return fail_std;                                \
+  }                                                 \
+  catch (...) {                                     \
+    ymk::set_error("unknown C++ exception");        \
+    return fail_other;                              \
+  }
+#define YMK_API_END \
+  return 0;         \
+  YMK_API_CATCH(1, 2)
+#define YMK_API_END_OR(fail) YMK_API_CATCH(fail, fail)
+
 // ---------------------------------------------------------------- device allocations and the forwards
 // Contract since round 6: a forward (ymk_*_forward) neither allocates nor frees device / pinned memory, builds no weight copy
 // and waits for no stream when the caller sized the workspace first (ymk_model_reserve) - everything a forward needs beyond

@@ -138,18 +138,14 @@ extern "C" {
 int ymk_crop_u8_record_words(void) { return ymk::CR_REC; }
 
 int ymk_crop_u8(const int* blob_dev, int64_t blob_words, int n, int64_t total_chunks, void* stream) {
-  try {
-    YMK_CHECK(n >= 0 && n <= 65535 && blob_words >= 0 && total_chunks >= 0, "bad argument");
-    YMK_CHECK(total_chunks <= 0x7fffffffLL * ymk::CR_THREADS, "at most (2^31 - 1) * 256 chunks per launch");
-    if (n == 0 || total_chunks == 0) return 0;
-    YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n * ymk::CR_REC, "record table");
-    const unsigned grid = (unsigned)((total_chunks + ymk::CR_THREADS - 1) / ymk::CR_THREADS);
-    hipLaunchKernelGGL(ymk::k_crop_u8, dim3(grid), dim3(ymk::CR_THREADS), 0, (hipStream_t)stream, blob_dev, n, (long long)total_chunks);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(n >= 0 && n <= 65535 && blob_words >= 0 && total_chunks >= 0, "bad argument");
+  YMK_CHECK(total_chunks <= 0x7fffffffLL * ymk::CR_THREADS, "at most (2^31 - 1) * 256 chunks per launch");
+  if (n == 0 || total_chunks == 0) return 0;
+  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n * ymk::CR_REC, "record table");
+  const unsigned grid = (unsigned)((total_chunks + ymk::CR_THREADS - 1) / ymk::CR_THREADS);
+  hipLaunchKernelGGL(ymk::k_crop_u8, dim3(grid), dim3(ymk::CR_THREADS), 0, (hipStream_t)stream, blob_dev, n, (long long)total_chunks);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 }

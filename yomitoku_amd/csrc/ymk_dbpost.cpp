@@ -376,14 +376,10 @@ int db_postprocess(const float* pred, int h, int w, float thresh, float box_thre
 extern "C" int ymk_db_postprocess(const float* prob_host, int h, int w, float thresh, float box_thresh, int min_size,
                                   int max_candidates, float unclip_ratio, int dest_w, int dest_h, int16_t* quads_out,
                                   double* scores_out, int capacity, int* count) {
-  try {
-    YMK_CHECK(prob_host && quads_out && scores_out && count, "null argument");
-    const int n = ymk::db_postprocess(prob_host, h, w, thresh, box_thresh, min_size, max_candidates, unclip_ratio, dest_w,
-                                      dest_h, quads_out, scores_out, capacity);
-    *count = n;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(prob_host && quads_out && scores_out && count, "null argument");
+  const int n = ymk::db_postprocess(prob_host, h, w, thresh, box_thresh, min_size, max_candidates, unclip_ratio, dest_w,
+                                    dest_h, quads_out, scores_out, capacity);
+  *count = n;
+  YMK_API_END
 }

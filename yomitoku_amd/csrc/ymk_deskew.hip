@@ -24,9 +24,7 @@
 // degrees) up to 9500 x 9500.  A larger page scores 0 everywhere, k = 0, flag 0: it is copied, not failed.
 // No overflow: |y c|, |x s| <= 16382 * 2^14 < 2^28 and m << 14 <= 2^28: below 2^30.  The rotation: see k_dsk_rotate.
 
-#include "ymk_common.h"
-
-#include <algorithm>
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -50,10 +48,6 @@ __host__ __device__ __forceinline__ bool dk_fits(int h, int w, int s_max) {
   return h + 2 * dk_margin(w, s_max) <= DK_BINS && w + 2 * dk_margin(h, s_max) <= DK_BINS;
 }
 
-__device__ __forceinline__ long long dk_word64(const int* r, int k) {
-  return (long long)(((unsigned long long)(unsigned)r[k + 1] << 32) | (unsigned long long)(unsigned)r[k]);
-}
-
 // A page's record, read and checked against the buffers' sizes as bz_page of ymk_binarize.hip does: a kernel takes a page whose
 // record fails the check for what it touches as absent.
 struct DkPage {
@@ -66,10 +60,10 @@ struct DkPage {
 __device__ __forceinline__ DkPage dk_page(const int* blob, int p, const DkLimits& lim) {
   const int* r = blob + (size_t)p * DK_REC;
   DkPage g;
-  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)dk_word64(r, 0));
-  g.dst = reinterpret_cast<unsigned char*>((unsigned long long)dk_word64(r, 11));
+  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
+  g.dst = reinterpret_cast<unsigned char*>((unsigned long long)page_word64(r, 11));
   g.h = r[2], g.w = r[3], g.ch = r[4];
-  g.packed_at = dk_word64(r, 6), g.luma_at = dk_word64(r, 8), g.sat_at = dk_word64(r, 14);
+  g.packed_at = page_word64(r, 6), g.luma_at = page_word64(r, 8), g.sat_at = page_word64(r, 14);
   g.ok = g.h >= 1 && g.w >= 1 && g.h <= DK_MAX_SIDE && g.w <= DK_MAX_SIDE && g.src != nullptr && (g.ch == 1 || g.ch == 3);
   g.row_words = g.ok ? (g.w + 31) >> 5 : 0;
   // the plane: the page itself, or h w bytes of luma_dev at a multiple of 4
@@ -284,14 +278,12 @@ __global__ __launch_bounds__(RT_THREADS) void k_dsk_rotate(const int* __restrict
 
 // ------------------------------------------------------------------------------------------------ host
 static void dk_check_table(const int* blob_dev, int64_t blob_words, int n_pages) {
-  YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n_pages * DK_REC, "page table: n records");
+  check_page_table(blob_dev, blob_words, n_pages, DK_REC, 3, 4096, "0..4096 pages", "page table: n records");
 }
 static void dk_check_angles(int n_angles, int s_max) {
   YMK_CHECK(n_angles >= 1 && n_angles <= DK_MAX_ANGLES && (n_angles & 1) == 1, "1..401 angles, an odd number");
   YMK_CHECK(s_max >= 0 && s_max < DK_ONE, "s_max in 0 .. 2^14 - 1");
 }
-static void dk_aligned(const void* p, const char* what) { YMK_CHECK(p && ((uintptr_t)p & 7) == 0, what); }
 static DkLimits dk_limits(int64_t packed_bytes, int64_t sat_bytes, int64_t luma_bytes) {
   YMK_CHECK(packed_bytes >= 0 && sat_bytes >= 0 && luma_bytes >= 0, "negative size");
   return DkLimits{packed_bytes / 4, sat_bytes / 4, luma_bytes};
@@ -309,136 +301,112 @@ extern "C" {
 int ymk_dsk_page_words(void) { return ymk::DK_REC; }
 
 int ymk_dsk_check_angles(const int* table_host, int n_angles, int* s_max_out) {
-  try {
-    YMK_CHECK(table_host && s_max_out, "bad argument");
-    YMK_CHECK(n_angles >= 1 && n_angles <= ymk::DK_MAX_ANGLES && (n_angles & 1) == 1, "1..401 angles, an odd number");
-    const int K = n_angles / 2;
-    int s_max = 0;
-    for (int a = 0; a < n_angles; ++a) {
-      const int s = table_host[2 * a], c = table_host[2 * a + 1], sm = table_host[2 * (n_angles - 1 - a)], cm = table_host[2 * (n_angles - 1 - a) + 1];
-      YMK_CHECK(c > 0 && c <= ymk::DK_ONE && s > -ymk::DK_ONE && s < ymk::DK_ONE, "an angle of the table: 0 < c <= 2^14, |s| < 2^14");
-      YMK_CHECK(s == -sm && c == cm, "the table is symmetric about its middle");
-      const long long norm = (long long)s * s + (long long)c * c, one = (long long)ymk::DK_ONE * ymk::DK_ONE;
-      YMK_CHECK(norm >= one - 4 * ymk::DK_ONE && norm <= one + 4 * ymk::DK_ONE, "s^2 + c^2 = 2^28 to rounding");
-      s_max = std::max(s_max, s < 0 ? -s : s);
-    }
-    YMK_CHECK(table_host[2 * K] == 0 && table_host[2 * K + 1] == ymk::DK_ONE, "the middle angle is 0");
-    *s_max_out = s_max;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(table_host && s_max_out, "bad argument");
+  YMK_CHECK(n_angles >= 1 && n_angles <= ymk::DK_MAX_ANGLES && (n_angles & 1) == 1, "1..401 angles, an odd number");
+  const int K = n_angles / 2;
+  int s_max = 0;
+  for (int a = 0; a < n_angles; ++a) {
+    const int s = table_host[2 * a], c = table_host[2 * a + 1], sm = table_host[2 * (n_angles - 1 - a)], cm = table_host[2 * (n_angles - 1 - a) + 1];
+    YMK_CHECK(c > 0 && c <= ymk::DK_ONE && s > -ymk::DK_ONE && s < ymk::DK_ONE, "an angle of the table: 0 < c <= 2^14, |s| < 2^14");
+    YMK_CHECK(s == -sm && c == cm, "the table is symmetric about its middle");
+    const long long norm = (long long)s * s + (long long)c * c, one = (long long)ymk::DK_ONE * ymk::DK_ONE;
+    YMK_CHECK(norm >= one - 4 * ymk::DK_ONE && norm <= one + 4 * ymk::DK_ONE, "s^2 + c^2 = 2^28 to rounding");
+    s_max = std::max(s_max, s < 0 ? -s : s);
   }
+  YMK_CHECK(table_host[2 * K] == 0 && table_host[2 * K + 1] == ymk::DK_ONE, "the middle angle is 0");
+  *s_max_out = s_max;
+  YMK_API_END
 }
 
 int ymk_dsk_scratch_bytes(const int* h, const int* w, const int* ch, int n_pages, int n_angles, int s_max, int64_t* sizes5_out, int* fits_out) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes5_out && (n_pages == 0 || (h && w && ch)), "bad argument");
-    ymk::dk_check_angles(n_angles, s_max);
-    int64_t luma = 0, cells = 0, words = 0;
-    for (int k = 0; k < n_pages; ++k) {
-      YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::DK_MAX_SIDE && w[k] <= ymk::DK_MAX_SIDE, "a page has 1..16383 pixels on a side");
-      YMK_CHECK(ch[k] == 1 || ch[k] == 3, "a page has one or three channels");
-      const int64_t px = (int64_t)h[k] * w[k];
-      if (ch[k] == 3) luma += (px + 15) & ~15LL;
-      cells += px;
-      words += (int64_t)h[k] * ((w[k] + 31) >> 5);
-      if (fits_out) fits_out[k] = ymk::dk_fits(h[k], w[k], s_max) ? 1 : 0;
-    }
-    sizes5_out[0] = luma;
-    sizes5_out[1] = ((cells + 1) & ~1LL) * 4;
-    sizes5_out[2] = ((words + 1) & ~1LL) * 4;
-    sizes5_out[3] = (int64_t)n_pages * n_angles * 8;
-    sizes5_out[4] = (int64_t)n_pages * ymk::DK_CHOICE * 4;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes5_out && (n_pages == 0 || (h && w && ch)), "bad argument");
+  ymk::dk_check_angles(n_angles, s_max);
+  int64_t luma = 0, cells = 0, words = 0;
+  for (int k = 0; k < n_pages; ++k) {
+    YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::DK_MAX_SIDE && w[k] <= ymk::DK_MAX_SIDE, "a page has 1..16383 pixels on a side");
+    YMK_CHECK(ch[k] == 1 || ch[k] == 3, "a page has one or three channels");
+    const int64_t px = (int64_t)h[k] * w[k];
+    if (ch[k] == 3) luma += (px + 15) & ~15LL;
+    cells += px;
+    words += (int64_t)h[k] * ((w[k] + 31) >> 5);
+    if (fits_out) fits_out[k] = ymk::dk_fits(h[k], w[k], s_max) ? 1 : 0;
   }
+  sizes5_out[0] = luma;
+  sizes5_out[1] = ((cells + 1) & ~1LL) * 4;
+  sizes5_out[2] = ((words + 1) & ~1LL) * 4;
+  sizes5_out[3] = (int64_t)n_pages * n_angles * 8;
+  sizes5_out[4] = (int64_t)n_pages * ymk::DK_CHOICE * 4;
+  YMK_API_END
 }
 
 int ymk_dsk_luma(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, unsigned char* luma_dev, int64_t luma_bytes,
                  int64_t packed_bytes, int64_t sat_bytes, int* planes_dev, void* stream) {
-  try {
-    YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::dk_check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(luma_bytes == 0 || (luma_dev && ((uintptr_t)luma_dev & 7) == 0), "planes: 8-byte aligned");
-    YMK_CHECK(planes_dev && ((uintptr_t)planes_dev & 3) == 0, "null or misaligned table of the planes");
-    const ymk::DkLimits lim = ymk::dk_limits(packed_bytes, sat_bytes, luma_bytes);
-    const hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ymk::k_dsk_luma, dim3(ymk::dk_byte_blocks(max_pixels, ymk::LM_THREADS), (unsigned)n_pages), dim3(ymk::LM_THREADS), 0, s,
-                       blob_dev, lim, luma_dev);
-    YMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ymk::k_dsk_planes, dim3((unsigned)((n_pages + 63) / 64)), dim3(64), 0, s, blob_dev, lim, n_pages,
-                       (const unsigned char*)luma_dev, planes_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::dk_check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(luma_bytes == 0 || (luma_dev && ((uintptr_t)luma_dev & 7) == 0), "planes: 8-byte aligned");
+  YMK_CHECK(planes_dev && ((uintptr_t)planes_dev & 3) == 0, "null or misaligned table of the planes");
+  const ymk::DkLimits lim = ymk::dk_limits(packed_bytes, sat_bytes, luma_bytes);
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ymk::k_dsk_luma, dim3(ymk::dk_byte_blocks(max_pixels, ymk::LM_THREADS), (unsigned)n_pages), dim3(ymk::LM_THREADS), 0, s,
+                     blob_dev, lim, luma_dev);
+  YMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ymk::k_dsk_planes, dim3((unsigned)((n_pages + 63) / 64)), dim3(64), 0, s, blob_dev, lim, n_pages,
+                     (const unsigned char*)luma_dev, planes_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_dsk_scores(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* packed_dev, int64_t packed_bytes, int64_t sat_bytes,
                    int64_t luma_bytes, const int* table_dev, int n_angles, int s_max, uint64_t* scores_dev, void* stream) {
-  try {
-    ymk::dk_check_angles(n_angles, s_max);
-    if (n_pages == 0) return 0;
-    ymk::dk_check_table(blob_dev, blob_words, n_pages);
-    ymk::dk_aligned(packed_dev, "packed rows: 8-byte aligned");
-    ymk::dk_aligned(scores_dev, "scores: 8-byte aligned");
-    YMK_CHECK(table_dev && ((uintptr_t)table_dev & 3) == 0, "null or misaligned angle table");
-    const ymk::DkLimits lim = ymk::dk_limits(packed_bytes, sat_bytes, luma_bytes);
-    const hipStream_t s = (hipStream_t)stream;
-    YMK_HIP(hipMemsetAsync(scores_dev, 0, (size_t)n_pages * n_angles * sizeof(uint64_t), s));
-    hipLaunchKernelGGL(ymk::k_dsk_scores, dim3(2u * (unsigned)n_angles, (unsigned)n_pages), dim3(ymk::SC_THREADS), 0, s, blob_dev, lim,
-                       (const unsigned*)packed_dev, table_dev, n_angles, s_max, (unsigned long long*)scores_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  ymk::dk_check_angles(n_angles, s_max);
+  if (n_pages == 0) return 0;
+  ymk::dk_check_table(blob_dev, blob_words, n_pages);
+  ymk::check_aligned8(packed_dev, "packed rows: 8-byte aligned");
+  ymk::check_aligned8(scores_dev, "scores: 8-byte aligned");
+  YMK_CHECK(table_dev && ((uintptr_t)table_dev & 3) == 0, "null or misaligned angle table");
+  const ymk::DkLimits lim = ymk::dk_limits(packed_bytes, sat_bytes, luma_bytes);
+  const hipStream_t s = (hipStream_t)stream;
+  YMK_HIP(hipMemsetAsync(scores_dev, 0, (size_t)n_pages * n_angles * sizeof(uint64_t), s));
+  hipLaunchKernelGGL(ymk::k_dsk_scores, dim3(2u * (unsigned)n_angles, (unsigned)n_pages), dim3(ymk::SC_THREADS), 0, s, blob_dev, lim,
+                     (const unsigned*)packed_dev, table_dev, n_angles, s_max, (unsigned long long*)scores_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_dsk_choose(const int* blob_dev, int64_t blob_words, int n_pages, int64_t packed_bytes, int64_t sat_bytes, int64_t luma_bytes,
                    const uint64_t* scores_dev, int n_angles, int s_max, int dead, int* choice_dev, void* stream) {
-  try {
-    ymk::dk_check_angles(n_angles, s_max);
-    YMK_CHECK(dead >= 0, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::dk_check_table(blob_dev, blob_words, n_pages);
-    ymk::dk_aligned(scores_dev, "scores: 8-byte aligned");
-    ymk::dk_aligned(choice_dev, "choice words: 8-byte aligned");
-    const ymk::DkLimits lim = ymk::dk_limits(packed_bytes, sat_bytes, luma_bytes);
-    hipLaunchKernelGGL(ymk::k_dsk_choose, dim3((unsigned)n_pages), dim3(64), 0, (hipStream_t)stream, blob_dev, lim,
-                       (const unsigned long long*)scores_dev, n_angles, s_max, dead, choice_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  ymk::dk_check_angles(n_angles, s_max);
+  YMK_CHECK(dead >= 0, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::dk_check_table(blob_dev, blob_words, n_pages);
+  ymk::check_aligned8(scores_dev, "scores: 8-byte aligned");
+  ymk::check_aligned8(choice_dev, "choice words: 8-byte aligned");
+  const ymk::DkLimits lim = ymk::dk_limits(packed_bytes, sat_bytes, luma_bytes);
+  hipLaunchKernelGGL(ymk::k_dsk_choose, dim3((unsigned)n_pages), dim3(64), 0, (hipStream_t)stream, blob_dev, lim,
+                     (const unsigned long long*)scores_dev, n_angles, s_max, dead, choice_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_dsk_rotate(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_bytes, const int* table_dev, int n_angles,
                    const int* choice_dev, void* stream) {
-  try {
-    ymk::dk_check_angles(n_angles, 0);
-    YMK_CHECK(max_bytes >= 0 && max_bytes <= 3LL * 16383LL * 16383LL, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::dk_check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(table_dev && ((uintptr_t)table_dev & 3) == 0, "null or misaligned angle table");
-    YMK_CHECK(choice_dev && ((uintptr_t)choice_dev & 3) == 0, "null or misaligned choice words");
-    hipLaunchKernelGGL(ymk::k_dsk_rotate, dim3(ymk::dk_byte_blocks(max_bytes, ymk::RT_THREADS), (unsigned)n_pages), dim3(ymk::RT_THREADS), 0,
-                       (hipStream_t)stream, blob_dev, table_dev, n_angles, choice_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  ymk::dk_check_angles(n_angles, 0);
+  YMK_CHECK(max_bytes >= 0 && max_bytes <= 3LL * 16383LL * 16383LL, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::dk_check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(table_dev && ((uintptr_t)table_dev & 3) == 0, "null or misaligned angle table");
+  YMK_CHECK(choice_dev && ((uintptr_t)choice_dev & 3) == 0, "null or misaligned choice words");
+  hipLaunchKernelGGL(ymk::k_dsk_rotate, dim3(ymk::dk_byte_blocks(max_bytes, ymk::RT_THREADS), (unsigned)n_pages), dim3(ymk::RT_THREADS), 0,
+                     (hipStream_t)stream, blob_dev, table_dev, n_angles, choice_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_dsk_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, unsigned char* luma_dev, int64_t luma_bytes,

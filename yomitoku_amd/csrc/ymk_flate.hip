@@ -9,8 +9,9 @@
 //                all lanes, the segment's symbol counts from LDS into the page's histogram with integer atomics.  Measured on a
 //                wave of 16 pages of 1600 x 1200 x 3 (19 200 segments of 4801 bytes): 3.1 ms on document pages, 11.3 ms on
 //                textured pages where nearly every byte is a literal - the walk's chain of dependent LDS reads is the step.
-//   k_fl_tables  one wave per page: the three length sets (libjpeg's merge rule across the lanes, Figure K.3's limiter), the
-//                canonical codes, the header's bits, the file's exact size, the page's Adler-32 folded from the segments' sums.
+//   k_fl_tables  one wave per page: the three length sets (the shared construction of ymk_pages.h: libjpeg's merge rule across the
+//                lanes, Figure K.3's limiter - the JPEG encoder's optimised tables come from the same code), the canonical codes,
+//                the header's bits, the file's exact size, the page's Adler-32 folded from the segments' sums.
 //   k_fl_code    one wave per segment: its tokens under the page's tables, LSB first, into LDS (a lane a chunk of tokens, the
 //                chunks' bit offsets by a scan of the lanes) and from there into the segment's slot; its bit count.
 //   k_fl_scan    one block per page: the segments' bit counts -> every piece's bit offset in the file; a page whose counts do
@@ -29,9 +30,7 @@
 // of at most 7 bits with at most 7 extra bits: 4498.  With 78 9C, the pad and the checksum: 2 + ceil((4498 + 15 N + 15) / 8) + 4
 // bytes for N = h (1 + w c) filtered bytes.
 
-#include "ymk_common.h"
-
-#include <algorithm>
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -58,10 +57,6 @@ struct FlLimits {
   int n_index;
 };
 
-__device__ __forceinline__ long long fl_word64(const int* r, int k) {
-  return (long long)(((unsigned long long)(unsigned)r[k + 1] << 32) | (unsigned long long)(unsigned)r[k]);
-}
-
 // A page's record, read and checked against the buffers' sizes with the channels it ARRIVED with (the most it can take): a page
 // whose record fails is absent for every kernel.  ch: the channels it is coded with - 1 for a three-channel page the grey test
 // found grey.
@@ -75,9 +70,9 @@ struct FlPage {
 __device__ __forceinline__ FlPage fl_page(const int* blob, int p, const FlLimits& lim) {
   const int* r = blob + (size_t)p * FL_REC;
   FlPage g;
-  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)fl_word64(r, 0));
+  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
   g.h = r[2], g.w = r[3], g.ch_src = r[4], g.index = r[5];
-  g.filt_at = fl_word64(r, 6), g.seg_at = fl_word64(r, 8), g.slot_at = fl_word64(r, 10), g.out_at = fl_word64(r, 12);
+  g.filt_at = page_word64(r, 6), g.seg_at = page_word64(r, 8), g.slot_at = page_word64(r, 10), g.out_at = page_word64(r, 12);
   g.capacity = r[14], g.grey_at = r[15];
   g.ok = g.h >= 1 && g.w >= 1 && g.h <= FL_MAX_SIDE && g.w <= FL_MAX_SIDE && (g.ch_src == 1 || g.ch_src == 3) && g.src != nullptr &&
          g.index >= 0 && g.index < lim.n_index && g.grey_at >= 0 && g.grey_at <= lim.n_index;
@@ -229,52 +224,20 @@ __global__ __launch_bounds__(64) void k_fl_rows(const int* __restrict__ blob, Fl
 }
 
 // ------------------------------------------------------------------------------------------------ tables
-__device__ __forceinline__ unsigned long long fl_wave_min(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-
 // The code lengths of `n` <= 320 frequencies (LDS) under `limit` <= 15 into out (LDS), by all 64 lanes of the one wave: symbol
-// k * 64 + lane sits in register k.  k_jpeg_optimal_tables' merges; no reserved code point, so the Kraft sum stays 1.
+// k * 64 + lane sits in register k.  The construction is ymk_pages.h's, the one k_jpeg_optimal_tables runs; what is flate's own:
+// no reserved code point, so the Kraft sum stays 1, and a single used symbol gets a code of one bit.
 __device__ void fl_huff(const unsigned* freq_in, int n, int limit, unsigned char* out, int* s_key, int* s_bits, int* s_cum) {
   const int lane = threadIdx.x;
   unsigned freq[5];
-  int len[5], id[5], used = 0;
+  int len[5], used = 0;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const int s = k * 64 + lane;
     freq[k] = s < n ? min(freq_in[s], 0x3fffffffu) : 0u;
-    len[k] = 0, id[k] = s;
     used += __popcll(__ballot(freq[k] != 0));
   }
-  constexpr unsigned long long NONE = ~0ull;
-  for (int merge = 0; merge + 1 < n; ++merge) {
-    unsigned long long k1 = NONE, k2 = NONE;
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-      if (freq[k]) k1 = min(k1, (unsigned long long)freq[k] << 32 | (unsigned)(0xffff - (k * 64 + lane)));
-    k1 = fl_wave_min(k1);
-    const int c1 = 0xffff - (int)(k1 & 0xffff);
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-      if (freq[k] && k * 64 + lane != c1) k2 = min(k2, (unsigned long long)freq[k] << 32 | (unsigned)(0xffff - (k * 64 + lane)));
-    k2 = fl_wave_min(k2);
-    if (k2 == NONE) break;  // the same in every lane
-    const int c2 = 0xffff - (int)(k2 & 0xffff);
-    const unsigned long long sum64 = (k1 >> 32) + (k2 >> 32);
-    const unsigned sum = sum64 > 0xfffffffeull ? 0xfffffffeu : (unsigned)sum64;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const int s = k * 64 + lane;
-      if (s == c1) freq[k] = sum;
-      if (s == c2) freq[k] = 0;
-      if (id[k] == c1 || id[k] == c2) ++len[k], id[k] = c1;
-    }
-  }
+  huff_merge_lengths(freq, len, n - 1, lane);  // a round removes a live symbol
   s_bits[lane] = 0;
   __syncthreads();
   int longest = 0;
@@ -291,16 +254,7 @@ __device__ void fl_huff(const unsigned* freq_in, int n, int limit, unsigned char
   for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
   __syncthreads();
   if (lane == 0) {  // Figure K.3 with `limit`, then the first place of every length
-    for (int i = longest; i > limit; --i)
-      while (s_bits[i] > 0) {
-        int j = i - 2;
-        while (j > 0 && s_bits[j] == 0) --j;
-        if (j == 0) {  // not a tree's counts: not reached with lengths from the merges above
-          s_bits[i] = 0;
-          break;
-        }
-        s_bits[i] -= 2, s_bits[i - 1] += 1, s_bits[j + 1] += 2, s_bits[j] -= 1;
-      }
+    huff_limit_counts(s_bits, longest, limit);
     int at = 0;
     for (int l = 1; l <= limit; ++l) s_cum[l] = at, at += s_bits[l];
     s_cum[limit + 1] = at;
@@ -314,8 +268,7 @@ __device__ void fl_huff(const unsigned* freq_in, int n, int limit, unsigned char
     if (key != 0x7fffffff) {
       int rank = 0;  // the symbol's place by (length before limiting, symbol)
       for (int o = 0; o < n; ++o) rank += s_key[o] < key;
-      l = 1;
-      while (l < limit && rank >= s_cum[l + 1]) ++l;
+      l = huff_length_of_rank(s_cum, rank, limit);
     }
     out[s] = (unsigned char)l;
   }
@@ -506,12 +459,7 @@ __global__ __launch_bounds__(64) void k_fl_code(const int* __restrict__ blob, Fl
       mine += (int)((s_tab[t & 0xff] >> 16) & 15);
     }
   }
-  int incl = mine;  // inclusive scan over the lanes
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(incl, o);
-    if (lane >= o) incl += v;
-  }
+  const int incl = wave_inclusive_scan(mine, lane);
   const int total = __shfl(incl, 63);
   const bool fits = total <= 15 * n;  // always, with lengths of at most 15 bits and tokens of k_fl_rows
   if (fits) {
@@ -565,12 +513,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_fl_scan(const int* __restrict__ 
   }
   part[t] = sum;
   __syncthreads();
-  for (int o = 1; o < FS_THREADS; o <<= 1) {
-    const unsigned long long add = t >= o ? part[t - o] : 0ull;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
+  block_inclusive_scan_u64<FS_THREADS>(part, t);
   const unsigned long long first = mh[2], tail_at = (unsigned long long)mh[6] << 32 | mh[5];
   bad |= first + part[FS_THREADS - 1] != tail_at;
   bad = __syncthreads_or(bad);
@@ -604,11 +547,7 @@ __global__ __launch_bounds__(FG_THREADS) void k_fl_gather(const int* __restrict_
   unsigned char* file = out + g.out_at;
   for (int k = blockIdx.x * FG_THREADS + threadIdx.x; k < words; k += gridDim.x * FG_THREADS) {
     const unsigned long long bit = 32ull * (unsigned)k;
-    int r = 0, hi = pieces - 1;  // the last piece whose first bit is at or before `bit` (a piece has at least one bit)
-    while (r < hi) {
-      const int mid = (r + hi + 1) >> 1;
-      if (mo[mid] <= bit) r = mid; else hi = mid - 1;
-    }
+    int r = last_piece_at_or_before(mo, pieces, bit);
     unsigned acc = 0;
     int filled = 0, s = (int)(bit - mo[r]);
     while (filled < 32 && r < pieces) {
@@ -644,10 +583,8 @@ static FlLimits fl_limits(int n_index, int64_t filt_bytes, int64_t segs, int64_t
   return FlLimits{filt_bytes, segs, slot_bytes / 4, out_bytes, n_index};
 }
 static void fl_check_table(const int* blob_dev, int64_t blob_words, int n_pages, int n_index) {
-  YMK_CHECK(n_pages >= 0 && n_pages <= n_index, "0..n_index pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n_pages * FL_REC, "page table: n records");
+  check_page_table(blob_dev, blob_words, n_pages, FL_REC, 3, n_index, "0..n_index pages", "page table: n records");
 }
-static void fl_aligned(const void* p, const char* what) { YMK_CHECK(p && ((uintptr_t)p & 7) == 0, what); }
 static dim3 fl_segment_grid(int n_pages, int max_rows, int max_row_segments) {
   YMK_CHECK(max_rows >= 1 && max_rows <= FL_MAX_SIDE, "max_rows: the largest page's rows");
   YMK_CHECK(max_row_segments >= 1 && max_row_segments <= fl_row_segments(FL_MAX_SIDE, 3), "max_row_segments: the widest page's");
@@ -656,11 +593,11 @@ static dim3 fl_segment_grid(int n_pages, int max_rows, int max_row_segments) {
 
 static void launch_fl_rows(hipStream_t s, const int* blob, int n_pages, const FlLimits& lim, int max_rows, int max_row_segments, const int* grey,
                            unsigned char* filt, uint16_t* tokens, uint32_t* segtok, uint32_t* segadler, int* hist) {
-  fl_aligned(filt, "filtered bytes: 8-byte aligned");
-  fl_aligned(tokens, "tokens: 8-byte aligned");
-  fl_aligned(segtok, "token counts: 8-byte aligned");
-  fl_aligned(segadler, "checksum parts: 8-byte aligned");
-  fl_aligned(hist, "histograms: 8-byte aligned");
+  check_aligned8(filt, "filtered bytes: 8-byte aligned");
+  check_aligned8(tokens, "tokens: 8-byte aligned");
+  check_aligned8(segtok, "token counts: 8-byte aligned");
+  check_aligned8(segadler, "checksum parts: 8-byte aligned");
+  check_aligned8(hist, "histograms: 8-byte aligned");
   YMK_HIP(hipMemsetAsync(hist, 0, (size_t)lim.n_index * FL_HIST * sizeof(int), s));
   hipLaunchKernelGGL(k_fl_rows, fl_segment_grid(n_pages, max_rows, max_row_segments), dim3(64), 0, s, blob, lim, grey, filt,
                      (unsigned short*)tokens, segtok, segadler, hist);
@@ -668,10 +605,10 @@ static void launch_fl_rows(hipStream_t s, const int* blob, int n_pages, const Fl
 }
 static void launch_fl_tables(hipStream_t s, const int* blob, int n_pages, const FlLimits& lim, const int* grey, const int* hist,
                              const uint32_t* segadler, uint32_t* tables, uint32_t* head, int* sizes) {
-  fl_aligned(hist, "histograms: 8-byte aligned");
-  fl_aligned(segadler, "checksum parts: 8-byte aligned");
-  fl_aligned(tables, "tables: 8-byte aligned");
-  fl_aligned(head, "heads: 8-byte aligned");
+  check_aligned8(hist, "histograms: 8-byte aligned");
+  check_aligned8(segadler, "checksum parts: 8-byte aligned");
+  check_aligned8(tables, "tables: 8-byte aligned");
+  check_aligned8(head, "heads: 8-byte aligned");
   YMK_CHECK(sizes && ((uintptr_t)sizes & 3) == 0, "null or misaligned sizes");
   hipLaunchKernelGGL(k_fl_tables, dim3((unsigned)n_pages), dim3(64), 0, s, blob, lim, grey, hist, segadler, tables, head, sizes);
   YMK_HIP(hipGetLastError());
@@ -679,50 +616,39 @@ static void launch_fl_tables(hipStream_t s, const int* blob, int n_pages, const 
 static void launch_fl_code(hipStream_t s, const int* blob, int n_pages, const FlLimits& lim, int max_rows, int max_row_segments,
                            const uint16_t* tokens, const uint32_t* segtok, const uint32_t* tables, const uint32_t* head, uint32_t* slots,
                            uint32_t* segbits) {
-  fl_aligned(tokens, "tokens: 8-byte aligned");
-  fl_aligned(segtok, "token counts: 8-byte aligned");
-  fl_aligned(tables, "tables: 8-byte aligned");
-  fl_aligned(head, "heads: 8-byte aligned");
-  fl_aligned(slots, "slots: 8-byte aligned");
-  fl_aligned(segbits, "bit counts: 8-byte aligned");
+  check_aligned8(tokens, "tokens: 8-byte aligned");
+  check_aligned8(segtok, "token counts: 8-byte aligned");
+  check_aligned8(tables, "tables: 8-byte aligned");
+  check_aligned8(head, "heads: 8-byte aligned");
+  check_aligned8(slots, "slots: 8-byte aligned");
+  check_aligned8(segbits, "bit counts: 8-byte aligned");
   hipLaunchKernelGGL(k_fl_code, fl_segment_grid(n_pages, max_rows, max_row_segments), dim3(64), 0, s, blob, lim, (const unsigned short*)tokens,
                      segtok, tables, head, slots, segbits);
   YMK_HIP(hipGetLastError());
 }
 static void launch_fl_scan(hipStream_t s, const int* blob, int n_pages, const FlLimits& lim, const uint32_t* segbits, uint32_t* head,
                            uint64_t* off, int* sizes) {
-  fl_aligned(segbits, "bit counts: 8-byte aligned");
-  fl_aligned(head, "heads: 8-byte aligned");
-  fl_aligned(off, "offsets: 8-byte aligned");
+  check_aligned8(segbits, "bit counts: 8-byte aligned");
+  check_aligned8(head, "heads: 8-byte aligned");
+  check_aligned8(off, "offsets: 8-byte aligned");
   YMK_CHECK(sizes && ((uintptr_t)sizes & 3) == 0, "null or misaligned sizes");
   hipLaunchKernelGGL(k_fl_scan, dim3((unsigned)n_pages), dim3(FS_THREADS), 0, s, blob, lim, segbits, head, (unsigned long long*)off, sizes);
   YMK_HIP(hipGetLastError());
 }
 static void launch_fl_gather(hipStream_t s, const int* blob, int n_pages, const FlLimits& lim, const uint32_t* slots, const uint32_t* head,
                              const uint64_t* off, unsigned char* out, int64_t max_capacity) {
-  fl_aligned(slots, "slots: 8-byte aligned");
-  fl_aligned(head, "heads: 8-byte aligned");
-  fl_aligned(off, "offsets: 8-byte aligned");
+  check_aligned8(slots, "slots: 8-byte aligned");
+  check_aligned8(head, "heads: 8-byte aligned");
+  check_aligned8(off, "offsets: 8-byte aligned");
   YMK_CHECK(out && ((uintptr_t)out & 15) == 0, "output: 16-byte aligned");
   YMK_CHECK(max_capacity >= 0 && max_capacity <= 0x7fffffffLL, "bad capacity");
-  const int64_t per_block = (int64_t)FG_THREADS * 4 * 4;
-  const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_capacity + per_block - 1) / per_block, 1), 1024);
-  hipLaunchKernelGGL(k_fl_gather, dim3(gx, (unsigned)n_pages), dim3(FG_THREADS), 0, s, blob, lim, slots, head, (const unsigned long long*)off, out);
+  hipLaunchKernelGGL(k_fl_gather, dim3(file_word_grid(max_capacity, FG_THREADS), (unsigned)n_pages), dim3(FG_THREADS), 0, s, blob, lim, slots, head, (const unsigned long long*)off, out);
   YMK_HIP(hipGetLastError());
 }
 
 }  // namespace ymk
 
 extern "C" {
-
-#define FL_TRY try {
-#define FL_END                        \
-  return 0;                           \
-  }                                   \
-  catch (const std::exception& e) {   \
-    ymk::set_error(e.what());         \
-    return 1;                         \
-  }
 
 int ymk_flate_page_words(void) { return ymk::FL_REC; }
 
@@ -733,7 +659,7 @@ int64_t ymk_flate_file_capacity(int h, int w, int channels) {
 }
 
 int ymk_flate_scratch_bytes(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes8_out) {
-  FL_TRY
+  YMK_API_BEGIN
   YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes8_out && (n_pages == 0 || (h && w && channels)), "bad argument");
   int64_t segs = 0, filt = 0, slots = 0;
   for (int k = 0; k < n_pages; ++k) {
@@ -751,63 +677,63 @@ int ymk_flate_scratch_bytes(const int* h, const int* w, const int* channels, int
   sizes8_out[5] = ((slots + 1) & ~1LL) * 4;           // slots_dev
   sizes8_out[6] = (int64_t)n_pages * ymk::FL_HIST * 4;  // hist_dev, tables_dev, each
   sizes8_out[7] = (int64_t)n_pages * ymk::FL_HEAD * 4;  // head_dev
-  FL_END
+  YMK_API_END
 }
 
 int ymk_flate_rows(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
                    int64_t out_bytes, int max_rows, int max_row_segments, const int* grey_dev, unsigned char* filt_dev, uint16_t* tokens_dev,
                    uint32_t* segtok_dev, uint32_t* segadler_dev, int* hist_dev, void* stream) {
-  FL_TRY
+  YMK_API_BEGIN
   if (n_pages == 0) return 0;
   ymk::fl_check_table(blob_dev, blob_words, n_pages, n_index);
   const ymk::FlLimits lim = ymk::fl_limits(n_index, filt_bytes, segs, slot_bytes, out_bytes);
   ymk::launch_fl_rows((hipStream_t)stream, blob_dev, n_pages, lim, max_rows, max_row_segments, grey_dev, filt_dev, tokens_dev, segtok_dev,
                       segadler_dev, hist_dev);
-  FL_END
+  YMK_API_END
 }
 
 int ymk_flate_tables(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
                      int64_t out_bytes, const int* grey_dev, const int* hist_dev, const uint32_t* segadler_dev, uint32_t* tables_dev,
                      uint32_t* head_dev, int* sizes_dev, void* stream) {
-  FL_TRY
+  YMK_API_BEGIN
   if (n_pages == 0) return 0;
   ymk::fl_check_table(blob_dev, blob_words, n_pages, n_index);
   const ymk::FlLimits lim = ymk::fl_limits(n_index, filt_bytes, segs, slot_bytes, out_bytes);
   ymk::launch_fl_tables((hipStream_t)stream, blob_dev, n_pages, lim, grey_dev, hist_dev, segadler_dev, tables_dev, head_dev, sizes_dev);
-  FL_END
+  YMK_API_END
 }
 
 int ymk_flate_code(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
                    int64_t out_bytes, int max_rows, int max_row_segments, const uint16_t* tokens_dev, const uint32_t* segtok_dev,
                    const uint32_t* tables_dev, const uint32_t* head_dev, uint32_t* slots_dev, uint32_t* segbits_dev, void* stream) {
-  FL_TRY
+  YMK_API_BEGIN
   if (n_pages == 0) return 0;
   ymk::fl_check_table(blob_dev, blob_words, n_pages, n_index);
   const ymk::FlLimits lim = ymk::fl_limits(n_index, filt_bytes, segs, slot_bytes, out_bytes);
   ymk::launch_fl_code((hipStream_t)stream, blob_dev, n_pages, lim, max_rows, max_row_segments, tokens_dev, segtok_dev, tables_dev, head_dev,
                       slots_dev, segbits_dev);
-  FL_END
+  YMK_API_END
 }
 
 int ymk_flate_scan(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
                    int64_t out_bytes, const uint32_t* segbits_dev, uint32_t* head_dev, uint64_t* off_dev, int* sizes_dev, void* stream) {
-  FL_TRY
+  YMK_API_BEGIN
   if (n_pages == 0) return 0;
   ymk::fl_check_table(blob_dev, blob_words, n_pages, n_index);
   const ymk::FlLimits lim = ymk::fl_limits(n_index, filt_bytes, segs, slot_bytes, out_bytes);
   ymk::launch_fl_scan((hipStream_t)stream, blob_dev, n_pages, lim, segbits_dev, head_dev, off_dev, sizes_dev);
-  FL_END
+  YMK_API_END
 }
 
 int ymk_flate_gather(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs, int64_t slot_bytes,
                      int64_t out_bytes, const uint32_t* slots_dev, const uint32_t* head_dev, const uint64_t* off_dev, unsigned char* out_dev,
                      int64_t max_capacity, void* stream) {
-  FL_TRY
+  YMK_API_BEGIN
   if (n_pages == 0) return 0;
   ymk::fl_check_table(blob_dev, blob_words, n_pages, n_index);
   const ymk::FlLimits lim = ymk::fl_limits(n_index, filt_bytes, segs, slot_bytes, out_bytes);
   ymk::launch_fl_gather((hipStream_t)stream, blob_dev, n_pages, lim, slots_dev, head_dev, off_dev, out_dev, max_capacity);
-  FL_END
+  YMK_API_END
 }
 
 int ymk_flate_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int n_index, int64_t filt_bytes, int64_t segs,
@@ -815,7 +741,7 @@ int ymk_flate_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages,
                            unsigned char* filt_dev, uint16_t* tokens_dev, uint32_t* segtok_dev, uint32_t* segadler_dev, uint32_t* segbits_dev,
                            int* hist_dev, uint32_t* tables_dev, uint32_t* head_dev, uint64_t* off_dev, uint32_t* slots_dev,
                            unsigned char* out_dev, int64_t max_capacity, int* sizes_dev, void* stream) {
-  FL_TRY
+  YMK_API_BEGIN
   if (n_pages == 0) return 0;
   ymk::fl_check_table(blob_dev, blob_words, n_pages, n_index);
   const ymk::FlLimits lim = ymk::fl_limits(n_index, filt_bytes, segs, slot_bytes, out_bytes);
@@ -825,6 +751,6 @@ int ymk_flate_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages,
   ymk::launch_fl_code(s, blob_dev, n_pages, lim, max_rows, max_row_segments, tokens_dev, segtok_dev, tables_dev, head_dev, slots_dev, segbits_dev);
   ymk::launch_fl_scan(s, blob_dev, n_pages, lim, segbits_dev, head_dev, off_dev, sizes_dev);
   ymk::launch_fl_gather(s, blob_dev, n_pages, lim, slots_dev, head_dev, off_dev, out_dev, max_capacity);
-  FL_END
+  YMK_API_END
 }
 }

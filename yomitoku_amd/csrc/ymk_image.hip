@@ -439,88 +439,64 @@ void crop_batch(hipStream_t s, const PageLevels& lv, const CropDesc* descs_dev, 
 #include "../../include/ymk.h"
 extern "C" {
 int ymk_det_preprocess(const unsigned char* bgr_dev, int h, int w, int oh, int ow, float* x_dev, void* stream) {
-  try {
-    YMK_CHECK(bgr_dev && x_dev && h > 0 && w > 0 && oh > 0 && ow > 0, "bad argument");
-    ymk::det_preprocess((hipStream_t)stream, bgr_dev, h, w, oh, ow, x_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(bgr_dev && x_dev && h > 0 && w > 0 && oh > 0 && ow > 0, "bad argument");
+  ymk::det_preprocess((hipStream_t)stream, bgr_dev, h, w, oh, ow, x_dev);
+  YMK_API_END
 }
 int ymk_pil_resize_to_chw(const unsigned char* page_dev, int page_w, int x0, int y0, const int* xbounds_dev,
                           const int* xcoef_dev, int ksize_x, const int* ybounds_dev, const int* ycoef_dev, int ksize_y,
                           int oh, int ow, float* x_dev, void* stream) {
-  try {
-    YMK_CHECK(page_dev && xbounds_dev && xcoef_dev && ybounds_dev && ycoef_dev && x_dev, "null argument");
-    ymk::pil_resize_to_chw((hipStream_t)stream, page_dev, page_w, x0, y0, xbounds_dev, xcoef_dev, ksize_x, ybounds_dev,
-                           ycoef_dev, ksize_y, oh, ow, x_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(page_dev && xbounds_dev && xcoef_dev && ybounds_dev && ycoef_dev && x_dev, "null argument");
+  ymk::pil_resize_to_chw((hipStream_t)stream, page_dev, page_w, x0, y0, xbounds_dev, xcoef_dev, ksize_x, ybounds_dev,
+                         ycoef_dev, ksize_y, oh, ow, x_dev);
+  YMK_API_END
 }
 int ymk_pil_resize_batch_to_chw(const int* blob_dev, int n, int oh, int ow, float* x_dev, void* stream) {
-  try {
-    YMK_CHECK(blob_dev && x_dev && n >= 0 && oh > 0 && ow > 0, "bad argument");
-    ymk::pil_resize_batch_to_chw((hipStream_t)stream, blob_dev, n, oh, ow, x_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(blob_dev && x_dev && n >= 0 && oh > 0 && ow > 0, "bad argument");
+  ymk::pil_resize_batch_to_chw((hipStream_t)stream, blob_dev, n, oh, ow, x_dev);
+  YMK_API_END
 }
 int ymk_pil_batch_record_words(void) { return ymk::PIL_BATCH_REC; }
 int ymk_crop_batch(const unsigned char* page_dev, int page_h, int page_w, const void* descs_dev, int n, int max_warp_w,
                    int max_warp_h, unsigned char* scratch_dev, float* out_dev, int batch_w, int out_h, void* stream) {
-  try {
-    YMK_CHECK(page_dev && descs_dev && scratch_dev && out_dev, "null argument");
-    ymk::PageLevels lv{};
-    for (int i = 0; i < ymk::MAX_LEVELS; ++i) {  // a descriptor naming a level > 0 reads the page: callers with a pyramid use _levels
-      lv.p[i] = page_dev;
-      lv.H[i] = page_h;
-      lv.W[i] = page_w;
-    }
-    ymk::crop_batch((hipStream_t)stream, lv, (const ymk::CropDesc*)descs_dev, n, max_warp_w, max_warp_h, scratch_dev, out_dev,
-                    batch_w, out_h);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(page_dev && descs_dev && scratch_dev && out_dev, "null argument");
+  ymk::PageLevels lv{};
+  for (int i = 0; i < ymk::MAX_LEVELS; ++i) {  // a descriptor naming a level > 0 reads the page: callers with a pyramid use _levels
+    lv.p[i] = page_dev;
+    lv.H[i] = page_h;
+    lv.W[i] = page_w;
   }
+  ymk::crop_batch((hipStream_t)stream, lv, (const ymk::CropDesc*)descs_dev, n, max_warp_w, max_warp_h, scratch_dev, out_dev,
+                  batch_w, out_h);
+  YMK_API_END
 }
 int ymk_crop_batch_levels(const unsigned char* const* level_pages_dev, const int* level_h, const int* level_w, int n_levels,
                           const void* descs_dev, int n, int max_warp_w, int max_warp_h, unsigned char* scratch_dev,
                           float* out_dev, int batch_w, int out_h, void* stream) {
-  try {
-    YMK_CHECK(level_pages_dev && level_h && level_w && descs_dev && scratch_dev && out_dev, "null argument");
-    YMK_CHECK(n_levels >= 1 && n_levels <= ymk::MAX_LEVELS, "1..4 pyramid levels");
-    ymk::PageLevels lv{};
-    for (int i = 0; i < ymk::MAX_LEVELS; ++i) {
-      const int k = i < n_levels && level_pages_dev[i] ? i : 0;  // unused levels alias the page
-      lv.p[i] = level_pages_dev[k];
-      lv.H[i] = level_h[k];
-      lv.W[i] = level_w[k];
-    }
-    YMK_CHECK(lv.p[0] != nullptr, "level 0 (the page) is required");
-    ymk::crop_batch((hipStream_t)stream, lv, (const ymk::CropDesc*)descs_dev, n, max_warp_w, max_warp_h, scratch_dev, out_dev,
-                    batch_w, out_h);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(level_pages_dev && level_h && level_w && descs_dev && scratch_dev && out_dev, "null argument");
+  YMK_CHECK(n_levels >= 1 && n_levels <= ymk::MAX_LEVELS, "1..4 pyramid levels");
+  ymk::PageLevels lv{};
+  for (int i = 0; i < ymk::MAX_LEVELS; ++i) {
+    const int k = i < n_levels && level_pages_dev[i] ? i : 0;  // unused levels alias the page
+    lv.p[i] = level_pages_dev[k];
+    lv.H[i] = level_h[k];
+    lv.W[i] = level_w[k];
   }
+  YMK_CHECK(lv.p[0] != nullptr, "level 0 (the page) is required");
+  ymk::crop_batch((hipStream_t)stream, lv, (const ymk::CropDesc*)descs_dev, n, max_warp_w, max_warp_h, scratch_dev, out_dev,
+                  batch_w, out_h);
+  YMK_API_END
 }
 int ymk_halve_u8c3(const unsigned char* src_dev, int h, int w, unsigned char* dst_dev, int dst_h, int dst_w, void* stream) {
-  try {
-    YMK_CHECK(src_dev && dst_dev && h > 0 && w > 0 && dst_h > 0 && dst_w > 0, "bad argument");
-    ymk::halve_u8c3((hipStream_t)stream, src_dev, h, w, dst_dev, dst_h, dst_w);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(src_dev && dst_dev && h > 0 && w > 0 && dst_h > 0 && dst_w > 0, "bad argument");
+  ymk::halve_u8c3((hipStream_t)stream, src_dev, h, w, dst_dev, dst_h, dst_w);
+  YMK_API_END
 }
 int ymk_crop_desc_size(void) { return (int)sizeof(ymk::CropDesc); }
 }

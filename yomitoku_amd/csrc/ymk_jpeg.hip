@@ -30,15 +30,16 @@
 //   k_jpeg_histogram      k_jpeg_entropy's decomposition (one wave per interval, 64 blocks at a time in LDS, the same DC
 //                         predecessor): the symbols the coder will emit are counted in LDS, the non-zero bins added to the page's
 //                         histogram (integer atomicAdd: the sums do not depend on the order).
-//   k_jpeg_optimal_tables one workgroup per page, one wave per table.  libjpeg's rule: the two rarest symbols are merged until
-//                         one is left (two wave arg-min reductions per merge, the tie rule in the key; a subtree id per symbol
-//                         instead of libjpeg's chain), the lengths limited to 16 bits (Annex K.3), the codes assigned (Annex C).
+//   k_jpeg_optimal_tables one workgroup per page, one wave per table.  The construction is the shared one of ymk_pages.h, which
+//                         the Deflate coder (ymk_flate.hip) runs too: libjpeg's rule - the two rarest symbols are merged until
+//                         one is left - and the lengths limited to 16 bits (Annex K.3).  The kernel's own: the reserved symbol
+//                         256 and the removal of its code point, the codes assigned (Annex C), the DHT segments.
 //                         Output: the page's symbol -> code table in c_luts' layout, and its DHT segments as bytes.
 //   k_jpeg_entropy<true>  s_lut filled from the page's table; YMK_JPEG_BLOCK_STREAM_BYTES_OPT per block (a DC code may have 16 bits).
 //   k_jpeg_compact<true>  the header is the blob's up to SOF0, the page's DHT bytes, the blob's from DRI.
 //
 // Nothing is allocated and nothing waited for; no workgroup waits for another (every stage is a launch of its own).
-#include "ymk_common.h"
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -223,7 +224,7 @@ struct JpegPage {
 // Record p, checked against the limits: a record that does not fit is no page (never trusted).
 __device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const JpegLimits& lim, int p, JpegPage& g) {
   const int* r = blob + (size_t)p * JP_REC;
-  g.src = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)r[1] << 32) | (unsigned long long)(unsigned)r[0]);
+  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
   g.h = r[2], g.w = r[3], g.ch = r[4];
   JpegMode m;
   if (g.src == nullptr || g.h < 1 || g.w < 1 || g.h > 16383 || g.w > 16383 || !jpeg_mode(g.ch, r[15], m)) return false;
@@ -232,7 +233,7 @@ __device__ __forceinline__ bool jpeg_page(const int* __restrict__ blob, const Jp
   g.mcu_w = (g.w + (8 << m.lh) - 1) >> (3 + m.lh), g.mcu_h = (g.h + (8 << m.lv) - 1) >> (3 + m.lv);
   g.tile_w = (g.w + (1 << m.lt) - 1) >> m.lt, g.tile_h = (g.h + (1 << m.lt) - 1) >> m.lt;
   g.first_mcu = r[5], g.first_block = r[6], g.first_interval = r[7];
-  g.out_off = (long long)(((unsigned long long)(unsigned)r[9] << 32) | (unsigned long long)(unsigned)r[8]);
+  g.out_off = page_word64(r, 8);
   g.capacity = r[10], g.hdr_off = r[11], g.hdr_len = r[12], g.q_off = r[13];
   g.hdr_split = min(max(r[14], 0), max(g.hdr_len, 0));
   const long long mcus = (long long)g.mcu_w * g.mcu_h;
@@ -479,15 +480,6 @@ __device__ __forceinline__ int encode_block(const short* c, int pred, const unsi
   return bits;
 }
 
-__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // Block `b` of a restart interval: its component (0 Y, 1 Cb, 2 Cr) - an MCU is per - 2 luminance blocks, then Cb, then Cr; a
 // one-component page's is its block -
 __device__ __forceinline__ int jpeg_component(const JpegPage& g, int b) { return g.comps == 3 ? max(b % g.per - (g.per - 3), 0) : 0; }
@@ -643,17 +635,8 @@ __global__ __launch_bounds__(64) void k_jpeg_histogram(const int* __restrict__ b
 }
 
 // ------------------------------------------------------------------------------------------------ optimal tables
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-
 // One workgroup per page, wave t makes table t of DC 0, AC 0, DC 1, AC 1 (a grey page: the first two; the other two come out
-// empty).  Symbol s = k * 64 + lane sits in register k of its lane; the reserved symbol 256 in lane 0.
+// empty).  Symbol s = k * 64 + lane sits in register k of its lane (huff_merge_lengths, ymk_pages.h); the reserved symbol 256 in lane 0.
 // Frequencies: a symbol's count is at most the symbols of one class of a 16383 x 16383 page - the most are the chrominance's at
 // 4:4:4, 2 * 2048 * 2048 blocks of at most 64 -, and so is the sum of a table's, 5.4e8: below libjpeg's 1e9 sentinel ("no
 // symbol") and inside an int.  Counts from elsewhere are
@@ -673,38 +656,13 @@ __global__ __launch_bounds__(256) void k_jpeg_optimal_tables(const int* __restri
   const int n = t < (g.comps == 3 ? 4 : 2) ? (ac ? 256 : 16) : 0;  // symbols this table may have
   const int* src = hist + (size_t)page * JP_LUT_WORDS + cls * (256 + 16) + (ac ? 0 : 256);
   unsigned freq[5];
-  int len[5], id[5];
+  int len[5];
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     const int s = k * 64 + lane;
     freq[k] = k < 4 ? (s < n ? (unsigned)min(max(src[s], 0), 0x3fffffff) : 0u) : (lane == 0 ? 1u : 0u);
-    len[k] = 0, id[k] = s;
   }
-  constexpr unsigned long long NONE = ~0ull;
-  for (int merge = 0; merge < 256; ++merge) {
-    // the smallest non-zero frequency, among equals the largest symbol: libjpeg scans upward with <=
-    unsigned long long k1 = NONE, k2 = NONE;
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-      if (freq[k]) k1 = min(k1, (unsigned long long)freq[k] << 32 | (unsigned)(0xffff - (k * 64 + lane)));
-    k1 = wave_min_u64(k1);
-    const int c1 = 0xffff - (int)(k1 & 0xffff);
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-      if (freq[k] && k * 64 + lane != c1) k2 = min(k2, (unsigned long long)freq[k] << 32 | (unsigned)(0xffff - (k * 64 + lane)));
-    k2 = wave_min_u64(k2);
-    if (k2 == NONE) break;  // the same in every lane
-    const int c2 = 0xffff - (int)(k2 & 0xffff);
-    const unsigned long long sum64 = (k1 >> 32) + (k2 >> 32);
-    const unsigned sum = sum64 > 0xfffffffeull ? 0xfffffffeu : (unsigned)sum64;  // saturates on counts no page has: NONE stays free
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const int s = k * 64 + lane;
-      if (s == c1) freq[k] = sum;
-      if (s == c2) freq[k] = 0;
-      if (id[k] == c1 || id[k] == c2) ++len[k], id[k] = c1;  // both subtrees one bit longer, and one subtree from here on
-    }
-  }
+  huff_merge_lengths(freq, len, 256, lane);  // at most 257 live symbols
   for (int i = lane; i < 260; i += 64) s_bits[t][i] = 0;
   __syncthreads();
 #pragma unroll
@@ -721,16 +679,7 @@ __global__ __launch_bounds__(256) void k_jpeg_optimal_tables(const int* __restri
   for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
   if (lane == 0) {  // tens of steps: Figure K.3, then the first code and the first place of every length
     int* bits = s_bits[t];
-    for (int i = longest; i > 16; --i)
-      while (bits[i] > 0) {
-        int j = i - 2;
-        while (j > 0 && bits[j] == 0) --j;
-        if (j == 0) {  // not a tree's counts: not reached with lengths from the merges above
-          bits[i] = 0;
-          break;
-        }
-        bits[i] -= 2, bits[i - 1] += 1, bits[j + 1] += 2, bits[j] -= 1;
-      }
+    huff_limit_counts(bits, longest, 16);
     int top = 16;
     while (top > 0 && bits[top] == 0) --top;
     if (top > 0) --bits[top];  // the reserved symbol's code
@@ -752,8 +701,7 @@ __global__ __launch_bounds__(256) void k_jpeg_optimal_tables(const int* __restri
       int rank = 0;  // the symbol's place by (length before limiting, value)
       for (int o = 0; o < 256; ++o) rank += s_key[t][o] < key;
       if (rank < total) {
-        int l = 1;
-        while (l < 16 && rank >= s_cum[t][l + 1]) ++l;
+        const int l = huff_length_of_rank(s_cum[t], rank, 16);
         entry = (unsigned)(s_first[t][l] + rank - s_cum[t][l]) | (unsigned)l << 16;
         s_seg[t][5 + 16 + rank] = (unsigned char)s;
       }
@@ -858,7 +806,7 @@ constexpr int GT_THREADS = 256, GT_GROUP = 48;  // a group: 16 pixels = three 16
 __global__ __launch_bounds__(GT_THREADS) void k_jpeg_pages_grey(const int* __restrict__ blob, int* __restrict__ diff) {
   const int p = blockIdx.y;
   const int* r = blob + (size_t)p * JP_REC;
-  const unsigned char* src = reinterpret_cast<const unsigned char*>(((unsigned long long)(unsigned)r[1] << 32) | (unsigned long long)(unsigned)r[0]);
+  const unsigned char* src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
   const int h = r[2], w = r[3];
   if (src == nullptr || h < 1 || w < 1 || h > 16383 || w > 16383 || r[4] != 3) {  // the whole block
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(diff + p, -1);
@@ -951,8 +899,7 @@ static JpegMode checked_mode(int channels, int mode) {
   return m;
 }
 static void check_table(const int* blob_dev, int64_t blob_words, int n_pages) {
-  YMK_CHECK(n_pages >= 0 && n_pages <= 4096, "0..4096 pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 15) == 0 && blob_words >= (int64_t)n_pages * JP_REC, "page table: 16-byte aligned, n records");
+  check_page_table(blob_dev, blob_words, n_pages, JP_REC, 15, 4096, "0..4096 pages", "page table: 16-byte aligned, n records");
 }
 
 static void launch_coefficients(hipStream_t s, const int* blob, const JpegLimits& lim, int n_pages, int16_t* coef) {
@@ -1013,14 +960,10 @@ extern "C" {
 int ymk_jpeg_page_words(void) { return ymk::JP_REC; }
 
 int ymk_jpeg_quant_tables(int quality, int* zigzag128_out) {
-  try {
-    YMK_CHECK(zigzag128_out, "null output");
-    ymk::quant_tables(quality, zigzag128_out);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(zigzag128_out, "null output");
+  ymk::quant_tables(quality, zigzag128_out);
+  YMK_API_END
 }
 
 int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out, int capacity) {
@@ -1028,16 +971,13 @@ int ymk_jpeg_header(int h, int w, int channels, int quality, unsigned char* out,
 }
 
 int ymk_jpeg_header_mode(int h, int w, int channels, int mode, int quality, unsigned char* out, int capacity) {
-  try {
-    YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
-    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, ymk::checked_mode(channels, mode), quality);
-    YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
-    std::memcpy(out, hdr.data(), hdr.size());
-    return (int)hdr.size();
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return -1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
+  const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, ymk::checked_mode(channels, mode), quality);
+  YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
+  std::memcpy(out, hdr.data(), hdr.size());
+  return (int)hdr.size();
+  YMK_API_END_OR(-1)
 }
 
 int ymk_jpeg_header_opt(int h, int w, int channels, int quality, unsigned char* out, int capacity, int* split_out) {
@@ -1045,17 +985,14 @@ int ymk_jpeg_header_opt(int h, int w, int channels, int quality, unsigned char* 
 }
 
 int ymk_jpeg_header_opt_mode(int h, int w, int channels, int mode, int quality, unsigned char* out, int capacity, int* split_out) {
-  try {
-    YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
-    YMK_CHECK(split_out, "null output");
-    const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, ymk::checked_mode(channels, mode), quality, false, split_out);
-    YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
-    std::memcpy(out, hdr.data(), hdr.size());
-    return (int)hdr.size();
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return -1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(h >= 1 && w >= 1 && h <= 16383 && w <= 16383 && (channels == 1 || channels == 3), "page: 1..16383 pixels on a side, 1 or 3 channels");
+  YMK_CHECK(split_out, "null output");
+  const std::vector<unsigned char> hdr = ymk::jpeg_header(h, w, ymk::checked_mode(channels, mode), quality, false, split_out);
+  YMK_CHECK(out && capacity >= (int)hdr.size(), "header buffer too small");
+  std::memcpy(out, hdr.data(), hdr.size());
+  return (int)hdr.size();
+  YMK_API_END_OR(-1)
 }
 
 int ymk_jpeg_scratch_bytes_opt(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes9_out) {
@@ -1063,17 +1000,13 @@ int ymk_jpeg_scratch_bytes_opt(const int* h, const int* w, const int* channels, 
 }
 
 int ymk_jpeg_scratch_bytes_opt_mode(const int* h, const int* w, const int* channels, const int* modes, int n_pages, int64_t* sizes9_out) {
-  try {
-    YMK_CHECK(sizes9_out, "bad argument");
-    if (ymk_jpeg_scratch_bytes_mode(h, w, channels, modes, n_pages, sizes9_out)) return 1;
-    sizes9_out[4] = sizes9_out[1] * YMK_JPEG_BLOCK_STREAM_BYTES_OPT;
-    sizes9_out[6] = sizes9_out[7] = (int64_t)n_pages * YMK_JPEG_TABLE_WORDS * (int64_t)sizeof(int);
-    sizes9_out[8] = (int64_t)n_pages * YMK_JPEG_DHT_BYTES;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(sizes9_out, "bad argument");
+  if (ymk_jpeg_scratch_bytes_mode(h, w, channels, modes, n_pages, sizes9_out)) return 1;
+  sizes9_out[4] = sizes9_out[1] * YMK_JPEG_BLOCK_STREAM_BYTES_OPT;
+  sizes9_out[6] = sizes9_out[7] = (int64_t)n_pages * YMK_JPEG_TABLE_WORDS * (int64_t)sizeof(int);
+  sizes9_out[8] = (int64_t)n_pages * YMK_JPEG_DHT_BYTES;
+  YMK_API_END
 }
 
 int ymk_jpeg_scratch_bytes(const int* h, const int* w, const int* channels, int n_pages, int64_t* sizes6_out) {
@@ -1081,227 +1014,179 @@ int ymk_jpeg_scratch_bytes(const int* h, const int* w, const int* channels, int 
 }
 
 int ymk_jpeg_scratch_bytes_mode(const int* h, const int* w, const int* channels, const int* modes, int n_pages, int64_t* sizes6_out) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes6_out && (n_pages == 0 || (h && w && channels)), "bad argument");
-    int64_t tiles = 0, blocks = 0, intervals = 0;
-    for (int p = 0; p < n_pages; ++p) {
-      YMK_CHECK(h[p] >= 1 && w[p] >= 1 && h[p] <= 16383 && w[p] <= 16383 && (channels[p] == 1 || channels[p] == 3),
-                "page: 1..16383 pixels on a side, 1 or 3 channels");
-      const ymk::JpegMode m = ymk::checked_mode(channels[p], modes ? modes[p] : 0);
-      const int64_t mw = (w[p] + (8 << m.lh) - 1) >> (3 + m.lh), mh = (h[p] + (8 << m.lv) - 1) >> (3 + m.lv);
-      tiles += (int64_t)((w[p] + (1 << m.lt) - 1) >> m.lt) * ((h[p] + (1 << m.lt) - 1) >> m.lt);
-      blocks += mw * mh * (m.comps == 3 ? (1 << (m.lh + m.lv)) + 2 : 1);
-      intervals += mh;
-    }
-    sizes6_out[0] = tiles, sizes6_out[1] = blocks, sizes6_out[2] = intervals;
-    sizes6_out[3] = blocks * 64 * (int64_t)sizeof(int16_t);
-    sizes6_out[4] = blocks * YMK_JPEG_BLOCK_STREAM_BYTES;
-    sizes6_out[5] = intervals * 2 * (int64_t)sizeof(int);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes6_out && (n_pages == 0 || (h && w && channels)), "bad argument");
+  int64_t tiles = 0, blocks = 0, intervals = 0;
+  for (int p = 0; p < n_pages; ++p) {
+    YMK_CHECK(h[p] >= 1 && w[p] >= 1 && h[p] <= 16383 && w[p] <= 16383 && (channels[p] == 1 || channels[p] == 3),
+              "page: 1..16383 pixels on a side, 1 or 3 channels");
+    const ymk::JpegMode m = ymk::checked_mode(channels[p], modes ? modes[p] : 0);
+    const int64_t mw = (w[p] + (8 << m.lh) - 1) >> (3 + m.lh), mh = (h[p] + (8 << m.lv) - 1) >> (3 + m.lv);
+    tiles += (int64_t)((w[p] + (1 << m.lt) - 1) >> m.lt) * ((h[p] + (1 << m.lt) - 1) >> m.lt);
+    blocks += mw * mh * (m.comps == 3 ? (1 << (m.lh + m.lv)) + 2 : 1);
+    intervals += mh;
   }
+  sizes6_out[0] = tiles, sizes6_out[1] = blocks, sizes6_out[2] = intervals;
+  sizes6_out[3] = blocks * 64 * (int64_t)sizeof(int16_t);
+  sizes6_out[4] = blocks * YMK_JPEG_BLOCK_STREAM_BYTES;
+  sizes6_out[5] = intervals * 2 * (int64_t)sizeof(int);
+  YMK_API_END
 }
 
 int ymk_jpeg_coefficients(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int16_t* coef_dev,
                           int64_t total_blocks, void* stream) {
-  try {
-    const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, 0x7fffffffLL, -1);
-    if (n_pages == 0 || total_mcus == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    ymk::launch_coefficients((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, 0x7fffffffLL, -1);
+  if (n_pages == 0 || total_mcus == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  ymk::launch_coefficients((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_entropy(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
                      uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, int64_t total_intervals, void* stream) {
-  try {
-    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
-    if (n_pages == 0 || total_intervals == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    ymk::launch_entropy((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
+  if (n_pages == 0 || total_intervals == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  ymk::launch_entropy((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_compact(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* stream_dev, int64_t stream_bytes,
                      int64_t total_blocks, const int* intervals_dev, int64_t total_intervals, unsigned char* out_dev, int64_t out_bytes,
                      int* lengths_dev, void* stream) {
-  try {
-    YMK_CHECK(out_bytes >= 0, "bad argument");
-    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, out_bytes);
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    if (total_intervals == 0) {
-      YMK_CHECK(lengths_dev, "null lengths");
-      YMK_HIP(hipMemsetAsync(lengths_dev, 0xff, (size_t)n_pages * sizeof(int), (hipStream_t)stream));
-      return 0;
-    }
-    ymk::launch_compact((hipStream_t)stream, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
+  YMK_API_BEGIN
+  YMK_CHECK(out_bytes >= 0, "bad argument");
+  const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, out_bytes);
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  if (total_intervals == 0) {
+    YMK_CHECK(lengths_dev, "null lengths");
+    YMK_HIP(hipMemsetAsync(lengths_dev, 0xff, (size_t)n_pages * sizeof(int), (hipStream_t)stream));
     return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
   }
+  ymk::launch_compact((hipStream_t)stream, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_encode_pages(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
                           int64_t total_intervals, int16_t* coef_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
                           unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream) {
-  try {
-    YMK_CHECK(out_bytes >= 0, "bad argument");
-    const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, total_intervals, out_bytes);
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(total_mcus > 0 && total_intervals > 0, "pages without MCUs");
-    const hipStream_t s = (hipStream_t)stream;
-    ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
-    ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
-    ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(out_bytes >= 0, "bad argument");
+  const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, total_intervals, out_bytes);
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(total_mcus > 0 && total_intervals > 0, "pages without MCUs");
+  const hipStream_t s = (hipStream_t)stream;
+  ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
+  ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev);
+  ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_histogram(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
                        int64_t total_intervals, int* hist_dev, void* stream) {
-  try {
-    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    if (total_intervals == 0) {
-      YMK_CHECK(hist_dev, "null histograms");
-      YMK_HIP(hipMemsetAsync(hist_dev, 0, (size_t)n_pages * ymk::JP_LUT_WORDS * sizeof(int), (hipStream_t)stream));
-      return 0;
-    }
-    ymk::launch_histogram((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, hist_dev);
+  YMK_API_BEGIN
+  const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  if (total_intervals == 0) {
+    YMK_CHECK(hist_dev, "null histograms");
+    YMK_HIP(hipMemsetAsync(hist_dev, 0, (size_t)n_pages * ymk::JP_LUT_WORDS * sizeof(int), (hipStream_t)stream));
     return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
   }
+  ymk::launch_histogram((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, hist_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_optimal_tables(const int* blob_dev, int64_t blob_words, int n_pages, const int* hist_dev, uint32_t* tables_dev,
                             unsigned char* dht_dev, void* stream) {
-  try {
-    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, 0x7fffffffLL, 0x7fffffffLL, -1);
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    ymk::launch_tables((hipStream_t)stream, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, 0x7fffffffLL, 0x7fffffffLL, -1);
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  ymk::launch_tables((hipStream_t)stream, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_entropy_opt(const int* blob_dev, int64_t blob_words, int n_pages, const int16_t* coef_dev, int64_t total_blocks,
                          const uint32_t* tables_dev, uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev,
                          int64_t total_intervals, void* stream) {
-  try {
-    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
-    if (n_pages == 0 || total_intervals == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(tables_dev, "null tables");
-    ymk::launch_entropy((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, -1);
+  if (n_pages == 0 || total_intervals == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(tables_dev, "null tables");
+  ymk::launch_entropy((hipStream_t)stream, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_compact_opt(const int* blob_dev, int64_t blob_words, int n_pages, const uint32_t* stream_dev, int64_t stream_bytes,
                          int64_t total_blocks, const int* intervals_dev, int64_t total_intervals, const unsigned char* dht_dev,
                          unsigned char* out_dev, int64_t out_bytes, int* lengths_dev, void* stream) {
-  try {
-    YMK_CHECK(out_bytes >= 0, "bad argument");
-    const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, out_bytes);
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    if (total_intervals == 0) {
-      YMK_CHECK(lengths_dev, "null lengths");
-      YMK_HIP(hipMemsetAsync(lengths_dev, 0xff, (size_t)n_pages * sizeof(int), (hipStream_t)stream));
-      return 0;
-    }
-    YMK_CHECK(dht_dev, "null DHT records");
-    ymk::launch_compact((hipStream_t)stream, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
+  YMK_API_BEGIN
+  YMK_CHECK(out_bytes >= 0, "bad argument");
+  const ymk::JpegLimits lim = ymk::limits(blob_words, 0x7fffffffLL / ymk::JP_WAVES, total_blocks, total_intervals, out_bytes);
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  if (total_intervals == 0) {
+    YMK_CHECK(lengths_dev, "null lengths");
+    YMK_HIP(hipMemsetAsync(lengths_dev, 0xff, (size_t)n_pages * sizeof(int), (hipStream_t)stream));
     return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
   }
+  YMK_CHECK(dht_dev, "null DHT records");
+  ymk::launch_compact((hipStream_t)stream, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_encode_pages_opt(const int* blob_dev, int64_t blob_words, int n_pages, int64_t total_mcus, int64_t total_blocks,
                               int64_t total_intervals, int16_t* coef_dev, int* hist_dev, uint32_t* tables_dev, unsigned char* dht_dev,
                               uint32_t* stream_dev, int64_t stream_bytes, int* intervals_dev, unsigned char* out_dev, int64_t out_bytes,
                               int* lengths_dev, void* stream) {
-  try {
-    YMK_CHECK(out_bytes >= 0, "bad argument");
-    const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, total_intervals, out_bytes);
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(total_mcus > 0 && total_intervals > 0, "pages without MCUs");
-    YMK_CHECK(tables_dev && dht_dev, "null scratch");
-    const hipStream_t s = (hipStream_t)stream;
-    ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
-    ymk::launch_histogram(s, blob_dev, lim, n_pages, coef_dev, hist_dev);
-    ymk::launch_tables(s, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
-    ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
-    ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(out_bytes >= 0, "bad argument");
+  const ymk::JpegLimits lim = ymk::limits(blob_words, total_mcus, total_blocks, total_intervals, out_bytes);
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(total_mcus > 0 && total_intervals > 0, "pages without MCUs");
+  YMK_CHECK(tables_dev && dht_dev, "null scratch");
+  const hipStream_t s = (hipStream_t)stream;
+  ymk::launch_coefficients(s, blob_dev, lim, n_pages, coef_dev);
+  ymk::launch_histogram(s, blob_dev, lim, n_pages, coef_dev, hist_dev);
+  ymk::launch_tables(s, blob_dev, lim, n_pages, hist_dev, tables_dev, dht_dev);
+  ymk::launch_entropy(s, blob_dev, lim, n_pages, coef_dev, stream_dev, stream_bytes, intervals_dev, tables_dev);
+  ymk::launch_compact(s, blob_dev, lim, n_pages, stream_dev, stream_bytes, intervals_dev, out_dev, lengths_dev, dht_dev);
+  YMK_API_END
 }
 
 int ymk_jpeg_pages_grey(const int* blob_dev, int64_t blob_words, int n_pages, int64_t max_pixels, int* diff_dev, void* stream) {
-  try {
-    YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
-    if (n_pages == 0) return 0;
-    ymk::check_table(blob_dev, blob_words, n_pages);
-    YMK_CHECK(diff_dev && ((uintptr_t)diff_dev & 3) == 0, "null or misaligned output");
-    const hipStream_t s = (hipStream_t)stream;
-    YMK_HIP(hipMemsetAsync(diff_dev, 0, (size_t)n_pages * sizeof(int), s));
-    // four groups per thread where the largest page has that many; 256 blocks per page at the most (the loops stride the rest)
-    const int64_t per_block = (int64_t)ymk::GT_THREADS * 16 * 4;
-    const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_pixels + per_block - 1) / per_block, 1), 256);
-    hipLaunchKernelGGL(ymk::k_jpeg_pages_grey, dim3(gx, (unsigned)n_pages), dim3(ymk::GT_THREADS), 0, s, blob_dev, diff_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(max_pixels >= 0 && max_pixels <= 16383LL * 16383LL, "bad argument");
+  if (n_pages == 0) return 0;
+  ymk::check_table(blob_dev, blob_words, n_pages);
+  YMK_CHECK(diff_dev && ((uintptr_t)diff_dev & 3) == 0, "null or misaligned output");
+  const hipStream_t s = (hipStream_t)stream;
+  YMK_HIP(hipMemsetAsync(diff_dev, 0, (size_t)n_pages * sizeof(int), s));
+  // four groups per thread where the largest page has that many; 256 blocks per page at the most (the loops stride the rest)
+  const int64_t per_block = (int64_t)ymk::GT_THREADS * 16 * 4;
+  const unsigned gx = (unsigned)std::min<int64_t>(std::max<int64_t>((max_pixels + per_block - 1) / per_block, 1), 256);
+  hipLaunchKernelGGL(ymk::k_jpeg_pages_grey, dim3(gx, (unsigned)n_pages), dim3(ymk::GT_THREADS), 0, s, blob_dev, diff_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_pil_resize_u8_record_words(void) { return ymk::RS_REC; }
 
 int ymk_pil_resize_u8(const int* blob_dev, int64_t blob_words, int n, int max_oh, int max_ow, void* stream) {
-  try {
-    YMK_CHECK(n >= 0 && n <= 65535 && max_oh >= 0 && max_oh <= 65535 && max_ow >= 0, "at most 65535 images and output rows per launch");
-    if (n == 0 || max_oh == 0 || max_ow == 0) return 0;
-    YMK_CHECK(blob_dev && blob_words >= (int64_t)n * ymk::RS_REC, "record table");
-    hipLaunchKernelGGL(ymk::k_pil_resize_u8, dim3((max_ow + 255) / 256, max_oh, n), dim3(256), 0, (hipStream_t)stream, blob_dev,
-                       (long long)blob_words);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(n >= 0 && n <= 65535 && max_oh >= 0 && max_oh <= 65535 && max_ow >= 0, "at most 65535 images and output rows per launch");
+  if (n == 0 || max_oh == 0 || max_ow == 0) return 0;
+  YMK_CHECK(blob_dev && blob_words >= (int64_t)n * ymk::RS_REC, "record table");
+  hipLaunchKernelGGL(ymk::k_pil_resize_u8, dim3((max_ow + 255) / 256, max_oh, n), dim3(256), 0, (hipStream_t)stream, blob_dev,
+                     (long long)blob_words);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 }

@@ -19,9 +19,7 @@
 // A page's pyramids: the foreground's levels 0 .. L one behind the other, then the background's; level l + 1 has ceil(H_l / 2) x
 // ceil(W_l / 2) words, the last 1 x 1.  At most 15 levels (16383 = 2^14 - 1), at most 4/3 H0 W0 + 15 words.
 
-#include "ymk_common.h"
-
-#include <algorithm>
+#include "ymk_pages.h"
 
 #include "../../include/ymk.h"
 
@@ -47,10 +45,6 @@ __host__ __device__ __forceinline__ long long mr_pyramid_words(int H0, int W0) {
   }
 }
 
-__device__ __forceinline__ long long mr_word64(const int* r, int k) {
-  return (long long)(((unsigned long long)(unsigned)r[k + 1] << 32) | (unsigned long long)(unsigned)r[k]);
-}
-
 // One layer of a page: log2 of its cell, level 0's size, where its pyramid and its image are.
 struct MrLayer {
   int shift, H0, W0;
@@ -67,9 +61,9 @@ struct MrPage {
 __device__ __forceinline__ MrPage mr_page(const int* blob, int p, int bg_cell, int fg_cell, const MrLimits& lim) {
   const int* r = blob + (size_t)p * MR_REC;
   MrPage g;
-  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)mr_word64(r, 0));
+  g.src = reinterpret_cast<const unsigned char*>((unsigned long long)page_word64(r, 0));
   g.h = r[2], g.w = r[3], g.ch = r[4];
-  g.packed_at = mr_word64(r, 6);
+  g.packed_at = page_word64(r, 6);
   g.ok = g.h >= 1 && g.w >= 1 && g.h <= MR_MAX_SIDE && g.w <= MR_MAX_SIDE && g.src != nullptr && (g.ch == 1 || g.ch == 3);
   g.row_words = g.ok ? (g.w + 31) >> 5 : 0;
   g.fg.shift = mr_log2(fg_cell), g.bg.shift = mr_log2(bg_cell);
@@ -81,7 +75,7 @@ __device__ __forceinline__ MrPage mr_page(const int* blob, int p, int bg_cell, i
   const long long fg_words = mr_pyramid_words(g.fg.H0, g.fg.W0), bg_words = mr_pyramid_words(g.bg.H0, g.bg.W0);
   const long long fg_bytes = (long long)g.fg.H0 * g.fg.W0 * g.ch, bg_bytes = (long long)g.bg.H0 * g.bg.W0 * g.ch;
   g.fg.pyr_at = (long long)r[5], g.bg.pyr_at = g.fg.pyr_at + fg_words;
-  g.fg.img_at = mr_word64(r, 11), g.bg.img_at = g.fg.img_at + ((fg_bytes + 15) & ~15LL);
+  g.fg.img_at = page_word64(r, 11), g.bg.img_at = g.fg.img_at + ((fg_bytes + 15) & ~15LL);
   g.ok = g.packed_at >= 0 && g.packed_at + (long long)g.h * g.row_words <= lim.packed_words && g.fg.pyr_at >= 0 &&
          g.bg.pyr_at + bg_words <= lim.pyr_words && g.fg.img_at >= 0 && (g.fg.img_at & 15) == 0 && g.bg.img_at + bg_bytes <= lim.layers_bytes;
   return g;
@@ -234,8 +228,7 @@ struct MrCall {
 };
 static MrCall mr_check(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, int64_t packed_bytes,
                        const void* pyr_dev, int64_t pyr_bytes, int64_t layers_bytes) {
-  YMK_CHECK(n_pages >= 1 && n_pages <= 4096, "0..4096 pages");
-  YMK_CHECK(blob_dev && ((uintptr_t)blob_dev & 3) == 0 && blob_words >= (int64_t)n_pages * MR_REC, "page table: n records");
+  check_page_table(blob_dev, blob_words, n_pages, MR_REC, 3, 4096, "0..4096 pages", "page table: n records");  // no caller comes with 0
   YMK_CHECK(mr_cell_ok(bg_cell) && mr_cell_ok(fg_cell), "a cell is 1, 2, 4, 8 or 16");
   YMK_CHECK(max_h >= 1 && max_w >= 1 && max_h <= MR_MAX_SIDE && max_w <= MR_MAX_SIDE, "a page has 1..16383 pixels on a side");
   YMK_CHECK(pyr_dev && ((uintptr_t)pyr_dev & 7) == 0, "pyramids: 8-byte aligned");
@@ -254,93 +247,77 @@ extern "C" {
 int ymk_mrc_page_words(void) { return ymk::MR_REC; }
 
 int ymk_mrc_scratch_bytes(const int* h, const int* w, const int* ch, int n_pages, int bg_cell, int fg_cell, int64_t* sizes6_out, int64_t* places_out) {
-  try {
-    YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes6_out && (n_pages == 0 || (h && w && ch)), "bad argument");
-    YMK_CHECK(ymk::mr_cell_ok(bg_cell) && ymk::mr_cell_ok(fg_cell), "a cell is 1, 2, 4, 8 or 16");
-    int64_t luma = 0, cells = 0, words = 0, pyr = 0, layers = 0;
-    for (int k = 0; k < n_pages; ++k) {
-      YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::MR_MAX_SIDE && w[k] <= ymk::MR_MAX_SIDE, "a page has 1..16383 pixels on a side");
-      YMK_CHECK(ch[k] == 1 || ch[k] == 3, "a page has one or three channels");
-      const int64_t px = (int64_t)h[k] * w[k];
-      if (ch[k] == 3) luma += (px + 15) & ~15LL;
-      cells += px;
-      words += (int64_t)h[k] * ((w[k] + 31) >> 5);
-      const int fH = (h[k] + fg_cell - 1) / fg_cell, fW = (w[k] + fg_cell - 1) / fg_cell;
-      const int bH = (h[k] + bg_cell - 1) / bg_cell, bW = (w[k] + bg_cell - 1) / bg_cell;
-      const int64_t fg_at = layers, bg_at = fg_at + (((int64_t)fH * fW * ch[k] + 15) & ~15LL);
-      if (places_out) places_out[3 * k] = pyr, places_out[3 * k + 1] = fg_at, places_out[3 * k + 2] = bg_at;
-      pyr += ymk::mr_pyramid_words(fH, fW) + ymk::mr_pyramid_words(bH, bW);
-      layers = bg_at + (((int64_t)bH * bW * ch[k] + 15) & ~15LL);
-      YMK_CHECK(pyr < (1LL << 31), "the pyramids of a call have fewer than 2^31 words");
-    }
-    sizes6_out[0] = luma;
-    sizes6_out[1] = ((cells + 1) & ~1LL) * 4;
-    sizes6_out[2] = ((words + 1) & ~1LL) * 4;
-    sizes6_out[3] = ((pyr + 1) & ~1LL) * 4;
-    sizes6_out[4] = layers;
-    sizes6_out[5] = (((int64_t)n_pages + 1) & ~1LL) * 4;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_pages >= 0 && n_pages <= 4096 && sizes6_out && (n_pages == 0 || (h && w && ch)), "bad argument");
+  YMK_CHECK(ymk::mr_cell_ok(bg_cell) && ymk::mr_cell_ok(fg_cell), "a cell is 1, 2, 4, 8 or 16");
+  int64_t luma = 0, cells = 0, words = 0, pyr = 0, layers = 0;
+  for (int k = 0; k < n_pages; ++k) {
+    YMK_CHECK(h[k] >= 1 && w[k] >= 1 && h[k] <= ymk::MR_MAX_SIDE && w[k] <= ymk::MR_MAX_SIDE, "a page has 1..16383 pixels on a side");
+    YMK_CHECK(ch[k] == 1 || ch[k] == 3, "a page has one or three channels");
+    const int64_t px = (int64_t)h[k] * w[k];
+    if (ch[k] == 3) luma += (px + 15) & ~15LL;
+    cells += px;
+    words += (int64_t)h[k] * ((w[k] + 31) >> 5);
+    const int fH = (h[k] + fg_cell - 1) / fg_cell, fW = (w[k] + fg_cell - 1) / fg_cell;
+    const int bH = (h[k] + bg_cell - 1) / bg_cell, bW = (w[k] + bg_cell - 1) / bg_cell;
+    const int64_t fg_at = layers, bg_at = fg_at + (((int64_t)fH * fW * ch[k] + 15) & ~15LL);
+    if (places_out) places_out[3 * k] = pyr, places_out[3 * k + 1] = fg_at, places_out[3 * k + 2] = bg_at;
+    pyr += ymk::mr_pyramid_words(fH, fW) + ymk::mr_pyramid_words(bH, bW);
+    layers = bg_at + (((int64_t)bH * bW * ch[k] + 15) & ~15LL);
+    YMK_CHECK(pyr < (1LL << 31), "the pyramids of a call have fewer than 2^31 words");
   }
+  sizes6_out[0] = luma;
+  sizes6_out[1] = ((cells + 1) & ~1LL) * 4;
+  sizes6_out[2] = ((words + 1) & ~1LL) * 4;
+  sizes6_out[3] = ((pyr + 1) & ~1LL) * 4;
+  sizes6_out[4] = layers;
+  sizes6_out[5] = (((int64_t)n_pages + 1) & ~1LL) * 4;
+  YMK_API_END
 }
 
 int ymk_mrc_cells(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, const uint32_t* packed_dev,
                   int64_t packed_bytes, uint32_t* pyr_dev, int64_t pyr_bytes, int64_t layers_bytes, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    const ymk::MrCall c = ymk::mr_check(blob_dev, blob_words, n_pages, max_h, max_w, bg_cell, fg_cell, packed_bytes, pyr_dev, pyr_bytes, layers_bytes);
-    YMK_CHECK(packed_dev && ((uintptr_t)packed_dev & 7) == 0, "packed rows: 8-byte aligned");
-    const dim3 grid((unsigned)((max_w + ymk::MR_TILE_W - 1) / ymk::MR_TILE_W), (unsigned)((max_h + ymk::MR_TILE_H - 1) / ymk::MR_TILE_H), (unsigned)n_pages);
-    hipLaunchKernelGGL(ymk::k_mrc_cells, grid, dim3(64), 0, (hipStream_t)stream, blob_dev, c.lim, bg_cell, fg_cell, (const unsigned*)packed_dev,
-                       (unsigned*)pyr_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  const ymk::MrCall c = ymk::mr_check(blob_dev, blob_words, n_pages, max_h, max_w, bg_cell, fg_cell, packed_bytes, pyr_dev, pyr_bytes, layers_bytes);
+  YMK_CHECK(packed_dev && ((uintptr_t)packed_dev & 7) == 0, "packed rows: 8-byte aligned");
+  const dim3 grid((unsigned)((max_w + ymk::MR_TILE_W - 1) / ymk::MR_TILE_W), (unsigned)((max_h + ymk::MR_TILE_H - 1) / ymk::MR_TILE_H), (unsigned)n_pages);
+  hipLaunchKernelGGL(ymk::k_mrc_cells, grid, dim3(64), 0, (hipStream_t)stream, blob_dev, c.lim, bg_cell, fg_cell, (const unsigned*)packed_dev,
+                     (unsigned*)pyr_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_mrc_pull(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, int64_t packed_bytes,
                  uint32_t* pyr_dev, int64_t pyr_bytes, int64_t layers_bytes, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    const ymk::MrCall c = ymk::mr_check(blob_dev, blob_words, n_pages, max_h, max_w, bg_cell, fg_cell, packed_bytes, pyr_dev, pyr_bytes, layers_bytes);
-    int H = c.max_H0, W = c.max_W0;
-    for (int level = 1; level < ymk::MR_MAX_LEVELS && !(H == 1 && W == 1); ++level) {
-      H = (H + 1) >> 1, W = (W + 1) >> 1;
-      hipLaunchKernelGGL(ymk::k_mrc_pull, dim3(ymk::mr_cell_blocks((int64_t)H * W, ymk::PL_THREADS), 2u, (unsigned)n_pages), dim3(ymk::PL_THREADS), 0,
-                         (hipStream_t)stream, blob_dev, c.lim, bg_cell, fg_cell, level, (unsigned*)pyr_dev);
-      YMK_HIP(hipGetLastError());
-    }
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  const ymk::MrCall c = ymk::mr_check(blob_dev, blob_words, n_pages, max_h, max_w, bg_cell, fg_cell, packed_bytes, pyr_dev, pyr_bytes, layers_bytes);
+  int H = c.max_H0, W = c.max_W0;
+  for (int level = 1; level < ymk::MR_MAX_LEVELS && !(H == 1 && W == 1); ++level) {
+    H = (H + 1) >> 1, W = (W + 1) >> 1;
+    hipLaunchKernelGGL(ymk::k_mrc_pull, dim3(ymk::mr_cell_blocks((int64_t)H * W, ymk::PL_THREADS), 2u, (unsigned)n_pages), dim3(ymk::PL_THREADS), 0,
+                       (hipStream_t)stream, blob_dev, c.lim, bg_cell, fg_cell, level, (unsigned*)pyr_dev);
+    YMK_HIP(hipGetLastError());
   }
+  YMK_API_END
 }
 
 int ymk_mrc_push(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, int64_t packed_bytes,
                  const uint32_t* pyr_dev, int64_t pyr_bytes, unsigned char* layers_dev, int64_t layers_bytes, int* flags_dev, void* stream) {
-  try {
-    if (n_pages == 0) return 0;
-    const ymk::MrCall c = ymk::mr_check(blob_dev, blob_words, n_pages, max_h, max_w, bg_cell, fg_cell, packed_bytes, pyr_dev, pyr_bytes, layers_bytes);
-    YMK_CHECK(layers_bytes == 0 || (layers_dev && ((uintptr_t)layers_dev & 15) == 0), "layers: 16-byte aligned");
-    YMK_CHECK(flags_dev && ((uintptr_t)flags_dev & 3) == 0, "null or misaligned flags");
-    const hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ymk::k_mrc_flags, dim3((unsigned)((n_pages + 63) / 64)), dim3(64), 0, s, blob_dev, c.lim, bg_cell, fg_cell, n_pages,
-                       (const unsigned*)pyr_dev, flags_dev);
-    YMK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ymk::k_mrc_push, dim3(ymk::mr_cell_blocks((int64_t)c.max_H0 * c.max_W0, ymk::PS_THREADS), 2u, (unsigned)n_pages),
-                       dim3(ymk::PS_THREADS), 0, s, blob_dev, c.lim, bg_cell, fg_cell, (const unsigned*)pyr_dev, (const int*)flags_dev, layers_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  if (n_pages == 0) return 0;
+  const ymk::MrCall c = ymk::mr_check(blob_dev, blob_words, n_pages, max_h, max_w, bg_cell, fg_cell, packed_bytes, pyr_dev, pyr_bytes, layers_bytes);
+  YMK_CHECK(layers_bytes == 0 || (layers_dev && ((uintptr_t)layers_dev & 15) == 0), "layers: 16-byte aligned");
+  YMK_CHECK(flags_dev && ((uintptr_t)flags_dev & 3) == 0, "null or misaligned flags");
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ymk::k_mrc_flags, dim3((unsigned)((n_pages + 63) / 64)), dim3(64), 0, s, blob_dev, c.lim, bg_cell, fg_cell, n_pages,
+                     (const unsigned*)pyr_dev, flags_dev);
+  YMK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ymk::k_mrc_push, dim3(ymk::mr_cell_blocks((int64_t)c.max_H0 * c.max_W0, ymk::PS_THREADS), 2u, (unsigned)n_pages),
+                     dim3(ymk::PS_THREADS), 0, s, blob_dev, c.lim, bg_cell, fg_cell, (const unsigned*)pyr_dev, (const int*)flags_dev, layers_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_mrc_pages(const int* blob_dev, int64_t blob_words, int n_pages, int max_h, int max_w, int bg_cell, int fg_cell, unsigned char* luma_dev,

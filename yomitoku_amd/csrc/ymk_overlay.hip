@@ -435,89 +435,73 @@ int ymk_overlay_chunk(void) { return ymk::OV_CHUNK; }
 
 int ymk_draw_overlay(unsigned char* canvas_dev, int h, int w, const int* cmds_dev, int n, const int* tile_offsets_dev,
                      const int* tile_cmds_dev, int n_list, const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream) {
-  try {
-    YMK_CHECK(canvas_dev && h > 0 && w > 0 && h <= 16383 && w <= 16383, "canvas: 1..16383 pixels on a side");
-    YMK_CHECK(n >= 0 && n_list >= 0 && atlas_bytes >= 0, "bad argument");
-    if (n == 0 || n_list == 0) return 0;
-    YMK_CHECK(cmds_dev && tile_offsets_dev && tile_cmds_dev, "null command / list pointer");
-    YMK_CHECK(atlas_dev || atlas_bytes == 0, "null atlas with a non-zero size");
-    YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0, "command records must be 16-byte aligned");
-    const dim3 grid((w + ymk::OV_TILE - 1) / ymk::OV_TILE, (h + ymk::OV_TILE - 1) / ymk::OV_TILE);
-    hipLaunchKernelGGL(ymk::k_draw_overlay, grid, dim3(ymk::OV_THREADS), 0, (hipStream_t)stream, canvas_dev, h, w, cmds_dev, n,
-                       tile_offsets_dev, tile_cmds_dev, n_list, atlas_dev, (long long)atlas_bytes);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(canvas_dev && h > 0 && w > 0 && h <= 16383 && w <= 16383, "canvas: 1..16383 pixels on a side");
+  YMK_CHECK(n >= 0 && n_list >= 0 && atlas_bytes >= 0, "bad argument");
+  if (n == 0 || n_list == 0) return 0;
+  YMK_CHECK(cmds_dev && tile_offsets_dev && tile_cmds_dev, "null command / list pointer");
+  YMK_CHECK(atlas_dev || atlas_bytes == 0, "null atlas with a non-zero size");
+  YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0, "command records must be 16-byte aligned");
+  const dim3 grid((w + ymk::OV_TILE - 1) / ymk::OV_TILE, (h + ymk::OV_TILE - 1) / ymk::OV_TILE);
+  hipLaunchKernelGGL(ymk::k_draw_overlay, grid, dim3(ymk::OV_THREADS), 0, (hipStream_t)stream, canvas_dev, h, w, cmds_dev, n,
+                     tile_offsets_dev, tile_cmds_dev, n_list, atlas_dev, (long long)atlas_bytes);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_overlay_cull_pass(void) { return ymk::OV_THREADS; }
 
 int ymk_overlay_layout(int* cmds_dev, int n_cmds, int16_t* bounds_dev, const int* runs_dev, int n_runs, const int* codes_dev,
                        int n_codes, const int* glyphs_dev, int n_glyphs, const int64_t* canvases_dev, int n_canvases, void* stream) {
-  try {
-    YMK_CHECK(n_cmds >= 0 && n_runs >= 0 && n_codes >= 0 && n_glyphs >= 0 && n_canvases >= 0 && n_canvases <= 65535, "bad argument");
-    if (n_cmds == 0) return 0;
-    YMK_CHECK(cmds_dev && bounds_dev, "null command / bounds pointer");
-    YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0 && ((uintptr_t)bounds_dev & 7) == 0 && ((uintptr_t)canvases_dev & 7) == 0,
-              "command records must be 16-byte, bounds and the canvas table 8-byte aligned");
-    if (n_runs > 0) {
-      YMK_CHECK(runs_dev && (codes_dev || n_codes == 0) && (glyphs_dev || n_glyphs == 0), "null run / code / glyph pointer");
-      hipLaunchKernelGGL(ymk::k_overlay_layout, dim3(n_runs), dim3(ymk::OV_SCAN), 0, (hipStream_t)stream, cmds_dev, n_cmds, runs_dev,
-                         n_runs, codes_dev, n_codes, glyphs_dev, n_glyphs);
-      YMK_HIP(hipGetLastError());
-    }
-    if (n_canvases > 0) {
-      YMK_CHECK(canvases_dev, "null canvas table");
-      const int gx = std::min(std::max((n_cmds + 255) / 256, 1), 256);
-      hipLaunchKernelGGL(ymk::k_overlay_bounds, dim3(gx, n_canvases), dim3(256), 0, (hipStream_t)stream, cmds_dev, n_cmds,
-                         (short*)bounds_dev, (const long long*)canvases_dev, n_canvases);
-      YMK_HIP(hipGetLastError());
-    }
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
+  YMK_API_BEGIN
+  YMK_CHECK(n_cmds >= 0 && n_runs >= 0 && n_codes >= 0 && n_glyphs >= 0 && n_canvases >= 0 && n_canvases <= 65535, "bad argument");
+  if (n_cmds == 0) return 0;
+  YMK_CHECK(cmds_dev && bounds_dev, "null command / bounds pointer");
+  YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0 && ((uintptr_t)bounds_dev & 7) == 0 && ((uintptr_t)canvases_dev & 7) == 0,
+            "command records must be 16-byte, bounds and the canvas table 8-byte aligned");
+  if (n_runs > 0) {
+    YMK_CHECK(runs_dev && (codes_dev || n_codes == 0) && (glyphs_dev || n_glyphs == 0), "null run / code / glyph pointer");
+    hipLaunchKernelGGL(ymk::k_overlay_layout, dim3(n_runs), dim3(ymk::OV_SCAN), 0, (hipStream_t)stream, cmds_dev, n_cmds, runs_dev,
+                       n_runs, codes_dev, n_codes, glyphs_dev, n_glyphs);
+    YMK_HIP(hipGetLastError());
   }
+  if (n_canvases > 0) {
+    YMK_CHECK(canvases_dev, "null canvas table");
+    const int gx = std::min(std::max((n_cmds + 255) / 256, 1), 256);
+    hipLaunchKernelGGL(ymk::k_overlay_bounds, dim3(gx, n_canvases), dim3(256), 0, (hipStream_t)stream, cmds_dev, n_cmds,
+                       (short*)bounds_dev, (const long long*)canvases_dev, n_canvases);
+    YMK_HIP(hipGetLastError());
+  }
+  YMK_API_END
 }
 
 int ymk_draw_overlay_pages(unsigned char* canvases_dev, int64_t canvas_bytes, const int64_t* table_dev, int n_canvases,
                            int64_t total_tiles, const int* cmds_dev, int n_cmds, const int16_t* bounds_dev,
                            const unsigned char* atlas_dev, int64_t atlas_bytes, void* stream) {
-  try {
-    YMK_CHECK(canvas_bytes >= 0 && n_canvases >= 0 && total_tiles >= 0 && total_tiles <= 0x7fffffffLL && n_cmds >= 0 &&
-                  atlas_bytes >= 0, "bad argument");
-    if (n_canvases == 0 || total_tiles == 0 || n_cmds == 0) return 0;
-    YMK_CHECK(canvases_dev && table_dev && cmds_dev && bounds_dev, "null canvas / table / command / bounds pointer");
-    YMK_CHECK(atlas_dev || atlas_bytes == 0, "null atlas with a non-zero size");
-    YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0 && ((uintptr_t)bounds_dev & 7) == 0 && ((uintptr_t)table_dev & 7) == 0,
-              "command records must be 16-byte, bounds and the canvas table 8-byte aligned");
-    hipLaunchKernelGGL(ymk::k_draw_overlay_pages, dim3((unsigned)total_tiles), dim3(ymk::OV_THREADS), 0, (hipStream_t)stream,
-                       canvases_dev, (long long)canvas_bytes, (const long long*)table_dev, n_canvases, cmds_dev, n_cmds,
-                       (const short*)bounds_dev, atlas_dev, (long long)atlas_bytes);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(canvas_bytes >= 0 && n_canvases >= 0 && total_tiles >= 0 && total_tiles <= 0x7fffffffLL && n_cmds >= 0 &&
+                atlas_bytes >= 0, "bad argument");
+  if (n_canvases == 0 || total_tiles == 0 || n_cmds == 0) return 0;
+  YMK_CHECK(canvases_dev && table_dev && cmds_dev && bounds_dev, "null canvas / table / command / bounds pointer");
+  YMK_CHECK(atlas_dev || atlas_bytes == 0, "null atlas with a non-zero size");
+  YMK_CHECK(((uintptr_t)cmds_dev & 15) == 0 && ((uintptr_t)bounds_dev & 7) == 0 && ((uintptr_t)table_dev & 7) == 0,
+            "command records must be 16-byte, bounds and the canvas table 8-byte aligned");
+  hipLaunchKernelGGL(ymk::k_draw_overlay_pages, dim3((unsigned)total_tiles), dim3(ymk::OV_THREADS), 0, (hipStream_t)stream,
+                     canvases_dev, (long long)canvas_bytes, (const long long*)table_dev, n_canvases, cmds_dev, n_cmds,
+                     (const short*)bounds_dev, atlas_dev, (long long)atlas_bytes);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 
 int ymk_heatmap_blend(unsigned char* canvas_dev, int h, int w, const float* prob_dev, int mh, int mw, const unsigned char* jet_dev,
                       void* stream) {
-  try {
-    YMK_CHECK(canvas_dev && prob_dev && jet_dev, "null pointer");
-    YMK_CHECK(h > 0 && w > 0 && h <= 16383 && w <= 16383 && mh > 0 && mw > 0 && mh <= 16383 && mw <= 16383,
-              "canvas and map: 1..16383 on a side");
-    hipLaunchKernelGGL(ymk::k_heatmap_blend, dim3((w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, canvas_dev, h, w, prob_dev,
-                       mh, mw, jet_dev);
-    YMK_HIP(hipGetLastError());
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(canvas_dev && prob_dev && jet_dev, "null pointer");
+  YMK_CHECK(h > 0 && w > 0 && h <= 16383 && w <= 16383 && mh > 0 && mw > 0 && mh <= 16383 && mw <= 16383,
+            "canvas and map: 1..16383 on a side");
+  hipLaunchKernelGGL(ymk::k_heatmap_blend, dim3((w + 255) / 256, h), dim3(256), 0, (hipStream_t)stream, canvas_dev, h, w, prob_dev,
+                     mh, mw, jet_dev);
+  YMK_HIP(hipGetLastError());
+  YMK_API_END
 }
 }

@@ -170,18 +170,14 @@ void table_hole_rects(int h, int w, const int* boxes, int n, int pad, int close_
 
 extern "C" int ymk_table_hole_rects(int h, int w, const int* cell_boxes, int n, int pad, int close_ksize, int min_area,
                                     int* rects_out, int capacity, int* count) {
-  try {
-    YMK_CHECK(count != nullptr && (n == 0 || cell_boxes != nullptr) && (capacity == 0 || rects_out != nullptr), "null argument");
-    YMK_CHECK(h >= 0 && w >= 0 && (long)h * w <= (1L << 28), "table crop too large");
-    std::vector<int> rects;
-    ymk::table_hole_rects(h, w, cell_boxes, n, pad, close_ksize, min_area, rects);
-    const int found = (int)rects.size() / 4;
-    YMK_CHECK(found <= capacity, "ymk_table_hole_rects: " + std::to_string(found) + " rectangles, capacity " + std::to_string(capacity));
-    std::copy(rects.begin(), rects.end(), rects_out);
-    *count = found;
-    return 0;
-  } catch (const std::exception& e) {
-    ymk::set_error(e.what());
-    return 1;
-  }
+  YMK_API_BEGIN
+  YMK_CHECK(count != nullptr && (n == 0 || cell_boxes != nullptr) && (capacity == 0 || rects_out != nullptr), "null argument");
+  YMK_CHECK(h >= 0 && w >= 0 && (long)h * w <= (1L << 28), "table crop too large");
+  std::vector<int> rects;
+  ymk::table_hole_rects(h, w, cell_boxes, n, pad, close_ksize, min_area, rects);
+  const int found = (int)rects.size() / 4;
+  YMK_CHECK(found <= capacity, "ymk_table_hole_rects: " + std::to_string(found) + " rectangles, capacity " + std::to_string(capacity));
+  std::copy(rects.begin(), rects.end(), rects_out);
+  *count = found;
+  YMK_API_END
 }
